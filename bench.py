@@ -29,6 +29,27 @@ from benchlib.costs import H, W, NS, NI, UNITS_PER_RAY, executed_per_ray, colour
 from benchlib import report                                                                        # noqa: E402
 
 
+DUMP_LIMIT_BYTES = (64 << 20) - (1 << 16)          # 64 MB in all, .npy headers included
+
+
+def dump_outputs(d, **arrays):
+    """Each array (a tensor on any device) -> d/<name>.npy in float32.  An array above DUMP_LIMIT_BYTES in all is written as a fixed sample of its pixels (the
+    last axis kept whole): the flat pixel indices drawn by a seeded generator, sorted, stored beside it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        x = a.detach().float().cpu().numpy()
+        if total > DUMP_LIMIT_BYTES:
+            px = x.reshape(-1, x.shape[-1])
+            share = DUMP_LIMIT_BYTES * (x.size * 4) // total                 # this array's part of the limit, index included
+            keep = max(1, min(px.shape[0], share // (px.shape[1] * 4 + 8)))
+            idx = np.sort(np.random.default_rng(0).choice(px.shape[0], keep, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            x = px[idx]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(x, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -60,6 +81,9 @@ def main():
                          "next call and, after the timed region, by nrf_renderer_nonfinite (reported as nonfinite_chunks); auto = one host read-back at the end of every frame call "
                          "(+ an NRF_PREC_F32 re-render of flagged chunks), what a host that renders single frames gets by default")
     ap.add_argument("--dense-mb", type=float, default=-1, help="override the baked dense-level budget of the hash fast path (MB)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step -- the gathered frames [frames, H, W, 3] a caller of the step "
+                         "receives -- as DIR/rgb.npy (float32; rank 0; a fixed, seeded sample of pixels beyond 64 MB): two builds compared output for output")
     ap.add_argument("--kernel-stats", default="profiles/round6/r8m_single_lane_kernel_stats.csv",
                     help="named in roofline.kernel_stats: the committed rocprofv3 --kernel-trace --stats summary of the single-lane pass the roofline re-derives from")
     args = ap.parse_args()
@@ -242,6 +266,8 @@ def main():
         lanes_info["requested"] = "env:" + forced_env
     elapsed, frames, poses, host_s, render_tiles = timed_run(args.scaling, args.steps, args.warmup, pick_lanes=True)
     lanes_timed = lanes_info["chosen"] or lib.nrf_get_render_lanes()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rgb=frames)
     nframes = len(poses)
     # at N > 1 the other scaling mode rides along in `also` (every rank takes part; fewer steps)
     other = None

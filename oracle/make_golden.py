@@ -44,6 +44,14 @@ def main():
     ck = os.path.join(out, "ckpt")
     os.makedirs(ck, exist_ok=True)
     subprocess.check_call([drv, "ckpt_save", ck])
+    # the other direction: SHA-256 of the archives nerfpp_amd.checkpoint writes for tests/test_host_cpu.py::test_written_checkpoints_restore_a_reference_model
+    # (that test restores them through ref_driver wherever it is built, and holds a machine without it to these bytes)
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import test_host_cpu as T
+    with tempfile.TemporaryDirectory() as tmp:
+        T.write_checkpoint_in_fresh_process(tmp)
+        with open(T.CKPT_WRITTEN_SHA256, "w") as f:
+            f.writelines(f"{h}  {fn}\n" for fn, h in T.checkpoint_sha256(tmp).items())
     return 0
 
 

@@ -222,29 +222,78 @@ def test_read_reference_checkpoints(manifest):
     np.testing.assert_allclose(opt["moments"][0][1], np.float32(0.01) * g0 * g0, rtol=2e-6)
 
 
-def test_written_checkpoints_restore_a_reference_model(tmp_path):
-    """SaveCheckpoint -> the reference's torch::load into ITS HashEmbedder / NeRFSmall (oracle/_ref/ref_driver ckpt_load) -> same numbers."""
-    import subprocess
-    from nerfpp_amd import checkpoint as CK
-    drv = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
-    if not os.path.exists(drv):
-        pytest.skip("oracle/_ref/ref_driver not built (needs /root/reference)")
+CKPT_WRITTEN_SHA256 = os.path.join(ROOT, "tests", "golden", "ckpt_written.sha256")
+
+
+def written_checkpoint_inputs():
+    """The seeded model / embedder / Adam state / CuHashEmbedder state of test_written_checkpoints_restore_a_reference_model (also oracle/make_golden.py)."""
     rng = np.random.RandomState(4)
     model = {f"model_{n}.weight": rng.randn(*s).astype(np.float32) for n, s in (("sigma_net_0", (64, 8)), ("sigma_net_1", (64, 64)), ("sigma_net_2", (16, 64)),
                                                                               ("color_net_0", (64, 31)), ("color_net_1", (64, 64)), ("color_net_2", (3, 64)))}
     emb = {f"embedder_embeddings_{l}.weight": rng.randn(4096, 2).astype(np.float32) for l in range(4)}
-    d = str(tmp_path / "ck"); out = str(tmp_path / "out"); os.makedirs(out)
     # Adam state in the optimizer's parameter order (NeRFExecutor.h:508-535: the embedder's parameters, then the model's)
     shapes = [v.shape for v in emb.values()] + [v.shape for v in model.values()]
     mom = [(rng.randn(*s_).astype(np.float32), rng.rand(*s_).astype(np.float32)) for s_ in shapes]
     mom[2] = None                                                      # a parameter that has not been stepped yet has no state
-    assert not CK.WouldRestore(str(tmp_path))
-    CK.SaveCheckpoint(d, embedder=emb, model=model, global_step=77, optimizer=dict(moments=mom, step=41, lr=3e-4))
-    assert CK.WouldRestore(d)                                           # the reference's own condition (NeRFExecutor.h:541-546): start + optimizer + model files
     cu_p = {"embedder_embeddings": rng.randn(4 * 4096, 2).astype(np.float32)}
     cu_b = {"embedder_primes": (268435459 + np.arange(12, dtype=np.int32) * 4).reshape(4, 1, 3), "embedder_biases": np.full((4, 3), 0.5, np.float32),
             "embedder_feat_local_size": np.full(4, 4096, np.int32), "embedder_feat_local_idx": (np.arange(4) * 4096).astype(np.int32)}
-    CK.save_module(os.path.join(d, "cu_embedder_checkpoint.pt"), cu_p, cu_b)
+    return model, emb, mom, cu_p, cu_b
+
+
+def write_checkpoint_in_fresh_process(d):
+    """SaveCheckpoint + the CuHashEmbedder archive of written_checkpoint_inputs() into `d`, in a child process: TorchScript numbers the classes it
+    compiles per process (___torch_mangle_<n>), so only a fresh process writes the same bytes every time."""
+    code = ("import sys; sys.path[:0] = [sys.argv[1], sys.argv[2]]\n"
+            "from test_host_cpu import written_checkpoint_inputs\n"
+            "from nerfpp_amd import checkpoint as CK\n"
+            "model, emb, mom, cu_p, cu_b = written_checkpoint_inputs()\n"
+            "CK.SaveCheckpoint(sys.argv[3], embedder=emb, model=model, global_step=77, optimizer=dict(moments=mom, step=41, lr=3e-4))\n"
+            "CK.save_module(sys.argv[3] + '/cu_embedder_checkpoint.pt', cu_p, cu_b)\n")
+    subprocess.check_call([sys.executable, "-c", code, ROOT, os.path.join(ROOT, "tests"), d])
+
+
+def checkpoint_sha256(d):
+    """Per archive in `d`: SHA-256 over its members (name, bytes) except the debug tables (*.debug_pkl: source ranges, with the absolute path of the writing
+    checkout) and .data/serialization_id (derived from them) -- code, pickles and tensor data, what torch::load reads."""
+    import hashlib
+    import zipfile
+    out = {}
+    for f in sorted(os.listdir(d)):
+        if not f.endswith(".pt"):
+            continue
+        h = hashlib.sha256()
+        with zipfile.ZipFile(os.path.join(d, f)) as z:
+            for n in z.namelist():
+                if n.endswith(".debug_pkl") or n.endswith("/.data/serialization_id"):
+                    continue
+                h.update(n.encode() + b"\0" + z.read(n))
+        out[f] = h.hexdigest()
+    return out
+
+
+def test_written_checkpoints_restore_a_reference_model(tmp_path):
+    """SaveCheckpoint -> the reference's torch::load into ITS HashEmbedder / NeRFSmall (oracle/_ref/ref_driver ckpt_load) -> same numbers.  Where ref_driver is
+    not built, the archives must hold byte for byte what it restored when tests/golden/ckpt_written.sha256 was recorded (oracle/make_golden.py); where it
+    is, both hold."""
+    from nerfpp_amd import checkpoint as CK
+    model, emb, mom, cu_p, cu_b = written_checkpoint_inputs()
+    d = str(tmp_path / "ck"); out = str(tmp_path / "out"); os.makedirs(out)
+    assert not CK.WouldRestore(str(tmp_path))
+    write_checkpoint_in_fresh_process(d)
+    assert CK.WouldRestore(d)                                           # the reference's own condition (NeRFExecutor.h:541-546): start + optimizer + model files
+    want = dict(line.split()[::-1] for line in open(CKPT_WRITTEN_SHA256) if line.strip())
+    assert checkpoint_sha256(d) == want, "the archives differ from the ones the reference restored (re-record with oracle/make_golden.py where ref_driver is built)"
+    back = CK.LoadCheckpoint(d)
+    assert back["would_restore"] and back["optimizer"]["step"] == 41 and back["optimizer"]["moments"][2] is None
+    np.testing.assert_array_equal(back["optimizer"]["moments"][5][1], mom[5][1])
+    for k, v in model.items():
+        np.testing.assert_array_equal(back["model"][k], v)
+    for k, v in emb.items():
+        np.testing.assert_array_equal(back["embedder"][k], v)
+    drv = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
+    if not os.path.exists(drv):
+        return
     subprocess.check_call([drv, "ckpt_load", d, out], stdout=subprocess.DEVNULL)
     for k, v in model.items():
         np.testing.assert_array_equal(np.load(os.path.join(out, "m." + k + ".npy")), v)
@@ -264,9 +313,6 @@ def test_written_checkpoints_restore_a_reference_model(tmp_path):
         np.testing.assert_array_equal(np.load(f), mv[0])
         np.testing.assert_array_equal(np.load(os.path.join(out, f"opt.{i}.exp_avg_sq.npy")), mv[1])
         assert np.load(os.path.join(out, f"opt.{i}.step.npy"))[0] == 41
-    back = CK.LoadCheckpoint(d)
-    assert back["would_restore"] and back["optimizer"]["step"] == 41 and back["optimizer"]["moments"][2] is None
-    np.testing.assert_array_equal(back["optimizer"]["moments"][5][1], mom[5][1])
 
 
 def test_bench_launcher_reports_failing_ranks_without_hanging():

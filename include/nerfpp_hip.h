@@ -329,6 +329,49 @@ NRF_API int nrf_relevancy_image(const float *d_relevancy, int64_t n, int rel_str
 NRF_API int nrf_colormap_jet_u8(const uint8_t *d_gray, int64_t n, uint8_t *d_bgr, void *stream);
 NRF_API int nrf_colormap_jet_lut(uint8_t *lut_host /*[256*3]*/);
 
+/* ---- language targets from a cached CLIP pyramid: PyramidEmbedding (PyramidEmbedder.h:32-81, PyramidEmbedder.cpp:4-310) ----
+ * The reference computes LeRF training targets on the host, one pixel per call of GetPixelValue inside an OpenMP loop (NeRFDataset.cpp:180-193), and its relevancy
+ * preview the same way for every pixel of a view (NeRFExecutor.h:803-831).  A pyramid here holds the reference's cache (pyramid_embeddings.pt, PyramidEmbedding::Save /
+ * Load, PyramidEmbedder.cpp:199-223) in device memory: one dense fp32 block [nh][nw][D] per (image, level), levels -1 .. max_zoom_out, for every level whose grid is
+ * not empty.  Building a pyramid (RuCLIP over OpenCV tiles, PyramidEmbedder::operator() / GetNextSample) is not done here.
+ *
+ * nrf_pyramid_level_geometry : window size and grid of one level (GetNearestPatchIndicesSingleScale, :15-19, the reference's int / float / double mix): host only;
+ *                              out = {win, nw, nh}; nw or nh <= 0 means the level has no grid.
+ * nrf_pyramid_max_zoom_out   : PyramidEmbedderProperties::MaxZoomOut as the dataset sets it (NeRFDataset.cpp:86, :178): int(min(log2f(wmax / clip), log2f(hmax / clip)))
+ *                              with integer quotients, over wh [n, 2] = {W, H} per view; host only.  A largest view narrower or lower than clip (log2f(0)) is rejected.
+ * nrf_pyramid_create         : empty pyramid for n_images views of sizes wh [n, 2] = {W, H} (host).  D = lang_embed_dim, clip = clip_input_img_size (square, :73),
+ *                              overlap = pyr_embedder_overlap.  Allocates every block; nrf_pyramid_memory_bytes = the sum of nw * nh * D * 4 over them.
+ * nrf_pyramid_set_entries    : n cache entries: keys host int32 [n, 4] = {hor_pos_idx, vert_pos_idx, zoom_out_idx, data_img_id} (the std::map key), emb host fp32
+ *                              [n, d] (the [1, D] tensors).  d must equal D; a key outside its image's levels or grid is rejected (NRF_ERR_INVALID_ARG, nothing
+ *                              stored).  A key given again replaces the earlier row.  Synchronises `stream` (the host arrays are released before returning).
+ * nrf_pyramid_pixel_values   : GetPixelValue(x, y, scale, img_id, properties, {W, H}) (:230-310) for n pixels: d_x, d_y device int64 [n], each converted to float as the
+ *                              dataset's .to(kFloat) does; row k of d_out (out_stride floats apart, >= D) receives pixel k's [D] embedding.  The call sites' argument
+ *                              orders differ and are the caller's: get_batch passes x = rand_h, y = rand_w (NeRFDataset.cpp:186-187), the preview x = column, y = row.
+ *                              Bit for bit the reference's ATen fp32 arithmetic (the three degenerate Interpolate forms included); a scale above the top level gives
+ *                              0/0, i.e. NaN rows, as the reference's does.  Both levels the scale selects (z1 and z2, :97-113) must have every entry, img_id must be a
+ *                              view of the pyramid and scale a positive finite number: otherwise NRF_ERR_INVALID_ARG before any launch (the reference throws on the
+ *                              undefined tensor of a missing map entry).  Pinned by a restatement of the reference's arithmetic (tests/test_pyramid_*.py), not by a
+ *                              golden of the compiled reference (PyramidEmbedder.cpp needs OpenCV and RuCLIP).
+ * nrf_pyramid_relevancy_preview : the preview loop of NeRFExecutor::Train (NeRFExecutor.h:803-831) for view img_id: GetPixelValue(i, j, scale) for every column i and
+ *                              row j, Relevancy against the phrases (device [n_pos, D] / [n_neg, D], as nrf_lerf_relevancy takes them), cv::saturate_cast<uchar>(rel *
+ *                              255) into d_gray [H * W] (row j, column i at j * W + i), and with d_bgr (optional, [H * W, 3]) cv::applyColorMap(COLORMAP_JET) as
+ *                              nrf_colormap_jet_u8.  saturate_cast is OpenCV's cvRound (cvtss2si on x86: round half to even; NaN gives INT_MIN, i.e. 0) then a clamp.
+ *                              Rows go through the workspace in chunks; nrf_pyramid_relevancy_preview_workspace_bytes(p, img_id, rows) sizes it for `rows` rows at
+ *                              a time (NRF_ERR_WORKSPACE below one row).  PARITY UNPINNED beyond the pixel values, as nrf_lerf_relevancy and the colormap are:
+ *                              OpenCV is not in this image. */
+typedef struct nrf_pyramid nrf_pyramid;
+NRF_API int nrf_pyramid_level_geometry(int img_w, int img_h, int clip, float overlap, int zoom, int *out /*[3] = win, nw, nh*/);
+NRF_API int nrf_pyramid_max_zoom_out(const int *wh /*[n, 2]*/, int n_images, int clip, int *out);
+NRF_API int nrf_pyramid_create(int d, int clip_size, float overlap, int max_zoom_out, int n_images, const int *wh /*[n, 2]*/, nrf_pyramid **out);
+NRF_API int nrf_pyramid_destroy(nrf_pyramid *p);
+NRF_API int64_t nrf_pyramid_memory_bytes(const nrf_pyramid *p);
+NRF_API int nrf_pyramid_set_entries(nrf_pyramid *p, int64_t n, const int32_t *keys /*[n, 4]*/, const float *emb /*[n, d]*/, int d, void *stream);
+NRF_API int nrf_pyramid_pixel_values(const nrf_pyramid *p, int img_id, float scale, const int64_t *d_x, const int64_t *d_y, int64_t n, float *d_out, int64_t out_stride,
+                                     void *stream);
+NRF_API size_t nrf_pyramid_relevancy_preview_workspace_bytes(const nrf_pyramid *p, int img_id, int rows);
+NRF_API int nrf_pyramid_relevancy_preview(const nrf_pyramid *p, int img_id, float scale, const float *d_positives, int n_pos, const float *d_negatives, int n_neg,
+                                          int positive_id, uint8_t *d_gray, uint8_t *d_bgr, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* SamplePDF, deterministic branch (Sampler.h:6-43).  bins [n,nb], weights [n,nb-1], u [ns] device
  * (= linspace(0,1,ns)).  sum_vec: fp32 lanes of the host whose torch::sum order is reproduced for the
  * pdf normaliser (8 = any AVX2+/AVX-512 x86 build of ATen; 0 = order-free double accumulation).

@@ -94,6 +94,8 @@ SYMBOLS = [
     "nrf_lerf_batchify_rays_workspace_bytes", "nrf_lerf_batchify_rays", "nrf_lerf_render_rows_workspace_bytes", "nrf_lerf_render_rows",
     "nrf_fp32_gemm_available", "nrf_get_train_gemm", "nrf_set_train_gemm", "nrf_gemm_nt_bf16x3", "nrf_gemm_nt_f16x3", "nrf_gemm_tn_bf16x3", "nrf_layer_grad_split", "nrf_huber_rows_nanmean", "nrf_lerf_head_backward_workspace_bytes", "nrf_lerf_head_backward", "nrf_lerf_backward_points_workspace_bytes", "nrf_lerf_backward_points",
     "nrf_lerf_renderer_last_features", "nrf_lerf_backward_points_src", "nrf_scratch_trim",
+    "nrf_pyramid_level_geometry", "nrf_pyramid_max_zoom_out", "nrf_pyramid_create", "nrf_pyramid_destroy", "nrf_pyramid_memory_bytes", "nrf_pyramid_set_entries",
+    "nrf_pyramid_pixel_values", "nrf_pyramid_relevancy_preview_workspace_bytes", "nrf_pyramid_relevancy_preview",
 ]
 NRF_COMM_ID_BYTES = 128
 
@@ -135,6 +137,8 @@ def lib():
         L.nrf_hash_backward_packed_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_head_backward_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_backward_points_workspace_bytes.restype = C.c_size_t
+        L.nrf_pyramid_memory_bytes.restype = C.c_int64
+        L.nrf_pyramid_relevancy_preview_workspace_bytes.restype = C.c_size_t
         _lib = L
     return _lib
 

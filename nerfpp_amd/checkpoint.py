@@ -33,6 +33,25 @@ def load_tensor(path):
     return dict(m.named_parameters(), **dict(m.named_buffers()))["0"].detach().numpy().copy()
 
 
+def save_tensor_list(path, tensors):
+    """torch::save(std::vector<Tensor>, path): one archive holding the tensors as parameters named "0", "1", ... (OutputArchive::write, is_buffer = false)."""
+    m = _Holder()
+    for i, t in enumerate(tensors):
+        t = torch.as_tensor(np.ascontiguousarray(t))
+        m.register_parameter(str(i), torch.nn.Parameter(t, requires_grad=False))
+    torch.jit.script(m).save(path)
+
+
+def load_tensor_list(path):
+    """torch::load(std::vector<Tensor>, path): the tensors stored under "0", "1", ... in index order, as host arrays."""
+    m = torch.jit.load(path, map_location="cpu")
+    named = dict(m.named_parameters(), **dict(m.named_buffers()))
+    out = []
+    while str(len(out)) in named:
+        out.append(named[str(len(out))].detach().numpy().copy())
+    return out
+
+
 def blob(params):
     """Concatenate in checkpoint order: the `params` argument of nrf_mlp_*_create / the table of nrf_hash_set_table (NGP mode)."""
     return np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in params.values()])

@@ -1,8 +1,9 @@
 """Ray-batch producer of the training loop -- NeRFDataset::get_batch / GetRayBatch (NeRFDataset.cpp:44-65, :109-208) and the Blender
 camera / bounds helpers the executor calls once per dataset (load_blender.h:83-124) -- SURVEY section 8f, row N2.
 
-Image decoding, COLMAP / Blender file parsing and the CLIP pyramid are out of scope (loaders); a view here is the already
-decoded record the reference keeps in NeRFDatasetParams::Views: H, W, K [3,3], Pose [3|4, 4] and the image as an fp32 [H, W, 3] tensor.
+Image decoding, COLMAP / Blender file parsing and building the CLIP pyramid are out of scope (loaders); a view here is the already
+decoded record the reference keeps in NeRFDatasetParams::Views: H, W, K [3,3], Pose [3|4, 4] and the image as an fp32 [H, W, 3] tensor.  With LeRF
+parameters the batch also carries its language targets, read on the device from the pyramid's cache (nerfpp_amd/pyramid.py).
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -13,6 +14,7 @@ import torch
 
 from . import _lib as L
 from .modules import _ptr, _stream, _dev_f32
+from .pyramid import PyramidEmbedderProperties, PyramidEmbedding, MaxZoomOut
 
 
 @dataclass
@@ -24,6 +26,14 @@ class View:                       # NeRFDatasetParams::Views[i]
     Image: Optional[torch.Tensor] = None      # [H, W, 3] fp32 on the GPU
     Near: float = 0.0
     Far: float = 0.0
+
+
+@dataclass
+class LeRFDataParams:             # LeRFDatasetParams (NeRFDatasetParams.h:177), the fields get_batch reads
+    clip_input_img_size: int
+    pyr_embedder_overlap: float
+    lang_embed_dim: int
+    pyramid: PyramidEmbedding     # the cache the reference loads from pyramid_embeddings.pt (NeRFDataset.cpp:96-98)
 
 
 def _k9(K):
@@ -59,9 +69,16 @@ class NeRFDataset:
     with torch::randint from the global generator; here they are a pure function of (seed, iteration, element) (include/nrf_rng.h), so
     a training run is reproducible and a batch can be regenerated from its iteration number alone."""
 
-    def __init__(self, views, batch_size, precorp_iters=0, precorp_frac=0.5, seed=0):
+    def __init__(self, views, batch_size, precorp_iters=0, precorp_frac=0.5, seed=0, lerf: Optional[LeRFDataParams] = None):
         self.Views, self.BatchSize, self.PrecorpIters, self.PrecorpFrac, self.Seed = list(views), int(batch_size), int(precorp_iters), float(precorp_frac), int(seed)
         self.CurrentIter, self.CurrentImageIdx = 0, 0
+        self.LeRFParams = lerf
+        if lerf is not None:
+            # InitializePyramidClipEmbedding (NeRFDataset.cpp:67-105): the properties get_batch builds (:164-178), the cache uploaded once
+            clip = int(lerf.clip_input_img_size)
+            self.PyramidProperties = PyramidEmbedderProperties(ImgSize=(clip, clip), Overlap=float(lerf.pyr_embedder_overlap),
+                                                               MaxZoomOut=MaxZoomOut(self.Views, clip))
+            lerf.pyramid.to_device(self.Views, self.PyramidProperties, d=int(lerf.lang_embed_dim))
 
     def SetCurrentIter(self, i):
         self.CurrentIter = int(i)
@@ -80,7 +97,11 @@ class NeRFDataset:
             target = torch.empty((n, c), device=img.device, dtype=torch.float32)
             L.check(L.lib().nrf_gather_pixels(_ptr(img), v.H, v.W, c, _ptr(rh), _ptr(rw), C.c_int64(n), _ptr(target), _stream()))
         o, d, cone = GetRayBatch(rh, rw, v.H, v.W, v.K, v.Pose)
-        return dict(rays_o=o, rays_d=d, cone_angle=cone, Near=v.Near, Far=v.Far, target_s=target, rand_h=rh, rand_w=rw)
+        out = dict(rays_o=o, rays_d=d, cone_angle=cone, Near=v.Near, Far=v.Far, target_s=target, rand_h=rh, rand_w=rw)
+        if self.LeRFParams is not None:
+            # :180-193: GetPixelValue(rand_h, rand_w, 0.5f, CurrentImageIdx, ..., Size(W, H)) per pixel -- the row as x, as the reference passes it
+            out["target_lang_embedding"] = self.LeRFParams.pyramid.GetPixelValue(rh, rw, 0.5, self.CurrentImageIdx)
+        return out
 
 
 def GetBoundsForObj(views):

@@ -38,7 +38,8 @@ enum {
     NRF_ERR_HIP = 2,          /* a HIP runtime call / kernel launch failed (no device, OOM, ...) */
     NRF_ERR_UNSUPPORTED = 3,  /* valid in the reference, not built here (message says what) */
     NRF_ERR_WORKSPACE = 4,    /* caller's workspace too small */
-    NRF_ERR_NONFINITE = 5     /* a matrix-core render produced inf / NaN network outputs (an fp16 operand left its range): see nrf_render_params.overflow_policy */
+    NRF_ERR_NONFINITE = 5     /* non-finite values where finite ones are required: a matrix-core render produced inf / NaN network outputs (an fp16 operand left its
+                                 range, see nrf_render_params.overflow_policy), or a lattice handed to nrf_isosurface_emit holds inf / NaN */
 };
 
 NRF_API int nrf_version(void);
@@ -518,6 +519,34 @@ NRF_API int nrf_renderer_nonfinite(const nrf_renderer *r, int64_t *flagged_chunk
 NRF_API size_t nrf_run_network_workspace_bytes(const nrf_renderer *r, int64_t n, int s);
 NRF_API int nrf_run_network(const nrf_renderer *r, const float *d_pts, const float *d_viewdirs, int64_t n, int s, int precision,
                             float *d_raw, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh export (mesh.hip; no counterpart in the reference: its scenes are looked at through rendered images only)
+ * ------------------------------------------------------------------------------------------- */
+/* Density lattice: d_sigma [nz][ny][nx] (x fastest) = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at P(i, j, k), bit for bit, keep-mask rule of
+ * NeRFRenderer.h:187-188 included (outside the hash box a 4-column net gives 0).  bbox[6] (host): min xyz, max xyz; P = bmin + (float)i * step per axis,
+ * step = (bmax - bmin) / (float)(n - 1), one fp32 rounding per operation; nx, ny, nz >= 2.  The colour net is not evaluated: hash grid + NeRFSmall and the classic
+ * PE(10) / PE(4) network run their exact-fp32 density kernels (the coarse pass's), any other renderer the F32 network.  Work goes in slabs of slab_points lattice
+ * points (<= 0: 2^22; at most 2^30), so the workspace is bounded whatever the resolution; the result does not depend on slab_points.  LeRF renderers are not covered. */
+NRF_API size_t nrf_density_grid_workspace_bytes(const nrf_renderer *r, int nx, int ny, int nz, int64_t slab_points);
+NRF_API int nrf_density_grid(const nrf_renderer *r, const float *bbox, int nx, int ny, int nz, float *d_sigma, int64_t slab_points,
+                             void *d_workspace, size_t workspace_bytes, void *stream);
+/* Isosurface of a lattice d_sigma [nz][ny][nx] (lattice points as above) at level iso: marching tetrahedra on the Kuhn split of each cell into 6 tetrahedra.
+ *   inside: f > iso.  Edges start at lattice point a, 7 types in the order (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1); one vertex per crossed edge (one end
+ *   inside), ordered by (linear index of a, type), at p = P(a) + t (P(b) - P(a)), t = (iso - f_a) / (f_b - f_a) (fp32).  Cells in linear order of their min corner c,
+ *   tetrahedra in the axis-permutation order xyz, xzy, yxz, yzx, zxy, zyx (chain c, + e_p0, + e_p1, c + (1,1,1)); 1 or 3 corners inside: one triangle on the odd
+ *   corner's three edges in chain order; 2 inside {a, b}, 2 outside {c, d}: (ac, ad, bd), (ac, bd, bc).  Counter-clockwise seen from outside (f <= iso), decided from the
+ *   case and the permutation's parity.  Degenerate triangles (f_b == iso) are kept.  Normals (optional): n = -g / |g| (0 where |g| = 0) of the lattice gradient (central
+ *   differences, one-sided at the border) interpolated with the same t.  Output order comes from integer prefix scans: two runs give the same arrays.
+ * Two calls over one workspace: nrf_isosurface_count classifies, scans and returns the vertex and triangle counts and the number of non-finite lattice values -- it
+ * SYNCHRONISES the stream to read them back (as does nrf_isosurface_emit, to check them); counts beyond int32 are refused (NRF_ERR_INVALID_ARG).  Then the host
+ * allocates d_verts [V,3], d_faces [F,3] (int32), d_normals [V,3] (or NULL) and calls nrf_isosurface_emit with the same lattice, box, iso and workspace;
+ * it returns NRF_ERR_NONFINITE (nothing written) when the lattice holds a non-finite value. */
+NRF_API size_t nrf_isosurface_workspace_bytes(int nx, int ny, int nz);
+NRF_API int nrf_isosurface_count(const float *d_sigma, int nx, int ny, int nz, const float *bbox, float iso, int64_t *n_verts, int64_t *n_tris, int64_t *n_nonfinite,
+                                 void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_isosurface_emit(const float *d_sigma, int nx, int ny, int nz, const float *bbox, float iso, float *d_verts, int32_t *d_faces, float *d_normals,
+                                int64_t n_verts, int64_t n_tris, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */

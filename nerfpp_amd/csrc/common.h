@@ -20,6 +20,10 @@ void set_error(const char *fmt, ...);
 // hipMallocAsync / hipFreeAsync (same return type), which proved unsafe inside the LibTorch host
 hipError_t scratch_take(void **out, size_t bytes, hipStream_t st);
 hipError_t scratch_give(void *p, hipStream_t st);
+// render.hip, for mesh.hip: sigma = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at p explicit points [p, 3], bit for bit, on the exact-fp32 density kernels where the
+// renderer has them (1 <= p <= 2^30)
+size_t renderer_density_ws_bytes(const nrf_renderer *r, int64_t p);
+int renderer_density(const nrf_renderer *r, const float *pts, int64_t p, float *sigma, void *ws, size_t ws_bytes, hipStream_t st);
 
 #define NRF_CHECK_ARG(cond, ...)                                   \
     do {                                                           \

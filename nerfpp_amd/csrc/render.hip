@@ -983,3 +983,58 @@ int nrf_render_rows(const nrf_renderer *r, const nrf_view *v, const nrf_render_p
 }
 
 }  // extern "C"
+
+namespace nrf {
+
+// ---------------------------------------------------------------------------------------------------
+// density at explicit points for the mesh export (mesh.hip: nrf_density_grid)
+// ---------------------------------------------------------------------------------------------------
+__global__ void k_take_column(int64_t p, int c, int col, const float *__restrict__ raw, float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < p) out[i] = raw[i * c + col];
+}
+
+// which kernels serve renderer_density: the coarse pass's exact-fp32 sigma kernels, on the same conditions as the render path uses them
+static bool density_hash_exact(const nrf_renderer *r) { return fast_path(r, NRF_PREC_F16_SPLIT) && mlp_small_sigma_f32_available(r->desc.mlp); }
+static bool density_classic_exact(const nrf_renderer *r)
+{
+    return !r->desc.hash && r->desc.pe_freqs == 10 && r->desc.dirs_encoder == NRF_DIRS_PE && r->desc.dirs_param == 4 && r->desc.mlp->out_dims == 4 &&
+           mlp_nerf_sigma_f32_available(r->desc.mlp);
+}
+
+size_t renderer_density_ws_bytes(const nrf_renderer *r, int64_t p)
+{
+    if (density_hash_exact(r)) return align_up((size_t)p * 16 * sizeof(__half2), 256) * 2 + align_up((size_t)p, 256) + 1024;          // run_sigma_fast's layout
+    if (density_classic_exact(r)) return align_up((size_t)p * 4 * sizeof(float), 256) + align_up(32 * sizeof(__half), 256) + 1024;       // raw rows + one direction row
+    return align_up((size_t)p * r->desc.mlp->out_dims * sizeof(float), 256) + align_up(3 * sizeof(float), 256) + network_ws_bytes(r, p, NRF_PREC_F32) + 1024;
+}
+
+int renderer_density(const nrf_renderer *r, const float *pts, int64_t p, float *sigma, void *ws, size_t ws_bytes, hipStream_t st)
+{
+    if (p <= 0) return NRF_OK;
+    if (ws_bytes < renderer_density_ws_bytes(r, p)) { set_error("renderer_density: workspace %zu < %zu bytes", ws_bytes, renderer_density_ws_bytes(r, p)); return NRF_ERR_WORKSPACE; }
+    // hash grid + NeRFSmall: level-major encode + mlp_small_sigma_f32_lm, keep mask applied by the kernel (the coarse pass's sigma, equal to NRF_PREC_F32's)
+    if (density_hash_exact(r)) return run_sigma_fast(r, PointSource{pts, nullptr, nullptr, 0, 1}, p, 1, sigma, ws, ws_bytes, st);
+    Bump bump(ws, ws_bytes);
+    const int c = r->desc.mlp->out_dims;
+    float *raw = bump.take<float>((size_t)p * c);
+    if (density_classic_exact(r)) {
+        // the classic coarse kernel: exact-fp32 density branch; its fused split-precision colour tail reads one zero direction row (all points are "ray 0": s = p) and
+        // its rgb columns are dropped
+        __half *dirs = bump.take<__half>(32);
+        NRF_HIP(hipMemsetAsync(dirs, 0, 32 * sizeof(__half), st));
+        NRF_TRY(mlp_nerf_exact_coarse(r->desc.mlp, pts, nullptr, 0, nullptr, (int)p, dirs, nullptr, p, raw, st));
+    } else {
+        // any other renderer: the F32 network over the points (one ray of p samples: a single zero view direction; sigma does not read it)
+        float *vd = bump.take<float>(3);
+        NRF_HIP(hipMemsetAsync(vd, 0, 3 * sizeof(float), st));
+        void *nws = bump.take<char>(0);
+        NRF_TRY(run_network(r, PointSource{pts, nullptr, nullptr, 0, (int)p}, r->in_views > 0 ? vd : nullptr, 3, 1, (int)p, NRF_PREC_F32, raw, nws, ws_bytes - bump.off, st));
+    }
+    hipLaunchKernelGGL(k_take_column, dim3((unsigned)ceil_div(p, 256)), dim3(256), 0, st, p, c, 3, raw, sigma);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
+}  // namespace nrf

@@ -499,6 +499,21 @@ typedef struct nrf_render_outputs {   /* NeRFRendererOutputs / NeRFRenderResult 
     float *d_z_fine;          /* [n, n_samples + n_importance] */
 } nrf_render_outputs;
 
+/* Normal maps of a render: the *_normals entries below take this beside the two structs above, which keep their layout (a caller compiled against an earlier header
+ * hands the library structs of that size).  The plain entries render no normals.
+ *   NRF_NORMALS_DENSITY    d_normals [n,3] = sum_i w_i n_i over the final samples and weights in ascending order (summed in fp64, rounded once), n_i = -g / max(|g|, 1e-8),
+ *                          g = nrf_density_grad at the point the fine network saw (the perturbed one with cone rays / preconditioning); a zero-weight sample
+ *                          contributes 0.  Hash grid + NeRFSmall renderers, every precision.
+ *   NRF_NORMALS_PREDICTED  d_pred_normals [n,3] = sum_i w_i (v / max(|v|, 1e-8)), v = raw_i[4:7] of a NeRFSmall with the predicted-normals head, NRF_PREC_F32 only.
+ * RGB, disparity, accumulation, depth and weights equal the plain entry's bit for bit.  bits = 0 is the plain entry (same workspace size).  A set bit with a NULL
+ * output, unknown bits (NRF_ERR_INVALID_ARG) or an unsupported renderer / network / precision (NRF_ERR_UNSUPPORTED, NRF_ERR_INVALID_ARG) fail before any launch. */
+enum { NRF_NORMALS_DENSITY = 1, NRF_NORMALS_PREDICTED = 2 };
+typedef struct nrf_render_normals {
+    int bits;                 /* NRF_NORMALS_* */
+    float *d_normals;         /* [n,3] when bits & NRF_NORMALS_DENSITY */
+    float *d_pred_normals;    /* [n,3] when bits & NRF_NORMALS_PREDICTED */
+} nrf_render_normals;
+
 typedef struct nrf_renderer nrf_renderer;
 
 NRF_API int nrf_renderer_create(const nrf_renderer_desc *desc, nrf_renderer **out);
@@ -548,6 +563,19 @@ NRF_API int nrf_isosurface_count(const float *d_sigma, int nx, int ny, int nz, c
 NRF_API int nrf_isosurface_emit(const float *d_sigma, int nx, int ny, int nz, const float *bbox, float iso, float *d_verts, int32_t *d_faces, float *d_normals,
                                 int64_t n_verts, int64_t n_tris, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Density gradient (normals.hip; the reference's calculate_normals, never finished there)
+ * ------------------------------------------------------------------------------------------- */
+/* d_sigma [p] (may be NULL) = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at d_pts [p,3], bit for bit (keep mask of NeRFRenderer.h:187-188 included: it writes
+ * column -1, so a 4-column net gives 0 outside the hash box and a 7-column one keeps sigma); d_grad [p,3] = d sigma / d x, forward mode: the encoder's derivative in
+ * the cell the forward pass chooses (CuHashEmbedder: of the unrounded fp32 blend, 0 on an axis the box clamp moved; HashEmbedder: torch autograd of
+ * HashEmbedderImpl::forward), the tangents through the sigma net in fp32 beside the exact primal, masked by its ReLUs; 0 where sigma is replaced by 0.  Hash grid
+ * (either mode) + NeRFSmall with 32 features, hidden_dim 64 and 2 or 3 sigma-net layers; anything else is NRF_ERR_UNSUPPORTED.  The call needs no workspace
+ * (the workspace size is 0; both arguments are accepted for symmetry with nrf_density_grid) and launches in bounded slabs. */
+NRF_API size_t nrf_density_grad_workspace_bytes(const nrf_renderer *r, int64_t p);
+NRF_API int nrf_density_grad(const nrf_renderer *r, const float *d_pts, int64_t p, float *d_sigma, float *d_grad, void *d_workspace, size_t workspace_bytes,
+                             void *stream);
+
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */
 NRF_API size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p);
@@ -572,6 +600,17 @@ NRF_API int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ra
 NRF_API size_t nrf_render_rows_workspace_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p);
 NRF_API int nrf_render_rows(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, const float *d_t, const float *d_u,
                             const nrf_render_outputs *out, float *d_rays_out, float *d_near_far, void *d_workspace, size_t workspace_bytes, void *stream);
+/* The three render entries with normal maps (nrf_render_normals above); same arguments and results otherwise. */
+NRF_API size_t nrf_render_rays_normals_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p, int bits);
+NRF_API int nrf_render_rays_normals(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const nrf_render_params *p, const float *d_t, const float *d_u,
+                                    const nrf_render_outputs *out, const nrf_render_normals *normals, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_batchify_rays_normals_workspace_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p, int bits);
+NRF_API int nrf_batchify_rays_normals(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const float *d_t,
+                                      const float *d_u, const nrf_render_outputs *out, const nrf_render_normals *normals, void *d_workspace, size_t workspace_bytes,
+                                      void *stream);
+NRF_API size_t nrf_render_rows_normals_workspace_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, int bits);
+NRF_API int nrf_render_rows_normals(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, const float *d_t, const float *d_u, const nrf_render_outputs *out,
+                                    const nrf_render_normals *normals, float *d_rays_out, float *d_near_far, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training step: NeRFExecutor::Train, NeRFExecutor.h:862-995.

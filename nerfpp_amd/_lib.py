@@ -20,6 +20,7 @@ NRF_PROF_NAMES = ("hash", "mlp", "composite", "sample", "other", "sigma", "mlp_c
 NRF_COARSE_AUTO, NRF_COARSE_FULL, NRF_COARSE_SIGMA_F32 = 0, 1, 2
 NRF_OVERFLOW_AUTO, NRF_OVERFLOW_RERENDER, NRF_OVERFLOW_ERROR, NRF_OVERFLOW_DEFERRED, NRF_OVERFLOW_IGNORE = 0, 1, 2, 3, 4
 NRF_ERR_NONFINITE = 5
+NRF_NORMALS_DENSITY, NRF_NORMALS_PREDICTED = 1, 2          # nrf_render_normals.bits
 
 
 class HashDesc(C.Structure):
@@ -54,6 +55,10 @@ class RenderOutputs(C.Structure):
                                           "d_z_coarse", "d_raw_coarse", "d_weights_coarse", "d_z_fine")]
 
 
+class RenderNormals(C.Structure):          # nrf_render_normals: beside RenderParams / RenderOutputs in the *_normals entries
+    _fields_ = [("bits", C.c_int), ("d_normals", C.c_void_p), ("d_pred_normals", C.c_void_p)]
+
+
 class LerfRendererDesc(C.Structure):
     _fields_ = [("lang_embed", C.c_void_p), ("lerf", C.c_void_p)]
 
@@ -82,8 +87,10 @@ SYMBOLS = [
     "nrf_raw2outputs", "nrf_raw2weights", "nrf_raw2weights_gather", "nrf_render_clip_embedding", "nrf_sample_pdf", "nrf_fine_depths", "nrf_fine_depths_merge",
     "nrf_rng_fill", "nrf_jitter_z", "nrf_tangent_scatter", "nrf_precondition", "nrf_raw2outputs_noise", "nrf_sample_pdf_rand", "nrf_fine_depths_rand",
     "nrf_renderer_create", "nrf_renderer_destroy", "nrf_run_network_workspace_bytes", "nrf_run_network",
-    "nrf_density_grid_workspace_bytes", "nrf_density_grid", "nrf_isosurface_workspace_bytes", "nrf_isosurface_count", "nrf_isosurface_emit",
+    "nrf_density_grid_workspace_bytes", "nrf_density_grid", "nrf_density_grad_workspace_bytes", "nrf_density_grad", "nrf_isosurface_workspace_bytes", "nrf_isosurface_count", "nrf_isosurface_emit",
     "nrf_render_rays_workspace_bytes", "nrf_render_rays", "nrf_batchify_rays_workspace_bytes", "nrf_batchify_rays", "nrf_render_rows_workspace_bytes", "nrf_render_rows",
+    "nrf_render_rays_normals_workspace_bytes", "nrf_render_rays_normals", "nrf_batchify_rays_normals_workspace_bytes", "nrf_batchify_rays_normals",
+    "nrf_render_rows_normals_workspace_bytes", "nrf_render_rows_normals",
     "nrf_normalize_depth", "nrf_to_u8",
     "nrf_huber_loss", "nrf_raw2outputs_backward", "nrf_raw2outputs_backward_noise", "nrf_mask_sigma_grad", "nrf_mlp_backward_workspace_bytes", "nrf_mlp_backward", "nrf_mlp_backward_f16_workspace_bytes", "nrf_mlp_backward_f16", "nrf_mlp_backward_f16_lm", "nrf_mlp_backward_f16_flags", "nrf_hash_encode_lm_f16", "nrf_hash_encode_lm_f16_strided", "nrf_lerf_sigma_lm", "nrf_lerf_sigma_lm_strided", "nrf_lerf_render_embedding_lm", "nrf_lerf_render_embedding_lm_gather", "nrf_lerf_geo_bytes", "nrf_lerf_sigma_geo_lm_strided", "nrf_lerf_sigma_exact_available", "nrf_lerf_sigma_exact_lm_strided", "nrf_lerf_render_embedding_lm_geo", "nrf_hash_backward_packed_workspace_bytes", "nrf_hash_backward_rays_packed", "nrf_hash_backward_binned_workspace_bytes", "nrf_hash_backward_binned_workspace_bytes_for", "nrf_hash_backward_rays_binned", "nrf_mlp_set_params", "nrf_mlp_device_repack_images", "nrf_mlp_set_input_rms_hint", "nrf_mlp_set_split_scaling", "nrf_mlp_get_split_scales", "nrf_renderer_nonfinite", "nrf_hash_memory_bytes", "nrf_lerf_renderer_nonfinite",
     "nrf_hash_backward", "nrf_hash_backward_rays", "nrf_hash_tv_loss", "nrf_adam_step", "nrf_adam_step_guarded", "nrf_renderer_last_features", "nrf_mlp_backward_f16_lm_src", "nrf_mask_sigma_grad_src", "nrf_mlp_backward_f16_flags_async", "nrf_mlp_backward_f16_flags_device",
@@ -125,10 +132,14 @@ def lib():
         L.nrf_scratch_trim.restype = C.c_size_t
         L.nrf_run_network_workspace_bytes.restype = C.c_size_t
         L.nrf_density_grid_workspace_bytes.restype = C.c_size_t
+        L.nrf_density_grad_workspace_bytes.restype = C.c_size_t
         L.nrf_isosurface_workspace_bytes.restype = C.c_size_t
         L.nrf_render_rays_workspace_bytes.restype = C.c_size_t
         L.nrf_batchify_rays_workspace_bytes.restype = C.c_size_t
         L.nrf_render_rows_workspace_bytes.restype = C.c_size_t
+        L.nrf_render_rays_normals_workspace_bytes.restype = C.c_size_t
+        L.nrf_batchify_rays_normals_workspace_bytes.restype = C.c_size_t
+        L.nrf_render_rows_normals_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_render_rays_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_batchify_rays_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_render_rows_workspace_bytes.restype = C.c_size_t

@@ -24,6 +24,13 @@ hipError_t scratch_give(void *p, hipStream_t st);
 // renderer has them (1 <= p <= 2^30)
 size_t renderer_density_ws_bytes(const nrf_renderer *r, int64_t p);
 int renderer_density(const nrf_renderer *r, const float *pts, int64_t p, float *sigma, void *ws, size_t ws_bytes, hipStream_t st);
+struct PointSource;
+// normals.hip: sigma and d sigma / d x of a hash grid + NeRFSmall (sigma == raw[..., 3] of NRF_PREC_F32 bit for bit); points whose wsel is 0 are skipped (nothing
+// written).  NULL from density_grad_unsupported: the pair is in the built family, else the reason it is not
+const char *density_grad_unsupported(const nrf_hash *h, const nrf_mlp *m);
+int density_grad_launch(const nrf_hash *h, const nrf_mlp *m, const PointSource &ps, int64_t p, const float *wsel, float *sigma, float *grad, hipStream_t st);
+//   out[ray] = sum_j w[ray][j] * sign * safe_normalize(v[row][v_col .. v_col + 2]), row = src ? src[ray * s + j] : ray * s + j, ascending j, w == 0 skipped
+int normals_composite(int64_t n, int s, const float *v, int v_stride, int v_col, const int32_t *src, float sign, const float *weights, float *out, hipStream_t st);
 
 #define NRF_CHECK_ARG(cond, ...)                                   \
     do {                                                           \

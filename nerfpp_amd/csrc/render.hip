@@ -303,6 +303,31 @@ static int run_network(const nrf_renderer *r, const PointSource &ps, const float
     return NRF_OK;
 }
 
+// A render call as the library runs it: the caller's nrf_render_params / nrf_render_outputs and, beside them, the normals request of the *_normals entries
+// (nrf_render_normals).  The public structs keep the layout callers were compiled against: an entry never reads past what such a caller handed it.
+struct RenderParamsX : nrf_render_params {
+    int normals;              // NRF_NORMALS_* bits (0: the plain entries)
+};
+struct RenderOutputsX : nrf_render_outputs {
+    float *d_normals, *d_pred_normals;
+};
+static RenderParamsX params_x(const nrf_render_params *p, const nrf_render_normals *nm)
+{
+    RenderParamsX x{};
+    static_cast<nrf_render_params &>(x) = *p;
+    x.normals = nm ? nm->bits : 0;
+    return x;
+}
+static RenderOutputsX outputs_x(const nrf_render_outputs *o, const nrf_render_normals *nm)
+{
+    RenderOutputsX x{};
+    static_cast<nrf_render_outputs &>(x) = *o;
+    x.d_normals = nm ? nm->d_normals : nullptr;
+    x.d_pred_normals = nm ? nm->d_pred_normals : nullptr;
+    return x;
+}
+static size_t rays_ws_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p, int normals);
+
 }  // namespace nrf
 
 using namespace nrf;
@@ -397,7 +422,12 @@ int nrf_run_network(const nrf_renderer *r, const float *d_pts, const float *d_vi
     return run_network(r, ps, d_viewdirs, 3, n, s, precision, d_raw, d_workspace, workspace_bytes, as_stream(stream));   // generic boundary: row-major path
 }
 
-size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p)
+size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p) { return rays_ws_bytes(r, n, p, 0); }
+size_t nrf_render_rays_normals_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p, int bits) { return rays_ws_bytes(r, n, p, bits); }
+
+}  // extern "C"
+
+size_t nrf::rays_ws_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p, int normals)
 {
     if (!r || !p) return 0;
     const int s = p->n_samples, sf = p->n_samples + p->n_importance;
@@ -419,12 +449,35 @@ size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const n
     b += align_up((size_t)n * s * 64, 256) + align_up((size_t)n * sf * 16, 256);                 // geo hand-over: operand fragments of the coarse columns, outputs by column
     if (p->perturb > 0.0f) b += align_up((size_t)n * s * 4, 256);                             // un-jittered depths
     if (p->has_cone || p->precond_alpha > 0.0f) b += align_up((size_t)n * sf * 12, 256);     // explicit sample points
+    const int so = p->n_importance > 0 ? sf : s;
+    if (normals) b += align_up((size_t)n * so * 4, 256);                                        // normals: the final weights when the caller does not keep them
+    if (normals & NRF_NORMALS_DENSITY) b += align_up((size_t)n * so * 12, 256);                 // ... and the density gradients of the final samples
     return b;
 }
 
-}  // extern "C"
-
 namespace nrf {
+
+// the normals request against the renderer and the outputs, before any launch
+static int normals_check(const nrf_renderer *r, const RenderParamsX *p, const RenderOutputsX *out, const char *who)
+{
+    if (!p->normals) return NRF_OK;
+    NRF_CHECK_ARG((p->normals & ~(NRF_NORMALS_DENSITY | NRF_NORMALS_PREDICTED)) == 0, "%s: normals %d sets bits beyond NRF_NORMALS_DENSITY | NRF_NORMALS_PREDICTED", who,
+                  p->normals);
+    if (p->normals & NRF_NORMALS_DENSITY) {
+        NRF_CHECK_ARG(out->d_normals, "%s: NRF_NORMALS_DENSITY with a NULL d_normals", who);
+        if (const char *why = density_grad_unsupported(r->desc.hash, r->desc.mlp)) { set_error("%s: %s", who, why); return NRF_ERR_UNSUPPORTED; }
+    }
+    if (p->normals & NRF_NORMALS_PREDICTED) {
+        NRF_CHECK_ARG(out->d_pred_normals, "%s: NRF_NORMALS_PREDICTED with a NULL d_pred_normals", who);
+        const nrf_mlp *m = r->desc.mlp;
+        if (!m || m->family != MLP_SMALL || !m->small.use_pred_normal) {
+            set_error("%s: NRF_NORMALS_PREDICTED needs a NeRFSmall with the predicted-normals head (use_pred_normal)", who);
+            return NRF_ERR_UNSUPPORTED;
+        }
+        NRF_CHECK_ARG(p->precision == NRF_PREC_F32, "%s: predicted normals are rendered in NRF_PREC_F32 only (the head has no matrix-core image)", who);
+    }
+    return NRF_OK;
+}
 
 static int flag_buffers(const nrf_renderer *r)
 {
@@ -461,8 +514,8 @@ static int take_deferred(const nrf_renderer *r, bool wait, const char *who, int 
 static inline int policy_of(const nrf_render_params *p) { return p->overflow_policy == NRF_OVERFLOW_AUTO ? NRF_OVERFLOW_RERENDER : p->overflow_policy; }
 static inline bool detects(const nrf_render_params *p) { return p->precision != NRF_PREC_F32 && policy_of(p) != NRF_OVERFLOW_IGNORE; }
 
-static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const nrf_render_params *p,
-                            const float *d_t, const float *d_u, const nrf_render_outputs *out, void *d_workspace, size_t workspace_bytes, void *stream, uint32_t *d_flag);
+static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const RenderParamsX *p,
+                            const float *d_t, const float *d_u, const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, void *stream, uint32_t *d_flag);
 
 // After `slots` chunk words were written on `st`: what the policy says.  chunk_of(i, &first, &count) names the rays of chunk i.
 template <class ChunkOf, class Rerender>
@@ -495,12 +548,12 @@ static int settle_flags(const nrf_renderer *r, const nrf_render_params *p, int s
 }
 
 // one chunk again in NRF_PREC_F32 into the same outputs (workspace: the caller's when it is large enough, else stream-ordered scratch)
-static int rerender_f32(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const nrf_render_params *p, const float *d_t, const float *d_u,
-                        const nrf_render_outputs *out, void *d_workspace, size_t workspace_bytes, hipStream_t st)
+static int rerender_f32(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const RenderParamsX *p, const float *d_t, const float *d_u,
+                        const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, hipStream_t st)
 {
-    nrf_render_params q = *p;
+    RenderParamsX q = *p;
     q.precision = NRF_PREC_F32;
-    const size_t need = nrf_render_rays_workspace_bytes(r, n, &q);
+    const size_t need = rays_ws_bytes(r, n, &q, q.normals);
     void *ws = d_workspace; size_t wsb = workspace_bytes; void *tmp = nullptr;
     if (need > workspace_bytes) { NRF_HIP(scratch_take(&tmp, need, st)); ws = tmp; wsb = need; }
     const int rc = render_rays_impl(r, d_rays, ray_stride, n, &q, d_t, d_u, out, ws, wsb, st, nullptr);
@@ -522,10 +575,12 @@ int nrf_renderer_nonfinite(const nrf_renderer *r, int64_t *flagged_chunks, int64
     return rc == NRF_ERR_NONFINITE ? NRF_OK : rc;          // the counters ARE the report here
 }
 
-int nrf_render_rays(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const nrf_render_params *p,
-                    const float *d_t, const float *d_u, const nrf_render_outputs *out, void *d_workspace, size_t workspace_bytes, void *stream)
+}  // extern "C"
+
+static int render_rays_entry(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const RenderParamsX *p, const float *d_t, const float *d_u,
+                             const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    NRF_CHECK_ARG(r && p && out, "nrf_render_rays: null pointer");
+    NRF_TRY(normals_check(r, p, out, "nrf_render_rays"));
     NRF_CHECK_ARG(p->overflow_policy >= NRF_OVERFLOW_AUTO && p->overflow_policy <= NRF_OVERFLOW_IGNORE, "nrf_render_rays: overflow_policy %d is not an NRF_OVERFLOW_* value", p->overflow_policy);
     if (n == 0 || !detects(p)) return render_rays_impl(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, stream, nullptr);
     hipStream_t st = as_stream(stream);
@@ -536,12 +591,32 @@ int nrf_render_rays(const nrf_renderer *r, const float *d_rays, int ray_stride, 
     return settle_flags(r, p, 1, st, "nrf_render_rays", [](int) {}, [&](int) { return rerender_f32(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, st); });
 }
 
+extern "C" {
+
+int nrf_render_rays(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const nrf_render_params *p,
+                    const float *d_t, const float *d_u, const nrf_render_outputs *out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(r && p && out, "nrf_render_rays: null pointer");
+    const RenderParamsX px = params_x(p, nullptr);
+    const RenderOutputsX ox = outputs_x(out, nullptr);
+    return render_rays_entry(r, d_rays, ray_stride, n, &px, d_t, d_u, &ox, d_workspace, workspace_bytes, stream);
+}
+
+int nrf_render_rays_normals(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const nrf_render_params *p, const float *d_t, const float *d_u,
+                            const nrf_render_outputs *out, const nrf_render_normals *normals, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(r && p && out && normals, "nrf_render_rays_normals: null pointer");
+    const RenderParamsX px = params_x(p, normals);
+    const RenderOutputsX ox = outputs_x(out, normals);
+    return render_rays_entry(r, d_rays, ray_stride, n, &px, d_t, d_u, &ox, d_workspace, workspace_bytes, stream);
+}
+
 }  // extern "C"
 
 namespace nrf {
 
-static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const nrf_render_params *p,
-                            const float *d_t, const float *d_u, const nrf_render_outputs *out, void *d_workspace, size_t workspace_bytes, void *stream, uint32_t *d_flag)
+static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const RenderParamsX *p,
+                            const float *d_t, const float *d_u, const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, void *stream, uint32_t *d_flag)
 {
     r->last_view.valid = false;          // (set again below by the feature-reusing fast path)
     r->chunk_serial++;
@@ -556,8 +631,8 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
     NRF_CHECK_ARG(p->precond_alpha == 0.0f || p->has_bbox, "nrf_render_rays: stochastic preconditioning reflects at the bounding box (NeRFRenderer.h:436-442): bbox required");
     NRF_CHECK_ARG(p->perturb == 0.0f || p->n_samples >= 2, "nrf_render_rays: Perturb > 0 needs n_samples >= 2");
     NRF_CHECK_ARG(p->coarse_mode >= NRF_COARSE_AUTO && p->coarse_mode <= NRF_COARSE_SIGMA_F32, "nrf_render_rays: coarse_mode %d is not an NRF_COARSE_* value", p->coarse_mode);
-    if (workspace_bytes < nrf_render_rays_workspace_bytes(r, n, p)) {
-        set_error("nrf_render_rays: workspace %zu < %zu bytes", workspace_bytes, nrf_render_rays_workspace_bytes(r, n, p));
+    if (workspace_bytes < rays_ws_bytes(r, n, p, p->normals)) {
+        set_error("nrf_render_rays: workspace %zu < %zu bytes", workspace_bytes, rays_ws_bytes(r, n, p, p->normals));
         return NRF_ERR_WORKSPACE;
     }
     hipStream_t st = as_stream(stream);
@@ -604,6 +679,9 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
     float *raw_cols = ni > 0 ? bump.take<float>((size_t)n * sf * 4) : nullptr;
     float *z_plain = p->perturb > 0.0f ? bump.take<float>((size_t)n * s) : nullptr;
     float *bump_pts = (p->has_cone || p->precond_alpha > 0.0f) ? bump.take<float>((size_t)n * sf * 3) : nullptr;
+    const int so = ni > 0 ? sf : s;
+    float *nrm_w = (p->normals && !out->d_weights) ? bump.take<float>((size_t)n * so) : nullptr;
+    float *nrm_g = (p->normals & NRF_NORMALS_DENSITY) ? bump.take<float>((size_t)n * so * 3) : nullptr;
     void *nws = bump.take<char>(0);
     const size_t nws_bytes = workspace_bytes - bump.off;
     const float *viewdirs = r->in_views > 0 ? d_rays + 8 : nullptr;
@@ -625,6 +703,16 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
     StochPoints sp{};
     sp.cone = cone; sp.cone_angle = p->cone_angle; sp.clamp = cone && p->has_bbox; sp.alpha = p->precond_alpha;
     for (int a = 0; a < 3; a++) { sp.box.mn[a] = p->bbox[a]; sp.box.mx[a] = p->bbox[3 + a]; }
+    // normals of the final samples (the request of the *_normals entries, nrf_render_normals), after the compositing that wrote their weights: the density gradient at the points the network saw,
+    // and the predicted-normals columns of the F32 network's rows (the only precision the head has: raw holds every row in depth order)
+    auto normals_tail = [&](const PointSource &src, const float *wts, const float *raw_rows) -> int {
+        if (p->normals & NRF_NORMALS_DENSITY) {
+            NRF_TRY(density_grad_launch(r->desc.hash, r->desc.mlp, src, n * (int64_t)so, wts, nullptr, nrm_g, st));
+            NRF_TRY(normals_composite(n, so, nrm_g, 3, 0, nullptr, -1.0f, wts, out->d_normals, st));
+        }
+        if (p->normals & NRF_NORMALS_PREDICTED) NRF_TRY(normals_composite(n, so, raw_rows, c, 4, nullptr, 1.0f, wts, out->d_pred_normals, st));
+        return NRF_OK;
+    };
 
     // z_vals; pts = o + d*z formed inside the encoder                           (NeRFRenderer.h:393-419)
     if (jitter) {
@@ -671,8 +759,9 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
         // step with N_importance = 0 differentiated garbage; found by tools/scratch/train_fuzz.py)
         if (out->d_raw && raw_c != out->d_raw) NRF_HIP(hipMemcpyAsync(out->d_raw, raw_c, (size_t)n * s * c * sizeof(float), hipMemcpyDeviceToDevice, st));
         // the reference leaves result.Outputs UNDEFINED in this case (:423 vs :448); the coarse maps are what a caller wants
-        return launch_raw2outputs(raw_c, z_c, d_rays + 3, ray_stride, n, s, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
-                                  out->d_weights ? out->d_weights : w_c, out->d_depth, nz, st, fastc, nullptr, nullptr, 0, d_flag);
+        NRF_TRY(launch_raw2outputs(raw_c, z_c, d_rays + 3, ray_stride, n, s, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
+                                   out->d_weights ? out->d_weights : w_c, out->d_depth, nz, st, fastc, nullptr, nullptr, 0, d_flag));
+        return p->normals ? normals_tail(ps, out->d_weights ? out->d_weights : w_c, raw_c) : NRF_OK;
     }
     NRF_TRY(launch_raw2outputs(raw_c, z_c, d_rays + 3, ray_stride, n, s, sigma_only ? 1 : c, sigma_only ? 0 : 3, p->white_bkgr, nullptr, nullptr, nullptr, w_c, nullptr, nz,
                                st, false));   // :423  always the exact arithmetic: these weights choose the fine samples
@@ -716,8 +805,10 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
         } else NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats, rw.feats_lo, rw.cols, dirs16, dirs_lo, sf, rw.keep, n * (int64_t)sf, raw_f, st, rw.src));
     } else NRF_TRY(network(psf, sf, raw_f));                                                                       // :447
     nz.stream = NRF_RNG_NOISE_FINE;
-    return launch_raw2outputs(raw_final, z_f, d_rays + 3, ray_stride, n, sf, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
-                              out->d_weights, out->d_depth, nz, st, fastc, src_final, raw2_final, split_final, d_flag);     // :448
+    float *w_final = out->d_weights ? out->d_weights : nrm_w;
+    NRF_TRY(launch_raw2outputs(raw_final, z_f, d_rays + 3, ray_stride, n, sf, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
+                               w_final, out->d_depth, nz, st, fastc, src_final, raw2_final, split_final, d_flag));     // :448
+    return p->normals ? normals_tail(psf, w_final, raw_f) : NRF_OK;
 }
 
 }  // namespace nrf
@@ -726,9 +817,9 @@ extern "C" {
 
 
 // ---- BatchifyRays (NeRFRenderer.h:465-525) and the pose branch of Render (:530-605) as single calls ----
-static nrf_render_outputs slice_outputs(const nrf_render_outputs &o, int64_t i, int s, int so, int sf, int c)
+static RenderOutputsX slice_outputs(const RenderOutputsX &o, int64_t i, int s, int so, int sf, int c)
 {
-    nrf_render_outputs q = o;
+    RenderOutputsX q = o;
     if (q.d_rgb) q.d_rgb += i * 3;
     if (q.d_disp) q.d_disp += i;
     if (q.d_acc) q.d_acc += i;
@@ -739,6 +830,8 @@ static nrf_render_outputs slice_outputs(const nrf_render_outputs &o, int64_t i, 
     if (q.d_raw_coarse) q.d_raw_coarse += i * s * c;
     if (q.d_weights_coarse) q.d_weights_coarse += i * s;
     if (q.d_z_fine) q.d_z_fine += i * sf;
+    if (q.d_normals) q.d_normals += i * 3;
+    if (q.d_pred_normals) q.d_pred_normals += i * 3;
     return q;
 }
 
@@ -785,13 +878,18 @@ int nrf_renderer_set_lanes(nrf_renderer *r, int lanes)
     return NRF_OK;
 }
 
-size_t nrf_batchify_rays_workspace_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p)
+static size_t batchify_ws_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p, int normals)
 {
     if (!r || !p || chunk <= 0) return 0;
     const int lanes = lanes_for(r);
     const int64_t lc = lane_chunk(n, chunk, lanes);
-    if (lc > 0 && lc < n) return (size_t)lanes * align_up(nrf_render_rays_workspace_bytes(r, lc, p), 256);
-    return nrf_render_rays_workspace_bytes(r, n < chunk ? n : (int64_t)chunk, p);
+    if (lc > 0 && lc < n) return (size_t)lanes * align_up(rays_ws_bytes(r, lc, p, normals), 256);
+    return rays_ws_bytes(r, n < chunk ? n : (int64_t)chunk, p, normals);
+}
+size_t nrf_batchify_rays_workspace_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p) { return batchify_ws_bytes(r, n, chunk, p, 0); }
+size_t nrf_batchify_rays_normals_workspace_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p, int bits)
+{
+    return batchify_ws_bytes(r, n, chunk, p, bits);
 }
 
 int nrf_get_render_lanes(void) { return render_lanes(); }
@@ -835,15 +933,15 @@ static int lanes_of(const nrf_renderer *r, int lanes, hipStream_t *st, hipEvent_
     return NRF_OK;
 }
 
-int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const float *d_t,
-                      const float *d_u, const nrf_render_outputs *out, void *d_workspace, size_t workspace_bytes, void *stream)
+static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const RenderParamsX *p, const float *d_t,
+                         const float *d_u, const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    NRF_CHECK_ARG(r && p && out, "nrf_batchify_rays: null pointer");
+    NRF_TRY(normals_check(r, p, out, "nrf_batchify_rays"));
     NRF_CHECK_ARG(chunk > 0 && n >= 0, "nrf_batchify_rays: Chunk must be positive");
     NRF_CHECK_ARG(p->overflow_policy >= NRF_OVERFLOW_AUTO && p->overflow_policy <= NRF_OVERFLOW_IGNORE, "nrf_batchify_rays: overflow_policy %d is not an NRF_OVERFLOW_* value", p->overflow_policy);
     const int s = p->n_samples, sf = p->n_samples + p->n_importance, so = p->n_importance > 0 ? sf : s;
     const int c = r->desc.mlp->out_dims;
-    nrf_render_params q = *p;
+    RenderParamsX q = *p;
     // before any lane forks, on the caller's stream: the split image's range scales for the table as it is now, and the chunk words of this call cleared
     if (p->precision == NRF_PREC_F16_SPLIT) NRF_TRY(ensure_scales(r, as_stream(stream)));
     const bool det = n > 0 && detects(p);
@@ -861,9 +959,9 @@ int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ray_stride
         const int slots = (int)(done_chunks.size() < (size_t)NRF_FLAG_SLOTS ? done_chunks.size() : (size_t)NRF_FLAG_SLOTS);
         return settle_flags(r, p, slots, as_stream(stream), "nrf_batchify_rays", [](int) {}, [&](int slot) -> int {
             for (size_t j = (size_t)slot; j < done_chunks.size(); j += NRF_FLAG_SLOTS) {
-                nrf_render_params q2 = *p;
+                RenderParamsX q2 = *p;
                 q2.ray_base = p->ray_base + done_chunks[j].first;
-                const nrf_render_outputs o2 = slice_outputs(*out, done_chunks[j].first, s, so, sf, c);
+                const RenderOutputsX o2 = slice_outputs(*out, done_chunks[j].first, s, so, sf, c);
                 NRF_TRY(rerender_f32(r, d_rays + done_chunks[j].first * ray_stride, ray_stride, done_chunks[j].count, &q2, d_t, d_u, &o2, d_workspace, workspace_bytes, as_stream(stream)));
             }
             return NRF_OK;
@@ -871,7 +969,7 @@ int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ray_stride
     };
     const int L = lanes_for(r);
     const int64_t lc = lane_chunk(n, chunk, L);
-    const size_t part = lc > 0 && lc < n ? align_up(nrf_render_rays_workspace_bytes(r, lc, p), 256) : 0;
+    const size_t part = lc > 0 && lc < n ? align_up(rays_ws_bytes(r, lc, p, p->normals), 256) : 0;
     if (part > 0 && (size_t)L * part <= workspace_bytes && d_workspace) {
         // fork from the caller's stream, each chunk on the least-loaded lane in that lane's slice of the workspace, join
         hipStream_t st = as_stream(stream), lane[NRF_MAX_LANES];
@@ -909,7 +1007,7 @@ int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ray_stride
             if (m < 1) m = rem < lc ? rem : lc;                                 // Chunk < 8 on the lane path: lc / 8 == 0 must not leave an empty chunk (the loop would never advance)
             if (m > rem) m = rem;
             q.ray_base = p->ray_base + i;
-            const nrf_render_outputs o = slice_outputs(*out, i, s, so, sf, c);
+            const RenderOutputsX o = slice_outputs(*out, i, s, so, sf, c);
             rc = render_rays_impl(r, d_rays + i * ray_stride, ray_stride, m, &q, d_t, d_u, &o, static_cast<char *>(d_workspace) + (size_t)k * part, part, lane[k], flag_of(done_chunks.size()));
             done_chunks.push_back({i, m});
             given[k] += m;
@@ -928,12 +1026,31 @@ int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ray_stride
     for (int64_t i = 0; i < n; i += chunk) {                                                                      // :476
         const int64_t m = n - i < chunk ? n - i : (int64_t)chunk;
         q.ray_base = p->ray_base + i;
-        const nrf_render_outputs o = slice_outputs(*out, i, s, so, sf, c);
+        const RenderOutputsX o = slice_outputs(*out, i, s, so, sf, c);
         NRF_TRY(render_rays_impl(r, d_rays + i * ray_stride, ray_stride, m, &q, d_t, d_u, &o, d_workspace, workspace_bytes, stream, flag_of(done_chunks.size())));
         done_chunks.push_back({i, m});
     }
     if (done_chunks.size() != 1) r->last_view.valid = false;
     return settle();
+}
+
+int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const float *d_t,
+                      const float *d_u, const nrf_render_outputs *out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(r && p && out, "nrf_batchify_rays: null pointer");
+    const RenderParamsX px = params_x(p, nullptr);
+    const RenderOutputsX ox = outputs_x(out, nullptr);
+    return batchify_impl(r, d_rays, ray_stride, n, chunk, &px, d_t, d_u, &ox, d_workspace, workspace_bytes, stream);
+}
+
+int nrf_batchify_rays_normals(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const float *d_t,
+                              const float *d_u, const nrf_render_outputs *out, const nrf_render_normals *normals, void *d_workspace, size_t workspace_bytes,
+                              void *stream)
+{
+    NRF_CHECK_ARG(r && p && out && normals, "nrf_batchify_rays_normals: null pointer");
+    const RenderParamsX px = params_x(p, normals);
+    const RenderOutputsX ox = outputs_x(out, normals);
+    return batchify_impl(r, d_rays, ray_stride, n, chunk, &px, d_t, d_u, &ox, d_workspace, workspace_bytes, stream);
 }
 
 // The hash features the most recent render left in its workspace (a single-chunk render of the feature-reusing fast path, CuHashEmbedder grid): level-major fp16
@@ -951,17 +1068,19 @@ extern "C" NRF_API int nrf_renderer_last_features(const nrf_renderer *r, const v
 
 extern "C" int nrf_view_check(const nrf_view *v, const char *who);
 
-size_t nrf_render_rows_workspace_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p)
+static size_t rows_ws_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, int normals)
 {
     if (!r || !v || !p || v->chunk <= 0 || v->rows < 0 || v->w <= 0) return 0;
     const int64_t n = (int64_t)v->rows * v->w;
-    return align_up((size_t)n * (v->use_viewdirs ? 11 : 8) * sizeof(float), 256) + 256 + nrf_batchify_rays_workspace_bytes(r, n, v->chunk, p);
+    return align_up((size_t)n * (v->use_viewdirs ? 11 : 8) * sizeof(float), 256) + 256 + batchify_ws_bytes(r, n, v->chunk, p, normals);
 }
+size_t nrf_render_rows_workspace_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p) { return rows_ws_bytes(r, v, p, 0); }
+size_t nrf_render_rows_normals_workspace_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, int bits) { return rows_ws_bytes(r, v, p, bits); }
 
-int nrf_render_rows(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, const float *d_t, const float *d_u, const nrf_render_outputs *out,
-                    float *d_rays_out, float *d_near_far, void *d_workspace, size_t workspace_bytes, void *stream)
+static int render_rows_impl(const nrf_renderer *r, const nrf_view *v, const RenderParamsX *p, const float *d_t, const float *d_u, const RenderOutputsX *out,
+                            float *d_rays_out, float *d_near_far, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    NRF_CHECK_ARG(r && p && out, "nrf_render_rows: null pointer");
+    NRF_TRY(normals_check(r, p, out, "nrf_render_rows"));
     NRF_TRY(nrf_view_check(v, "nrf_render_rows"));
     // Ndc with cone rays (ThinRay = false): NDCRays multiplies cone_angle by |d_ndc| / |rays_d| AFTER rays_d has been replaced by d_ndc (RayUtils.h:73-81) -- the
     // quotient of a finite non-zero number by itself, exactly 1.0 -- so every ray keeps the camera's cone_angle bit for bit, as a [.., 1] tensor there, as the scalar
@@ -969,17 +1088,35 @@ int nrf_render_rows(const nrf_renderer *r, const nrf_view *v, const nrf_render_p
     const int64_t n = (int64_t)v->rows * v->w;
     if (n == 0) return nrf_view_rays(v, nullptr, d_near_far, stream);        // an empty tile: only Near / Far (= +inf / -inf) are defined
     const int stride = v->use_viewdirs ? 11 : 8;
-    if (workspace_bytes < nrf_render_rows_workspace_bytes(r, v, p)) {
-        set_error("nrf_render_rows: workspace %zu < %zu bytes", workspace_bytes, nrf_render_rows_workspace_bytes(r, v, p));
+    if (workspace_bytes < rows_ws_bytes(r, v, p, p->normals)) {
+        set_error("nrf_render_rows: workspace %zu < %zu bytes", workspace_bytes, rows_ws_bytes(r, v, p, p->normals));
         return NRF_ERR_WORKSPACE;
     }
     Bump bump(d_workspace, workspace_bytes);
     float *rays = d_rays_out ? d_rays_out : bump.take<float>((size_t)n * stride);
     void *ws = bump.take<char>(0);
     NRF_TRY(nrf_view_rays(v, rays, d_near_far, stream));                                                          // :541-583, :602-603
-    nrf_render_params q = *p;
+    RenderParamsX q = *p;
     q.ray_base = p->ray_base + (int64_t)v->row0 * v->w;
-    return nrf_batchify_rays(r, rays, stride, n, v->chunk, &q, d_t, d_u, out, ws, workspace_bytes - bump.off, stream);   // :586-590
+    return batchify_impl(r, rays, stride, n, v->chunk, &q, d_t, d_u, out, ws, workspace_bytes - bump.off, stream);   // :586-590
+}
+
+int nrf_render_rows(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, const float *d_t, const float *d_u, const nrf_render_outputs *out,
+                    float *d_rays_out, float *d_near_far, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(r && p && out, "nrf_render_rows: null pointer");
+    const RenderParamsX px = params_x(p, nullptr);
+    const RenderOutputsX ox = outputs_x(out, nullptr);
+    return render_rows_impl(r, v, &px, d_t, d_u, &ox, d_rays_out, d_near_far, d_workspace, workspace_bytes, stream);
+}
+
+int nrf_render_rows_normals(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, const float *d_t, const float *d_u, const nrf_render_outputs *out,
+                            const nrf_render_normals *normals, float *d_rays_out, float *d_near_far, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(r && p && out && normals, "nrf_render_rows_normals: null pointer");
+    const RenderParamsX px = params_x(p, normals);
+    const RenderOutputsX ox = outputs_x(out, normals);
+    return render_rows_impl(r, v, &px, d_t, d_u, &ox, d_rays_out, d_near_far, d_workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
@@ -1038,3 +1175,26 @@ int renderer_density(const nrf_renderer *r, const float *pts, int64_t p, float *
 }
 
 }  // namespace nrf
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------------
+// density gradient at explicit points (normals.hip)
+// ---------------------------------------------------------------------------------------------------
+size_t nrf_density_grad_workspace_bytes(const nrf_renderer *r, int64_t p)
+{
+    (void)r; (void)p;
+    return 0;
+}
+
+int nrf_density_grad(const nrf_renderer *r, const float *d_pts, int64_t p, float *d_sigma, float *d_grad, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    (void)d_workspace; (void)workspace_bytes;
+    NRF_CHECK_ARG(r, "nrf_density_grad: null renderer");
+    NRF_CHECK_ARG(p >= 0, "nrf_density_grad: negative point count %lld", (long long)p);
+    NRF_CHECK_ARG(p == 0 || (d_pts && d_grad), "nrf_density_grad: null points or gradient");
+    if (const char *why = density_grad_unsupported(r->desc.hash, r->desc.mlp)) { set_error("nrf_density_grad: %s", why); return NRF_ERR_UNSUPPORTED; }
+    return density_grad_launch(r->desc.hash, r->desc.mlp, PointSource{d_pts, nullptr, nullptr, 0, 1}, p, nullptr, d_sigma, d_grad, as_stream(stream));
+}
+
+}  // extern "C"

@@ -76,12 +76,38 @@ def Isosurface(sigma, bbox, threshold):
     return verts, faces, normals
 
 
-def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, precision=L.NRF_PREC_F32):
-    """DensityGrid -> Isosurface -> per-vertex colour: sigmoid of RunNetwork's rgb at the vertex seen along -normal (a ray hitting the surface head-on), in chunks."""
+def DensityGradient(renderer, pts):
+    """nrf_density_grad: (sigma [...], grad [..., 3]) at pts [..., 3].  sigma == RunNetwork(pts, ..., NRF_PREC_F32)[..., 3] bit for bit; grad = d sigma / d x,
+    the analytic gradient of the hash grid + NeRFSmall sigma net (0 where sigma is masked to 0).  Hash-grid renderers only."""
+    if not hasattr(renderer, "EmbedFn") or not isinstance(renderer.EmbedFn, _HashBase) or not hasattr(renderer, "NeRF"):
+        raise L.NrfError(f"unsupported: DensityGradient is built for hash-grid renderers with NeRFSmall, not {type(renderer).__name__} on "
+                         f"{type(getattr(renderer, 'EmbedFn', None)).__name__}")
+    x = _dev_f32(pts)
+    if x.shape[-1] != 3:
+        raise L.NrfError(f"DensityGradient: pts must be [..., 3], got {tuple(x.shape)}")
+    lead = tuple(x.shape[:-1])
+    x = x.reshape(-1, 3).contiguous()
+    sigma = torch.empty(lead, device=x.device, dtype=torch.float32)
+    grad = torch.empty(lead + (3,), device=x.device, dtype=torch.float32)
+    L.check(L.lib().nrf_density_grad(renderer._r, _ptr(x), C.c_int64(x.shape[0]), _ptr(sigma), _ptr(grad), None, C.c_size_t(0), _stream()))
+    return sigma, grad
+
+
+def _safe_normalize(v, eps=1e-8):
+    return v / torch.linalg.vector_norm(v, dim=-1, keepdim=True).clamp_min(eps)
+
+
+def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, precision=L.NRF_PREC_F32, normals="lattice"):
+    """DensityGrid -> Isosurface -> per-vertex colour: sigmoid of RunNetwork's rgb at the vertex seen along -normal (a ray hitting the surface head-on), in chunks.
+    normals="lattice": the isosurface's central-difference normals; "field": -safe_normalize(DensityGradient(vertices)), the field's own analytic normal
+    (also the colour's view direction)."""
+    if normals not in ("lattice", "field"):
+        raise L.NrfError(f"ExtractMesh: normals must be 'lattice' or 'field', got {normals!r}")
     bb = _bbox(renderer, bbox)
     sigma = DensityGrid(renderer, bb, resolution)
-    verts, faces, normals = Isosurface(sigma, bb, threshold)
+    verts, faces, lattice_normals = Isosurface(sigma, bb, threshold)
     del sigma
+    normals = lattice_normals if normals == "lattice" else -_safe_normalize(DensityGradient(renderer, verts)[1])
     rgb = None
     if colors:
         rgb = torch.empty_like(verts)

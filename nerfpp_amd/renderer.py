@@ -125,6 +125,9 @@ class NeRFRendererOutputs:            # NeRFRenderer.h:12-18
     AccMap: Optional[torch.Tensor] = None
     Weights: Optional[torch.Tensor] = None
     DepthMap: Optional[torch.Tensor] = None
+    # NeRFRenderParams.CalculateNormals / UsePredNormal (the names RenderPath's commented writes use, NeRFExecutor.h): shaped like RGBMap
+    RenderedNormals: Optional[torch.Tensor] = None
+    RenderedPredNormals: Optional[torch.Tensor] = None
 
 
 class NeRFRenderResult:               # NeRFRenderer.h:20-26
@@ -178,6 +181,11 @@ class NeRFRenderParams:               # NeRFRenderer.h:28-44 (same defaults)
     OverflowPolicy: int = L.NRF_OVERFLOW_AUTO
     # not in the reference (it draws from torch's global RNG): seed of the counter-based draws of the stochastic branches
     Seed: int = 0
+    # NeRFExecutorParams.calculate_normals / use_pred_normal (declared there, never wired): Outputs.RenderedNormals = sum_i w_i * (-safe_normalize(grad sigma)) over
+    # the final samples (hash grid + NeRFSmall renderers), Outputs.RenderedPredNormals = sum_i w_i * safe_normalize(raw[..., 4:7]) (the predicted-normals head,
+    # NRF_PREC_F32).  Both off: the render is what it was
+    CalculateNormals: bool = False
+    UsePredNormal: bool = False
 
 
 class NeRFRenderer:
@@ -306,6 +314,10 @@ class NeRFRenderer:
         rp.overflow_policy = int(overflow_policy)
         return rp
 
+    @staticmethod
+    def _normal_bits(p):
+        return (L.NRF_NORMALS_DENSITY if p.CalculateNormals else 0) | (L.NRF_NORMALS_PREDICTED if p.UsePredNormal else 0)
+
     def _alloc_outputs(self, n, s, ni, dev, return_raw, return_weights, keep_intermediates):
         """(result, nrf_render_outputs) with every buffer sized for n rays."""
         sf = s + ni
@@ -331,6 +343,21 @@ class NeRFRenderer:
                 ex["z_fine"] = torch.empty((n, sf), device=dev)
                 ro.d_z_fine = _ptr(ex["z_fine"])
         return res, ro
+
+    @staticmethod
+    def _normals_request(res, n, dev, bits):
+        """nrf_render_normals for the *_normals entries, its buffers allocated into res.Outputs (None when no normals are asked for)."""
+        if not bits:
+            return None
+        nm = L.RenderNormals(int(bits), None, None)
+        o = res.Outputs
+        if bits & L.NRF_NORMALS_DENSITY:
+            o.RenderedNormals = torch.empty((n, 3), device=dev)
+            nm.d_normals = _ptr(o.RenderedNormals)
+        if bits & L.NRF_NORMALS_PREDICTED:
+            o.RenderedPredNormals = torch.empty((n, 3), device=dev)
+            nm.d_pred_normals = _ptr(o.RenderedPredNormals)
+        return nm
 
     def RenderRays(self, ray_batch, cone_angle, n_samples, return_raw=False, lin_disp=False, perturb=0.0, n_importance=0, white_bkgr=False,
                    raw_noise_std=0.0, stochastic_preconditioning_alpha=0.0, bounding_box=None, return_weights=True,
@@ -403,12 +430,17 @@ class NeRFRenderer:
             rp = self._params(s, ni, cone_angle, p.LinDisp, p.Perturb, p.WhiteBkgr, p.RawNoiseStd, p.StochasticPreconditioningAlpha, p.BoundingBox, p.Precision,
                               p.Seed, 0, p.CoarseMode, p.OverflowPolicy)
             res, ro = self._alloc_outputs(n, s, ni, dev, p.ReturnRaw, p.ReturnWeights, p.KeepIntermediates)
+            nm = self._normals_request(res, n, dev, self._normal_bits(p))
             rays_ = torch.empty((n, stride), device=dev, dtype=torch.float32)
             nf = torch.empty((2,), device=dev, dtype=torch.float32)
-            nb = lib.nrf_render_rows_workspace_bytes(self._r, C.byref(v), C.byref(rp))
-            ws = self._workspace(nb, dev)
-            L.check(lib.nrf_render_rows(self._r, C.byref(v), C.byref(rp), _ptr(self._linspace(s, dev)), _ptr(self._linspace(ni, dev)) if ni > 0 else None,
-                                        C.byref(ro), _ptr(rays_), _ptr(nf), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+            t, u = _ptr(self._linspace(s, dev)), _ptr(self._linspace(ni, dev)) if ni > 0 else None
+            if nm is None:
+                ws = self._workspace(lib.nrf_render_rows_workspace_bytes(self._r, C.byref(v), C.byref(rp)), dev)
+                L.check(lib.nrf_render_rows(self._r, C.byref(v), C.byref(rp), t, u, C.byref(ro), _ptr(rays_), _ptr(nf), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+            else:
+                ws = self._workspace(lib.nrf_render_rows_normals_workspace_bytes(self._r, C.byref(v), C.byref(rp), nm.bits), dev)
+                L.check(lib.nrf_render_rows_normals(self._r, C.byref(v), C.byref(rp), t, u, C.byref(ro), C.byref(nm), _ptr(rays_), _ptr(nf), _ptr(ws),
+                                                    C.c_size_t(ws.numel()), _stream()))
         else:
             if c2w_staticcam is not None:
                 raise L.NrfError("c2w_staticcam replaces the camera of a POSE render (NeRFRenderer.h:554-558); with an explicit ray batch pass those rays yourself")
@@ -432,10 +464,16 @@ class NeRFRenderer:
             rp = self._params(s, ni, None if p.ThinRay else cone_angle, p.LinDisp, p.Perturb, p.WhiteBkgr, p.RawNoiseStd, p.StochasticPreconditioningAlpha,
                               p.BoundingBox, p.Precision, p.Seed, 0, p.CoarseMode, p.OverflowPolicy)
             res, ro = self._alloc_outputs(n, s, ni, dev, p.ReturnRaw, p.ReturnWeights, p.KeepIntermediates)
-            nb = lib.nrf_batchify_rays_workspace_bytes(self._r, C.c_int64(n), int(p.Chunk), C.byref(rp))
-            ws = self._workspace(nb, dev)
-            L.check(lib.nrf_batchify_rays(self._r, _ptr(rays_), stride, C.c_int64(n), int(p.Chunk), C.byref(rp), _ptr(self._linspace(s, dev)),
-                                          _ptr(self._linspace(ni, dev)) if ni > 0 else None, C.byref(ro), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+            nm = self._normals_request(res, n, dev, self._normal_bits(p))
+            t, u = _ptr(self._linspace(s, dev)), _ptr(self._linspace(ni, dev)) if ni > 0 else None
+            if nm is None:
+                ws = self._workspace(lib.nrf_batchify_rays_workspace_bytes(self._r, C.c_int64(n), int(p.Chunk), C.byref(rp)), dev)
+                L.check(lib.nrf_batchify_rays(self._r, _ptr(rays_), stride, C.c_int64(n), int(p.Chunk), C.byref(rp), t, u, C.byref(ro), _ptr(ws), C.c_size_t(ws.numel()),
+                                              _stream()))
+            else:
+                ws = self._workspace(lib.nrf_batchify_rays_normals_workspace_bytes(self._r, C.c_int64(n), int(p.Chunk), C.byref(rp), nm.bits), dev)
+                L.check(lib.nrf_batchify_rays_normals(self._r, _ptr(rays_), stride, C.c_int64(n), int(p.Chunk), C.byref(rp), t, u, C.byref(ro), C.byref(nm), _ptr(ws),
+                                                      C.c_size_t(ws.numel()), _stream()))
             self._last_feature_view = self.feature_view()          # (None unless this was a single-chunk render of the feature-reusing fast path)
             nf = None
             if n > 0:
@@ -443,6 +481,10 @@ class NeRFRenderer:
                 L.check(lib.nrf_near_far_range_device(_ptr(rays_), C.c_int64(n), stride, _ptr(nf), _stream()))   # :602-603 without the reference's two host stalls
         out = res.Outputs
         out.RGBMap = out.RGBMap.reshape(sh)                                                               # :591-592
+        if out.RenderedNormals is not None:
+            out.RenderedNormals = out.RenderedNormals.reshape(sh)
+        if out.RenderedPredNormals is not None:
+            out.RenderedPredNormals = out.RenderedPredNormals.reshape(sh)
         if len(sh) > 2:
             out.DispMap = out.DispMap.reshape(sh[0], sh[1]); out.DepthMap = out.DepthMap.reshape(sh[0], sh[1])   # :594-600
         res._nf_dev = nf
@@ -903,6 +945,8 @@ class LeRFRenderer:
     def Render(self, h, w, k, render_params: NeRFRenderParams, rays=(None, None, None), c2w=None, row0=0, rows=None):
         """LeRFRenderer.cpp:265-330."""
         p = render_params
+        if getattr(p, "CalculateNormals", False) or getattr(p, "UsePredNormal", False):
+            raise L.NrfError("unsupported: CalculateNormals / UsePredNormal are built for hash-grid renderers with NeRFSmall, not the LeRF renderer")
         if self._single_call_ok(p) and (c2w is not None or (rays[0] is not None and torch.as_tensor(rays[0]).numel() > 0)):
             return self._render_single_call(h, w, k, p, rays, c2w, row0, rows)
         if c2w is not None:

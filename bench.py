@@ -16,6 +16,11 @@ are resident in HBM before the timed region.
 Workloads (BASELINE.json configs):  --workload hash    HashNeRF: CuHashEmbedder L16 T2^19 F2 + CuSHEncoder(4) + NeRFSmall
                                      --workload classic PE(10)/PE(4) + NeRF 8x256
 Rank 0 prints ONE compact JSON line (< 4 KB: benchlib/report.py); the full record goes to bench_detail.json and to stderr.
+
+A plain run does what the headline needs: set up, settle the clock, pick the lane count, warm up, time the K steps, write --dump-outputs, print the line.  Everything
+else it can measure or check -- the CPU baseline, the secondary workloads and precisions (`also`), the other scaling mode, the collective cross-check and the
+data-parallel training step at N > 1, the per-kernel profiled passes behind `roofline`, the parity checks against the CPU oracle and the F32 mode -- runs with
+--full (the --no-* options still switch single parts of it off).
 """
 import argparse
 import os
@@ -59,6 +64,9 @@ def main():
     ap.add_argument("--precision", default=None, choices=["f16", "f16x3", "f32"],
                     help="MLP arithmetic: f16 = matrix cores, fp16 operands; f16x3 = matrix cores, hi+lo fp16 operand pairs (fp32-grade); f32 = FMA chains "
                          "(== oracle bitwise).  Default: f16x3 (fp32-grade pixels; the reference computes in fp32)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check: cpu_baseline, the secondary lines of `also`, the collective cross-check, the "
+                         "profiled passes behind roofline, the parity checks against the CPU oracle and the F32 mode (off by default: a plain run times the steps and prints the line)")
     ap.add_argument("--no-settle", action="store_true", help="skip the settling phase before the warmup steps (counter passes: tools/gpu_pmc*.sh count the frames of a run)")
     ap.add_argument("--no-isolated", action="store_true", help="skip the single-lane pass behind roofline.isolated")
     ap.add_argument("--no-also", action="store_true", help="skip the short secondary measurements (other precision, classic workload) at N = 1")
@@ -105,7 +113,7 @@ def main():
         args.scaling = "strong" if world > 1 else "weak"   # N = 1: the two coincide (one frame per step), reported as "weak" per the driver's contract
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from benchlib.cpu import cpu_baseline
         cpu = cpu_baseline(args.workload)        # before the GPU is initialised (it may spawn a child process)
 
@@ -271,7 +279,7 @@ def main():
     nframes = len(poses)
     # at N > 1 the other scaling mode rides along in `also` (every rank takes part; fewer steps)
     other = None
-    if world > 1 and not args.no_also:
+    if args.full and world > 1 and not args.no_also:
         o_scaling = "weak" if args.scaling == "strong" else "strong"
         o_steps = max(2, args.steps // 2)
         o_dt, o_frames, o_poses, o_host, _ = timed_run(o_scaling, o_steps, 1)
@@ -282,7 +290,7 @@ def main():
     # It runs on a helper thread with a deadline so that nothing it does can cost the run its result line.
     collective_check = None
     stuck = False
-    if use_dist and args.backend == "nccl":
+    if args.full and use_dist and args.backend == "nccl":
         import threading
         box = {}
 
@@ -308,7 +316,7 @@ def main():
 
     # data-parallel TRAINING step at N > 1 (every rank takes part; `also`): the gradient all-reduce behind the C ABI.  On a helper thread with a deadline, like the cross-check
     dp_train = None
-    if use_dist and world > 1 and not args.no_also and not stuck:
+    if args.full and use_dist and world > 1 and not args.no_also and not stuck:
         import threading
         box2 = {}
 
@@ -328,7 +336,7 @@ def main():
     # per-kernel times, never from the timed region: a short SINGLE-LANE pass with the event bracketing on (each kernel has the GPU to itself: `roofline`), and, when
     # the timed region ran on more lanes, a short pass on that many (the same kernels sharing the CUs: context)
     isolated = shared = None
-    if not args.no_isolated and not stuck:
+    if args.full and not args.no_isolated and not stuck:
         i_steps = max(3, min(5, args.steps))
         isolated = profiled_pass(args.scaling, i_steps, 1)
         if lanes_timed > 1:
@@ -401,11 +409,12 @@ def main():
         if cpu is not None:
             detail["cpu_baseline"] = cpu
         # parity of what was just timed (cpu_baseline leg, checker use of oracle/): GPU render vs the CPU oracle on identical weights/pose
-        try:
-            detail["psnr_vs_oracle_db"] = extras.quality_check(sc, renderer, rp, K, poses[0], args)
-        except Exception as e:
-            detail["psnr_vs_oracle_db"] = f"unavailable: {e}"
-        if not args.no_parity:
+        if args.full:
+            try:
+                detail["psnr_vs_oracle_db"] = extras.quality_check(sc, renderer, rp, K, poses[0], args)
+            except Exception as e:
+                detail["psnr_vs_oracle_db"] = f"unavailable: {e}"
+        if args.full and not args.no_parity:
             try:
                 detail["parity_full_frame_vs_f32"] = extras.full_frame_parity(sc, renderer, rp, K, poses[0], args, scene, L)
             except Exception as e:
@@ -430,7 +439,7 @@ def main():
         # the gathered frame of the first pose, hashed: equal strings at different N (or launchers) = the sharded render is the single-GPU render bit for bit
         import hashlib
         detail["frame_sha256"] = hashlib.sha256(frames[0].reshape(H, W, 3).contiguous().cpu().numpy().tobytes()).hexdigest()
-        if world == 1 and not use_dist and not args.no_also:
+        if args.full and world == 1 and not use_dist and not args.no_also:
             detail["also"] = extras.secondary_measurements(args, scene, L, K, poses[0], sc)
         # The contract is ONE JSON line.  RCCL prints a version banner through C stdio when the process exits, and tearing the process group down is a collective
         # that a slow or already-gone peer can stall: drain what is buffered, print the line, flush -- and in the distributed case every rank then leaves without

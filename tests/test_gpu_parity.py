@@ -3337,7 +3337,7 @@ def test_two_real_rccl_ranks_gather_the_single_rank_frame(tmp_path):
     """Config 4 on REAL RCCL, where the box has two GPUs (the driver's SCALE node; skipped on the one-GPU box, where two ranks can only share a device over gloo):
     (a) tests/helpers/rccl_two_rank_worker.py under torch.distributed.run -- uneven row tiles through the ncclBroadcast group of nrf_allgather_tiles and even ones through
     ncclAllGather, synchronous and overlapped, against torch.distributed's collective and against the full frame; nrf_comm_world == 2 on a communicator made by the
-    bounded (blocking) rendezvous;  (b) `bench.py --gpus 2 --collective cabi` on nccl: the gathered 800x800 frame's sha256 == the single-rank frame's."""
+    bounded (blocking) rendezvous;  (b) `bench.py --gpus 2 --collective cabi --full` on nccl: the gathered 800x800 frame's sha256 == the single-rank frame's."""
     import json, os, subprocess, sys
     from conftest import ROOT
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), NRF_BENCH_TIMEOUT="600")
@@ -3355,7 +3355,7 @@ def test_two_real_rccl_ranks_gather_the_single_rank_frame(tmp_path):
     assert any(f["rows"] == 3 for l in lines for f in l["frames"].values()) and any(f["rows"] == 2 for l in lines for f in l["frames"].values()), "uneven tiles: 3 + 2 rows of 5"
     common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-parity", "--no-also", "--no-isolated"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, timeout=900, env=env)
-    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--collective", "cabi"] + common, capture_output=True, text=True, timeout=900, env=env)
+    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--collective", "cabi", "--full"] + common, capture_output=True, text=True, timeout=900, env=env)
     assert one.returncode == 0 and two.returncode == 0, (one.stderr[-1500:], two.stderr[-1500:])
     l1 = json.loads([x for x in one.stdout.splitlines() if x.startswith("{")][-1]); l2 = json.loads([x for x in two.stdout.splitlines() if x.startswith("{")][-1])
     assert l2["n_gpus"] == 2 and l2["ranks_seen_by_rccl"] == 2 and l2["scaling"] == "strong" and l2["tile_rows"] == 400
@@ -3528,14 +3528,14 @@ def test_drop_in_data_parallel_training_two_thread_ranks_end_with_identical_repl
 
 
 def test_bench_two_rank_rehearsal_carries_the_data_parallel_training_step():
-    """`python bench.py --gpus 2 --backend gloo` WITH its `also` part (two ranks sharing this box's GPU): besides the other scaling mode every rank runs the data-parallel
+    """`python bench.py --gpus 2 --backend gloo --full` WITH its `also` part (two ranks sharing this box's GPU): besides the other scaling mode every rank runs the data-parallel
     training step (benchlib/extras.py::dp_train_step_measurement: a Trainer per rank on its own ray batch, gradients averaged before Adam -- torch.distributed here, the C-ABI
     nrf_allreduce_grads with --backend nccl) and the line's `also` names it; the replicas' parameter checksums agree exactly after the steps."""
     import json, os, subprocess, sys
     from conftest import ROOT
     env = dict(os.environ, NRF_BENCH_TIMEOUT="900")
-    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-parity",
-                          "--no-isolated"], capture_output=True, text=True, timeout=1200, env=env)
+    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+                          "--no-parity", "--no-isolated"], capture_output=True, text=True, timeout=1200, env=env)
     assert two.returncode == 0, two.stderr[-2500:]
     line = json.loads([x for x in two.stdout.splitlines() if x.startswith("{")][-1])
     names = [a.get("workload") for a in line.get("also", [])]

@@ -330,6 +330,14 @@ def test_bench_launcher_reports_failing_ranks_without_hanging():
     assert r.returncode != 0 and "cabi" in r.stderr
 
 
+def test_bench_full_option_is_off_by_default():
+    """A plain `bench.py` run times the headline only; every other measurement and check is behind --full (argparse answers --help before any GPU API is touched)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stderr[-500:]
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert 'ap.add_argument("--full", action="store_true"' in src, "off unless asked for"
+
+
 def _canned_bench_detail(world):
     """A full bench record assembled from canned measurements (round 3's HIP-event totals) through the same functions bench.py calls on the GPU box."""
     from benchlib import roofline as RF

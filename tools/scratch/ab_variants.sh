@@ -3,7 +3,7 @@
 for i in 1 2 3; do
   for v in default "$@"; do
     if [ $v = default ]; then unset NRF_LIB_PATH; else export NRF_LIB_PATH=$PWD/tune/$v/libnerfpp_hip.so; fi
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-also --no-parity --steps 20 --warmup 3 >/dev/null 2>&1
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-also --no-parity --steps 20 --warmup 3 >/dev/null 2>&1
     python - "$v" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json")); r = d["roofline"]; n = r["isolated_steps"]

@@ -834,6 +834,38 @@ NRF_API int nrf_lerf_render_rows(const nrf_lerf_renderer *r, const nrf_view *v, 
                                  float *d_rays_out, float *d_near_far, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LeRF relevancy in 3D (lerf_query.hip; no counterpart in the reference, which reads the language field through rendered images only)
+ * ------------------------------------------------------------------------------------------- */
+/* Per point x_i: d_relevancy[i] = Relevancy(normalize(le(x_i), eps 1e-8), positives[positive_id], negatives) -- the formula of nrf_lerf_relevancy: logits at temperature
+ * 10, a pairwise softmax against each negative, the negative the positive does worst against (first on ties); n_neg = 0 gives (0, 0).  le = the head's 768-wide language
+ * embedding (LeRFImpl::forward, LeRF.cpp:75-110).  The keep mask does not touch relevancy.  d_sigma [p] (NULL: not wanted) = sigma_le, equal in every precision to
+ * nrf_mlp_forward(..., NRF_PREC_F32)[..., -1] bit for bit, with the keep mask (LeRFRenderer.cpp:17-18) in the point and grid entries.
+ * precision:
+ *   NRF_PREC_F32         the composed path: nrf_mlp_forward(F32) in chunks, normalise, relevancy.  Any LeRF head, any number of negatives.
+ *   NRF_PREC_F16_SPLIT   one fused matrix-core kernel per slab from the sigma net's (sigma, geo32) output: LE0 -> a, ||W a||^2 = a^T (W^T W) a (the render pass's Gram
+ *   NRF_PREC_F16_MFMA    layer), q . W a = (W^T q) . a for the 1 + n_neg prompts (U = W^T q built in fp64 into the workspace on every call), the relevancy in
+ *                        registers; no 768-wide value exists.  SPLIT carries LE0 and the U tile as hi + lo fp16 pairs, MFMA as plain fp16.  The head must have
+ *                        the matrix-core shape (in 128 / hidden 256 / 2+2 layers / geo 32 / embedding 768) and 1 + n_neg <= 32: NRF_ERR_UNSUPPORTED otherwise.
+ * Results do not depend on p or slab_points, bit for bit; a lattice point gets the same bits from the grid entry as from the point entry.  Only the caller's workspace is
+ * used; nothing the renderer owns is written (the feature view of nrf_lerf_renderer_last_features stays valid); prompts and weights are read anew on every call.
+ * Errors: no prompts set, positive_id out of range, NULL d_relevancy: NRF_ERR_INVALID_ARG; workspace too small: NRF_ERR_WORKSPACE; p == 0: NRF_OK, nothing launched.
+ * Non-finite network values are not detected (no overflow policy here): they reach the outputs. */
+/* The head alone on fp32 feature rows d_x [p, 128] (16-byte aligned), explicit device prompts [n_pos, 768] / [n_neg, 768] as nrf_lerf_relevancy takes them.  In the fused
+ * precisions the rows are split hi / lo for LE0 and sigma_le (when wanted) comes from the F32 network: rows are not fp16 numbers in general. */
+NRF_API size_t nrf_lerf_head_relevancy_workspace_bytes(const nrf_mlp *m, int64_t p, int n_neg, int precision);
+NRF_API int nrf_lerf_head_relevancy(const nrf_mlp *m, const float *d_x, int64_t p, const float *d_positives, int n_pos, const float *d_negatives, int n_neg,
+                                    int positive_id, int precision, float *d_sigma, float *d_relevancy, void *d_ws, size_t ws_bytes, void *stream);
+/* Points d_pts [p, 3] through the renderer's language grid and head, prompts from nrf_lerf_set_prompts.  Fused precisions: the level-major fp16 encode, sigma_le and the
+ * geo planes from the exact-fp32 density pass (sigma_lerf_f32.hip), the fused kernel; slabs of slab_points points (<= 0: 2^22; at most 2^30) bound the workspace. */
+NRF_API size_t nrf_lerf_point_relevancy_workspace_bytes(const nrf_lerf_renderer *r, int64_t p, int precision, int64_t slab_points);
+NRF_API int nrf_lerf_point_relevancy(const nrf_lerf_renderer *r, const float *d_pts, int64_t p, int positive_id, int precision, float *d_sigma, float *d_relevancy,
+                                     int64_t slab_points, void *d_ws, size_t ws_bytes, void *stream);
+/* The lattice of nrf_density_grid (bbox[6] on the host, P = bmin + (float)i * step, x fastest): d_relevancy [nz][ny][nx][2], d_sigma [nz][ny][nx], in slabs as above. */
+NRF_API size_t nrf_lerf_relevancy_grid_workspace_bytes(const nrf_lerf_renderer *r, int nx, int ny, int nz, int precision, int64_t slab_points);
+NRF_API int nrf_lerf_relevancy_grid(const nrf_lerf_renderer *r, const float *bbox, int nx, int ny, int nz, int positive_id, int precision, float *d_sigma,
+                                    float *d_relevancy, int64_t slab_points, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N1, LeRF branch of the optimisation step (NeRFExecutor.h:955-982): lang_loss and its backward into LeRFImpl and the language grid
  * ------------------------------------------------------------------------------------------- */
 /* lang_loss = huber_loss(pred, target, reduction none, delta).sum(-1).nanmean() (NeRFExecutor.h:970-974; delta 1.25 there): d_loss [1]; d_grad [n, e] = d loss / d pred

@@ -98,6 +98,8 @@ SYMBOLS = [
     "nrf_tile_partition", "nrf_comm_unique_id", "nrf_comm_create", "nrf_comm_create_timeout", "nrf_comm_wrap", "nrf_comm_destroy", "nrf_comm_world", "nrf_comm_rank", "nrf_allgather_tiles", "nrf_allreduce_grads",
     "nrf_profile_enable", "nrf_profile_is_enabled", "nrf_profile_read", "nrf_set_render_lanes", "nrf_get_render_lanes", "nrf_renderer_set_lanes", "nrf_lerf_renderer_set_lanes",
     "nrf_lerf_relevancy", "nrf_relevancy_image", "nrf_colormap_jet_u8", "nrf_colormap_jet_lut",
+    "nrf_lerf_head_relevancy_workspace_bytes", "nrf_lerf_head_relevancy", "nrf_lerf_point_relevancy_workspace_bytes", "nrf_lerf_point_relevancy",
+    "nrf_lerf_relevancy_grid_workspace_bytes", "nrf_lerf_relevancy_grid",
     "nrf_lerf_renderer_create", "nrf_lerf_renderer_destroy", "nrf_lerf_set_prompts", "nrf_lerf_render_rays_workspace_bytes", "nrf_lerf_render_rays",
     "nrf_lerf_batchify_rays_workspace_bytes", "nrf_lerf_batchify_rays", "nrf_lerf_render_rows_workspace_bytes", "nrf_lerf_render_rows",
     "nrf_fp32_gemm_available", "nrf_get_train_gemm", "nrf_set_train_gemm", "nrf_gemm_nt_bf16x3", "nrf_gemm_nt_f16x3", "nrf_gemm_tn_bf16x3", "nrf_layer_grad_split", "nrf_huber_rows_nanmean", "nrf_lerf_head_backward_workspace_bytes", "nrf_lerf_head_backward", "nrf_lerf_backward_points_workspace_bytes", "nrf_lerf_backward_points",
@@ -141,6 +143,9 @@ def lib():
         L.nrf_batchify_rays_normals_workspace_bytes.restype = C.c_size_t
         L.nrf_render_rows_normals_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_render_rays_workspace_bytes.restype = C.c_size_t
+        L.nrf_lerf_head_relevancy_workspace_bytes.restype = C.c_size_t
+        L.nrf_lerf_point_relevancy_workspace_bytes.restype = C.c_size_t
+        L.nrf_lerf_relevancy_grid_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_batchify_rays_workspace_bytes.restype = C.c_size_t
         L.nrf_lerf_render_rows_workspace_bytes.restype = C.c_size_t
         L.nrf_mlp_backward_workspace_bytes.restype = C.c_size_t

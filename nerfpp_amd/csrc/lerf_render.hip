@@ -182,6 +182,13 @@ static int jet_lut_device(const uint8_t **out, hipStream_t st)
     return NRF_OK;
 }
 
+// the parts of a renderer the 3D relevancy query reads (lerf_query.hip)
+void lerf_renderer_query_parts(const nrf_lerf_renderer *r, const nrf_hash **h, const nrf_mlp **m, const float **pos, int *n_pos, const float **neg, int *n_neg, int *embed_dim)
+{
+    *h = r->desc.lang_embed; *m = r->desc.lerf;
+    *pos = r->d_pos; *n_pos = r->n_pos; *neg = r->d_neg; *n_neg = r->n_neg; *embed_dim = r->embed_dim;
+}
+
 static int lerf_lanes(const nrf_lerf_renderer *r) { return r->lanes < 1 ? 1 : (r->lanes > NRF_LERF_MAX_LANES ? NRF_LERF_MAX_LANES : r->lanes); }
 
 struct LerfPlan {

@@ -64,6 +64,28 @@ struct Args {
 constexpr int GEO_FRAGS = 3;                                        // fragments 0, 1: sigma + geo[0..30]; fragment 2: geo[31] (the fourth is all zero)
 constexpr int64_t GEO_BYTES_PER_COLUMN = GEO_FRAGS * 2 * 2 * 16;    // 192
 
+// The 3D relevancy query (lerf_query.hip, kernel in mlp_lerf_split_mfma.hip): kernel B's LE0 + Gram layers from the geo planes, then ONE 32-neuron tile of
+// U = W^T [positive; negatives] (prompt slot k = row k; unused slots zero) and the relevancy epilogue.  Its weight image, in the caller's workspace:
+// [LE0 8 tiles x 12 k-steps | Gram 8 tiles x 16 | U 1 tile x 16] (hi, lo) fragment pairs, the first two copied from the split image.
+constexpr int QUERY_IMAGE_FRAGS = 2 * (8 * 12 + 8 * 16 + 16);       // 480 KB
+struct QueryArgs {
+    const __half *x_lm;                     // level-major fp16 features [16][pstride][8] (hi parts) ...
+    const __half *x_lo;                     // ... and their lo parts in the same layout, or NULL (exact fp16 features)
+    int64_t pstride;
+    const void *geo; int64_t geo_stride;    // the (sigma, geo32) operand planes (Args::geo)
+    const float *u_scale;                   // device: the image's U is U / u_scale (a power of two)
+    float gram_scale;                       // set by the launcher
+    int n_neg;                              // 0 .. 31
+    float *rel;                             // [p, 2]
+};
+
+}  // namespace lerf
+
+// kernel of the query: precision split (hi + lo in LE0 and the U tile) or not (fp16 operands); img: the query image above
+int lerf_split_query(const nrf_mlp *m, const lerf::QueryArgs &a, int64_t p, const void *img, bool split, hipStream_t st);
+
+namespace lerf {
+
 }  // namespace lerf
 
 // split-precision passes (mlp_lerf_split_mfma.hip); same arguments as the fp16 launchers

@@ -733,7 +733,188 @@ static int launch_lerf_split(const nrf_mlp *m, const Args &a_in, int64_t p, hipS
     return NRF_OK;
 }
 
+// ---- the 3D relevancy query (lerf_query.hip): kernel B from the geo planes with the ray sum replaced by ONE more 32-neuron tile ----
+// Per point: LE0 -> a (ReLU), ||W a||^2 = a^T G a from the block-triangular Gram layer (hi only, as kernel B), d = U^T a with U = W^T [pos; negs] (256 x 32, built per
+// call into the caller's workspace), s_k = d_k / max(||W a||, 1e-8), then the relevancy of k_lerf_relevancy in registers.  No 768-wide value exists.
+// The weight stream walks a private image [LE0 8 tiles | Gram 8 tiles | U 1 tile] (a copy of the first two from the split image, then the U tile): 17 chunks.
+struct NetQ {
+    using B = NetS<4, 2>;
+    struct F {                                     // Net<5> with ONE tile in layer 4 (the U tile, chained operand like LE1's kernel-B shape)
+        static constexpr int tiles(int l) { return l == 4 ? 1 : Net<5>::tiles(l); }
+        static constexpr int ks_nat(int l) { return Net<5>::ks_nat(l); }
+        static constexpr int ks_ch(int l) { return Net<5>::ks_ch(l); }
+        static constexpr bool nat_first(int l) { return Net<5>::nat_first(l); }
+        static constexpr int ks(int l) { return Net<5>::ks(l); }
+    };
+    static constexpr int NB = B::total_chunks();   // 16
+    static constexpr int first_chunk(int l) { return l <= 4 ? B::first_chunk(l) : NB + 1; }
+    static constexpr int total_chunks() { return NB + 1; }
+    static constexpr int layer_of(int ci) { return ci < NB ? B::layer_of(ci) : 4; }
+    static constexpr int chunk_frags(int ci) { return 2 * F::ks(layer_of(ci)); }
+    static constexpr bool hi_only(int ci) { return ci < NB && B::hi_only(ci); }
+    static constexpr int tile_of(int ci) { return ci < NB ? B::tile_of(ci) : 0; }
+    static constexpr int k0(int ci) { return ci < NB ? B::k0(ci) : 0; }
+    static constexpr int k0_dma(int ci) { return k0(ci) & ~3; }
+    static constexpr int dma_frags(int ci) { return ci < NB ? B::dma_frags(ci) : 2 * 16; }
+    static constexpr int chunk_off(int ci) { return ci < NB ? B::chunk_off(ci) - B::image_off() : B::chunk_off(NB) - B::image_off(); }
+};
+static_assert(NetQ::chunk_off(NetQ::NB) == 8 * 2 * 12 + 8 * 2 * 16 && QUERY_IMAGE_FRAGS == NetQ::chunk_off(NetQ::NB) + 32, "query image: LE0, Gram, U");
+static_assert(NetQ::B::chunk_off(0) - NetQ::B::image_off() == 0, "the query image starts at LE0");
+
+// operand prefetch of the query kernel (GeoPF without merge map and render weight): chunk 4's tail DMAs tile t + 1's geo and feature fragments into the wave's
+// slots.  XLO: the features carry a lo plane (fp32 feature rows split hi / lo, nrf_lerf_head_relevancy), read straight into registers when the tile starts
+// (the wave's LDS slots hold 14 fragments: 22 would not fit beside the weight buffers) -- the head entry is not the lattice's hot path
+template <bool XLO>
+struct QueryPF {
+    const QueryArgs &in;
+    half8 *oper;               // the wave's slots: [QOPER][64 lanes] fragments
+    int h;
+    int64_t q1;                // tile t + 1: sample index of this lane (clamped to the launch)
+    static constexpr int QOPER = 2 * GEO_FRAGS + 8;
+    static constexpr int count(int ci) { return ci == 4 ? QOPER : 0; }
+    __device__ __forceinline__ void load_operands()
+    {
+        const half8 *gb = reinterpret_cast<const half8 *>(in.geo) + ((q1 << 1) + h);
+        const __half *xb = in.x_lm + ((int64_t)h * in.pstride + q1) * 8;
+#pragma unroll
+        for (int f = 0; f < 2 * GEO_FRAGS; f++)
+            __builtin_amdgcn_global_load_lds(gb + (int64_t)f * in.geo_stride * 2, (__attribute__((address_space(3))) void *)(oper + f * 64), 16, 0, 0);
+#pragma unroll
+        for (int s = 0; s < 8; s++)
+            __builtin_amdgcn_global_load_lds(xb + (int64_t)(2 * s) * in.pstride * 8, (__attribute__((address_space(3))) void *)(oper + (2 * GEO_FRAGS + s) * 64), 16, 0, 0);
+    }
+    template <int CI>
+    __device__ __forceinline__ void issue() { if constexpr (CI == 4) load_operands(); }
+    template <int CI> __device__ __forceinline__ void kstep(int) {}
+    __device__ __forceinline__ void take(half8 (&bb)[4][2], half8 (&xin)[8][2], int lane, int64_t qc) const
+    {
+        if constexpr (XLO) {
+            const __half *xl = in.x_lo + ((int64_t)h * in.pstride + qc) * 8;
+#pragma unroll
+            for (int s = 0; s < 8; s++) xin[s][1] = *reinterpret_cast<const half8 *>(xl + (int64_t)(2 * s) * in.pstride * 8);
+        }
+        const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)(oper + lane);
+#pragma unroll
+        for (int f = 0; f < GEO_FRAGS; f++)
+            asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4" : "=&v"(bb[f][0]), "=&v"(bb[f][1]) : "v"(a), "i"(f * 2048), "i"(f * 2048 + 1024));
+#pragma unroll
+        for (int s = 0; s < 8; s += 2)
+            asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4" : "=&v"(xin[s][0]), "=&v"(xin[s + 1][0]) : "v"(a), "i"((2 * GEO_FRAGS + s) * 1024), "i"((2 * GEO_FRAGS + s) * 1024 + 1024));
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int f = 0; f < GEO_FRAGS; f++) asm volatile("" : "+v"(bb[f][0]), "+v"(bb[f][1]));
+#pragma unroll
+        for (int s = 0; s < 8; s++) asm volatile("" : "+v"(xin[s][0]));
+    }
+};
+
+struct KeepTileS {
+    f32x16 d;
+    static constexpr int UNITS = 0;
+    __device__ __forceinline__ void operator()(int, const f32x16 &t) { d = t; }
+};
+
+// SPLIT: hi + lo operand pairs in LE0 and the U tile (NRF_PREC_F16_SPLIT); false: the hi parts alone (NRF_PREC_F16_MFMA)
+template <bool SPLIT, bool XLO>
+__global__ void __launch_bounds__(64 * SNW, 1)
+k_lerf_query(int64_t npts, QueryArgs in, const half8 *__restrict__ img)
+{
+    using N = NetQ;
+    using PF = QueryPF<XLO>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    half8 *wbuf = reinterpret_cast<half8 *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    half8 *oper = wbuf + 3 * SMAXF * 64 + wave * (PF::QOPER * 64);
+    stage_all<N, 0>(wbuf, img, wave, lane, std::make_integer_sequence<int, N::dma_frags(0) / SNW>{});
+    stage_all<N, 1>(wbuf + SMAXF * 64, img, wave, lane, std::make_integer_sequence<int, N::dma_frags(1) / SNW>{});
+    __syncthreads();
+    int cur = 0;
+    f32x16 accs[2];
+    const int64_t ntiles = (npts + 31) / 32;
+    const int64_t nblocks = (ntiles + SNW - 1) / SNW;
+    // this lane's point in the wave's tile of block blk; past the end: the last point (loaded, computed, never stored)
+    auto sample_of = [&](int64_t blk) -> int64_t {
+        const int64_t q = (blk * SNW + wave) * 32 + r;
+        return q < npts ? q : npts - 1;
+    };
+    const float uscale = *in.u_scale;
+    const float gscale = in.gram_scale;
+    const int nneg = in.n_neg;
+    PF pf{in, oper, h, sample_of(blockIdx.x)};
+    pf.load_operands();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    half8 ba[16][2];
+#pragma unroll 1
+    for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        CtxS cx{wbuf, img, lane, h, wave, &cur, accs};
+        const int64_t q = (blk * SNW + wave) * 32 + r;
+        half8 bb[4][2], xin[8][2], none[1][2];
+        pf.take(bb, xin, lane, q < npts ? q : npts - 1);
+        bb[3][0] = half8{0, 0, 0, 0, 0, 0, 0, 0}; bb[3][1] = bb[3][0];
+        if constexpr (!XLO) {
+#pragma unroll
+            for (int s = 0; s < 8; s++) xin[s][1] = bb[3][0];
+        }
+        pf.q1 = sample_of(blk + gridDim.x);
+        ConvHookS<true, 16> c2{ba, 0.0f};
+        layer_s<N, 2, SPLIT && XLO, SPLIT, SPLIT>(cx, xin, bb, c2, pf);            // LE0: cat[geo, in] -> 256, ReLU   (chunk 4's tail: tile t + 1's operands)
+        DotHookS ssq{ba};
+        layer_s<N, 3, false, NRF_LERF_GRAM_ALO != 0, NRF_LERF_GRAM_GLO != 0>(cx, none, ba, ssq, pf);      // ||W a||^2 = a . (W^T W) a, as kernel B
+        KeepTileS ut;
+        layer_s<N, 4, false, SPLIT, SPLIT>(cx, none, ba, ut, pf);                   // d = U^T a: row k of the tile = prompt k (0 positive, 1.. negatives)
+        const float tot = fmaxf(ssq.ss + __shfl_xor(ssq.ss, 32), 0.0f) * gscale;
+        const float inv = uscale / fmaxf(sqrtf(tot), 1e-8f);
+        // register i of lane half hh holds prompt 8 (i >> 2) + 4 hh + (i & 3): both halves gather all 32 (the swap below), the h = 0 lane stores
+        float v[32];
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const float mine = ut.d[i], other = __shfl_xor(mine, 32);
+            v[8 * (i >> 2) + (i & 3)] = (h == 0 ? mine : other) * inv;
+            v[8 * (i >> 2) + 4 + (i & 3)] = (h == 0 ? other : mine) * inv;
+        }
+        // k_lerf_relevancy's epilogue: pairwise softmax at temperature 10, the negative the positive does worst against (first on ties); no negatives: (0, 0)
+        float best0 = 0.0f, best1 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 31; j++) {
+            if (j < nneg) {
+                const float a = 10.0f * v[0], b = 10.0f * v[j + 1], m = fmaxf(a, b);
+                const float ea = expf(a - m), eb = expf(b - m), sum = ea + eb;
+                const float s0 = ea / sum, s1 = eb / sum;
+                if (j == 0 || s0 < best0) { best0 = s0; best1 = s1; }
+            }
+        }
+        if (h == 0 && q < npts) *reinterpret_cast<float2 *>(in.rel + 2 * q) = float2{best0, best1};
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 }  // namespace lerf
+
+int lerf_split_query(const nrf_mlp *m, const lerf::QueryArgs &a_in, int64_t p, const void *img, bool split, hipStream_t st)
+{
+    using namespace lerf;
+    QueryArgs a = a_in;
+    a.gram_scale = m->lerf_gram_scale;
+    const bool xlo = a.x_lo != nullptr;
+    const size_t lds = (size_t)3 * SMAXF * 1024 + (size_t)SNW * QueryPF<false>::QOPER * 1024;
+    const int64_t nblocks = ceil_div(ceil_div(p, (int64_t)32), (int64_t)SNW);
+    const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);          // persistent: one 4-wave workgroup per CU
+    const void *k = split ? (xlo ? reinterpret_cast<const void *>(k_lerf_query<true, true>) : reinterpret_cast<const void *>(k_lerf_query<true, false>))
+                          : (xlo ? reinterpret_cast<const void *>(k_lerf_query<false, true>) : reinterpret_cast<const void *>(k_lerf_query<false, false>));
+    NRF_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          // idempotent; every device a process drives is covered
+    ProfScope prof(NRF_PROF_MLP, st);
+    const half8 *im = reinterpret_cast<const half8 *>(img);
+    if (split) {
+        if (xlo) hipLaunchKernelGGL((k_lerf_query<true, true>), dim3(grid), dim3(64 * SNW), lds, st, p, a, im);
+        else hipLaunchKernelGGL((k_lerf_query<true, false>), dim3(grid), dim3(64 * SNW), lds, st, p, a, im);
+    } else {
+        if (xlo) hipLaunchKernelGGL((k_lerf_query<false, true>), dim3(grid), dim3(64 * SNW), lds, st, p, a, im);
+        else hipLaunchKernelGGL((k_lerf_query<false, false>), dim3(grid), dim3(64 * SNW), lds, st, p, a, im);
+    }
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
 
 int lerf_split_available(const nrf_mlp *m) { return m && m->family == MLP_LERF && m->d_packed_split != nullptr && m->packed_split_bytes == (size_t)2 * lerf::IMAGE_FRAGS * 1024; }
 

@@ -23,6 +23,7 @@ class Mesh:
     Faces: torch.Tensor                       # [F, 3] int32, counter-clockwise seen from outside
     Normals: torch.Tensor                     # [V, 3] f32, outward unit normals (0 where the lattice gradient vanishes)
     Colors: Optional[torch.Tensor] = None     # [V, 3] f32 in [0, 1]
+    Relevancy: Optional[torch.Tensor] = None  # [V, 2] (or [V]) f32: LeRF relevancy of the vertices (query.VertexRelevancy); SavePLY writes column 0
 
 
 def _resolution(resolution):
@@ -30,6 +31,20 @@ def _resolution(resolution):
     if len(r) != 3:
         raise L.NrfError(f"resolution must be an int or (nx, ny, nz), got {resolution!r}")
     return r
+
+
+def _lattice_points_at(bb, nx, ny, nz, idx):
+    """P(i) of flat lattice indices idx (x fastest) as nrf_density_grid forms them: bmin + (float)i * step, step = (bmax - bmin) / (n - 1), fp32 per operation."""
+    b = torch.as_tensor(np.asarray(bb, np.float32), device=idx.device)
+    n = torch.tensor([nx, ny, nz], device=idx.device)
+    step = (b[3:] - b[:3]) / (n - 1).to(torch.float32)
+    i = idx.to(torch.int64)
+    ijk = torch.stack([i % nx, (i // nx) % ny, i // (nx * ny)], dim=-1).to(torch.float32)
+    return b[:3] + ijk * step
+
+
+def _lattice_points(bb, nx, ny, nz, device):
+    return _lattice_points_at(bb, nx, ny, nz, torch.arange(nx * ny * nz, device=device))
 
 
 def _bbox(renderer, bbox):
@@ -119,14 +134,16 @@ def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, pre
 
 
 def SavePLY(path, mesh):
-    """Binary little-endian PLY: x y z nx ny nz (float), red green blue (uchar, clamp(round(255 c))) when the mesh has colours, faces as
-    `list uchar int vertex_indices`."""
+    """Binary little-endian PLY: x y z nx ny nz (float), red green blue (uchar, clamp(round(255 c))) when the mesh has colours, relevancy (float, column 0 of
+    Relevancy) when it has one, faces as `list uchar int vertex_indices`."""
     v = mesh.Vertices.detach().cpu().numpy().astype("<f4")
     n = mesh.Normals.detach().cpu().numpy().astype("<f4")
     fc = mesh.Faces.detach().cpu().numpy().astype("<i4")
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if mesh.Colors is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if mesh.Relevancy is not None:
+        fields += [("relevancy", "<f4")]
     rec = np.empty(v.shape[0], dtype=np.dtype(fields))
     for k, name in enumerate(("x", "y", "z")):
         rec[name] = v[:, k]
@@ -135,6 +152,9 @@ def SavePLY(path, mesh):
         c = np.clip(np.rint(mesh.Colors.detach().cpu().numpy().astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
         for k, name in enumerate(("red", "green", "blue")):
             rec[name] = c[:, k]
+    if mesh.Relevancy is not None:
+        r = mesh.Relevancy.detach().cpu()
+        rec["relevancy"] = (r[:, 0] if r.dim() == 2 else r.reshape(-1)).numpy().astype("<f4")
     frec = np.empty(fc.shape[0], dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
     frec["n"] = 3
     frec["idx"] = fc
@@ -142,6 +162,8 @@ def SavePLY(path, mesh):
     head += [f"property float {name}" for name, _ in fields[:6]]
     if mesh.Colors is not None:
         head += ["property uchar red", "property uchar green", "property uchar blue"]
+    if mesh.Relevancy is not None:
+        head += ["property float relevancy"]
     head += [f"element face {fc.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     with open(path, "wb") as fh:
         fh.write(("\n".join(head) + "\n").encode("ascii"))

@@ -639,7 +639,27 @@ NRF_API int nrf_mask_sigma_grad(const uint8_t *d_keep, int64_t p, int c, float *
 NRF_API size_t nrf_mlp_backward_workspace_bytes(const nrf_mlp *m, int64_t p);
 NRF_API int nrf_mlp_backward(const nrf_mlp *m, const float *d_x, const float *d_g_out, int64_t p, float *d_g_params, float *d_g_x,
                              void *d_workspace, size_t workspace_bytes, void *stream);
-/* The same gradients on the matrix cores (fp16 operands, fp32 accumulation, power-of-two loss scaling chosen on the device from
+/* Training the predicted-normals head (normal_loss.hip): the two losses of NeRF.h:308-326 whose call site the reference left commented out (NeRFExecutor.h:929-952)
+ * because it never computed the density normals they need.  Per batch of n rays x s samples, coarse-only NRF_PREC_F32 renders of a 7-column NeRFSmall:
+ *   w = d_weights [n,s] (the render's, a constant), nrm = -g / max(|g|, 1e-8) with g = d_density_grad [n*s,3] (nrf_density_grad at the points the network saw, a
+ *   constant: the NRF_NORMALS_DENSITY definition without the composite), pred = d_raw[..., 4:7] as it is (not normalised), v = -d_dirs (rays_d as the batch holds it):
+ *   L_pn = mean over n*s*3 of (w pred - w nrm)^2                        PredNormalLoss, torch::mse_loss
+ *   L_or = mean over rays of sum_i w_i min(0, pred_i . v)^2             OrientationLoss on the PREDICTED normals, torch::mean over rays
+ * d_losses: device [2] = (L_pn, L_or), unweighted.  d_g_raw [n*s,7]: columns 4:7 receive d (pred_normal_weight L_pn + orientation_weight L_or) / d pred; columns 0:4
+ * are not touched (nrf_raw2outputs_backward(c = 7) fills them, and zeroes 4:7: call it first; nrf_mask_sigma_grad(c = 7) afterwards mirrors the forward's column -1
+ * mask, which with 7 columns is the normal's z).  A sample with w == 0 contributes exactly 0 whatever pred and g hold.  The sums are fp64 in a fixed order (block
+ * partials in the workspace, one ordered pass): two runs give the same bits.  c != 7: NRF_ERR_UNSUPPORTED. */
+NRF_API size_t nrf_normal_losses_workspace_bytes(int64_t n, int s);
+NRF_API int nrf_normal_losses(const float *d_weights, const float *d_density_grad, const float *d_raw, int c, const float *d_dirs, int d_stride, int64_t n, int s,
+                              float pred_normal_weight, float orientation_weight, float *d_g_raw, float *d_losses, void *d_workspace, size_t workspace_bytes, void *stream);
+/* nrf_mlp_backward for a NeRFSmall WITH the predicted-normals head and a g_out [p,7] whose columns 4:7 carry a gradient: they go back through the normals net (its
+ * weight gradients are accumulated into d_g_params), and the gradient of its input cat[sigma, geo_feat, input_pts] (NeRF.cpp:396) is added to the sigma net's output
+ * gradient and to d_g_x.  With g_out[:, 4:7] == 0 the first two nets' gradients and d_g_x equal nrf_mlp_backward's and the head's are 0.  (nrf_mlp_backward on such a
+ * handle reads the same 7-column rows and leaves the head's gradient at 0.)  fp32 layer products only; a handle without the head: NRF_ERR_UNSUPPORTED. */
+NRF_API size_t nrf_mlp_backward_pn_workspace_bytes(const nrf_mlp *m, int64_t p);
+NRF_API int nrf_mlp_backward_pn(const nrf_mlp *m, const float *d_x, const float *d_g_out, int64_t p, float *d_g_params, float *d_g_x,
+                                void *d_workspace, size_t workspace_bytes, void *stream);
+/* nrf_mlp_backward's gradients on the matrix cores (fp16 operands, fp32 accumulation, power-of-two loss scaling chosen on the device from
  * max|g_out|): one fused kernel per 2^22 points, forward + gradient chain + weight gradients.  Built for in 32 / views 16 / 64-wide /
  * 2-3 sigma + 3-4 colour layers; NRF_ERR_UNSUPPORTED otherwise.  Same arguments as nrf_mlp_backward.  The workspace is a fixed ~25 MB (one slot of operand
  * fragments per resident wave), whatever p. */

@@ -91,6 +91,12 @@ size_t mlp_workspace_bytes(const nrf_mlp *m, int64_t p, int prec);
 int mlp_forward(const nrf_mlp *m, const float *d_x, int x_stride, int64_t p, int prec, float *d_out, int out_stride,
                 void *d_ws, size_t ws_bytes, hipStream_t st);
 
+// fp32 backward of NeRFSmallImpl::forward, layer by layer (mlp.hip).  with_head (a handle with the predicted-normals head, g_out of 7 columns): columns 4:7 are
+// back-propagated through the normals net and its input gradient joins the sigma net's output gradient and g_x; false: the head receives no gradient (nrf_mlp_backward)
+size_t mlp_backward_workspace_bytes(const nrf_mlp *m, int64_t p);
+int mlp_small_backward(const nrf_mlp *m, const float *x, int xs, const float *g_out, int gos, int64_t p, float *g_params, float *g_x, int gxs, void *ws, size_t ws_bytes,
+                       hipStream_t st, bool with_head = false);
+
 // the generic fp32 building blocks of mlp.hip (forward: an FMA chain per output in ascending k == the oracle; backward: dW by a TN product over the points with one
 // atomic add per element and workgroup, g_in by the same forward kernel on the blob's own [out][in] matrix), shared with lerf_train.hip / the classic backward:
 //   y[pt][y_off + o] = act(sum_k W[o][k] concat(a, b)[pt][k] + bias[o])

@@ -335,20 +335,30 @@ size_t mlp_backward_workspace_bytes(const nrf_mlp *m, int64_t p)
     return align_up((size_t)c * m->max_width * sizeof(float), 256) * (m->layers.size() + 3);
 }
 
+static int run_sum_cols(int64_t npts, int n, const float *a, int a_stride, int a_off, const float *b, int b_stride, int b_off, float *y, int y_stride, hipStream_t st,
+                        const float *mask, int mask_stride);          // (defined with the classic backward below)
+
 int mlp_small_backward(const nrf_mlp *m, const float *x, int xs, const float *g_out, int gos, int64_t p, float *g_params, float *g_x, int gxs,
-                       void *ws, size_t ws_bytes, hipStream_t st)
+                       void *ws, size_t ws_bytes, hipStream_t st, bool with_head)
 {
     if (m->family != MLP_SMALL) { set_error("nrf_mlp_backward: built for the NeRFSmall family"); return NRF_ERR_UNSUPPORTED; }
     if (ws_bytes < mlp_backward_workspace_bytes(m, p)) { set_error("nrf_mlp_backward: workspace %zu < %zu bytes", ws_bytes, mlp_backward_workspace_bytes(m, p)); return NRF_ERR_WORKSPACE; }
     const auto &d = m->small;
-    // (a predicted-normals head, if the handle has one, sits behind these layers and receives no gradient: the training loss reads RGBMap only, NeRFExecutor.h:882-887,
-    // and nothing else reads the normals -- its parameters' gradient stays zero, as in the reference's autograd)
+    // (a predicted-normals head, if the handle has one, sits behind these layers.  Without with_head it receives no gradient: the training loss reads RGBMap only,
+    // NeRFExecutor.h:882-887, and nothing else reads the normals -- its parameters' gradient stays zero, as in the reference's autograd.  with_head: g_out[:, 4:7] is
+    // back-propagated through it first, see below)
     const int W = m->max_width, nl = d.num_layers + d.num_layers_color;
+    const int nn = with_head ? d.num_layers_normals : 0;
+    if (with_head && (!d.use_pred_normal || gos < 7)) { set_error("internal: mlp_small_backward: with_head needs the predicted-normals head and 7 gradient columns"); return NRF_ERR_INVALID_ARG; }
     const size_t buf = align_up((size_t)(p < BWD_CHUNK ? p : BWD_CHUNK) * W * sizeof(float), 256) / sizeof(float);
     float *base = reinterpret_cast<float *>(ws);
     std::vector<float *> H(nl);
     for (int l = 0; l < nl; l++) H[l] = base + (size_t)l * buf;
     float *G[3] = {base + (size_t)nl * buf, base + (size_t)(nl + 1) * buf, base + (size_t)(nl + 2) * buf};
+    // the head's share of the workspace (one buffer per head layer, mlp_backward_workspace_bytes): its nn - 1 hidden outputs and its input gradient
+    std::vector<float *> HN(nn > 0 ? nn - 1 : 0);
+    for (int l = 0; l + 1 < nn; l++) HN[l] = base + (size_t)(nl + 3 + l) * buf;
+    float *GNIN = nn > 0 ? base + (size_t)(nl + 3 + nn - 1) * buf : nullptr;          // d loss / d cat[sigma, geo_feat, input_pts] through the head
     const Seg none{nullptr, 0, 0, 0};
     for (int64_t p0 = 0; p0 < p; p0 += BWD_CHUNK) {
         const int64_t c = (p - p0) < BWD_CHUNK ? (p - p0) : BWD_CHUNK;
@@ -366,6 +376,26 @@ int mlp_small_backward(const nrf_mlp *m, const float *x, int xs, const float *g_
         for (int l = 0; l < d.num_layers_color; l++, li++) {
             NRF_TRY(run_linear_fast(c, l == 0 ? cv : cur, l == 0 ? cg : none, m, m->layers[li], l != d.num_layers_color - 1, H[li], W, 0, st));
             cur = Seg{H[li], W, 0, m->layers[li].out};
+        }
+        // ---- predicted-normals head (NeRF.cpp:393-407): hidden layers recomputed from cat[H_sigma (sigma, geo), input_pts], g_out[:, 4:7] back to that input ----
+        if (nn > 0) {
+            const Seg hs{H[sig_l], W, 0, 1 + d.geo_feat_dim}, hx{xc, xs, 0, d.input_ch};
+            Seg ncur = hs;
+            for (int l = 0; l + 1 < nn; l++) {
+                NRF_TRY(run_linear_fast(c, l == 0 ? hs : ncur, l == 0 ? hx : none, m, m->layers[nl + l], 1, HN[l], W, 0, st));
+                ncur = Seg{HN[l], W, 0, m->layers[nl + l].out};
+            }
+            Seg gn{gc, gos, 4, 3};
+            int gj = 0;
+            for (int l = nn - 1; l >= 0; l--) {
+                const LinearLayer &L = m->layers[nl + l];
+                if (l != nn - 1) NRF_TRY(run_relu_mask(c, L.out, const_cast<float *>(gn.p), gn.stride, HN[l], W, st));
+                NRF_TRY(run_grad_w_fast(c, gn, l == 0 ? hs : Seg{HN[l - 1], W, 0, L.in}, l == 0 ? hx : none, L.out, L.in, g_params + L.w_off, st, train_gemm_for(m)));
+                float *dst = (l == 0) ? GNIN : G[gj];
+                gj = (gj + 1) % 3;
+                NRF_TRY(run_backprop_fast(c, gn, m, L, dst, W, st));
+                gn = Seg{dst, W, 0, L.in};
+            }
         }
         // ---- colour net backward ----
         Seg g{gc, gos, 0, 3};
@@ -390,6 +420,7 @@ int mlp_small_backward(const nrf_mlp *m, const float *x, int xs, const float *g_
             hipLaunchKernelGGL(k_copy_col, dim3((unsigned)ceil_div(c, 256)), dim3(256), 0, st, c, g.p, g.stride, d.input_ch_views + k, gh, W, 1 + k);
             NRF_LAUNCH_CHECK();
         }
+        if (nn > 0) NRF_TRY(run_sum_cols(c, 1 + d.geo_feat_dim, gh, W, 0, GNIN, W, 0, gh, W, st, nullptr, 0));          // + the head's gradient of (sigma, geo)
         g = Seg{gh, W, 0, 1 + d.geo_feat_dim};
         for (int l = sig_l; l >= 0; l--) {
             const LinearLayer &L = m->layers[l];
@@ -404,6 +435,8 @@ int mlp_small_backward(const nrf_mlp *m, const float *x, int xs, const float *g_
             NRF_TRY(run_backprop_fast(c, g, m, L, dst, l == 0 ? gxs : W, st));
             g = Seg{dst, l == 0 ? gxs : W, 0, L.in};
         }
+        // ... and of input_pts, which the head reads beside the sigma net's output (cat[sigma, geo_feat, input_pts], NeRF.cpp:396)
+        if (nn > 0 && g_x) NRF_TRY(run_sum_cols(c, d.input_ch, g_x + p0 * gxs, gxs, 0, GNIN, W, 1 + d.geo_feat_dim, g_x + p0 * gxs, gxs, st, nullptr, 0));
     }
     return NRF_OK;
 }

@@ -21,7 +21,8 @@ from .renderer import NeRFRenderer, NeRFRenderParams, RngFill, StochasticPrecond
 
 class Trainer:
     def __init__(self, embedder: _HashBase, embeddirs, mlp: NeRFSmall, table, mlp_blob, learning_rate=5e-4, betas=(0.9, 0.99), eps=1e-15,
-                 tv_loss_weight=0.0, seed=0, mlp_backward="f32", hash_backward="f32", grad_sync=None, train_dense_budget=256 << 20):
+                 tv_loss_weight=0.0, seed=0, mlp_backward="f32", hash_backward="f32", grad_sync=None, train_dense_budget=256 << 20,
+                 pred_normal_loss_weight=0.0, orientation_loss_weight=0.0):
         # two configurations of the reference's train loop (NeRFExecutor.h:862-995): hash grid + NeRFSmall (main.cpp:220-221) and the classic PE(10) / PE(4) + NeRF 8x256
         # (NeRFImpl is a legal TNeRF of the same loop; its embedders have no parameters: `table` is None / empty there)
         self.has_table = isinstance(embedder, _HashBase)
@@ -51,6 +52,18 @@ class Trainer:
         if mlp_backward not in ("f32", "f16"):
             raise L.NrfError("mlp_backward must be 'f32' or 'f16'")
         self.mlp_backward = mlp_backward
+        # PredNormalLoss / OrientationLoss (NeRF.h:308-326; call site commented out in the reference, NeRFExecutor.h:929-952): train the predicted-normals head of a
+        # 7-column NeRFSmall against the density normals (nrf_density_grad), through the fp32 layer kernels.  Both 0 (the default): the step is what it was
+        self.pred_normal_loss_weight, self.orientation_loss_weight = float(pred_normal_loss_weight), float(orientation_loss_weight)
+        self.train_head = self.pred_normal_loss_weight != 0.0 or self.orientation_loss_weight != 0.0
+        if self.train_head:
+            if not self.has_table:
+                raise L.NrfError("pred_normal_loss_weight / orientation_loss_weight: the classic model has no predicted-normals head")
+            if mlp.GetOutputDims() != 7:
+                raise L.NrfError("pred_normal_loss_weight / orientation_loss_weight need a NeRFSmall with the predicted-normals head (use_pred_normal=True)")
+            if mlp_backward != "f32":
+                raise L.NrfError("pred_normal_loss_weight / orientation_loss_weight: the head trains through the fp32 layer kernels (mlp_backward='f32')")
+        self.normal_losses = torch.zeros((2,), device=dev)          # [PredNormalLoss, OrientationLoss] of the last step, unweighted, on the device
         # "f32": one float atomic per feature; "packed": both features of an entry in one 64-bit fixed-point atomic (nrf_hash_backward_rays_packed);
         # "binned": the same fixed-point contributions merged per table range in LDS before they reach memory (nrf_hash_backward_rays_binned; equals "packed" bit for bit)
         if hash_backward not in ("f32", "packed", "binned"):
@@ -111,14 +124,19 @@ class Trainer:
         L.check(lib.nrf_huber_loss(_ptr(rgb), _ptr(tgt), C.c_int64(rgb.numel()), _ptr(loss_mse), _ptr(g_rgb), _stream()))
         raw = res.Raw; s = n_samples_out
         z = res.Extras["z_fine"] if "z_fine" in res.Extras else res.Extras["z_coarse"]
-        assert raw.shape == (n, s, 4) and z.shape == (n, s)
+        c = int(self.mlp.GetOutputDims())                  # 4, or 7 with the predicted-normals head
+        assert raw.shape == (n, s, c) and z.shape == (n, s)
+        if self.train_head:
+            self._check_head_step(p=params, fine="z_fine" in res.Extras)
+            if res.Outputs.Weights is None:
+                raise L.NrfError("Trainer.backward with a normal-loss weight needs the render's weights (ReturnWeights=True)")
         g_raw = torch.empty_like(raw)
         p = params
         seed = int(p.Seed) if p is not None else 0
         fine = "z_fine" in res.Extras
         noise_std = float(p.RawNoiseStd) if p is not None else 0.0
         noise = RngFill(seed, L.NRF_RNG_NOISE_FINE if fine else L.NRF_RNG_NOISE_COARSE, 0, n * s, normal=True, device=rays.device) if noise_std > 0 else None
-        L.check(lib.nrf_raw2outputs_backward_noise(_ptr(raw), _ptr(z), C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, 4, int(white_bkgr), _ptr(noise),
+        L.check(lib.nrf_raw2outputs_backward_noise(_ptr(raw), _ptr(z), C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, c, int(white_bkgr), _ptr(noise),
                                                    C.c_float(noise_std), _ptr(g_rgb), _ptr(g_raw), _stream()))
         pts = torch.empty((n * s, 3), device=rays.device)
         L.check(lib.nrf_points(_ptr(rays), stride, _ptr(z), C.c_int64(n), s, _ptr(pts), _stream()))
@@ -129,6 +147,17 @@ class Trainer:
             ur = RngFill(seed, L.NRF_RNG_R_FINE if fine else L.NRF_RNG_R_COARSE, 0, n * s, device=rays.device)
             ut = RngFill(seed, L.NRF_RNG_THETA_FINE if fine else L.NRF_RNG_THETA_COARSE, 0, n * s, device=rays.device)
             pts = TangentScatter(pts.reshape(n, s, 3), z, float(cone_angle), rays[:, 3:6].contiguous(), p.BoundingBox if p is not None else None, ur, ut).reshape(n * s, 3)
+        if self.train_head:
+            # w and the density normals are constants of the step ("no gradient flows here", NeRFExecutor.h:948); the normals at the points the network saw
+            pts = pts.contiguous()
+            dgrad = torch.empty((n * s, 3), device=rays.device)
+            L.check(lib.nrf_density_grad(self.renderer._r, _ptr(pts), C.c_int64(n * s), None, _ptr(dgrad), None, C.c_size_t(0), _stream()))
+            w = res.Outputs.Weights.reshape(n, s).contiguous()
+            nbl = lib.nrf_normal_losses_workspace_bytes(C.c_int64(n), s)
+            if getattr(self, "_nws", None) is None or self._nws.numel() < nbl:
+                self._nws = torch.empty((int(nbl),), device="cuda", dtype=torch.uint8)
+            L.check(lib.nrf_normal_losses(_ptr(w), _ptr(dgrad), _ptr(raw), c, C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, C.c_float(self.pred_normal_loss_weight),
+                                          C.c_float(self.orientation_loss_weight), _ptr(g_raw), _ptr(self.normal_losses), _ptr(self._nws), C.c_size_t(self._nws.numel()), _stream()))
         dirs, _ = self.embeddirs.forward(rays[:, 8:11].contiguous())
         in_ch = self.embedder.GetOutputDims()
         self.g_blob.zero_(); self.g_table.zero_()
@@ -156,7 +185,7 @@ class Trainer:
             # fine points are not encoded a second time (0.6 ms of a 5.9 ms step)
             view = self._render_features(res, n, s) if (fine and cone_angle is None and not (p is not None and p.StochasticPreconditioningAlpha > 0)) else None
             if view is not None:
-                L.check(lib.nrf_mask_sigma_grad_src(C.c_void_p(view["keep"]), C.c_void_p(view["src"]), C.c_int64(n * s), 4, _ptr(g_raw), _stream()))
+                L.check(lib.nrf_mask_sigma_grad_src(C.c_void_p(view["keep"]), C.c_void_p(view["src"]), C.c_int64(n * s), c, _ptr(g_raw), _stream()))
                 L.check(lib.nrf_mlp_backward_f16_lm_src(self.mlp._m, C.c_void_p(view["feats"]), C.c_int64(view["cols"]), C.c_void_p(view["src"]), _ptr(dirs16), s, _ptr(g_raw),
                                                         C.c_int64(n * s), _ptr(self.g_blob), _ptr(g_x), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
             else:
@@ -164,7 +193,7 @@ class Trainer:
                 keep_u8 = torch.empty((n * s,), device=rays.device, dtype=torch.uint8)
                 ptsc = pts.contiguous()
                 L.check(lib.nrf_hash_encode_lm_f16(self.embedder._h, _ptr(ptsc), C.c_int64(n * s), _ptr(feats), _ptr(keep_u8), _stream()))
-                L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), C.c_int64(n * s), 4, _ptr(g_raw), _stream()))
+                L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), C.c_int64(n * s), c, _ptr(g_raw), _stream()))
                 L.check(lib.nrf_mlp_backward_f16_lm(self.mlp._m, _ptr(feats), _ptr(dirs16), s, _ptr(g_raw), C.c_int64(n * s), _ptr(self.g_blob), _ptr(g_x), _ptr(ws),
                                                     C.c_size_t(ws.numel()), _stream()))
             self.reused_render_features = view is not None
@@ -173,8 +202,11 @@ class Trainer:
             emb, keep = self.embedder.forward(pts)
             x = torch.cat([emb, dirs[:, None, :].expand(n, s, dirs.shape[1]).reshape(n * s, -1)], 1).contiguous()
             keep_u8 = keep.to(torch.uint8)
-            L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), C.c_int64(n * s), 4, _ptr(g_raw), _stream()))
+            # (the forward's mask writes column -1, NeRFRenderer.h:187-188: with 7 columns that is the predicted normal's z, and sigma's gradient is not masked)
+            L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), C.c_int64(n * s), c, _ptr(g_raw), _stream()))
             ws_fn, bw_fn = (lib.nrf_mlp_backward_f16_workspace_bytes, lib.nrf_mlp_backward_f16) if self.mlp_backward == "f16" else (lib.nrf_mlp_backward_workspace_bytes, lib.nrf_mlp_backward)
+            if self.train_head:          # g_raw[:, 4:7] carries the normal losses' gradient: back through the head as well
+                ws_fn, bw_fn = lib.nrf_mlp_backward_pn_workspace_bytes, lib.nrf_mlp_backward_pn
             nb = ws_fn(self.mlp._m, C.c_int64(n * s))
             ws = self._workspace(nb)
             L.check(bw_fn(self.mlp._m, _ptr(x), _ptr(g_raw), C.c_int64(n * s), _ptr(self.g_blob), _ptr(g_x), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
@@ -208,6 +240,13 @@ class Trainer:
                 L.check(lib.nrf_mlp_backward_f16_flags(_ptr(self._ws), fl, _stream()))
                 self.overflow = bool(fl[0] or fl[1])
         return loss_mse
+
+    def _check_head_step(self, p, fine):
+        """The head exists in coarse-only scenes (NeRFExecutor.h:487) and in NRF_PREC_F32: anything else is refused before a launch."""
+        if fine or (p is not None and int(p.NImportance) > 0):
+            raise L.NrfError("pred_normal_loss_weight / orientation_loss_weight: the predicted-normals head trains in coarse-only steps (NImportance == 0)")
+        if p is None or int(p.Precision) != L.NRF_PREC_F32:
+            raise L.NrfError("pred_normal_loss_weight / orientation_loss_weight: the predicted-normals head is NRF_PREC_F32 only (pass the step's NeRFRenderParams)")
 
     def _render_features(self, res, n, s):
         """The renderer's feature view (NeRFRenderer.feature_view) if it still belongs to `res`: recorded on the result (FeatureView) by the Render call that produced it, and the
@@ -281,6 +320,9 @@ class Trainer:
         # the fine depths, not the coarse pass's raw rows: gradients flow through the fine pass only (NeRFRenderer.h:429), and without a raw_coarse output the render is the
         # default path -- sigma net alone in the coarse pass, hash features kept per column for the fine pass -- whose features the backward then reads (feature_view)
         p.ReturnRaw, p.KeepIntermediates = True, "depths"
+        if self.train_head:
+            self._check_head_step(p, fine=False)
+            p.ReturnWeights = True                         # the normal losses are weighted by the render's (detached) weights
         p.Seed = (int(render_params.Seed) + 0x9E3779B97F4A7C15 * self.t) & ((1 << 64) - 1)
         cone = None if p.ThinRay else cone_angle
         res = self.renderer.Render(0, 0, None, p, rays=(rays_o, rays_d, cone))
@@ -342,6 +384,9 @@ class Trainer:
         for l in range(d.num_layers_color):
             o, i = (3 if l == d.num_layers_color - 1 else d.hidden_dim_color), ((d.input_ch_views + d.geo_feat_dim) if l == 0 else d.hidden_dim_color)
             mlp.append((f"model_color_net_{l}.weight", off, (o, i))); off += o * i
+        for l in range(d.num_layers_normals if d.use_pred_normal else 0):          # NeRF.cpp:343-347
+            o, i = (3 if l == d.num_layers_normals - 1 else d.hidden_dim_normals), ((1 + d.geo_feat_dim + d.input_ch) if l == 0 else d.hidden_dim_normals)
+            mlp.append((f"model_normals_net_{l}.weight", off, (o, i))); off += o * i
         assert off == self.blob.numel()
         return emb, mlp
 

@@ -652,6 +652,25 @@ NRF_API int nrf_mlp_backward(const nrf_mlp *m, const float *d_x, const float *d_
 NRF_API size_t nrf_normal_losses_workspace_bytes(int64_t n, int s);
 NRF_API int nrf_normal_losses(const float *d_weights, const float *d_density_grad, const float *d_raw, int c, const float *d_dirs, int d_stride, int64_t n, int s,
                               float pred_normal_weight, float orientation_weight, float *d_g_raw, float *d_losses, void *d_workspace, size_t workspace_bytes, void *stream);
+/* Two regularisers on how density is distributed along a ray (ray_reg.hip), both functions of one ray's (sigma_i, w_i, z_i): the distortion loss of mip-NeRF 360 on the
+ * render's weights and the reference's SigmaSparsityLoss (NeRF.h:302-306, a Cauchy loss on sigma that the reference declares and never calls).  Per batch of n rays x s samples:
+ *   alpha_i, T_i, w_i are recomputed from d_raw[..., 3], d_z, |d_dirs| and the optional draws d_noise [n,s] (NULL: none) exactly as nrf_raw2outputs(_noise) /
+ *   nrf_raw2outputs_backward_noise do: d_weights_out (optional, [n,s]) receives the render's Weights bit for bit.
+ *   t_i = (z_i - z_0) / (z_{s-1} - z_0); sample i owns [t_i, t_{i+1}]: m_i = (t_i + t_{i+1}) / 2, dl_i = t_{i+1} - t_i; the last sample (the 1e10 tail) has m = t_{s-1},
+ *   dl = 0.  A ray whose span z_{s-1} - z_0 is not > 0 (a missed ray, s == 1) contributes 0 to both losses and its gradient rows are not touched.
+ *   L_dist   = mean over the n rays of [ sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dl_i ]      evaluated in O(s) by prefix / suffix sums (z ascends)
+ *   L_sparse = mean over the n rays of sum_i log(1 + 2 sp_i^2), sp_i = max(raw[i,3], 0)                 (the density compositing uses, without the noise draw)
+ * d_losses: device [2] = (L_dist, L_sparse), unweighted.  d (distortion_weight L_dist + sparsity_weight L_sparse) / d raw[..., 3] is ADDED to column 3 of d_g_raw [n,s,c]
+ * -- L_dist through nrf_raw2outputs_backward's own chain from d/dw (TruncExp's clamped derivatives, the 1 - alpha >= 1e-10 guard, the relu mask on sigma + noise); z
+ * carries no gradient.  No other column is read or written: call it after nrf_raw2outputs_backward(_noise) (and nrf_normal_losses) and before nrf_mask_sigma_grad*, which
+ * then zeroes the regularisers' gradient outside the box with the image loss's.  c is 4 or 7 (NRF_ERR_UNSUPPORTED otherwise).  A weight of exactly 0 skips its term and
+ * leaves its loss word 0; both 0: NRF_OK without a launch, both words 0, d_g_raw and d_weights_out untouched, no workspace needed.  A negative or non-finite weight or
+ * s < 1: NRF_ERR_INVALID_ARG; a workspace below nrf_ray_regularizers_workspace_bytes(n, s) (one fp32 row per ray + one fp64 pair per four rays): NRF_ERR_WORKSPACE; nothing
+ * is launched then.  The loss sums are fp64 block partials combined in one ordered pass, no atomics: two runs give the same bits in d_losses and d_g_raw. */
+NRF_API size_t nrf_ray_regularizers_workspace_bytes(int64_t n, int s);
+NRF_API int nrf_ray_regularizers(const float *d_raw, const float *d_z, const float *d_dirs, int d_stride, int64_t n, int s, int c, const float *d_noise, float noise_std,
+                                 float distortion_weight, float sparsity_weight, float *d_g_raw, float *d_losses, float *d_weights_out, void *d_workspace,
+                                 size_t workspace_bytes, void *stream);
 /* nrf_mlp_backward for a NeRFSmall WITH the predicted-normals head and a g_out [p,7] whose columns 4:7 carry a gradient: they go back through the normals net (its
  * weight gradients are accumulated into d_g_params), and the gradient of its input cat[sigma, geo_feat, input_pts] (NeRF.cpp:396) is added to the sigma net's output
  * gradient and to d_g_x.  With g_out[:, 4:7] == 0 the first two nets' gradients and d_g_x equal nrf_mlp_backward's and the head's are 0.  (nrf_mlp_backward on such a

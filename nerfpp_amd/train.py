@@ -22,7 +22,7 @@ from .renderer import NeRFRenderer, NeRFRenderParams, RngFill, StochasticPrecond
 class Trainer:
     def __init__(self, embedder: _HashBase, embeddirs, mlp: NeRFSmall, table, mlp_blob, learning_rate=5e-4, betas=(0.9, 0.99), eps=1e-15,
                  tv_loss_weight=0.0, seed=0, mlp_backward="f32", hash_backward="f32", grad_sync=None, train_dense_budget=256 << 20,
-                 pred_normal_loss_weight=0.0, orientation_loss_weight=0.0):
+                 pred_normal_loss_weight=0.0, orientation_loss_weight=0.0, distortion_loss_weight=0.0, sparsity_loss_weight=0.0):
         # two configurations of the reference's train loop (NeRFExecutor.h:862-995): hash grid + NeRFSmall (main.cpp:220-221) and the classic PE(10) / PE(4) + NeRF 8x256
         # (NeRFImpl is a legal TNeRF of the same loop; its embedders have no parameters: `table` is None / empty there)
         self.has_table = isinstance(embedder, _HashBase)
@@ -64,6 +64,13 @@ class Trainer:
             if mlp_backward != "f32":
                 raise L.NrfError("pred_normal_loss_weight / orientation_loss_weight: the head trains through the fp32 layer kernels (mlp_backward='f32')")
         self.normal_losses = torch.zeros((2,), device=dev)          # [PredNormalLoss, OrientationLoss] of the last step, unweighted, on the device
+        # The distortion loss of mip-NeRF 360 on the fine pass's weights and the reference's SigmaSparsityLoss (NeRF.h:302-306, declared there and never called): one kernel
+        # (nrf_ray_regularizers) adds their gradient to d loss / d raw[..., 3] before the keep mask, so every backward path below is served.  Both 0: no call is issued
+        self.distortion_loss_weight, self.sparsity_loss_weight = float(distortion_loss_weight), float(sparsity_loss_weight)
+        if not (0.0 <= self.distortion_loss_weight < math.inf and 0.0 <= self.sparsity_loss_weight < math.inf):
+            raise L.NrfError("distortion_loss_weight / sparsity_loss_weight must be finite and >= 0")
+        self.ray_losses = torch.zeros((2,), device=dev)             # [L_dist, L_sparse] of the last step, unweighted, on the device
+        self._rws = None
         # "f32": one float atomic per feature; "packed": both features of an entry in one 64-bit fixed-point atomic (nrf_hash_backward_rays_packed);
         # "binned": the same fixed-point contributions merged per table range in LDS before they reach memory (nrf_hash_backward_rays_binned; equals "packed" bit for bit)
         if hash_backward not in ("f32", "packed", "binned"):
@@ -158,6 +165,14 @@ class Trainer:
                 self._nws = torch.empty((int(nbl),), device="cuda", dtype=torch.uint8)
             L.check(lib.nrf_normal_losses(_ptr(w), _ptr(dgrad), _ptr(raw), c, C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, C.c_float(self.pred_normal_loss_weight),
                                           C.c_float(self.orientation_loss_weight), _ptr(g_raw), _ptr(self.normal_losses), _ptr(self._nws), C.c_size_t(self._nws.numel()), _stream()))
+        if self.distortion_loss_weight > 0 or self.sparsity_loss_weight > 0:
+            # the same raw, depths, draws and directions as the RawToOutputs backward above; in a 64+128 step these are the fine pass's 192 samples (the only ones with a gradient)
+            nbr = lib.nrf_ray_regularizers_workspace_bytes(C.c_int64(n), s)
+            if self._rws is None or self._rws.numel() < nbr:
+                self._rws = torch.empty((int(nbr),), device="cuda", dtype=torch.uint8)
+            L.check(lib.nrf_ray_regularizers(_ptr(raw), _ptr(z), C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, c, _ptr(noise), C.c_float(noise_std),
+                                             C.c_float(self.distortion_loss_weight), C.c_float(self.sparsity_loss_weight), _ptr(g_raw), _ptr(self.ray_losses), None,
+                                             _ptr(self._rws), C.c_size_t(self._rws.numel()), _stream()))
         dirs, _ = self.embeddirs.forward(rays[:, 8:11].contiguous())
         in_ch = self.embedder.GetOutputDims()
         self.g_blob.zero_(); self.g_table.zero_()

@@ -5,6 +5,7 @@ fallback: if the shared object is missing, importing the compute API raises.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NRF_LIB_PATH") or os.path.join(_HERE, "lib", "libnerfpp_hip.so")   # NRF_LIB_PATH: tuning builds only
@@ -72,43 +73,215 @@ class View(C.Structure):          # nrf_view
                 ("row0", C.c_int), ("rows", C.c_int), ("use_viewdirs", C.c_int), ("ndc", C.c_int), ("chunk", C.c_int), ("bbox", C.c_float * 6)]
 
 
-# every symbol include/nerfpp_hip.h declares (tests check the library exports all of them)
-SYMBOLS = [
-    "nrf_version", "nrf_last_error", "nrf_status_string",
-    "nrf_get_rays", "nrf_ndc_rays", "nrf_aabb", "nrf_pack_rays", "nrf_pack_rays_viewsrc", "nrf_view_rays", "nrf_near_far_range", "nrf_near_far_range_device", "nrf_linspace", "nrf_z_vals", "nrf_points",
-    "nrf_precrop_bounds", "nrf_rand_pixels", "nrf_ray_batch", "nrf_gather_pixels",
-    "nrf_pe_encode", "nrf_sh_encode",
-    "nrf_hash_create", "nrf_hash_destroy", "nrf_hash_output_dims", "nrf_hash_table_elems", "nrf_hash_set_table", "nrf_hash_set_primes", "nrf_hash_set_dense_budget", "nrf_hash_get_dense_budget", "nrf_hash_get_level_scales", "nrf_hash_set_level_scales",
-    "nrf_hash_encode",
-    "nrf_mlp_small_param_count", "nrf_mlp_nerf_param_count", "nrf_mlp_small_create", "nrf_mlp_nerf_create", "nrf_mlp_destroy",
-    "nrf_mlp_output_dims", "nrf_mlp_forward",
-    "nrf_mlp_lerf_param_count", "nrf_mlp_lerf_create",
-    "nrf_lerf_mfma_available", "nrf_lerf_set_precision", "nrf_lerf_sigma", "nrf_lerf_render_embedding",
-    "nrf_raw2outputs", "nrf_raw2weights", "nrf_raw2weights_gather", "nrf_render_clip_embedding", "nrf_sample_pdf", "nrf_fine_depths", "nrf_fine_depths_merge",
-    "nrf_rng_fill", "nrf_jitter_z", "nrf_tangent_scatter", "nrf_precondition", "nrf_raw2outputs_noise", "nrf_sample_pdf_rand", "nrf_fine_depths_rand",
-    "nrf_renderer_create", "nrf_renderer_destroy", "nrf_run_network_workspace_bytes", "nrf_run_network",
-    "nrf_density_grid_workspace_bytes", "nrf_density_grid", "nrf_density_grad_workspace_bytes", "nrf_density_grad", "nrf_isosurface_workspace_bytes", "nrf_isosurface_count", "nrf_isosurface_emit",
-    "nrf_render_rays_workspace_bytes", "nrf_render_rays", "nrf_batchify_rays_workspace_bytes", "nrf_batchify_rays", "nrf_render_rows_workspace_bytes", "nrf_render_rows",
-    "nrf_render_rays_normals_workspace_bytes", "nrf_render_rays_normals", "nrf_batchify_rays_normals_workspace_bytes", "nrf_batchify_rays_normals",
-    "nrf_render_rows_normals_workspace_bytes", "nrf_render_rows_normals",
-    "nrf_normalize_depth", "nrf_to_u8",
-    "nrf_huber_loss", "nrf_raw2outputs_backward", "nrf_raw2outputs_backward_noise", "nrf_mask_sigma_grad", "nrf_mlp_backward_workspace_bytes", "nrf_mlp_backward", "nrf_mlp_backward_f16_workspace_bytes", "nrf_mlp_backward_f16", "nrf_mlp_backward_f16_lm", "nrf_mlp_backward_f16_flags", "nrf_hash_encode_lm_f16", "nrf_hash_encode_lm_f16_strided", "nrf_lerf_sigma_lm", "nrf_lerf_sigma_lm_strided", "nrf_lerf_render_embedding_lm", "nrf_lerf_render_embedding_lm_gather", "nrf_lerf_geo_bytes", "nrf_lerf_sigma_geo_lm_strided", "nrf_lerf_sigma_exact_available", "nrf_lerf_sigma_exact_lm_strided", "nrf_lerf_render_embedding_lm_geo", "nrf_hash_backward_packed_workspace_bytes", "nrf_hash_backward_rays_packed", "nrf_hash_backward_binned_workspace_bytes", "nrf_hash_backward_binned_workspace_bytes_for", "nrf_hash_backward_rays_binned", "nrf_mlp_set_params", "nrf_mlp_device_repack_images", "nrf_mlp_set_input_rms_hint", "nrf_mlp_set_split_scaling", "nrf_mlp_get_split_scales", "nrf_renderer_nonfinite", "nrf_hash_memory_bytes", "nrf_lerf_renderer_nonfinite",
-    "nrf_hash_backward", "nrf_hash_backward_rays", "nrf_hash_tv_loss", "nrf_adam_step", "nrf_adam_step_guarded", "nrf_renderer_last_features", "nrf_mlp_backward_f16_lm_src", "nrf_mask_sigma_grad_src", "nrf_mlp_backward_f16_flags_async", "nrf_mlp_backward_f16_flags_device",
-    "nrf_normal_losses_workspace_bytes", "nrf_normal_losses", "nrf_mlp_backward_pn_workspace_bytes", "nrf_mlp_backward_pn",
-    "nrf_ray_regularizers_workspace_bytes", "nrf_ray_regularizers",
-    "nrf_render_view_dims",
-    "nrf_tile_partition", "nrf_comm_unique_id", "nrf_comm_create", "nrf_comm_create_timeout", "nrf_comm_wrap", "nrf_comm_destroy", "nrf_comm_world", "nrf_comm_rank", "nrf_allgather_tiles", "nrf_allreduce_grads",
-    "nrf_profile_enable", "nrf_profile_is_enabled", "nrf_profile_read", "nrf_set_render_lanes", "nrf_get_render_lanes", "nrf_renderer_set_lanes", "nrf_lerf_renderer_set_lanes",
-    "nrf_lerf_relevancy", "nrf_relevancy_image", "nrf_colormap_jet_u8", "nrf_colormap_jet_lut",
-    "nrf_lerf_head_relevancy_workspace_bytes", "nrf_lerf_head_relevancy", "nrf_lerf_point_relevancy_workspace_bytes", "nrf_lerf_point_relevancy",
-    "nrf_lerf_relevancy_grid_workspace_bytes", "nrf_lerf_relevancy_grid",
-    "nrf_lerf_renderer_create", "nrf_lerf_renderer_destroy", "nrf_lerf_set_prompts", "nrf_lerf_render_rays_workspace_bytes", "nrf_lerf_render_rays",
-    "nrf_lerf_batchify_rays_workspace_bytes", "nrf_lerf_batchify_rays", "nrf_lerf_render_rows_workspace_bytes", "nrf_lerf_render_rows",
-    "nrf_fp32_gemm_available", "nrf_get_train_gemm", "nrf_set_train_gemm", "nrf_gemm_nt_bf16x3", "nrf_gemm_nt_f16x3", "nrf_gemm_tn_bf16x3", "nrf_layer_grad_split", "nrf_huber_rows_nanmean", "nrf_lerf_head_backward_workspace_bytes", "nrf_lerf_head_backward", "nrf_lerf_backward_points_workspace_bytes", "nrf_lerf_backward_points",
-    "nrf_lerf_renderer_last_features", "nrf_lerf_backward_points_src", "nrf_scratch_trim",
-    "nrf_pyramid_level_geometry", "nrf_pyramid_max_zoom_out", "nrf_pyramid_create", "nrf_pyramid_destroy", "nrf_pyramid_memory_bytes", "nrf_pyramid_set_entries",
-    "nrf_pyramid_pixel_values", "nrf_pyramid_relevancy_preview_workspace_bytes", "nrf_pyramid_relevancy_preview",
-]
+# The C ABI: one line per NRF_API function of include/nerfpp_hip.h, in the header's order, as name(argument kinds)->return kind.
+# Kinds: i int, l int64_t, z size_t, f float, d double, u uint32_t, q uint64_t, p any pointer (data, handle, struct, out-parameter,
+# pointer array, stream); returns also s const char * and v void, and no arrow means the int status.  lib() turns each line into
+# argtypes / restype, so call sites pass plain Python values; tests/test_host_cpu.py holds every line to the header.
+_KINDS = {"i": C.c_int, "l": C.c_int64, "z": C.c_size_t, "f": C.c_float, "d": C.c_double, "u": C.c_uint32, "q": C.c_uint64, "p": C.c_void_p,
+          "s": C.c_char_p, "v": None}
+_ABI = """
+    nrf_version()
+    nrf_last_error()->s
+    nrf_status_string(i)->s
+    nrf_get_rays(iippiipppp)
+    nrf_ndc_rays(iiffpplppp)
+    nrf_precrop_bounds(iiiifp)
+    nrf_rand_pixels(qliiiilppp)
+    nrf_ray_batch(pppplpppp)
+    nrf_gather_pixels(piiipplpp)
+    nrf_aabb(ppplfppp)
+    nrf_pack_rays(ppplipp)
+    nrf_pack_rays_viewsrc(pppplpp)
+    nrf_view_rays(pppp)
+    nrf_near_far_range(plippp)
+    nrf_near_far_range_device(plipp)
+    nrf_linspace(ffip)
+    nrf_z_vals(pilpiipp)
+    nrf_points(piplipp)
+    nrf_pe_encode(plipp)
+    nrf_sh_encode(pliipp)
+    nrf_hash_create(pp)
+    nrf_hash_destroy(p)->v
+    nrf_hash_output_dims(p)
+    nrf_hash_table_elems(p)->l
+    nrf_hash_set_table(ppip)
+    nrf_hash_set_primes(ppp)
+    nrf_hash_set_dense_budget(plp)
+    nrf_hash_get_dense_budget(p)->l
+    nrf_hash_memory_bytes(ppp)
+    nrf_hash_get_level_scales(pp)
+    nrf_hash_set_level_scales(ppp)
+    nrf_hash_encode(pplppp)
+    nrf_hash_encode_lm_f16(pplppp)
+    nrf_hash_encode_lm_f16_strided(pplplpp)
+    nrf_mlp_small_param_count(p)->l
+    nrf_mlp_nerf_param_count(p)->l
+    nrf_mlp_lerf_param_count(p)->l
+    nrf_mlp_lerf_create(ppipp)
+    nrf_mlp_small_create(ppipp)
+    nrf_mlp_nerf_create(ppipp)
+    nrf_mlp_destroy(p)->v
+    nrf_mlp_output_dims(p)
+    nrf_mlp_forward(pplipp)
+    nrf_raw2outputs(pppiliiipppppp)
+    nrf_raw2weights(piippilippppp)
+    nrf_raw2weights_gather(piipppilippppp)
+    nrf_lerf_mfma_available(p)
+    nrf_lerf_set_precision(pi)
+    nrf_lerf_sigma(ppplpp)
+    nrf_lerf_render_embedding(ppplipp)
+    nrf_lerf_sigma_lm(ppplpp)
+    nrf_lerf_render_embedding_lm(ppplipp)
+    nrf_lerf_sigma_lm_strided(pplplpp)
+    nrf_lerf_geo_bytes(l)->z
+    nrf_lerf_sigma_geo_lm_strided(pplplpplp)
+    nrf_lerf_sigma_exact_available(p)
+    nrf_lerf_sigma_exact_lm_strided(pplplpplp)
+    nrf_lerf_render_embedding_lm_geo(pplpplplipp)
+    nrf_lerf_render_embedding_lm_gather(pplpplipp)
+    nrf_render_clip_embedding(piiplipp)
+    nrf_lerf_relevancy(plipipiipp)
+    nrf_relevancy_image(plipp)
+    nrf_colormap_jet_u8(plpp)
+    nrf_colormap_jet_lut(p)
+    nrf_pyramid_level_geometry(iiifip)
+    nrf_pyramid_max_zoom_out(piip)
+    nrf_pyramid_create(iifiipp)
+    nrf_pyramid_destroy(p)
+    nrf_pyramid_memory_bytes(p)->l
+    nrf_pyramid_set_entries(plppip)
+    nrf_pyramid_pixel_values(pifpplplp)
+    nrf_pyramid_relevancy_preview_workspace_bytes(pii)->z
+    nrf_pyramid_relevancy_preview(pifpipiipppzp)
+    nrf_sample_pdf(pplipiippp)
+    nrf_fine_depths(pplipiipp)
+    nrf_fine_depths_merge(pplipiipppp)
+    nrf_rng_fill(quqlipp)
+    nrf_jitter_z(pplipp)
+    nrf_tangent_scatter(ppiplifppppp)
+    nrf_precondition(ppfplpp)
+    nrf_raw2outputs_noise(pppiliiipfpppppp)
+    nrf_sample_pdf_rand(pplipiippp)
+    nrf_fine_depths_rand(pplipiipp)
+    nrf_renderer_create(pp)
+    nrf_renderer_destroy(p)->v
+    nrf_renderer_last_features(pppppppp)
+    nrf_renderer_nonfinite(ppp)
+    nrf_run_network_workspace_bytes(pli)->z
+    nrf_run_network(pppliippzp)
+    nrf_density_grid_workspace_bytes(piiil)->z
+    nrf_density_grid(ppiiiplpzp)
+    nrf_isosurface_workspace_bytes(iii)->z
+    nrf_isosurface_count(piiipfppppzp)
+    nrf_isosurface_emit(piiipfpppllpzp)
+    nrf_density_grad_workspace_bytes(pl)->z
+    nrf_density_grad(pplpppzp)
+    nrf_render_rays_workspace_bytes(plp)->z
+    nrf_render_rays(ppilpppppzp)
+    nrf_batchify_rays_workspace_bytes(plip)->z
+    nrf_batchify_rays(ppilipppppzp)
+    nrf_render_rows_workspace_bytes(ppp)->z
+    nrf_render_rows(pppppppppzp)
+    nrf_render_rays_normals_workspace_bytes(plpi)->z
+    nrf_render_rays_normals(ppilppppppzp)
+    nrf_batchify_rays_normals_workspace_bytes(plipi)->z
+    nrf_batchify_rays_normals(ppilippppppzp)
+    nrf_render_rows_normals_workspace_bytes(pppi)->z
+    nrf_render_rows_normals(ppppppppppzp)
+    nrf_huber_loss(pplppp)
+    nrf_raw2outputs_backward(pppiliiippp)
+    nrf_raw2outputs_backward_noise(pppiliiipfppp)
+    nrf_mask_sigma_grad(plipp)
+    nrf_mlp_backward_workspace_bytes(pl)->z
+    nrf_mlp_backward(ppplpppzp)
+    nrf_normal_losses_workspace_bytes(li)->z
+    nrf_normal_losses(pppipiliffpppzp)
+    nrf_ray_regularizers_workspace_bytes(li)->z
+    nrf_ray_regularizers(pppiliipfffppppzp)
+    nrf_mlp_backward_pn_workspace_bytes(pl)->z
+    nrf_mlp_backward_pn(ppplpppzp)
+    nrf_mlp_backward_f16_workspace_bytes(pl)->z
+    nrf_mlp_backward_f16(ppplpppzp)
+    nrf_mlp_backward_f16_lm(pppiplpppzp)
+    nrf_mlp_backward_f16_lm_src(pplppiplpppzp)
+    nrf_mask_sigma_grad_src(pplipp)
+    nrf_mlp_backward_f16_flags(ppp)
+    nrf_mlp_backward_f16_flags_async(ppp)
+    nrf_mlp_backward_f16_flags_device(p)->p
+    nrf_mlp_set_params(ppip)
+    nrf_mlp_device_repack_images(p)
+    nrf_mlp_set_input_rms_hint(pfp)
+    nrf_mlp_set_split_scaling(pip)
+    nrf_mlp_get_split_scales(pppp)
+    nrf_hash_backward(pplppp)
+    nrf_hash_backward_rays(pplippp)
+    nrf_hash_backward_packed_workspace_bytes(p)->z
+    nrf_hash_backward_rays_packed(pplipppzp)
+    nrf_hash_backward_binned_workspace_bytes(pi)->z
+    nrf_hash_backward_binned_workspace_bytes_for(pli)->z
+    nrf_hash_backward_rays_binned(pplipppzp)
+    nrf_hash_tv_loss(ppipifppp)
+    nrf_adam_step(pppplffffip)
+    nrf_adam_step_guarded(pppplffffipip)
+    nrf_normalize_depth(plffpp)
+    nrf_to_u8(plpp)
+    nrf_render_view_dims(iipfppp)
+    nrf_tile_partition(iiipp)
+    nrf_comm_unique_id(p)
+    nrf_comm_create(piip)
+    nrf_comm_create_timeout(piidp)
+    nrf_comm_wrap(pp)
+    nrf_comm_destroy(p)->v
+    nrf_comm_world(p)
+    nrf_comm_rank(p)
+    nrf_allgather_tiles(ppiiiipp)
+    nrf_allreduce_grads(pppilipp)
+    nrf_lerf_renderer_create(pp)
+    nrf_lerf_renderer_destroy(p)->v
+    nrf_lerf_renderer_nonfinite(pp)
+    nrf_lerf_renderer_set_lanes(pi)
+    nrf_lerf_set_prompts(ppipiip)
+    nrf_lerf_render_rays_workspace_bytes(plp)->z
+    nrf_lerf_render_rays(ppilpppppzp)
+    nrf_lerf_batchify_rays_workspace_bytes(plip)->z
+    nrf_lerf_batchify_rays(ppilipppppzp)
+    nrf_lerf_render_rows_workspace_bytes(ppp)->z
+    nrf_lerf_render_rows(pppppppppzp)
+    nrf_lerf_head_relevancy_workspace_bytes(plii)->z
+    nrf_lerf_head_relevancy(pplpipiiipppzp)
+    nrf_lerf_point_relevancy_workspace_bytes(plil)->z
+    nrf_lerf_point_relevancy(ppliipplpzp)
+    nrf_lerf_relevancy_grid_workspace_bytes(piiiil)->z
+    nrf_lerf_relevancy_grid(ppiiiiipplpzp)
+    nrf_huber_rows_nanmean(pplifppp)
+    nrf_lerf_head_backward_workspace_bytes(pli)->z
+    nrf_lerf_head_backward(pppppilipfppppppzp)
+    nrf_lerf_backward_points_workspace_bytes(pli)->z
+    nrf_lerf_backward_points(ppppilipfppppzp)
+    nrf_lerf_renderer_last_features(pppppppp)
+    nrf_lerf_backward_points_src(pplpppppilipfppppzp)
+    nrf_scratch_trim()->z
+    nrf_set_render_lanes(i)
+    nrf_get_render_lanes()
+    nrf_renderer_set_lanes(pi)
+    nrf_fp32_gemm_available()
+    nrf_get_train_gemm()
+    nrf_set_train_gemm(i)
+    nrf_gemm_nt_bf16x3(pilipiipipip)
+    nrf_gemm_tn_bf16x3(piipiilpiip)
+    nrf_layer_grad_split(piipiilpiipp)
+    nrf_gemm_nt_f16x3(pilipiipipip)
+    nrf_profile_enable(i)
+    nrf_profile_is_enabled()
+    nrf_profile_read(ppi)
+"""
+SIGNATURES = {}          # name -> (return kind, argument kinds); a line that is not an entry stops the import, naming itself
+for _entry in _ABI.split():
+    _m = re.fullmatch(r"(nrf_\w+)\(([ilzfduqp]*)\)(?:->([lzpsv]))?", _entry)
+    if _m is None or _m[1] in SIGNATURES:
+        raise ValueError(f"nerfpp_amd._lib: malformed or repeated signature entry {_entry!r}")
+    SIGNATURES[_m[1]] = (_m[3] or "i", _m[2])
+SYMBOLS = list(SIGNATURES)
 NRF_COMM_ID_BYTES = 128
 
 _lib = None
@@ -125,44 +298,10 @@ def lib():
             raise NrfError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(there is no CPU fallback for the HIP path)")
         L = C.CDLL(LIB_PATH)
-        L.nrf_last_error.restype = C.c_char_p
-        L.nrf_status_string.restype = C.c_char_p
-        L.nrf_hash_table_elems.restype = C.c_int64
-        L.nrf_mlp_backward_f16_flags_device.restype = C.c_void_p
-        L.nrf_hash_get_dense_budget.restype = C.c_int64
-        L.nrf_mlp_small_param_count.restype = C.c_int64
-        L.nrf_mlp_nerf_param_count.restype = C.c_int64
-        L.nrf_mlp_lerf_param_count.restype = C.c_int64
-        L.nrf_scratch_trim.restype = C.c_size_t
-        L.nrf_run_network_workspace_bytes.restype = C.c_size_t
-        L.nrf_density_grid_workspace_bytes.restype = C.c_size_t
-        L.nrf_density_grad_workspace_bytes.restype = C.c_size_t
-        L.nrf_isosurface_workspace_bytes.restype = C.c_size_t
-        L.nrf_render_rays_workspace_bytes.restype = C.c_size_t
-        L.nrf_batchify_rays_workspace_bytes.restype = C.c_size_t
-        L.nrf_render_rows_workspace_bytes.restype = C.c_size_t
-        L.nrf_render_rays_normals_workspace_bytes.restype = C.c_size_t
-        L.nrf_batchify_rays_normals_workspace_bytes.restype = C.c_size_t
-        L.nrf_render_rows_normals_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_render_rays_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_head_relevancy_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_point_relevancy_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_relevancy_grid_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_batchify_rays_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_render_rows_workspace_bytes.restype = C.c_size_t
-        L.nrf_mlp_backward_workspace_bytes.restype = C.c_size_t
-        L.nrf_mlp_backward_f16_workspace_bytes.restype = C.c_size_t
-        L.nrf_mlp_backward_pn_workspace_bytes.restype = C.c_size_t
-        L.nrf_normal_losses_workspace_bytes.restype = C.c_size_t
-        L.nrf_ray_regularizers_workspace_bytes.restype = C.c_size_t
-        L.nrf_hash_backward_binned_workspace_bytes.restype = C.c_size_t
-        L.nrf_hash_backward_binned_workspace_bytes_for.restype = C.c_size_t
-        L.nrf_lerf_geo_bytes.restype = C.c_size_t
-        L.nrf_hash_backward_packed_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_head_backward_workspace_bytes.restype = C.c_size_t
-        L.nrf_lerf_backward_points_workspace_bytes.restype = C.c_size_t
-        L.nrf_pyramid_memory_bytes.restype = C.c_int64
-        L.nrf_pyramid_relevancy_preview_workspace_bytes.restype = C.c_size_t
+        for name, (ret, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = _KINDS[ret]
+            fn.argtypes = [_KINDS[k] for k in args]
         _lib = L
     return _lib
 

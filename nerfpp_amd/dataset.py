@@ -53,14 +53,14 @@ def GetRayBatch(rand_h, rand_w, H, W, K, c2w):
     o = torch.empty((n, 3), device=rh.device, dtype=torch.float32); d = torch.empty_like(o)
     cone = C.c_float(0)
     k, m = _k9(K), _m12(c2w)
-    L.check(L.lib().nrf_ray_batch(k.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), _ptr(rh), _ptr(rw), C.c_int64(n), _ptr(o), _ptr(d), C.byref(cone), _stream()))
+    L.check(L.lib().nrf_ray_batch(k.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), _ptr(rh), _ptr(rw), n, _ptr(o), _ptr(d), C.byref(cone), _stream()))
     return o, d, torch.tensor(cone.value, dtype=torch.float32)
 
 
 def CalculateBounds(h, w, current_iter, precorp_iters, precorp_frac):
     """NeRFDataset::CalculateBounds (NeRFDataset.cpp:44-65) -> (h_start, h_end, w_start, w_end), inclusive."""
     out = (C.c_int * 4)()
-    L.check(L.lib().nrf_precrop_bounds(int(h), int(w), int(current_iter), int(precorp_iters), C.c_float(precorp_frac), out))
+    L.check(L.lib().nrf_precrop_bounds(int(h), int(w), int(current_iter), int(precorp_iters), precorp_frac, out))
     return tuple(out)
 
 
@@ -89,13 +89,13 @@ class NeRFDataset:
         h0, h1, w0, w1 = CalculateBounds(v.H, v.W, self.CurrentIter, self.PrecorpIters, self.PrecorpFrac)
         n = self.BatchSize
         rh = torch.empty((n,), device="cuda", dtype=torch.int64); rw = torch.empty_like(rh)
-        L.check(L.lib().nrf_rand_pixels(C.c_uint64(self.Seed), C.c_int64(self.CurrentIter), h0, h1, w0, w1, C.c_int64(n), _ptr(rh), _ptr(rw), _stream()))
+        L.check(L.lib().nrf_rand_pixels(self.Seed, self.CurrentIter, h0, h1, w0, w1, n, _ptr(rh), _ptr(rw), _stream()))
         target = None
         if v.Image is not None:
             img = _dev_f32(v.Image)
             c = img.shape[-1]
             target = torch.empty((n, c), device=img.device, dtype=torch.float32)
-            L.check(L.lib().nrf_gather_pixels(_ptr(img), v.H, v.W, c, _ptr(rh), _ptr(rw), C.c_int64(n), _ptr(target), _stream()))
+            L.check(L.lib().nrf_gather_pixels(_ptr(img), v.H, v.W, c, _ptr(rh), _ptr(rw), n, _ptr(target), _stream()))
         o, d, cone = GetRayBatch(rh, rw, v.H, v.W, v.K, v.Pose)
         out = dict(rays_o=o, rays_d=d, cone_angle=cone, Near=v.Near, Far=v.Far, target_s=target, rand_h=rh, rand_w=rw)
         if self.LeRFParams is not None:

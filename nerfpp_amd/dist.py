@@ -85,7 +85,7 @@ class TileComm:
             dist.broadcast_object_list(box, src=0, group=group)
             buf = (C.c_ubyte * L.NRF_COMM_ID_BYTES).from_buffer_copy(box[0])
         self._c = C.c_void_p()
-        L.check(L.lib().nrf_comm_create_timeout(buf, self.world, self.rank, C.c_double(float(timeout_s)), C.byref(self._c)))
+        L.check(L.lib().nrf_comm_create_timeout(buf, self.world, self.rank, float(timeout_s), C.byref(self._c)))
         self._side = None
 
     class _Pending:
@@ -110,8 +110,7 @@ class TileComm:
             st = self._side
             st.wait_stream(cur)                      # the tiles' producers
             tiles.record_stream(st); out.record_stream(st)
-        L.check(L.lib().nrf_allgather_tiles(self._c, C.c_void_p(tiles.data_ptr()), int(f), int(h), int(w), int(c), C.c_void_p(out.data_ptr()),
-                                            C.c_void_p(st.cuda_stream)))
+        L.check(L.lib().nrf_allgather_tiles(self._c, tiles.data_ptr(), int(f), int(h), int(w), int(c), out.data_ptr(), st.cuda_stream))
         if not overlap:
             return out
         ev = torch.cuda.Event()
@@ -130,8 +129,8 @@ class TileComm:
         ptrs = (C.c_void_p * max(n, 1))(*[g.data_ptr() for g in gs])
         counts = (C.c_int64 * max(n, 1))(*[g.numel() for g in gs])
         skip = C.c_int(0)
-        L.check(L.lib().nrf_allreduce_grads(self._c, ptrs, counts, n, C.c_int64(int(bucket_bytes)), -1 if overflow is None else int(bool(overflow)), C.byref(skip),
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        L.check(L.lib().nrf_allreduce_grads(self._c, ptrs, counts, n, int(bucket_bytes), -1 if overflow is None else int(bool(overflow)), C.byref(skip),
+                                            torch.cuda.current_stream().cuda_stream))
         return bool(skip.value)
 
     def close(self):

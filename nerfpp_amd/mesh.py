@@ -61,12 +61,12 @@ def DensityGrid(renderer, bbox=None, resolution=256, slab_points=None):
     embedder's GetBoundingBox(); resolution is an int or (nx, ny, nz)."""
     nx, ny, nz = _resolution(resolution)
     bb = _bbox(renderer, bbox)
-    slab = C.c_int64(0 if slab_points is None else int(slab_points))
+    slab = 0 if slab_points is None else int(slab_points)
     lib = L.lib()
     dev = torch.device("cuda", torch.cuda.current_device())
     sigma = torch.empty((nz, ny, nx), device=dev, dtype=torch.float32)
     ws = torch.empty((int(lib.nrf_density_grid_workspace_bytes(renderer._r, nx, ny, nz, slab)),), device=dev, dtype=torch.uint8)
-    L.check(lib.nrf_density_grid(renderer._r, bb.ctypes.data_as(C.c_void_p), nx, ny, nz, _ptr(sigma), slab, _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+    L.check(lib.nrf_density_grid(renderer._r, bb.ctypes.data_as(C.c_void_p), nx, ny, nz, _ptr(sigma), slab, _ptr(ws), ws.numel(), _stream()))
     return sigma
 
 
@@ -81,13 +81,13 @@ def Isosurface(sigma, bbox, threshold):
     lib = L.lib()
     ws = torch.empty((int(lib.nrf_isosurface_workspace_bytes(nx, ny, nz)),), device=f.device, dtype=torch.uint8)
     nv, nt, nbad = C.c_int64(), C.c_int64(), C.c_int64()
-    L.check(lib.nrf_isosurface_count(_ptr(f), nx, ny, nz, bb.ctypes.data_as(C.c_void_p), C.c_float(threshold), C.byref(nv), C.byref(nt), C.byref(nbad),
-                                     _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+    L.check(lib.nrf_isosurface_count(_ptr(f), nx, ny, nz, bb.ctypes.data_as(C.c_void_p), threshold, C.byref(nv), C.byref(nt), C.byref(nbad),
+                                     _ptr(ws), ws.numel(), _stream()))
     verts = torch.empty((nv.value, 3), device=f.device, dtype=torch.float32)
     faces = torch.empty((nt.value, 3), device=f.device, dtype=torch.int32)
     normals = torch.empty_like(verts)
-    L.check(lib.nrf_isosurface_emit(_ptr(f), nx, ny, nz, bb.ctypes.data_as(C.c_void_p), C.c_float(threshold), _ptr(verts), _ptr(faces), _ptr(normals),
-                                    nv, nt, _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+    L.check(lib.nrf_isosurface_emit(_ptr(f), nx, ny, nz, bb.ctypes.data_as(C.c_void_p), threshold, _ptr(verts), _ptr(faces), _ptr(normals),
+                                    nv, nt, _ptr(ws), ws.numel(), _stream()))
     return verts, faces, normals
 
 
@@ -104,7 +104,7 @@ def DensityGradient(renderer, pts):
     x = x.reshape(-1, 3).contiguous()
     sigma = torch.empty(lead, device=x.device, dtype=torch.float32)
     grad = torch.empty(lead + (3,), device=x.device, dtype=torch.float32)
-    L.check(L.lib().nrf_density_grad(renderer._r, _ptr(x), C.c_int64(x.shape[0]), _ptr(sigma), _ptr(grad), None, C.c_size_t(0), _stream()))
+    L.check(L.lib().nrf_density_grad(renderer._r, _ptr(x), x.shape[0], _ptr(sigma), _ptr(grad), None, 0, _stream()))
     return sigma, grad
 
 

@@ -51,7 +51,7 @@ class Embedder(BaseEmbedder):
     def forward(self, x):
         x = _dev_f32(x).reshape(-1, 3)
         out = torch.empty((x.shape[0], self.GetOutputDims()), device=x.device, dtype=torch.float32)
-        L.check(L.lib().nrf_pe_encode(_ptr(x), C.c_int64(x.shape[0]), self.multires, _ptr(out), _stream()))
+        L.check(L.lib().nrf_pe_encode(_ptr(x), x.shape[0], self.multires, _ptr(out), _stream()))
         return out, None
 
 
@@ -69,7 +69,7 @@ class SHEncoder(BaseEmbedder):
     def forward(self, x):
         x = _dev_f32(x).reshape(-1, 3)
         out = torch.empty((x.shape[0], self.GetOutputDims()), device=x.device, dtype=torch.float32)
-        L.check(L.lib().nrf_sh_encode(_ptr(x), C.c_int64(x.shape[0]), self.degree, self.variant, _ptr(out), _stream()))
+        L.check(L.lib().nrf_sh_encode(_ptr(x), x.shape[0], self.degree, self.variant, _ptr(out), _stream()))
         return out, None
 
 
@@ -115,7 +115,7 @@ class _HashBase(BaseEmbedder):
     def set_dense_budget(self, nbytes):
         """Bytes of baked dense image for the coarse levels of the renderer's fast path (nrf_hash_set_dense_budget; 0 = every level hashed: what a
         training loop, which re-uploads the table every step, wants)."""
-        L.check(L.lib().nrf_hash_set_dense_budget(self._h, C.c_int64(int(nbytes)), _stream()))
+        L.check(L.lib().nrf_hash_set_dense_budget(self._h, int(nbytes), _stream()))
         self.dense_budget = int(nbytes)
 
     def level_scales(self):
@@ -146,7 +146,7 @@ class _HashBase(BaseEmbedder):
         x = _dev_f32(x).reshape(-1, 3)
         out = torch.empty((x.shape[0], self.GetOutputDims()), device=x.device, dtype=torch.float32)
         mask = torch.empty((x.shape[0],), device=x.device, dtype=torch.uint8)
-        L.check(L.lib().nrf_hash_encode(self._h, _ptr(x), C.c_int64(x.shape[0]), _ptr(out), _ptr(mask), _stream()))
+        L.check(L.lib().nrf_hash_encode(self._h, _ptr(x), x.shape[0], _ptr(out), _ptr(mask), _stream()))
         return out, mask.bool()
 
 
@@ -202,7 +202,7 @@ class BaseNeRF:
         x = x.reshape(-1, x.shape[-1])
         out = torch.empty((x.shape[0], self.GetOutputDims()), device=x.device, dtype=torch.float32)
         prec = self.precision if precision is None else precision
-        L.check(L.lib().nrf_mlp_forward(self._m, _ptr(x), C.c_int64(x.shape[0]), prec, _ptr(out), _stream()))
+        L.check(L.lib().nrf_mlp_forward(self._m, _ptr(x), x.shape[0], prec, _ptr(out), _stream()))
         return out
 
     __call__ = forward

@@ -38,7 +38,7 @@ def MaxZoomOut(views, clip):
 def LevelGeometry(img_w, img_h, clip, overlap, zoom):
     """(win, nw, nh) of one pyramid level (GetNearestPatchIndicesSingleScale, PyramidEmbedder.cpp:15-19); nw or nh <= 0: no grid at that level."""
     out = (C.c_int * 3)()
-    L.check(L.lib().nrf_pyramid_level_geometry(int(img_w), int(img_h), int(clip), C.c_float(overlap), int(zoom), out))
+    L.check(L.lib().nrf_pyramid_level_geometry(int(img_w), int(img_h), int(clip), overlap, int(zoom), out))
     return tuple(out)
 
 
@@ -88,8 +88,7 @@ class PyramidEmbedding:
         lib = L.lib()
         p = C.c_void_p()
         D = int(d if d is not None else self.D)
-        L.check(lib.nrf_pyramid_create(D, int(properties.ImgSize[0]), C.c_float(properties.Overlap), int(properties.MaxZoomOut), len(wh),
-                                       wh.ctypes.data_as(C.c_void_p), C.byref(p)))
+        L.check(lib.nrf_pyramid_create(D, int(properties.ImgSize[0]), properties.Overlap, int(properties.MaxZoomOut), len(wh), wh.ctypes.data_as(C.c_void_p), C.byref(p)))
         self._p, self.Properties, self._wh, self._d = p, properties, wh, D
         if self.Embeddings:
             keys = np.ascontiguousarray(list(self.Embeddings.keys()), np.int32).reshape(-1, 4)
@@ -98,7 +97,7 @@ class PyramidEmbedding:
             if len(width) != 1:
                 raise L.NrfError(f"embeddings of several widths {sorted(width)}")
             emb = np.ascontiguousarray(np.stack(rows), np.float32)
-            L.check(lib.nrf_pyramid_set_entries(p, C.c_int64(len(keys)), keys.ctypes.data_as(C.c_void_p), emb.ctypes.data_as(C.c_void_p), int(emb.shape[1]), _stream()))
+            L.check(lib.nrf_pyramid_set_entries(p, len(keys), keys.ctypes.data_as(C.c_void_p), emb.ctypes.data_as(C.c_void_p), int(emb.shape[1]), _stream()))
         return self
 
     def memory_bytes(self):
@@ -131,7 +130,7 @@ class PyramidEmbedding:
         if out is None:
             out = torch.empty((n, D), device=xs.device, dtype=torch.float32)
         assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == n and out.stride(1) == 1
-        L.check(L.lib().nrf_pyramid_pixel_values(p, int(img_id), C.c_float(scale), _ptr(xs), _ptr(ys), C.c_int64(n), _ptr(out), C.c_int64(out.stride(0)), _stream()))
+        L.check(L.lib().nrf_pyramid_pixel_values(p, int(img_id), scale, _ptr(xs), _ptr(ys), n, _ptr(out), out.stride(0), _stream()))
         return out
 
     def RelevancyPreview(self, img_id, positives, negatives, scale=0.5, positive_id=0, colored=True, rows_per_chunk=64):
@@ -154,6 +153,6 @@ class PyramidEmbedding:
         ws = torch.empty((int(lib.nrf_pyramid_relevancy_preview_workspace_bytes(p, int(img_id), int(rows_per_chunk))),), device="cuda", dtype=torch.uint8)
         gray = torch.empty((H, W), device="cuda", dtype=torch.uint8)
         bgr = torch.empty((H, W, 3), device="cuda", dtype=torch.uint8) if colored else None
-        L.check(lib.nrf_pyramid_relevancy_preview(p, int(img_id), C.c_float(scale), _ptr(pos), int(pos.shape[0]), _ptr(neg), int(neg.shape[0]), int(positive_id),
-                                                  _ptr(gray), _ptr(bgr), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+        L.check(lib.nrf_pyramid_relevancy_preview(p, int(img_id), scale, _ptr(pos), int(pos.shape[0]), _ptr(neg), int(neg.shape[0]), int(positive_id),
+                                                  _ptr(gray), _ptr(bgr), _ptr(ws), ws.numel(), _stream()))
         return gray, bgr

@@ -55,12 +55,12 @@ def PointRelevancy(lerf_renderer, pts, positive_id=0, precision=L.NRF_PREC_F16_S
         rel, sigma = _relevancy_composed(lerf_renderer, x, positive_id)
     else:
         lib = L.lib()
-        slab = C.c_int64(0 if slab_points is None else int(slab_points))
+        slab = 0 if slab_points is None else int(slab_points)
         rel = torch.empty((p, 2), device=x.device, dtype=torch.float32)
         sigma = torch.empty((p,), device=x.device, dtype=torch.float32) if return_sigma else None
-        ws = torch.empty((max(1, int(lib.nrf_lerf_point_relevancy_workspace_bytes(lerf_renderer._r, C.c_int64(p), int(precision), slab))),), device=x.device, dtype=torch.uint8)
-        L.check(lib.nrf_lerf_point_relevancy(lerf_renderer._r, _ptr(x), C.c_int64(p), int(positive_id), int(precision), _ptr(sigma) if sigma is not None else None,
-                                             _ptr(rel), slab, _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+        ws = torch.empty((max(1, int(lib.nrf_lerf_point_relevancy_workspace_bytes(lerf_renderer._r, p, int(precision), slab))),), device=x.device, dtype=torch.uint8)
+        L.check(lib.nrf_lerf_point_relevancy(lerf_renderer._r, _ptr(x), p, int(positive_id), int(precision), _ptr(sigma) if sigma is not None else None,
+                                             _ptr(rel), slab, _ptr(ws), ws.numel(), _stream()))
     rel = rel.reshape(lead + (2,))
     return (rel, sigma.reshape(lead)) if return_sigma else rel
 
@@ -76,12 +76,12 @@ def RelevancyGrid(lerf_renderer, bbox=None, resolution=256, positive_id=0, preci
         rel, sigma = PointRelevancy(lerf_renderer, _lattice_points(bb, nx, ny, nz, dev), positive_id, precision, return_sigma=True)
         return rel.reshape(nz, ny, nx, 2), sigma.reshape(nz, ny, nx)
     lib = L.lib()
-    slab = C.c_int64(0 if slab_points is None else int(slab_points))
+    slab = 0 if slab_points is None else int(slab_points)
     rel = torch.empty((nz, ny, nx, 2), device=dev, dtype=torch.float32)
     sigma = torch.empty((nz, ny, nx), device=dev, dtype=torch.float32)
     ws = torch.empty((max(1, int(lib.nrf_lerf_relevancy_grid_workspace_bytes(lerf_renderer._r, nx, ny, nz, int(precision), slab))),), device=dev, dtype=torch.uint8)
     L.check(lib.nrf_lerf_relevancy_grid(lerf_renderer._r, bb.ctypes.data_as(C.c_void_p), nx, ny, nz, int(positive_id), int(precision), _ptr(sigma), _ptr(rel), slab,
-                                        _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+                                        _ptr(ws), ws.numel(), _stream()))
     return rel, sigma
 
 

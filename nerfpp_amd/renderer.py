@@ -45,7 +45,7 @@ def NDCRays(h, w, focal, near, rays_o, rays_d, cone_angle=None):
     exactly 1.0 per ray (its [.., 1] tensor holds the scalar's value everywhere)."""
     o = _dev_f32(rays_o); d = _dev_f32(rays_d)
     oo = torch.empty_like(o); od = torch.empty_like(d)
-    L.check(L.lib().nrf_ndc_rays(h, w, C.c_float(focal), C.c_float(near), _ptr(o), _ptr(d), C.c_int64(o.numel() // 3), _ptr(oo), _ptr(od), _stream()))
+    L.check(L.lib().nrf_ndc_rays(h, w, focal, near, _ptr(o), _ptr(d), o.numel() // 3, _ptr(oo), _ptr(od), _stream()))
     return oo, od, cone_angle
 
 
@@ -54,7 +54,7 @@ def IntersectWithAABB(rays_o, rays_d, bounding_box, near_plane=0.0):
     o = _dev_f32(rays_o).reshape(-1, 3); d = _dev_f32(rays_d).reshape(-1, 3)
     bb = _host_f32(bounding_box, 6)
     nr = torch.empty((o.shape[0],), device=o.device, dtype=torch.float32); fr = torch.empty_like(nr)
-    L.check(L.lib().nrf_aabb(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), C.c_int64(o.shape[0]), C.c_float(near_plane), _ptr(nr), _ptr(fr), _stream()))
+    L.check(L.lib().nrf_aabb(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), o.shape[0], near_plane, _ptr(nr), _ptr(fr), _stream()))
     return nr, fr
 
 
@@ -71,18 +71,18 @@ def SamplePDF(bins, weights, nsamples, det=True, return_inds=False, sum_vec=ATEN
     inds = torch.empty((n, nsamples), device=bins.device, dtype=torch.int64) if return_inds else None
     if det:
         u = torch.linspace(0.0, 1.0, nsamples, dtype=torch.float32).to(bins.device)     # Sampler.h:21, ATen's own rounding
-        L.check(L.lib().nrf_sample_pdf(_ptr(bins), _ptr(weights), C.c_int64(n), nb, _ptr(u), nsamples, sum_vec, _ptr(samples), _ptr(inds), _stream()))
+        L.check(L.lib().nrf_sample_pdf(_ptr(bins), _ptr(weights), n, nb, _ptr(u), nsamples, sum_vec, _ptr(samples), _ptr(inds), _stream()))
     else:
         u = RngFill(seed, L.NRF_RNG_U_PDF, ray_base * nsamples, n * nsamples, device=bins.device).reshape(n, nsamples) if u is None else _dev_f32(u)
         assert u.shape == (n, nsamples)
-        L.check(L.lib().nrf_sample_pdf_rand(_ptr(bins), _ptr(weights), C.c_int64(n), nb, _ptr(u), nsamples, sum_vec, _ptr(samples), _ptr(inds), _stream()))
+        L.check(L.lib().nrf_sample_pdf_rand(_ptr(bins), _ptr(weights), n, nb, _ptr(u), nsamples, sum_vec, _ptr(samples), _ptr(inds), _stream()))
     return (samples, inds) if return_inds else samples
 
 
 def RngFill(seed, rng_stream, index0, count, normal=False, device="cuda"):
     """include/nrf_rng.h: element k = draw(seed, rng_stream, index0 + k); uniform on [0,1) or standard normal."""
     out = torch.empty((int(count),), device=device, dtype=torch.float32)
-    L.check(L.lib().nrf_rng_fill(C.c_uint64(int(seed)), C.c_uint32(int(rng_stream)), C.c_uint64(int(index0)), C.c_int64(int(count)), int(normal), _ptr(out), _stream()))
+    L.check(L.lib().nrf_rng_fill(int(seed), int(rng_stream), int(index0), int(count), int(normal), _ptr(out), _stream()))
     return out
 
 
@@ -90,7 +90,7 @@ def JitterZ(z_vals, t_rand):
     """NeRFRenderer.h:404-417 with explicit uniform draws t_rand [N,S]."""
     z = _dev_f32(z_vals); t = _dev_f32(t_rand)
     out = torch.empty_like(z)
-    L.check(L.lib().nrf_jitter_z(_ptr(z), _ptr(t), C.c_int64(z.shape[0]), z.shape[1], _ptr(out), _stream()))
+    L.check(L.lib().nrf_jitter_z(_ptr(z), _ptr(t), z.shape[0], z.shape[1], _ptr(out), _stream()))
     return out
 
 
@@ -101,7 +101,7 @@ def TangentScatter(pts, z_vals, cone_angle, rays_d, bounding_box=None, u_r=None,
     rays = torch.cat([torch.zeros_like(d), d], -1).contiguous()          # only columns 3..5 (rays_d) are read when pts are explicit
     bb = _host_f32(bounding_box, 6) if bounding_box is not None else None
     out = torch.empty_like(pts)
-    L.check(L.lib().nrf_tangent_scatter(_ptr(pts), _ptr(rays), 6, _ptr(z), C.c_int64(n), s, C.c_float(float(cone_angle)), _ptr(_dev_f32(u_r).reshape(n, s)),
+    L.check(L.lib().nrf_tangent_scatter(_ptr(pts), _ptr(rays), 6, _ptr(z), n, s, float(cone_angle), _ptr(_dev_f32(u_r).reshape(n, s)),
                                         _ptr(_dev_f32(u_theta).reshape(n, s)), bb.ctypes.data_as(C.c_void_p) if bb is not None else None, _ptr(out), _stream()))
     return out
 
@@ -111,7 +111,7 @@ def StochasticPrecondition(pts, noise, alpha, bounding_box):
     pts = _dev_f32(pts); nz = _dev_f32(noise)
     bb = _host_f32(bounding_box, 6)
     out = torch.empty_like(pts)
-    L.check(L.lib().nrf_precondition(_ptr(pts), _ptr(nz), C.c_float(alpha), bb.ctypes.data_as(C.c_void_p), C.c_int64(pts.numel() // 3), _ptr(out), _stream()))
+    L.check(L.lib().nrf_precondition(_ptr(pts), _ptr(nz), alpha, bb.ctypes.data_as(C.c_void_p), pts.numel() // 3, _ptr(out), _stream()))
     return out
 
 
@@ -256,9 +256,9 @@ class NeRFRenderer:
         vd = _dev_f32(view_dirs) if view_dirs is not None and view_dirs.numel() else None
         c = self.NeRF.GetOutputDims()
         raw = torch.empty((n, s, c), device=pts.device, dtype=torch.float32)
-        nb = L.lib().nrf_run_network_workspace_bytes(self._r, C.c_int64(n), s)
+        nb = L.lib().nrf_run_network_workspace_bytes(self._r, n, s)
         ws = self._workspace(nb, pts.device)
-        L.check(L.lib().nrf_run_network(self._r, _ptr(pts), _ptr(vd), C.c_int64(n), s, precision, _ptr(raw), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+        L.check(L.lib().nrf_run_network(self._r, _ptr(pts), _ptr(vd), n, s, precision, _ptr(raw), _ptr(ws), ws.numel(), _stream()))
         return raw
 
     def RawToOutputs(self, raw, cone_angle, z_vals, rays_d, raw_noise_std=0.0, white_bkgr=False, noise=None):
@@ -271,14 +271,14 @@ class NeRFRenderer:
             o = NeRFRendererOutputs(RGBMap=torch.empty((n, 3), device=raw.device), DispMap=torch.empty((n,), device=raw.device),
                                     AccMap=torch.empty((n,), device=raw.device), Weights=torch.empty((n, s), device=raw.device),
                                     DepthMap=torch.empty((n,), device=raw.device))
-            L.check(L.lib().nrf_raw2outputs_noise(_ptr(raw), _ptr(z), _ptr(d), 3, C.c_int64(n), s, c, int(white_bkgr), _ptr(_dev_f32(noise)),
-                                                  C.c_float(raw_noise_std), _ptr(o.RGBMap), _ptr(o.DispMap), _ptr(o.AccMap), _ptr(o.Weights), _ptr(o.DepthMap), _stream()))
+            L.check(L.lib().nrf_raw2outputs_noise(_ptr(raw), _ptr(z), _ptr(d), 3, n, s, c, int(white_bkgr), _ptr(_dev_f32(noise)),
+                                                  raw_noise_std, _ptr(o.RGBMap), _ptr(o.DispMap), _ptr(o.AccMap), _ptr(o.Weights), _ptr(o.DepthMap), _stream()))
             return o
         n, s, c = raw.shape
         o = NeRFRendererOutputs(RGBMap=torch.empty((n, 3), device=raw.device), DispMap=torch.empty((n,), device=raw.device),
                                 AccMap=torch.empty((n,), device=raw.device), Weights=torch.empty((n, s), device=raw.device),
                                 DepthMap=torch.empty((n,), device=raw.device))
-        L.check(L.lib().nrf_raw2outputs(_ptr(raw), _ptr(z), _ptr(d), 3, C.c_int64(n), s, c, int(white_bkgr), _ptr(o.RGBMap), _ptr(o.DispMap),
+        L.check(L.lib().nrf_raw2outputs(_ptr(raw), _ptr(z), _ptr(d), 3, n, s, c, int(white_bkgr), _ptr(o.RGBMap), _ptr(o.DispMap),
                                         _ptr(o.AccMap), _ptr(o.Weights), _ptr(o.DepthMap), _stream()))
         return o
 
@@ -373,10 +373,9 @@ class NeRFRenderer:
         rp = self._params(s, ni, cone_angle, lin_disp, perturb, white_bkgr, raw_noise_std, stochastic_preconditioning_alpha, bounding_box, precision, seed,
                           ray_base, coarse_mode)
         res, ro = self._alloc_outputs(n, s, ni, dev, return_raw, return_weights, keep_intermediates)
-        nb = L.lib().nrf_render_rays_workspace_bytes(self._r, C.c_int64(n), C.byref(rp))
+        nb = L.lib().nrf_render_rays_workspace_bytes(self._r, n, C.byref(rp))
         ws = self._workspace(nb, dev)
-        L.check(L.lib().nrf_render_rays(self._r, _ptr(rays), stride, C.c_int64(n), C.byref(rp), _ptr(t), _ptr(u), C.byref(ro), _ptr(ws),
-                                        C.c_size_t(ws.numel()), _stream()))
+        L.check(L.lib().nrf_render_rays(self._r, _ptr(rays), stride, n, C.byref(rp), _ptr(t), _ptr(u), C.byref(ro), _ptr(ws), ws.numel(), _stream()))
         return res
 
     def BatchifyRays(self, rays_flat, cone_angle, n_samples, chunk=1024 * 32, **kw):
@@ -436,11 +435,11 @@ class NeRFRenderer:
             t, u = _ptr(self._linspace(s, dev)), _ptr(self._linspace(ni, dev)) if ni > 0 else None
             if nm is None:
                 ws = self._workspace(lib.nrf_render_rows_workspace_bytes(self._r, C.byref(v), C.byref(rp)), dev)
-                L.check(lib.nrf_render_rows(self._r, C.byref(v), C.byref(rp), t, u, C.byref(ro), _ptr(rays_), _ptr(nf), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+                L.check(lib.nrf_render_rows(self._r, C.byref(v), C.byref(rp), t, u, C.byref(ro), _ptr(rays_), _ptr(nf), _ptr(ws), ws.numel(), _stream()))
             else:
                 ws = self._workspace(lib.nrf_render_rows_normals_workspace_bytes(self._r, C.byref(v), C.byref(rp), nm.bits), dev)
                 L.check(lib.nrf_render_rows_normals(self._r, C.byref(v), C.byref(rp), t, u, C.byref(ro), C.byref(nm), _ptr(rays_), _ptr(nf), _ptr(ws),
-                                                    C.c_size_t(ws.numel()), _stream()))
+                                                    ws.numel(), _stream()))
         else:
             if c2w_staticcam is not None:
                 raise L.NrfError("c2w_staticcam replaces the camera of a POSE render (NeRFRenderer.h:554-558); with an explicit ray batch pass those rays yourself")
@@ -458,27 +457,26 @@ class NeRFRenderer:
             n = o.shape[0]
             rays_ = torch.empty((n, stride), device=dev, dtype=torch.float32)
             if p.Ndc and p.UseViewdirs:                                  # viewdirs are taken before the warp (:549-561)
-                L.check(lib.nrf_pack_rays_viewsrc(_ptr(o), _ptr(d), _ptr(view_src.contiguous()), bb.ctypes.data_as(C.c_void_p), C.c_int64(n), _ptr(rays_), _stream()))
+                L.check(lib.nrf_pack_rays_viewsrc(_ptr(o), _ptr(d), _ptr(view_src.contiguous()), bb.ctypes.data_as(C.c_void_p), n, _ptr(rays_), _stream()))
             else:
-                L.check(lib.nrf_pack_rays(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), C.c_int64(n), int(p.UseViewdirs), _ptr(rays_), _stream()))   # :549-583
+                L.check(lib.nrf_pack_rays(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), n, int(p.UseViewdirs), _ptr(rays_), _stream()))   # :549-583
             rp = self._params(s, ni, None if p.ThinRay else cone_angle, p.LinDisp, p.Perturb, p.WhiteBkgr, p.RawNoiseStd, p.StochasticPreconditioningAlpha,
                               p.BoundingBox, p.Precision, p.Seed, 0, p.CoarseMode, p.OverflowPolicy)
             res, ro = self._alloc_outputs(n, s, ni, dev, p.ReturnRaw, p.ReturnWeights, p.KeepIntermediates)
             nm = self._normals_request(res, n, dev, self._normal_bits(p))
             t, u = _ptr(self._linspace(s, dev)), _ptr(self._linspace(ni, dev)) if ni > 0 else None
             if nm is None:
-                ws = self._workspace(lib.nrf_batchify_rays_workspace_bytes(self._r, C.c_int64(n), int(p.Chunk), C.byref(rp)), dev)
-                L.check(lib.nrf_batchify_rays(self._r, _ptr(rays_), stride, C.c_int64(n), int(p.Chunk), C.byref(rp), t, u, C.byref(ro), _ptr(ws), C.c_size_t(ws.numel()),
-                                              _stream()))
+                ws = self._workspace(lib.nrf_batchify_rays_workspace_bytes(self._r, n, int(p.Chunk), C.byref(rp)), dev)
+                L.check(lib.nrf_batchify_rays(self._r, _ptr(rays_), stride, n, int(p.Chunk), C.byref(rp), t, u, C.byref(ro), _ptr(ws), ws.numel(), _stream()))
             else:
-                ws = self._workspace(lib.nrf_batchify_rays_normals_workspace_bytes(self._r, C.c_int64(n), int(p.Chunk), C.byref(rp), nm.bits), dev)
-                L.check(lib.nrf_batchify_rays_normals(self._r, _ptr(rays_), stride, C.c_int64(n), int(p.Chunk), C.byref(rp), t, u, C.byref(ro), C.byref(nm), _ptr(ws),
-                                                      C.c_size_t(ws.numel()), _stream()))
+                ws = self._workspace(lib.nrf_batchify_rays_normals_workspace_bytes(self._r, n, int(p.Chunk), C.byref(rp), nm.bits), dev)
+                L.check(lib.nrf_batchify_rays_normals(self._r, _ptr(rays_), stride, n, int(p.Chunk), C.byref(rp), t, u, C.byref(ro), C.byref(nm), _ptr(ws),
+                                                      ws.numel(), _stream()))
             self._last_feature_view = self.feature_view()          # (None unless this was a single-chunk render of the feature-reusing fast path)
             nf = None
             if n > 0:
                 nf = torch.empty((2,), device=dev, dtype=torch.float32)          # Near / Far stay on the device until someone reads them (a training loop never does):
-                L.check(lib.nrf_near_far_range_device(_ptr(rays_), C.c_int64(n), stride, _ptr(nf), _stream()))   # :602-603 without the reference's two host stalls
+                L.check(lib.nrf_near_far_range_device(_ptr(rays_), n, stride, _ptr(nf), _stream()))   # :602-603 without the reference's two host stalls
         out = res.Outputs
         out.RGBMap = out.RGBMap.reshape(sh)                                                               # :591-592
         if out.RenderedNormals is not None:
@@ -500,7 +498,7 @@ def NormalizeDepth(depth_map, near, far):
     """(DepthMap - Near) / (Far - Near), NeRFExecutor.h:690."""
     d = _dev_f32(depth_map)
     out = torch.empty_like(d)
-    L.check(L.lib().nrf_normalize_depth(_ptr(d), C.c_int64(d.numel()), C.c_float(near), C.c_float(far), _ptr(out), _stream()))
+    L.check(L.lib().nrf_normalize_depth(_ptr(d), d.numel(), near, far, _ptr(out), _stream()))
     return out
 
 
@@ -508,7 +506,7 @@ def TorchTensorToCVMat(tensor_image):
     """NeRFRenderer.h:58-68 up to the cv::Mat wrap: squeeze, mul(255).clamp(0,255).to(u8); returns the uint8 tensor (on the GPU)."""
     t = _dev_f32(tensor_image).squeeze()
     out = torch.empty(t.shape, device=t.device, dtype=torch.uint8)
-    L.check(L.lib().nrf_to_u8(_ptr(t), C.c_int64(t.numel()), _ptr(out), _stream()))
+    L.check(L.lib().nrf_to_u8(_ptr(t), t.numel(), _ptr(out), _stream()))
     return out
 
 
@@ -523,8 +521,7 @@ def RenderViewDims(h, w, k, render_factor):
     K = _host_f32(k, 9)
     K1 = np.empty(9, np.float32)
     h1, w1 = C.c_int(0), C.c_int(0)
-    L.check(L.lib().nrf_render_view_dims(int(h), int(w), K.ctypes.data_as(C.c_void_p), C.c_float(float(render_factor)), C.byref(h1), C.byref(w1),
-                                         K1.ctypes.data_as(C.c_void_p)))
+    L.check(L.lib().nrf_render_view_dims(int(h), int(w), K.ctypes.data_as(C.c_void_p), float(render_factor), C.byref(h1), C.byref(w1), K1.ctypes.data_as(C.c_void_p)))
     return h1.value, w1.value, K1.reshape(3, 3)
 
 
@@ -575,7 +572,7 @@ def RenderCLIPEmbedding(embeds, weights):
 def _clip_embedding(e, stride, dim, w):
     n, s = w.shape
     out = torch.empty((n, dim), device=e.device, dtype=torch.float32)
-    L.check(L.lib().nrf_render_clip_embedding(_ptr(e), stride, dim, _ptr(w), C.c_int64(n), s, _ptr(out), _stream()))
+    L.check(L.lib().nrf_render_clip_embedding(_ptr(e), stride, dim, _ptr(w), n, s, _ptr(out), _stream()))
     return out
 
 
@@ -589,7 +586,7 @@ def Relevancy(embeds, positives, negatives, positive_id=0):
         return x.to(device=e.device, dtype=torch.float32).reshape(-1, e.shape[1]).contiguous()
     pos, neg = phrases(positives), phrases(negatives)
     out = torch.empty((e.shape[0], 2), device=e.device, dtype=torch.float32)
-    L.check(L.lib().nrf_lerf_relevancy(_ptr(e), C.c_int64(e.shape[0]), int(e.shape[1]), _ptr(pos), int(pos.shape[0]), _ptr(neg), int(neg.shape[0]), int(positive_id),
+    L.check(L.lib().nrf_lerf_relevancy(_ptr(e), e.shape[0], int(e.shape[1]), _ptr(pos), int(pos.shape[0]), _ptr(neg), int(neg.shape[0]), int(positive_id),
                                        _ptr(out), _stream()))
     return out
 
@@ -600,7 +597,7 @@ def RelevancyImage(relevancy):
     sh = r.shape[:-1]
     n = int(np.prod(sh)) if len(sh) else 1
     out = torch.empty((n, 3), device=r.device, dtype=torch.uint8)
-    L.check(L.lib().nrf_relevancy_image(_ptr(r), C.c_int64(n), int(r.shape[-1]), _ptr(out), _stream()))
+    L.check(L.lib().nrf_relevancy_image(_ptr(r), n, int(r.shape[-1]), _ptr(out), _stream()))
     return out.reshape(*sh, 3)
 
 
@@ -740,15 +737,14 @@ class LeRFRenderer:
             v.bbox = (C.c_float * 6)(*bb.tolist())
             nf = torch.empty((2,), **f32)
             ws = workspace(lib.nrf_lerf_render_rows_workspace_bytes(self._r, C.byref(v), C.byref(rp)))
-            L.check(lib.nrf_lerf_render_rows(self._r, C.byref(v), C.byref(rp), _ptr(t), _ptr(u), C.byref(ro), _ptr(rays_), _ptr(nf), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+            L.check(lib.nrf_lerf_render_rows(self._r, C.byref(v), C.byref(rp), _ptr(t), _ptr(u), C.byref(ro), _ptr(rays_), _ptr(nf), _ptr(ws), ws.numel(), _stream()))
             res._nf_dev = nf
         else:
-            L.check(lib.nrf_pack_rays(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), C.c_int64(n), int(p.UseViewdirs), _ptr(rays_), _stream()))
-            ws = workspace(lib.nrf_lerf_batchify_rays_workspace_bytes(self._r, C.c_int64(n), int(p.Chunk), C.byref(rp)))
-            L.check(lib.nrf_lerf_batchify_rays(self._r, _ptr(rays_), stride, C.c_int64(n), int(p.Chunk), C.byref(rp), _ptr(t), _ptr(u), C.byref(ro), _ptr(ws),
-                                               C.c_size_t(ws.numel()), _stream()))
+            L.check(lib.nrf_pack_rays(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), n, int(p.UseViewdirs), _ptr(rays_), _stream()))
+            ws = workspace(lib.nrf_lerf_batchify_rays_workspace_bytes(self._r, n, int(p.Chunk), C.byref(rp)))
+            L.check(lib.nrf_lerf_batchify_rays(self._r, _ptr(rays_), stride, n, int(p.Chunk), C.byref(rp), _ptr(t), _ptr(u), C.byref(ro), _ptr(ws), ws.numel(), _stream()))
             nfd = torch.empty((2,), device=rays_.device, dtype=torch.float32)
-            L.check(lib.nrf_near_far_range_device(_ptr(rays_), C.c_int64(n), stride, _ptr(nfd), _stream()))
+            L.check(lib.nrf_near_far_range_device(_ptr(rays_), n, stride, _ptr(nfd), _stream()))
             res._nf_dev = nfd
         res.Extras["rays_flat"] = rays_
         return res
@@ -772,15 +768,15 @@ class LeRFRenderer:
             flat = pts.reshape(-1, 3).contiguous()
             x = torch.empty((16, n * s, 8), device=pts.device, dtype=torch.float16)
             ku8 = torch.empty((n * s,), device=pts.device, dtype=torch.uint8)
-            L.check(L.lib().nrf_hash_encode_lm_f16(self.LangEmbedFn._h, _ptr(flat), C.c_int64(n * s), _ptr(x), _ptr(ku8), _stream()))
+            L.check(L.lib().nrf_hash_encode_lm_f16(self.LangEmbedFn._h, _ptr(flat), n * s, _ptr(x), _ptr(ku8), _stream()))
             if exact:
-                L.check(L.lib().nrf_lerf_sigma_exact_lm_strided(self.Lerf._m, _ptr(x), C.c_int64(n * s), _ptr(ku8), C.c_int64(n * s), _ptr(sig), None, C.c_int64(0), _stream()))
+                L.check(L.lib().nrf_lerf_sigma_exact_lm_strided(self.Lerf._m, _ptr(x), n * s, _ptr(ku8), n * s, _ptr(sig), None, 0, _stream()))
             else:
-                L.check(L.lib().nrf_lerf_sigma_lm(self.Lerf._m, _ptr(x), _ptr(ku8), C.c_int64(n * s), _ptr(sig), _stream()))
+                L.check(L.lib().nrf_lerf_sigma_lm(self.Lerf._m, _ptr(x), _ptr(ku8), n * s, _ptr(sig), _stream()))
             return sig, x
         x, keep = self.LangEmbedFn.forward(pts.reshape(-1, 3))
         ku8 = keep.to(torch.uint8)
-        L.check(L.lib().nrf_lerf_sigma(self.Lerf._m, _ptr(x), _ptr(ku8), C.c_int64(n * s), _ptr(sig), _stream()))
+        L.check(L.lib().nrf_lerf_sigma(self.Lerf._m, _ptr(x), _ptr(ku8), n * s, _ptr(sig), _stream()))
         return sig, x
 
     def _render_fine_reusing(self, rays, stride, z, pts, rays_d, ni):
@@ -795,28 +791,27 @@ class LeRFRenderer:
         x = torch.empty((16, cols, 8), device=dev, dtype=torch.float16)
         keep = torch.empty((cols,), device=dev, dtype=torch.uint8)
         sig = torch.empty((cols,), device=dev, dtype=torch.float32)           # [coarse n*s | new n*ni], the table's column order
-        L.check(lib.nrf_hash_encode_lm_f16_strided(h, _ptr(pts), C.c_int64(n * s), _ptr(x), C.c_int64(cols), _ptr(keep), _stream()))
+        L.check(lib.nrf_hash_encode_lm_f16_strided(h, _ptr(pts), n * s, _ptr(x), cols, _ptr(keep), _stream()))
         # split precision: the sigma pass also leaves (sigma, geo32) per column, and the embedding pass starts at LE0 from it (nrf_lerf_*_geo)
-        geo = torch.empty((int(lib.nrf_lerf_geo_bytes(C.c_int64(cols))),), device=dev, dtype=torch.uint8) if self.precision == L.NRF_PREC_F16_SPLIT and self.hand_over_geo else None
+        geo = torch.empty((int(lib.nrf_lerf_geo_bytes(cols)),), device=dev, dtype=torch.uint8) if self.precision == L.NRF_PREC_F16_SPLIT and self.hand_over_geo else None
         def sigma_pass(x_ptr, keep_t, count, sig_t, col0):
             if geo is None:
-                L.check(lib.nrf_lerf_sigma_lm_strided(m, x_ptr, C.c_int64(cols), _ptr(keep_t), C.c_int64(count), _ptr(sig_t), _stream()))
+                L.check(lib.nrf_lerf_sigma_lm_strided(m, x_ptr, cols, _ptr(keep_t), count, _ptr(sig_t), _stream()))
             else:
-                L.check(lib.nrf_lerf_sigma_geo_lm_strided(m, x_ptr, C.c_int64(cols), _ptr(keep_t), C.c_int64(count), _ptr(sig_t), C.c_void_p(geo.data_ptr() + col0 * 32),
-                                                          C.c_int64(cols), _stream()))
+                L.check(lib.nrf_lerf_sigma_geo_lm_strided(m, x_ptr, cols, _ptr(keep_t), count, _ptr(sig_t), geo.data_ptr() + col0 * 32, cols, _stream()))
         if self._exact_coarse_on():
             # coarse columns: sigma_le in exact fp32 (== the fp32 stage path bit for bit), and -- with the hand-over -- the sigma net's geo output split from the exact values
-            L.check(lib.nrf_lerf_sigma_exact_lm_strided(m, _ptr(x), C.c_int64(cols), _ptr(keep), C.c_int64(n * s), _ptr(sig), _ptr(geo), C.c_int64(cols), _stream()))
+            L.check(lib.nrf_lerf_sigma_exact_lm_strided(m, _ptr(x), cols, _ptr(keep), n * s, _ptr(sig), _ptr(geo), cols, _stream()))
         else:
             sigma_pass(_ptr(x), keep, n * s, sig, 0)
         out1 = self._weights_from_sigma(sig[:n * s].view(n, s), z, rays_d)
         u = NeRFRenderer._linspace(ni, dev)                                   # cached: a fresh host tensor's .to(device) is a synchronous copy per chunk
         zf = torch.empty((n, sf), device=dev); src = torch.empty((n, sf), device=dev, dtype=torch.int32); z_new = torch.empty((n, ni), device=dev)
-        L.check(lib.nrf_fine_depths_merge(_ptr(z), _ptr(out1.WeightsLE), C.c_int64(n), s, _ptr(u), ni, ATEN_SUM_VEC, _ptr(zf), _ptr(src), _ptr(z_new), _stream()))
+        L.check(lib.nrf_fine_depths_merge(_ptr(z), _ptr(out1.WeightsLE), n, s, _ptr(u), ni, ATEN_SUM_VEC, _ptr(zf), _ptr(src), _ptr(z_new), _stream()))
         pts_new = torch.empty((n, ni, 3), device=dev)
-        L.check(lib.nrf_points(_ptr(rays), stride, _ptr(z_new), C.c_int64(n), ni, _ptr(pts_new), _stream()))
-        x_new = C.c_void_p(x.data_ptr() + n * s * 8 * 2)                      # column n*s of level 0
-        L.check(lib.nrf_hash_encode_lm_f16_strided(h, _ptr(pts_new), C.c_int64(n * ni), x_new, C.c_int64(cols), _ptr(keep[n * s:]), _stream()))
+        L.check(lib.nrf_points(_ptr(rays), stride, _ptr(z_new), n, ni, _ptr(pts_new), _stream()))
+        x_new = x.data_ptr() + n * s * 8 * 2                                  # column n*s of level 0
+        L.check(lib.nrf_hash_encode_lm_f16_strided(h, _ptr(pts_new), n * ni, x_new, cols, _ptr(keep[n * s:]), _stream()))
         sigma_pass(x_new, keep[n * s:], n * ni, sig[n * s:], n * s)
         if self.compose_through_map:
             o = self._weights_from_sigma(sig, zf, rays_d, src)                 # sigma_le stays in column order; the compositing kernel reads through the merge map
@@ -825,9 +820,9 @@ class LeRFRenderer:
         E = self.Lerf.GetLangEmbedDim()
         acc = torch.empty((n, E), device=dev, dtype=torch.float32)
         if geo is None:
-            L.check(lib.nrf_lerf_render_embedding_lm_gather(m, _ptr(x), C.c_int64(cols), _ptr(src), _ptr(o.WeightsLE), C.c_int64(n), sf, _ptr(acc), _stream()))
+            L.check(lib.nrf_lerf_render_embedding_lm_gather(m, _ptr(x), cols, _ptr(src), _ptr(o.WeightsLE), n, sf, _ptr(acc), _stream()))
         else:
-            L.check(lib.nrf_lerf_render_embedding_lm_geo(m, _ptr(x), C.c_int64(cols), _ptr(src), _ptr(geo), C.c_int64(cols), _ptr(o.WeightsLE), C.c_int64(n), sf, _ptr(acc), _stream()))
+            L.check(lib.nrf_lerf_render_embedding_lm_geo(m, _ptr(x), cols, _ptr(src), _ptr(geo), cols, _ptr(o.WeightsLE), n, sf, _ptr(acc), _stream()))
         ones = torch.ones((n, 1), device=dev, dtype=torch.float32)
         o.RenderedLangEmbedding = _clip_embedding(acc, E, E, ones)
         return out1, o, zf
@@ -838,10 +833,10 @@ class LeRFRenderer:
         o = LeRFRendererOutputs(WeightsLE=torch.empty((n, s), device=sig.device), DepthMapLE=torch.empty((n,), device=sig.device),
                                 DispMapLE=torch.empty((n,), device=sig.device), AccMapLE=torch.empty((n,), device=sig.device))
         if src is None:
-            L.check(L.lib().nrf_raw2weights(_ptr(sig), 1, 0, _ptr(z), _ptr(rays_d), 3, C.c_int64(n), s, _ptr(o.WeightsLE), _ptr(o.DepthMapLE), _ptr(o.DispMapLE),
+            L.check(L.lib().nrf_raw2weights(_ptr(sig), 1, 0, _ptr(z), _ptr(rays_d), 3, n, s, _ptr(o.WeightsLE), _ptr(o.DepthMapLE), _ptr(o.DispMapLE),
                                             _ptr(o.AccMapLE), _stream()))
         else:
-            L.check(L.lib().nrf_raw2weights_gather(_ptr(sig), 1, 0, _ptr(src), _ptr(z), _ptr(rays_d), 3, C.c_int64(n), s, _ptr(o.WeightsLE), _ptr(o.DepthMapLE),
+            L.check(L.lib().nrf_raw2weights_gather(_ptr(sig), 1, 0, _ptr(src), _ptr(z), _ptr(rays_d), 3, n, s, _ptr(o.WeightsLE), _ptr(o.DepthMapLE),
                                                    _ptr(o.DispMapLE), _ptr(o.AccMapLE), _stream()))
         return o
 
@@ -853,7 +848,7 @@ class LeRFRenderer:
             E = self.Lerf.GetLangEmbedDim()
             acc = torch.empty((n, E), device=pts.device, dtype=torch.float32)
             fn = L.lib().nrf_lerf_render_embedding_lm if self.level_major else L.lib().nrf_lerf_render_embedding
-            L.check(fn(self.Lerf._m, _ptr(x), _ptr(o.WeightsLE), C.c_int64(n), s, _ptr(acc), _stream()))
+            L.check(fn(self.Lerf._m, _ptr(x), _ptr(o.WeightsLE), n, s, _ptr(acc), _stream()))
             ones = torch.ones((n, 1), device=pts.device, dtype=torch.float32)
             o.RenderedLangEmbedding = _clip_embedding(acc, E, E, ones)          # the final normalize of RenderCLIPEmbedding (LeRFRenderer.h:53)
         return o
@@ -880,7 +875,7 @@ class LeRFRenderer:
         o = LeRFRendererOutputs(LangEmbedding=raw[..., :lang_embed_dim], WeightsLE=torch.empty((n, s), device=raw.device),
                                 DepthMapLE=torch.empty((n,), device=raw.device), DispMapLE=torch.empty((n,), device=raw.device),
                                 AccMapLE=torch.empty((n,), device=raw.device))
-        L.check(L.lib().nrf_raw2weights(_ptr(raw), c, lang_embed_dim, _ptr(z), _ptr(d), 3, C.c_int64(n), s, _ptr(o.WeightsLE), _ptr(o.DepthMapLE),
+        L.check(L.lib().nrf_raw2weights(_ptr(raw), c, lang_embed_dim, _ptr(z), _ptr(d), 3, n, s, _ptr(o.WeightsLE), _ptr(o.DepthMapLE),
                                         _ptr(o.DispMapLE), _ptr(o.AccMapLE), _stream()))
         o.RenderedLangEmbedding = _clip_embedding(raw, c, lang_embed_dim, o.WeightsLE)
         return o
@@ -897,8 +892,8 @@ class LeRFRenderer:
         E = self.Lerf.GetLangEmbedDim()
         t = NeRFRenderer._linspace(s, dev)
         z = torch.empty((n, s), device=dev); pts = torch.empty((n, s, 3), device=dev)
-        L.check(L.lib().nrf_z_vals(_ptr(rays), stride, C.c_int64(n), _ptr(t), s, int(lin_disp), _ptr(z), _stream()))
-        L.check(L.lib().nrf_points(_ptr(rays), stride, _ptr(z), C.c_int64(n), s, _ptr(pts), _stream()))
+        L.check(L.lib().nrf_z_vals(_ptr(rays), stride, n, _ptr(t), s, int(lin_disp), _ptr(z), _stream()))
+        L.check(L.lib().nrf_points(_ptr(rays), stride, _ptr(z), n, s, _ptr(pts), _stream()))
         rays_d = rays[:, 3:6].contiguous()
         res = LeRFRenderResult()
         if self.fused and self.level_major and self.reuse_features and not return_raw and ni > 0 and s % 32 == 0 and (s + ni) % 32 == 0 and n * (s + ni) < (1 << 31):
@@ -914,9 +909,9 @@ class LeRFRenderer:
             if ni > 0:
                 u = NeRFRenderer._linspace(ni, dev)
                 zf = torch.empty((n, s + ni), device=dev)
-                L.check(L.lib().nrf_fine_depths(_ptr(z), _ptr(out1.WeightsLE), C.c_int64(n), s, _ptr(u), ni, ATEN_SUM_VEC, _ptr(zf), _stream()))
+                L.check(L.lib().nrf_fine_depths(_ptr(z), _ptr(out1.WeightsLE), n, s, _ptr(u), ni, ATEN_SUM_VEC, _ptr(zf), _stream()))
                 ptsf = torch.empty((n, s + ni, 3), device=dev)
-                L.check(L.lib().nrf_points(_ptr(rays), stride, _ptr(zf), C.c_int64(n), s + ni, _ptr(ptsf), _stream()))
+                L.check(L.lib().nrf_points(_ptr(rays), stride, _ptr(zf), n, s + ni, _ptr(ptsf), _stream()))
                 res.Outputs = self._render_fused(ptsf, zf, rays_d, want_embedding=True)
                 res.Extras["z_fine"] = zf
             res.Extras["z_coarse"] = z
@@ -929,9 +924,9 @@ class LeRFRenderer:
         if ni > 0:
             u = torch.linspace(0.0, 1.0, ni, dtype=torch.float32).to(dev)
             zf = torch.empty((n, s + ni), device=dev)
-            L.check(L.lib().nrf_fine_depths(_ptr(z), _ptr(out1.WeightsLE), C.c_int64(n), s, _ptr(u), ni, ATEN_SUM_VEC, _ptr(zf), _stream()))
+            L.check(L.lib().nrf_fine_depths(_ptr(z), _ptr(out1.WeightsLE), n, s, _ptr(u), ni, ATEN_SUM_VEC, _ptr(zf), _stream()))
             ptsf = torch.empty((n, s + ni, 3), device=dev)
-            L.check(L.lib().nrf_points(_ptr(rays), stride, _ptr(zf), C.c_int64(n), s + ni, _ptr(ptsf), _stream()))
+            L.check(L.lib().nrf_points(_ptr(rays), stride, _ptr(zf), n, s + ni, _ptr(ptsf), _stream()))
             raw = self.RunLENetwork(ptsf)
             res.Outputs = self.RawToLEOutputs(raw, zf, rays_d, E)
             res.Extras["z_fine"] = zf
@@ -958,7 +953,7 @@ class LeRFRenderer:
         n = o.shape[0]
         stride = 11 if p.UseViewdirs else 8
         rays_ = torch.empty((n, stride), device=o.device, dtype=torch.float32)
-        L.check(L.lib().nrf_pack_rays(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), C.c_int64(n), int(p.UseViewdirs), _ptr(rays_), _stream()))
+        L.check(L.lib().nrf_pack_rays(_ptr(o), _ptr(d), bb.ctypes.data_as(C.c_void_p), n, int(p.UseViewdirs), _ptr(rays_), _stream()))
         def one(i):
             return self.RenderRays(rays_[i:i + p.Chunk], None if p.ThinRay else cone_angle, p.NSamples, return_raw=p.ReturnRaw, lin_disp=p.LinDisp,
                                    perturb=p.Perturb, n_importance=p.NImportance, white_bkgr=p.WhiteBkgr, raw_noise_std=p.RawNoiseStd,
@@ -991,7 +986,7 @@ class LeRFRenderer:
         for k_ in (parts[0].Extras if parts else {}):
             res.Extras[k_] = torch.cat([q.Extras[k_] for q in parts], 0)
         nfd = torch.empty((2,), device=rays_.device, dtype=torch.float32)
-        L.check(L.lib().nrf_near_far_range_device(_ptr(rays_), C.c_int64(n), stride, _ptr(nfd), _stream()))
+        L.check(L.lib().nrf_near_far_range_device(_ptr(rays_), n, stride, _ptr(nfd), _stream()))
         res._nf_dev = nfd
         if self.LerfPositives is not None and self.LerfNegatives is not None and res.Outputs.RenderedLangEmbedding is not None:
             res.Outputs.Relevancy = Relevancy(res.Outputs.RenderedLangEmbedding, self.LerfPositives, self.LerfNegatives)      # LeRFRenderer.cpp:79

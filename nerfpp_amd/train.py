@@ -128,7 +128,7 @@ class Trainer:
         rgb = res.Outputs.RGBMap.reshape(n, 3).contiguous()
         tgt = _dev_f32(target).reshape(n, 3)
         loss_mse = torch.empty((2,), device=rgb.device); g_rgb = torch.empty_like(rgb)
-        L.check(lib.nrf_huber_loss(_ptr(rgb), _ptr(tgt), C.c_int64(rgb.numel()), _ptr(loss_mse), _ptr(g_rgb), _stream()))
+        L.check(lib.nrf_huber_loss(_ptr(rgb), _ptr(tgt), rgb.numel(), _ptr(loss_mse), _ptr(g_rgb), _stream()))
         raw = res.Raw; s = n_samples_out
         z = res.Extras["z_fine"] if "z_fine" in res.Extras else res.Extras["z_coarse"]
         c = int(self.mlp.GetOutputDims())                  # 4, or 7 with the predicted-normals head
@@ -143,10 +143,10 @@ class Trainer:
         fine = "z_fine" in res.Extras
         noise_std = float(p.RawNoiseStd) if p is not None else 0.0
         noise = RngFill(seed, L.NRF_RNG_NOISE_FINE if fine else L.NRF_RNG_NOISE_COARSE, 0, n * s, normal=True, device=rays.device) if noise_std > 0 else None
-        L.check(lib.nrf_raw2outputs_backward_noise(_ptr(raw), _ptr(z), C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, c, int(white_bkgr), _ptr(noise),
-                                                   C.c_float(noise_std), _ptr(g_rgb), _ptr(g_raw), _stream()))
+        L.check(lib.nrf_raw2outputs_backward_noise(_ptr(raw), _ptr(z), rays.data_ptr() + 12, stride, n, s, c, int(white_bkgr), _ptr(noise),
+                                                   noise_std, _ptr(g_rgb), _ptr(g_raw), _stream()))
         pts = torch.empty((n * s, 3), device=rays.device)
-        L.check(lib.nrf_points(_ptr(rays), stride, _ptr(z), C.c_int64(n), s, _ptr(pts), _stream()))
+        L.check(lib.nrf_points(_ptr(rays), stride, _ptr(z), n, s, _ptr(pts), _stream()))
         if p is not None and fine and p.StochasticPreconditioningAlpha > 0:          # NeRFRenderer.h:433-443 (fine pass only)
             pn = RngFill(seed, L.NRF_RNG_PRECOND, 0, n * s * 3, normal=True, device=rays.device)
             pts = StochasticPrecondition(pts, pn, float(p.StochasticPreconditioningAlpha), p.BoundingBox)
@@ -158,21 +158,21 @@ class Trainer:
             # w and the density normals are constants of the step ("no gradient flows here", NeRFExecutor.h:948); the normals at the points the network saw
             pts = pts.contiguous()
             dgrad = torch.empty((n * s, 3), device=rays.device)
-            L.check(lib.nrf_density_grad(self.renderer._r, _ptr(pts), C.c_int64(n * s), None, _ptr(dgrad), None, C.c_size_t(0), _stream()))
+            L.check(lib.nrf_density_grad(self.renderer._r, _ptr(pts), n * s, None, _ptr(dgrad), None, 0, _stream()))
             w = res.Outputs.Weights.reshape(n, s).contiguous()
-            nbl = lib.nrf_normal_losses_workspace_bytes(C.c_int64(n), s)
+            nbl = lib.nrf_normal_losses_workspace_bytes(n, s)
             if getattr(self, "_nws", None) is None or self._nws.numel() < nbl:
                 self._nws = torch.empty((int(nbl),), device="cuda", dtype=torch.uint8)
-            L.check(lib.nrf_normal_losses(_ptr(w), _ptr(dgrad), _ptr(raw), c, C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, C.c_float(self.pred_normal_loss_weight),
-                                          C.c_float(self.orientation_loss_weight), _ptr(g_raw), _ptr(self.normal_losses), _ptr(self._nws), C.c_size_t(self._nws.numel()), _stream()))
+            L.check(lib.nrf_normal_losses(_ptr(w), _ptr(dgrad), _ptr(raw), c, rays.data_ptr() + 12, stride, n, s, self.pred_normal_loss_weight,
+                                          self.orientation_loss_weight, _ptr(g_raw), _ptr(self.normal_losses), _ptr(self._nws), self._nws.numel(), _stream()))
         if self.distortion_loss_weight > 0 or self.sparsity_loss_weight > 0:
             # the same raw, depths, draws and directions as the RawToOutputs backward above; in a 64+128 step these are the fine pass's 192 samples (the only ones with a gradient)
-            nbr = lib.nrf_ray_regularizers_workspace_bytes(C.c_int64(n), s)
+            nbr = lib.nrf_ray_regularizers_workspace_bytes(n, s)
             if self._rws is None or self._rws.numel() < nbr:
                 self._rws = torch.empty((int(nbr),), device="cuda", dtype=torch.uint8)
-            L.check(lib.nrf_ray_regularizers(_ptr(raw), _ptr(z), C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), s, c, _ptr(noise), C.c_float(noise_std),
-                                             C.c_float(self.distortion_loss_weight), C.c_float(self.sparsity_loss_weight), _ptr(g_raw), _ptr(self.ray_losses), None,
-                                             _ptr(self._rws), C.c_size_t(self._rws.numel()), _stream()))
+            L.check(lib.nrf_ray_regularizers(_ptr(raw), _ptr(z), rays.data_ptr() + 12, stride, n, s, c, _ptr(noise), noise_std,
+                                             self.distortion_loss_weight, self.sparsity_loss_weight, _ptr(g_raw), _ptr(self.ray_losses), None,
+                                             _ptr(self._rws), self._rws.numel(), _stream()))
         dirs, _ = self.embeddirs.forward(rays[:, 8:11].contiguous())
         in_ch = self.embedder.GetOutputDims()
         self.g_blob.zero_(); self.g_table.zero_()
@@ -180,9 +180,9 @@ class Trainer:
             # classic model (NeRFRenderer.h:175-184 with Embedder / Embedder / NeRF): the encodings carry no parameters, so the chain ends at the network's own gradient
             emb, _ = self.embedder.forward(pts)
             x = torch.cat([emb, dirs[:, None, :].expand(n, s, dirs.shape[1]).reshape(n * s, -1)], 1).contiguous()
-            nb = lib.nrf_mlp_backward_workspace_bytes(self.mlp._m, C.c_int64(n * s))
+            nb = lib.nrf_mlp_backward_workspace_bytes(self.mlp._m, n * s)
             ws = self._workspace(nb)
-            L.check(lib.nrf_mlp_backward(self.mlp._m, _ptr(x), _ptr(g_raw), C.c_int64(n * s), _ptr(self.g_blob), None, _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+            L.check(lib.nrf_mlp_backward(self.mlp._m, _ptr(x), _ptr(g_raw), n * s, _ptr(self.g_blob), None, _ptr(ws), ws.numel(), _stream()))
             self.last = dict(g_rgb=g_rgb, g_raw=g_raw, g_x=None, x=x, pts=pts)
             self.overflow = False
             self._d_flags = None
@@ -193,24 +193,24 @@ class Trainer:
         if lm:
             # the fast path's own layout: level-major fp16 hash features + one fp16 direction row per ray; no [p, 48] fp32 input is formed
             dirs16 = dirs.to(torch.float16).contiguous()
-            nb = lib.nrf_mlp_backward_f16_workspace_bytes(self.mlp._m, C.c_int64(n * s))
+            nb = lib.nrf_mlp_backward_f16_workspace_bytes(self.mlp._m, n * s)
             ws = self._workspace(nb)
             # ... and where the forward render of THIS batch was the renderer's last call (a single-chunk render of the feature-reusing fast path), the features it
             # encoded are still in its workspace -- coarse columns, new samples' columns, the merge map: the same points, the same kernel, the same bits -- and the
             # fine points are not encoded a second time (0.6 ms of a 5.9 ms step)
             view = self._render_features(res, n, s) if (fine and cone_angle is None and not (p is not None and p.StochasticPreconditioningAlpha > 0)) else None
             if view is not None:
-                L.check(lib.nrf_mask_sigma_grad_src(C.c_void_p(view["keep"]), C.c_void_p(view["src"]), C.c_int64(n * s), c, _ptr(g_raw), _stream()))
-                L.check(lib.nrf_mlp_backward_f16_lm_src(self.mlp._m, C.c_void_p(view["feats"]), C.c_int64(view["cols"]), C.c_void_p(view["src"]), _ptr(dirs16), s, _ptr(g_raw),
-                                                        C.c_int64(n * s), _ptr(self.g_blob), _ptr(g_x), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+                L.check(lib.nrf_mask_sigma_grad_src(view["keep"], view["src"], n * s, c, _ptr(g_raw), _stream()))
+                L.check(lib.nrf_mlp_backward_f16_lm_src(self.mlp._m, view["feats"], view["cols"], view["src"], _ptr(dirs16), s, _ptr(g_raw),
+                                                        n * s, _ptr(self.g_blob), _ptr(g_x), _ptr(ws), ws.numel(), _stream()))
             else:
                 feats = torch.empty((16, n * s, 2), device=rays.device, dtype=torch.float16)
                 keep_u8 = torch.empty((n * s,), device=rays.device, dtype=torch.uint8)
                 ptsc = pts.contiguous()
-                L.check(lib.nrf_hash_encode_lm_f16(self.embedder._h, _ptr(ptsc), C.c_int64(n * s), _ptr(feats), _ptr(keep_u8), _stream()))
-                L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), C.c_int64(n * s), c, _ptr(g_raw), _stream()))
-                L.check(lib.nrf_mlp_backward_f16_lm(self.mlp._m, _ptr(feats), _ptr(dirs16), s, _ptr(g_raw), C.c_int64(n * s), _ptr(self.g_blob), _ptr(g_x), _ptr(ws),
-                                                    C.c_size_t(ws.numel()), _stream()))
+                L.check(lib.nrf_hash_encode_lm_f16(self.embedder._h, _ptr(ptsc), n * s, _ptr(feats), _ptr(keep_u8), _stream()))
+                L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), n * s, c, _ptr(g_raw), _stream()))
+                L.check(lib.nrf_mlp_backward_f16_lm(self.mlp._m, _ptr(feats), _ptr(dirs16), s, _ptr(g_raw), n * s, _ptr(self.g_blob), _ptr(g_x), _ptr(ws),
+                                                    ws.numel(), _stream()))
             self.reused_render_features = view is not None
             x = None
         else:
@@ -218,25 +218,25 @@ class Trainer:
             x = torch.cat([emb, dirs[:, None, :].expand(n, s, dirs.shape[1]).reshape(n * s, -1)], 1).contiguous()
             keep_u8 = keep.to(torch.uint8)
             # (the forward's mask writes column -1, NeRFRenderer.h:187-188: with 7 columns that is the predicted normal's z, and sigma's gradient is not masked)
-            L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), C.c_int64(n * s), c, _ptr(g_raw), _stream()))
+            L.check(lib.nrf_mask_sigma_grad(_ptr(keep_u8), n * s, c, _ptr(g_raw), _stream()))
             ws_fn, bw_fn = (lib.nrf_mlp_backward_f16_workspace_bytes, lib.nrf_mlp_backward_f16) if self.mlp_backward == "f16" else (lib.nrf_mlp_backward_workspace_bytes, lib.nrf_mlp_backward)
             if self.train_head:          # g_raw[:, 4:7] carries the normal losses' gradient: back through the head as well
                 ws_fn, bw_fn = lib.nrf_mlp_backward_pn_workspace_bytes, lib.nrf_mlp_backward_pn
-            nb = ws_fn(self.mlp._m, C.c_int64(n * s))
+            nb = ws_fn(self.mlp._m, n * s)
             ws = self._workspace(nb)
-            L.check(bw_fn(self.mlp._m, _ptr(x), _ptr(g_raw), C.c_int64(n * s), _ptr(self.g_blob), _ptr(g_x), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+            L.check(bw_fn(self.mlp._m, _ptr(x), _ptr(g_raw), n * s, _ptr(self.g_blob), _ptr(g_x), _ptr(ws), ws.numel(), _stream()))
         if self.hash_backward == "binned":
-            nbh = lib.nrf_hash_backward_binned_workspace_bytes_for(self.embedder._h, C.c_int64(n), s)      # records for this batch, not for a whole 2^18-point pass
+            nbh = lib.nrf_hash_backward_binned_workspace_bytes_for(self.embedder._h, n, s)      # records for this batch, not for a whole 2^18-point pass
             if self._hws is None or self._hws.numel() < nbh:
                 self._hws = torch.empty((int(nbh),), device="cuda", dtype=torch.uint8)
-            L.check(lib.nrf_hash_backward_rays_binned(self.embedder._h, _ptr(pts), C.c_int64(n), s, _ptr(g_x), _ptr(self.g_table), _ptr(self._hws), C.c_size_t(self._hws.numel()), _stream()))
+            L.check(lib.nrf_hash_backward_rays_binned(self.embedder._h, _ptr(pts), n, s, _ptr(g_x), _ptr(self.g_table), _ptr(self._hws), self._hws.numel(), _stream()))
         elif self.hash_backward == "packed":
             nbh = lib.nrf_hash_backward_packed_workspace_bytes(self.embedder._h)
             if self._hws is None or self._hws.numel() < nbh:
                 self._hws = torch.empty((int(nbh),), device="cuda", dtype=torch.uint8)
-            L.check(lib.nrf_hash_backward_rays_packed(self.embedder._h, _ptr(pts), C.c_int64(n), s, _ptr(g_x), _ptr(self.g_table), _ptr(self._hws), C.c_size_t(self._hws.numel()), _stream()))
+            L.check(lib.nrf_hash_backward_rays_packed(self.embedder._h, _ptr(pts), n, s, _ptr(g_x), _ptr(self.g_table), _ptr(self._hws), self._hws.numel(), _stream()))
         else:
-            L.check(lib.nrf_hash_backward_rays(self.embedder._h, _ptr(pts), C.c_int64(n), s, _ptr(g_x), _ptr(self.g_table), _stream()))
+            L.check(lib.nrf_hash_backward_rays(self.embedder._h, _ptr(pts), n, s, _ptr(g_x), _ptr(self.g_table), _stream()))
         self.last = dict(g_rgb=g_rgb, g_raw=g_raw, g_x=g_x, x=x, pts=pts)
         # fp16 gradient chain: was anything in it, or anything it produced, not finite?  (nrf_mlp_backward_f16_flags; the caller skips the step then.)  Without gradient
         # exchange the host does not wait for the answer: the optimizer step is guarded ON THE DEVICE by the two words (nrf_adam_step_guarded) and the host reads them
@@ -247,7 +247,7 @@ class Trainer:
             if self.grad_sync is None and defer_flags:
                 if self._h_flags is None:
                     self._h_flags = torch.zeros((2,), dtype=torch.int32).pin_memory()
-                L.check(lib.nrf_mlp_backward_f16_flags_async(_ptr(self._ws), C.c_void_p(self._h_flags.data_ptr()), _stream()))
+                L.check(lib.nrf_mlp_backward_f16_flags_async(_ptr(self._ws), self._h_flags.data_ptr(), _stream()))
                 self._flags_event = torch.cuda.Event(); self._flags_event.record(torch.cuda.current_stream())
                 self._d_flags = lib.nrf_mlp_backward_f16_flags_device(_ptr(self._ws))
             else:
@@ -319,7 +319,7 @@ class Trainer:
             cube = int(math.floor(min(max(float(np.float32(res) / np.float32(10.0)), e.BaseResolution - 1), e.FinestResolution - 1)))      # :269-273
             span = max(res - cube, 1)
             mv = np.array([self._rng_u32(self.seed, 18, (self.t * e.NLevels + level) * 3 + a) * span >> 32 for a in range(3)], np.int32)   # randint(0, res - cube), :276
-            L.check(L.lib().nrf_hash_tv_loss(e._h, _ptr(self.table), level, mv.ctypes.data_as(C.c_void_p), cube, C.c_float(self.tv_loss_weight), _ptr(self.tv_loss),
+            L.check(L.lib().nrf_hash_tv_loss(e._h, _ptr(self.table), level, mv.ctypes.data_as(C.c_void_p), cube, self.tv_loss_weight, _ptr(self.tv_loss),
                                              _ptr(self.g_table), _stream()))
 
     def step(self, rays_o, rays_d, target, render_params: NeRFRenderParams, cone_angle=None, global_step=None, n_iters=None, lrate_decay=None):
@@ -358,11 +358,10 @@ class Trainer:
             return loss_mse, res
         self.t += 1                                        # (a guarded step: taken back by _settle_flags if the device skipped the update)
         b1, b2 = self.betas
-        dfl, nfl = (C.c_void_p(self._d_flags), 2) if self._d_flags else (None, 0)
+        dfl, nfl = (self._d_flags, 2) if self._d_flags else (None, 0)
         for prm, g, m, v in ((self.table, self.g_table, self.m_table, self.v_table), (self.blob, self.g_blob, self.m_blob, self.v_blob)):
             if prm.numel():
-                L.check(L.lib().nrf_adam_step_guarded(_ptr(prm), _ptr(g), _ptr(m), _ptr(v), C.c_int64(prm.numel()), C.c_float(self.lr), C.c_float(b1), C.c_float(b2),
-                                                      C.c_float(self.eps), self.t, dfl, nfl, _stream()))
+                L.check(L.lib().nrf_adam_step_guarded(_ptr(prm), _ptr(g), _ptr(m), _ptr(v), prm.numel(), self.lr, b1, b2, self.eps, self.t, dfl, nfl, _stream()))
         self._push_params()
         if global_step is not None and lrate_decay:
             self.lr = self.learning_rate0 * math.pow(0.1, float(global_step) / (float(lrate_decay) * 1000.0))      # :992-996
@@ -471,7 +470,7 @@ def HuberRowsNanmean(pred, target, delta=1.25, want_grad=True):
     n, e = p.shape
     loss = torch.empty((1,), device=p.device)
     grad = torch.empty_like(p) if want_grad else None
-    L.check(L.lib().nrf_huber_rows_nanmean(_ptr(p), _ptr(t), C.c_int64(n), int(e), C.c_float(delta), _ptr(loss), _ptr(grad), _stream()))
+    L.check(L.lib().nrf_huber_rows_nanmean(_ptr(p), _ptr(t), n, int(e), delta, _ptr(loss), _ptr(grad), _stream()))
     return loss, grad
 
 
@@ -486,10 +485,10 @@ def LeRFHeadBackward(lerf, emb, keep, z, rays_d, g_rendered, noise=None, noise_s
     g_emb = torch.empty_like(emb) if want_g_emb else None
     rendered = torch.empty((n, E), device=emb.device); weights = torch.empty((n, s), device=emb.device)
     nz = None if noise is None else _dev_f32(noise)
-    nb = L.lib().nrf_lerf_head_backward_workspace_bytes(lerf._m, C.c_int64(n), int(s))
+    nb = L.lib().nrf_lerf_head_backward_workspace_bytes(lerf._m, n, int(s))
     ws = torch.empty((int(nb),), device=emb.device, dtype=torch.uint8)
-    L.check(L.lib().nrf_lerf_head_backward(lerf._m, _ptr(emb), _ptr(k8), _ptr(z), _ptr(d), 3, C.c_int64(n), int(s), _ptr(nz), C.c_float(noise_std), _ptr(g), _ptr(g_params),
-                                           _ptr(g_emb), _ptr(rendered), _ptr(weights), _ptr(ws), C.c_size_t(ws.numel()), _stream()))
+    L.check(L.lib().nrf_lerf_head_backward(lerf._m, _ptr(emb), _ptr(k8), _ptr(z), _ptr(d), 3, n, int(s), _ptr(nz), noise_std, _ptr(g), _ptr(g_params),
+                                           _ptr(g_emb), _ptr(rendered), _ptr(weights), _ptr(ws), ws.numel(), _stream()))
     return dict(g_params=g_params, g_emb=g_emb, rendered=rendered, weights=weights)
 
 
@@ -538,7 +537,7 @@ class LeRFTrainer:
         rendered = res.Outputs.RenderedLangEmbedding.reshape(n, -1).contiguous()
         loss, g = HuberRowsNanmean(rendered, target, self.delta)
         pts = torch.empty((n * s, 3), device=rays.device)
-        L.check(lib.nrf_points(_ptr(rays), stride, _ptr(z), C.c_int64(n), s, _ptr(pts), _stream()))
+        L.check(lib.nrf_points(_ptr(rays), stride, _ptr(z), n, s, _ptr(pts), _stream()))
         p = params
         seed = int(p.Seed)
         if p.StochasticPreconditioningAlpha > 0:                                     # LeRFRenderer.cpp:155-164
@@ -550,7 +549,7 @@ class LeRFTrainer:
         noise_std = float(p.RawNoiseStd)
         noise = RngFill(seed, L.NRF_RNG_NOISE_FINE, 0, n * s, normal=True, device=rays.device) if noise_std > 0 else None
         self.g_blob.zero_(); self.g_table.zero_()
-        nb = lib.nrf_lerf_backward_points_workspace_bytes(self.renderer._r, C.c_int64(n), int(s))
+        nb = lib.nrf_lerf_backward_points_workspace_bytes(self.renderer._r, n, int(s))
         if self._ws is None or self._ws.numel() < nb:
             self._ws = torch.empty((int(nb),), device="cuda", dtype=torch.uint8)
         pts = pts.contiguous()
@@ -563,12 +562,12 @@ class LeRFTrainer:
                 view = now
         self.reused_render_features = view is not None
         if view is not None:
-            L.check(lib.nrf_lerf_backward_points_src(self.renderer._r, C.c_void_p(view["feats"]), C.c_int64(view["cols"]), C.c_void_p(view["keep"]), C.c_void_p(view["src"]), _ptr(pts),
-                                                     _ptr(z), C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), int(s), _ptr(noise), C.c_float(noise_std), _ptr(g),
-                                                     _ptr(self.g_blob), _ptr(self.g_table), _ptr(self._ws), C.c_size_t(self._ws.numel()), _stream()))
+            L.check(lib.nrf_lerf_backward_points_src(self.renderer._r, view["feats"], view["cols"], view["keep"], view["src"], _ptr(pts),
+                                                     _ptr(z), rays.data_ptr() + 12, stride, n, int(s), _ptr(noise), noise_std, _ptr(g),
+                                                     _ptr(self.g_blob), _ptr(self.g_table), _ptr(self._ws), self._ws.numel(), _stream()))
         else:
-            L.check(lib.nrf_lerf_backward_points(self.renderer._r, _ptr(pts), _ptr(z), C.c_void_p(rays.data_ptr() + 12), stride, C.c_int64(n), int(s), _ptr(noise),
-                                                 C.c_float(noise_std), _ptr(g), _ptr(self.g_blob), _ptr(self.g_table), _ptr(self._ws), C.c_size_t(self._ws.numel()), _stream()))
+            L.check(lib.nrf_lerf_backward_points(self.renderer._r, _ptr(pts), _ptr(z), rays.data_ptr() + 12, stride, n, int(s), _ptr(noise),
+                                                 noise_std, _ptr(g), _ptr(self.g_blob), _ptr(self.g_table), _ptr(self._ws), self._ws.numel(), _stream()))
         self.last = dict(g_rendered=g, pts=pts)
         return loss
 
@@ -583,7 +582,6 @@ class LeRFTrainer:
         self.t += 1
         b1, b2 = self.betas
         for prm, g, m, v in ((self.table, self.g_table, self.m_table, self.v_table), (self.blob, self.g_blob, self.m_blob, self.v_blob)):
-            L.check(L.lib().nrf_adam_step(_ptr(prm), _ptr(g), _ptr(m), _ptr(v), C.c_int64(prm.numel()), C.c_float(self.lr), C.c_float(b1), C.c_float(b2),
-                                          C.c_float(self.eps), self.t, _stream()))
+            L.check(L.lib().nrf_adam_step(_ptr(prm), _ptr(g), _ptr(m), _ptr(v), prm.numel(), self.lr, b1, b2, self.eps, self.t, _stream()))
         self._push_params()
         return loss, res

@@ -1900,7 +1900,6 @@ def test_hash_backward_binned_equals_packed_bit_for_bit(api, mode, log2_t):
     side = int(host(wsb[65536:65540]).view(np.uint32)[0])       # entries of the LAST pass's side list (the workspace keeps the counter behind its 64-KB header)
     assert 0 < side <= 128 * 16, f"{mode}: the dominating sample's addends went through the side list ({side} entries)"
     # a workspace sized for THIS batch (records for n rays instead of a whole 2^18-point pass) serves the same call
-    lib.nrf_hash_backward_binned_workspace_bytes_for.restype = C.c_size_t
     nbf = lib.nrf_hash_backward_binned_workspace_bytes_for(e._h, C.c_int64(n), s)
     assert 0 < nbf <= nbb
     wsf = torch.empty(nbf, dtype=torch.uint8, device="cuda")

@@ -31,6 +31,49 @@ def test_library_builds_loads_and_exports_every_header_symbol():
     assert lib.nrf_status_string(0) == b"ok" and lib.nrf_version() >= 100
 
 
+def test_signature_table_matches_the_header_for_every_entry_point():
+    """_lib.SIGNATURES is the only place the Python side states the C ABI: every NRF_API declaration of the header, parsed
+    here independently, must give the same name, argument count, argument kinds and return kind, and the loaded library
+    must carry exactly those argtypes / restype.  No function is exempt."""
+    from nerfpp_amd import _lib
+    scalars = {"int": "i", "int64_t": "l", "size_t": "z", "float": "f", "double": "d", "uint32_t": "u", "uint64_t": "q"}
+    ctype = {"i": C.c_int, "l": C.c_int64, "z": C.c_size_t, "f": C.c_float, "d": C.c_double, "u": C.c_uint32, "q": C.c_uint64,
+             "p": C.c_void_p, "s": C.c_char_p, "v": None}
+
+    def kind(decl, fn, named):
+        if "*" in decl or "[" in decl:
+            return "p"
+        words = [w for w in decl.split() if w != "const"]
+        typ = " ".join(words[:-1] if named and len(words) > 1 else words)
+        assert typ in scalars, f"{fn}: no kind for `{decl.strip()}`"
+        return scalars[typ]
+
+    hdr = open(os.path.join(ROOT, "include", "nerfpp_hip.h")).read()
+    hdr = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+    decls = re.findall(r"\bNRF_API\s+([\w\s\*]+?)\b(nrf_\w+)\s*\(([^()]*)\)\s*;", hdr)
+    uses = sum(len(re.findall(r"\bNRF_API\b", line)) for line in hdr.splitlines() if not line.lstrip().startswith("#"))
+    assert len(decls) == uses >= 194, f"the regex parsed {len(decls)} of the header's {uses} NRF_API declarations"
+    header = {}
+    for ret, fn, args in decls:
+        ret = " ".join(ret.replace("*", " * ").split())
+        r = {"void": "v", "const char *": "s"}.get(ret) or kind(ret, fn, named=False)
+        a = "" if args.strip() in ("", "void") else "".join(kind(x, fn, named=True) for x in args.split(","))
+        assert fn not in header, f"{fn} is declared twice"
+        header[fn] = (r, a)
+    assert set(header) == set(_lib.SIGNATURES) == set(_lib.SYMBOLS), set(header) ^ set(_lib.SIGNATURES)
+    assert list(header) == _lib.SYMBOLS, "the table is kept in the header's order"
+    wrong = {fn: (_lib.SIGNATURES[fn], sig) for fn, sig in header.items() if _lib.SIGNATURES[fn] != sig}
+    assert not wrong, f"(table, header) differ for {wrong}"
+    lib = _lib.lib()
+    for fn, (r, a) in header.items():
+        f = getattr(lib, fn)
+        assert f.restype is ctype[r] and f.argtypes is not None and list(f.argtypes) == [ctype[k] for k in a], fn
+    with pytest.raises(TypeError):
+        lib.nrf_pe_encode(None, 4, 10, None)             # one argument short: refused before the call
+    with pytest.raises(C.ArgumentError):
+        lib.nrf_pe_encode(None, 4.0, 10, None, None)     # a float where the header says int64_t
+
+
 def test_argument_validation_needs_no_gpu():
     from nerfpp_amd import _lib
     lib = _lib.lib()

@@ -101,6 +101,32 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---- reductions over the 64 lanes of a wave ----
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// inclusive prefix sum in lane order (lane = the caller's lane id)
+__device__ __forceinline__ double wave_incl_scan(double v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double t = __shfl_up(v, off);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
 struct Bbox {
     float mn[3];
     float mx[3];

@@ -37,23 +37,6 @@ __device__ __forceinline__ T wave_sum_t(T v)
     return v;
 }
 
-__device__ __forceinline__ double wave_incl_scan(double v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------
 // C1  RawToOutputs
 // ------------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@
 // The LeRF embedding layer W (256 -> 768) is bias-free, so q . (W a) = (W^T q) . a: U = W^T [positive; negatives] (256 x 32) is built in fp64 into the caller's
 // workspace on EVERY call (prompts or weights changed since the last one are honoured; nothing is cached), scaled by a power of two into fp16 range and split
 // hi / lo like k_lerf_fill.  The split image's LE0 and Gram fragments are copied beside it (480 KB): the kernel's weight stream walks one image.
-#include "common.h"
+#include "chunk_loop.h"
 #include "mlp.h"
 #include "mlp_lerf_net.h"
 #include "stoch.h"
@@ -38,18 +38,6 @@ constexpr int64_t HEAD_SLAB = (int64_t)1 << 20;            // points per fused p
 constexpr size_t SPLIT_LE0_OFF = (size_t)2 * (8 * 8 + 2 * 16) * 1024;          // bytes of the split image before LE0 (sigma0, sigma1)
 constexpr size_t SPLIT_COPY = (size_t)(lerf::QUERY_IMAGE_FRAGS - 2 * 16) * 1024; // LE0 + Gram fragments
 
-struct Bump {
-    char *base;
-    size_t off = 0;
-    explicit Bump(void *b) : base(static_cast<char *>(b)) {}
-    template <class T> T *take(size_t count)
-    {
-        off = align_up(off, 256);
-        T *p = reinterpret_cast<T *>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
 struct Size {
     size_t b = 0;
     void add(size_t bytes) { b = align_up(b, 256) + bytes; }
@@ -92,7 +80,7 @@ __global__ void __launch_bounds__(512) k_query_fill(const float *__restrict__ u,
     const float gm = __uint_as_float(*umax_bits);
     int ex = 0;
     if (gm > 0.0f && gm <= 3.402823466e38f) (void)frexpf(gm / 1024.0f, &ex);
-    const int row = 32 * (ks >> 1) + lerf::perm_row(ks & 1, lane >> 5, j);
+    const int row = 32 * (ks >> 1) + perm_row(ks & 1, lane >> 5, j);
     const float v = ldexpf(u[(size_t)row * QSLOTS + (lane & 31)], -ex);
     const _Float16 hv = (_Float16)v;
     img[(size_t)f * 512 + e] = part == 0 ? hv : (_Float16)(v - (float)hv);
@@ -136,12 +124,6 @@ int build_image(const nrf_mlp *m, const QueryImage &q, const float *pos, const f
 
 // ---- the composed F32 path ----
 // k_lerf_relevancy's arithmetic (lerf_render.hip) with the phrases read from global memory: no bound on the number of negatives from an LDS phrase buffer
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __global__ void __launch_bounds__(256) k_query_relevancy_f32(const float *__restrict__ emb, int64_t n, int e, const float *__restrict__ pos, const float *__restrict__ neg,
                                                            int q, float *__restrict__ out)
 {

@@ -22,15 +22,13 @@
 // `Relevancy` is defined in the external module DeliriumV01D/RuCLIP (RuCLIPProcessor.h; relative path ../RuCLIP/src, no pinned version, absent from the reference tree)
 // and cv::applyColorMap is OpenCV's: both are restated from their published algorithms (oracle/nerf_oracle.c, orc_relevancy / orc_colormap_jet_lut, which say what exactly)
 // and anchored on the reference's call sites; no reference run or fixture pins them.
-#include "common.h"
+#include "chunk_loop.h"
 #include "mlp.h"
 #include "stoch.h"
 
 #include <cstdlib>
 #include <mutex>
 #include <vector>
-
-constexpr int NRF_LERF_MAX_LANES = 4;
 
 struct nrf_lerf_renderer {
     nrf_lerf_renderer_desc desc;
@@ -41,31 +39,19 @@ struct nrf_lerf_renderer {
     // lanes of this renderer's Chunk loop.  ONE by default: the LeRF kernels gain nothing from sharing the CUs (800x800 frame, same call: 1 lane 140-143 ms, 2 lanes
     // 146-147 ms at Chunk 32768; docs/history/profiles/round4/r4g_lerf_lane_chunk_sweep.log) -- their sum is matrix-bound and the F = 8 encode is at the HBM roofline by itself
     int lanes = 1;
-    // lanes of the Chunk loop (as nrf_renderer's): created on first use, bound to one device and one caller at a time
-    mutable std::mutex lane_mu;
-    mutable hipStream_t lane[NRF_LERF_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    mutable hipEvent_t lane_fork = nullptr, lane_done[NRF_LERF_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    mutable int lane_device = -1;
+    mutable nrf::Lanes chunk_lanes;   // lanes of the Chunk loop, created on first use (chunk_loop.h)
     // the pass's non-finite word (nrf_render_params.overflow_policy): ONE per call -- the pass has no fp32 single-call twin to render a flagged chunk again with, so a
     // flagged call is an error under every detecting policy; a pinned mirror and the event of a deferred copy
     mutable uint32_t *d_flag = nullptr, *h_flag = nullptr;
     mutable hipEvent_t flag_ev = nullptr;
     mutable bool flag_pending = false;
     mutable int64_t flagged_calls = 0;
-    // where the last chunk left the language features of its fine depths (nrf_lerf_renderer_last_features; as nrf_renderer's last_view): the level-major fp16 table
+    // where the last chunk left the language features of its fine depths (nrf_lerf_renderer_last_features; chunk_loop.h): the level-major fp16 table
     // [16][cols][8], the keep mask by column, the merge map [n, sf] -- in the caller's workspace; valid after a call that rendered exactly ONE chunk
-    mutable struct { const void *feats = nullptr; int64_t cols = 0; const uint8_t *keep = nullptr; const int32_t *src = nullptr; int64_t n = 0; int sf = 0; bool valid = false; } last_view;
-    mutable uint64_t chunk_serial = 0;
-    void drop_lanes() const
-    {
-        for (auto &st : lane) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }
-        for (auto &e : lane_done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        if (lane_fork) { (void)hipEventDestroy(lane_fork); lane_fork = nullptr; }
-        lane_device = -1;
-    }
+    mutable nrf::FeatureView view;
     ~nrf_lerf_renderer()
     {
-        drop_lanes();
+        chunk_lanes.drop();          // first: the lanes are drained before what their kernels write is freed
         if (flag_ev) { (void)hipEventSynchronize(flag_ev); (void)hipEventDestroy(flag_ev); }
         if (d_flag) (void)hipFree(d_flag);
         if (h_flag) (void)hipHostFree(h_flag);
@@ -76,30 +62,10 @@ struct nrf_lerf_renderer {
 
 namespace nrf {
 
-struct LBump {
-    char *base;
-    size_t off = 0;
-    explicit LBump(void *b) : base(static_cast<char *>(b)) {}
-    template <class T> T *take(size_t count)
-    {
-        off = align_up(off, 256);
-        T *p = reinterpret_cast<T *>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 // ---------------------------------------------------------------------------------------------------
 // Relevancy: one wave per ray.  logits = e . phrase (fp32, 768 terms: 12 per lane then a wave reduction), pairwise softmax at temperature 10 against each
 // negative, the pair whose positive probability is smallest (first on ties, as torch::argmin).  The phrases (1 + Q rows of E floats) sit in LDS.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 constexpr int REL_WAVES = 4;
 
 __global__ void __launch_bounds__(64 * REL_WAVES) k_lerf_relevancy(const float *__restrict__ emb, int64_t n, int e, const float *__restrict__ pos, const float *__restrict__ neg,
@@ -189,7 +155,7 @@ void lerf_renderer_query_parts(const nrf_lerf_renderer *r, const nrf_hash **h, c
     *pos = r->d_pos; *n_pos = r->n_pos; *neg = r->d_neg; *n_neg = r->n_neg; *embed_dim = r->embed_dim;
 }
 
-static int lerf_lanes(const nrf_lerf_renderer *r) { return r->lanes < 1 ? 1 : (r->lanes > NRF_LERF_MAX_LANES ? NRF_LERF_MAX_LANES : r->lanes); }
+static int lerf_lanes(const nrf_lerf_renderer *r) { return r->lanes < 1 ? 1 : (r->lanes > Lanes::MAX ? Lanes::MAX : r->lanes); }
 
 struct LerfPlan {
     int s, ni, sf, E;
@@ -252,27 +218,6 @@ static nrf_lerf_outputs slice(const nrf_lerf_outputs &o, int64_t i, int s, int s
     return q;
 }
 
-static int lerf_lanes_of(const nrf_lerf_renderer *r, int lanes, hipStream_t *st, hipEvent_t *fork, hipEvent_t *done)
-{
-    std::lock_guard<std::mutex> lk(r->lane_mu);
-    int dev = 0;
-    NRF_HIP(hipGetDevice(&dev));
-    if (r->lane_device >= 0 && r->lane_device != dev) {
-        (void)hipSetDevice(r->lane_device);
-        r->drop_lanes();
-        NRF_HIP(hipSetDevice(dev));
-    }
-    for (int i = 0; i < lanes; i++) {
-        if (!r->lane[i]) NRF_HIP(hipStreamCreateWithFlags(&r->lane[i], hipStreamNonBlocking));
-        if (!r->lane_done[i]) NRF_HIP(hipEventCreateWithFlags(&r->lane_done[i], hipEventDisableTiming));
-        st[i] = r->lane[i]; done[i] = r->lane_done[i];
-    }
-    if (!r->lane_fork) NRF_HIP(hipEventCreateWithFlags(&r->lane_fork, hipEventDisableTiming));
-    *fork = r->lane_fork;
-    r->lane_device = dev;
-    return NRF_OK;
-}
-
 }  // namespace nrf
 
 using namespace nrf;
@@ -287,10 +232,7 @@ extern "C" NRF_API int nrf_lerf_renderer_last_features(const nrf_lerf_renderer *
                                                        uint64_t *serial)
 {
     NRF_CHECK_ARG(r && d_feats_lm && cols && d_keep_cols && d_src && n && sf, "nrf_lerf_renderer_last_features: null pointer");
-    if (serial) *serial = r->chunk_serial;
-    if (!r->last_view.valid) { set_error("nrf_lerf_renderer_last_features: the last render call left no feature view (several chunks, or none yet)"); return NRF_ERR_UNSUPPORTED; }
-    *d_feats_lm = r->last_view.feats; *cols = r->last_view.cols; *d_keep_cols = r->last_view.keep; *d_src = r->last_view.src; *n = r->last_view.n; *sf = r->last_view.sf;
-    return NRF_OK;
+    return r->view.read(d_feats_lm, cols, d_keep_cols, d_src, n, sf, serial, "nrf_lerf_renderer_last_features: the last render call left no feature view (several chunks, or none yet)");
 }
 
 extern "C" {
@@ -360,7 +302,7 @@ void nrf_lerf_renderer_destroy(nrf_lerf_renderer *r) { delete r; }
 
 int nrf_lerf_renderer_set_lanes(nrf_lerf_renderer *r, int lanes)
 {
-    NRF_CHECK_ARG(r && lanes >= 1 && lanes <= NRF_LERF_MAX_LANES, "nrf_lerf_renderer_set_lanes: 1 .. %d lanes", NRF_LERF_MAX_LANES);
+    NRF_CHECK_ARG(r && lanes >= 1 && lanes <= Lanes::MAX, "nrf_lerf_renderer_set_lanes: 1 .. %d lanes", Lanes::MAX);
     r->lanes = lanes;
     return NRF_OK;
 }
@@ -475,8 +417,7 @@ static int lerf_render_rays_impl(const nrf_lerf_renderer *r, const float *d_rays
     NRF_CHECK_ARG(n >= 0 && (ray_stride == 8 || ray_stride == 11), "nrf_lerf_render_rays: packed rays are [n, 8 | 11]");
     LerfPlan pl;
     NRF_TRY(lerf_plan(r, p, &pl, "nrf_lerf_render_rays"));
-    r->last_view.valid = false;          // (set again at the end of the chunk)
-    r->chunk_serial++;
+    r->view.begin_chunk();          // (set again at the end of the chunk)
     if (n == 0) return NRF_OK;
     NRF_CHECK_ARG(d_rays && d_t && d_u && d_workspace, "nrf_lerf_render_rays: null pointer");
     NRF_CHECK_ARG(n * (int64_t)pl.sf < ((int64_t)1 << 31), "nrf_lerf_render_rays: %lld rays x %d samples exceed the 2^31 columns of one chunk; lower Chunk", (long long)n, pl.sf);
@@ -487,7 +428,7 @@ static int lerf_render_rays_impl(const nrf_lerf_renderer *r, const float *d_rays
     const nrf_mlp *m = r->desc.lerf;
     const int s = pl.s, ni = pl.ni, sf = pl.sf, E = pl.E;
     const int64_t cols = n * (int64_t)sf, nc = n * (int64_t)s, nn = n * (int64_t)ni;
-    LBump b(d_workspace);
+    Bump b(d_workspace);
     float *z = out->d_z_coarse ? out->d_z_coarse : b.take<float>((size_t)nc);
     if (out->d_z_coarse) (void)b.take<float>((size_t)nc);
     float *pts = b.take<float>((size_t)nc * 3);
@@ -537,7 +478,7 @@ static int lerf_render_rays_impl(const nrf_lerf_renderer *r, const float *d_rays
         if (out->d_relevancy)
             NRF_TRY(nrf_lerf_relevancy(emb, n, E, r->d_pos, r->n_pos, r->d_neg, r->n_neg, 0, out->d_relevancy, stream));     // LeRFRenderer.cpp:79 (one positive phrase)
     }
-    r->last_view.feats = x; r->last_view.cols = cols; r->last_view.keep = keep; r->last_view.src = src; r->last_view.n = n; r->last_view.sf = sf; r->last_view.valid = true;
+    r->view.set(x, cols, keep, src, n, sf);
     return NRF_OK;
 }
 
@@ -571,26 +512,18 @@ int nrf_lerf_batchify_rays(const nrf_lerf_renderer *r, const float *d_rays, int 
     if (part > 0 && (size_t)L * part <= workspace_bytes && d_workspace) {
         // the Chunk loop on lanes (as nrf_batchify_rays): consecutive chunks on L streams forked from and joined to the caller's, so that one chunk's gather-bound
         // F = 8 hash encode shares the CUs with another's matrix-bound passes.  Same kernels on the same slices: same results.
-        hipStream_t st = as_stream(stream), lane[NRF_LERF_MAX_LANES];
-        hipEvent_t fork = nullptr, done[NRF_LERF_MAX_LANES];
-        NRF_TRY(lerf_lanes_of(r, L, lane, &fork, done));
-        int rc = NRF_OK;
-        if (hipEventRecord(fork, st) != hipSuccess) { set_error("nrf_lerf_batchify_rays: forking the lanes failed"); rc = NRF_ERR_HIP; }
-        for (int j = 0; j < L && rc == NRF_OK; j++)
-            if (hipStreamWaitEvent(lane[j], fork, 0) != hipSuccess) { set_error("nrf_lerf_batchify_rays: forking the lanes failed"); rc = NRF_ERR_HIP; }
+        hipStream_t st = as_stream(stream), lane[Lanes::MAX];
+        hipEvent_t fork = nullptr, done[Lanes::MAX];
+        NRF_TRY(r->chunk_lanes.acquire(L, false, lane, &fork, done));
+        int rc = fork_lanes(st, fork, lane, L, "nrf_lerf_batchify_rays");
         int k = 0;
         for (int64_t i = 0; i < n && rc == NRF_OK; i += lc, k = (k + 1) % L) {                                                // :206
             const int64_t mm = n - i < lc ? n - i : lc;
             const nrf_lerf_outputs o = slice(*out, i, pl.s, pl.sf, pl.E);
             rc = lerf_render_rays_impl(r, d_rays + i * ray_stride, ray_stride, mm, p, d_t, d_u, &o, static_cast<char *>(d_workspace) + (size_t)k * part, part, lane[k], d_flag);
         }
-        for (int j = 0; j < L; j++) {
-            if (hipEventRecord(done[j], lane[j]) != hipSuccess || hipStreamWaitEvent(st, done[j], 0) != hipSuccess) {
-                if (rc == NRF_OK) { set_error("nrf_lerf_batchify_rays: joining the lanes failed"); rc = NRF_ERR_HIP; }
-                (void)hipStreamSynchronize(lane[j]);
-            }
-        }
-        if (n > lc) r->last_view.valid = false;          // the view describes ONE chunk's workspace
+        join_lanes(st, lane, done, L, "nrf_lerf_batchify_rays", rc);
+        if (n > lc) r->view.drop();          // the view describes ONE chunk's workspace
         return (rc == NRF_OK && n > 0) ? lerf_flag_end(r, p, st, "nrf_lerf_batchify_rays") : rc;
     }
     for (int64_t i = 0; i < n; i += chunk) {                                                                                  // :206
@@ -598,7 +531,7 @@ int nrf_lerf_batchify_rays(const nrf_lerf_renderer *r, const float *d_rays, int 
         const nrf_lerf_outputs o = slice(*out, i, pl.s, pl.sf, pl.E);
         NRF_TRY(lerf_render_rays_impl(r, d_rays + i * ray_stride, ray_stride, mm, p, d_t, d_u, &o, d_workspace, workspace_bytes, stream, d_flag));
     }
-    if (n > chunk) r->last_view.valid = false;          // the view describes ONE chunk's workspace
+    if (n > chunk) r->view.drop();          // the view describes ONE chunk's workspace
     return n > 0 ? lerf_flag_end(r, p, as_stream(stream), "nrf_lerf_batchify_rays") : NRF_OK;
 }
 
@@ -619,7 +552,7 @@ int nrf_lerf_render_rows(const nrf_lerf_renderer *r, const nrf_view *v, const nr
     const int stride = v->use_viewdirs ? 11 : 8;
     const size_t need = nrf_lerf_render_rows_workspace_bytes(r, v, p);
     if (workspace_bytes < need) { set_error("nrf_lerf_render_rows: workspace %zu < %zu bytes", workspace_bytes, need); return NRF_ERR_WORKSPACE; }
-    LBump b(d_workspace);
+    Bump b(d_workspace);
     float *rays = d_rays_out ? d_rays_out : b.take<float>((size_t)n * stride);
     void *ws = b.take<char>(0);
     NRF_TRY(nrf_view_rays(v, rays, d_near_far, stream));                                                                     // LeRFRenderer.cpp:275-305

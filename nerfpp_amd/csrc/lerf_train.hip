@@ -53,17 +53,10 @@ static int64_t lt_rays_per_pass(int64_t n, int64_t cpts, int s)
     return (n + passes - 1) / passes;
 }
 
-__device__ __forceinline__ double lt_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // block-wide sum of one double per thread (blockDim.x = 256: four waves); every thread gets the result
 __device__ __forceinline__ double lt_block_sum(double v, double *sh /*[4]*/)
 {
-    v = lt_wave_sum(v);
+    v = wave_sum(v);
     __syncthreads();                                 // sh may still be read from the previous use
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -82,7 +75,7 @@ __global__ void k_huber_rows(int64_t n, int e, float delta, const float *__restr
         const float z = fabsf(d);
         acc += (z < delta) ? 0.5 * (double)z * (double)z : (double)delta * ((double)z - 0.5 * (double)delta);
     }
-    acc = lt_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) row_loss[i] = (float)acc;
 }
 
@@ -121,7 +114,7 @@ __global__ void k_lt_point_norm(int64_t p, int e, float *__restrict__ h, int hs,
     const int lane = threadIdx.x & 63;
     double ss = 0.0;
     for (int k = lane; k < e; k += 64) { const float v = h[pt * hs + k]; ss += (double)v * (double)v; }
-    ss = lt_wave_sum(ss);
+    ss = wave_sum(ss);
     const float nr = (float)sqrt(ss);
     const float c = fmaxf(nr, 1e-8f);
     for (int k = lane; k < e; k += 64) h[pt * hs + k] = h[pt * hs + k] / c;
@@ -194,7 +187,7 @@ __global__ void __launch_bounds__(256) k_lt_ray(int s, int e, const float *__res
         float *row = le + (p0 + j) * hs;
         double t = 0.0;
         for (int k = lane; k < e; k += 64) t += (double)row[k] * (double)gv[k];
-        t = lt_wave_sum(t);
+        t = wave_sum(t);
         const float nr = nrm[p0 + j], c = fmaxf(nr, 1e-8f), w = wgt[j];
         const bool thr = nr >= 1e-8f && nr > 0.0f;
         const float hdot_over_c2 = (float)((double)w * t * (double)c / ((double)c * (double)c));     // g_le . h / c^2 with h = le c
@@ -300,7 +293,7 @@ __global__ void __launch_bounds__(256) k_ltg_ray_u(int s, int hd, const float *_
         double q = 0.0;
 #pragma unroll
         for (int i = 0; i < UK; i++) { const int k = lane + 64 * i; av[i] = k < hd ? ar[k] : 0.0f; if (k < hd) q += (double)av[i] * (double)sr[k]; }
-        q = lt_wave_sum(q);
+        q = wave_sum(q);
         const float nr = (float)sqrt(q > 0.0 ? q : 0.0);
         const float c = fmaxf(nr, 1e-8f);
         if (lane == 0) { cj[j] = c; pp[(p0 + j) * LTG_PP + 7] = nr; }
@@ -367,7 +360,7 @@ __global__ void __launch_bounds__(256) k_ltg_ray_g(int s, int hd, const float *_
         const float w = o[5], c = o[6], nr = o[7];
         double d = 0.0;
         for (int k = lane; k < hd; k += 64) d += (double)ar[k] * (double)qs[k];
-        d = lt_wave_sum(d);
+        d = wave_sum(d);
         const float t = (float)(d / (double)c);
         const bool thr = nr >= 1e-8f && nr > 0.0f;
         const float beta = thr ? (float)((double)w * (double)t / ((double)c * (double)nr)) : 0.0f;

@@ -1,6 +1,7 @@
 // mlp_lerf_net.h -- layer plan, fragment bookkeeping and kernel arguments of the LeRF head on the matrix cores, shared by mlp_lerf_mfma.hip (fp16 operands)
 // and mlp_lerf_split_mfma.hip (hi + lo fp16 operand pairs).  See mlp_lerf_mfma.hip for the formulation.
 #pragma once
+#include "mfma_frag.h"
 #include "mlp.h"
 
 namespace nrf {
@@ -14,8 +15,6 @@ constexpr int NW = 8;              // waves per workgroup
 constexpr int NBLK = 32 * NW;      // points per workgroup iteration (one 32-point tile per wave)
 constexpr int MAXF = 32;           // fragments (1 KB each) in the largest chunk
 constexpr int IN = 128, HID = 256, GEO = 32, EMB = 768;
-
-__host__ __device__ inline int perm_row(int s, int h, int j) { return 16 * s + 8 * (j >> 2) + 4 * h + (j & 3); }
 
 // Layers: 0 sigma0 [nat 8] -> 8 tiles ReLU | 1 sigma1 [chained 16] -> 2 tiles (row 0 = sigma, rows 1..32 = geo) | 2 LE0 [chained 4 | nat 8]
 // -> 8 tiles ReLU (cat[geo, in], LeRF.cpp) | 3 GRAM [chained 16] -> 8 tiles: t = (W^T W) a, ||LE1(a)||^2 = a . t | 4 LE1 [chained 16] -> 24 tiles

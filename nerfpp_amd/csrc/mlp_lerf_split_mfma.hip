@@ -102,13 +102,6 @@ __device__ __forceinline__ void stage_all(half8 *__restrict__ dst, const half8 *
     (stage_piece<N, CI, Qs>(dst, packed, wave, lane), ...);
 }
 
-__device__ __forceinline__ void split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo)
-{
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(v0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(v1));
-}
-
 // registers 8s..8s+7 of a finished tile -> the (hi, lo) operand fragments of k-step s.  The asm reads VALU results only (the max / the add).
 template <bool RELU>
 __device__ __forceinline__ void tile_to_frag2(const f32x16 &t, int s, half8 &hi, half8 &lo)

@@ -21,13 +21,6 @@ namespace {
 constexpr int NL_THREADS = 256;
 constexpr int NL_C = 7;            // columns of a raw row with the head: rgb, sigma, normal xyz
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // rows [base, base + cnt) of a row-major [total][W] fp32 array into LDS; `vec`: the array starts 16-byte aligned (a block's first row then does too: 256 W words)
 template <int W>
 __device__ __forceinline__ void stage_rows(const float *__restrict__ src, int64_t base, int cnt, bool vec, float *dst)
@@ -85,7 +78,7 @@ k_normal_losses(int64_t total, int s, const float *__restrict__ w, const float *
         float *o = g_raw + i * NL_C + 4;
         o[0] = gx; o[1] = gy; o[2] = gz;
     }
-    l_pn = wave_sum_d(l_pn); l_or = wave_sum_d(l_or);
+    l_pn = wave_sum(l_pn); l_or = wave_sum(l_or);
     if ((t & 63) == 0) { s_sum[0][t >> 6] = l_pn; s_sum[1][t >> 6] = l_or; }
     __syncthreads();
     if (t < 2) {

@@ -39,13 +39,6 @@ __device__ __forceinline__ double rr_incl_scan(double v, int lane)
     return v;
 }
 
-__device__ __forceinline__ double rr_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __global__ void __launch_bounds__(64 * RR_RAYS)
 k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *__restrict__ z, const float *__restrict__ dirs, int d_stride, const float *__restrict__ noise,
           float noise_std, float k_dist /* distortion_weight / n */, float k_sparse /* sparsity_weight / n */, int terms /* bit 0: distortion, bit 1: sparsity */, float *__restrict__ g_raw,
@@ -96,7 +89,7 @@ k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *_
                     w_tot += (double)w; m_tot += (double)w * (double)mj;
                 }
             }
-            w_tot = rr_wave_sum(w_tot); m_tot = rr_wave_sum(m_tot);
+            w_tot = wave_sum(w_tot); m_tot = wave_sum(m_tot);
             wave_sync();                                              // the wave reads its own lt row back below
         }
         if (dist_on || sparse_on) {
@@ -165,7 +158,7 @@ k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *_
             }
         }
     }
-    l_dist = rr_wave_sum(l_dist); l_sparse = rr_wave_sum(l_sparse);
+    l_dist = wave_sum(l_dist); l_sparse = wave_sum(l_sparse);
     if (lane == 0) { s_sum[0][wv] = l_dist; s_sum[1][wv] = l_sparse; }
     __syncthreads();
     if (threadIdx.x < 2) {

@@ -7,6 +7,7 @@
 // branches (jitter, cone rays / TangentScatter, sigma noise, preconditioning) add one point-generation launch per pass
 // (stoch.hip) whose draws are counter-based, and then run the same network kernels on explicit points.  One network
 // serves both passes and the fine pass re-evaluates all S + N_importance depths (NeRFRenderer.h:422,447).
+#include "chunk_loop.h"
 #include "encode.h"
 #include "hash_fast.h"
 #include "mlp.h"
@@ -16,17 +17,10 @@
 #include <cstdlib>
 #include <mutex>
 
-constexpr int NRF_MAX_LANES = 4;
-
 struct nrf_renderer {
     nrf_renderer_desc desc;
     int in_ch = 0, in_views = 0;
-    // the lanes of the Chunk loop (nrf_batchify_rays): auxiliary streams and the fork / join events, created on first use on the device that is current then and
-    // re-created when a later call comes on another device.  A renderer serves one device and one caller at a time (include/nerfpp_hip.h, nrf_batchify_rays).
-    mutable std::mutex lane_mu;
-    mutable hipStream_t lane[NRF_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    mutable hipEvent_t lane_fork = nullptr, lane_done[NRF_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    mutable int lane_device = -1;
+    mutable nrf::Lanes chunk_lanes;   // the lanes of the Chunk loop (nrf_batchify_rays), created on first use (chunk_loop.h)
     int lanes = 0;                // this renderer's lane count; 0: the process-wide default (nrf_set_render_lanes / NRF_RENDER_LANES)
     // non-finite words of the matrix-core precisions (nrf_render_params.overflow_policy): one per chunk of the current call on the device, a pinned host mirror for the
     // synchronous policies and one for the deferred copy, and the event that says the deferred copy has landed
@@ -35,21 +29,12 @@ struct nrf_renderer {
     mutable int deferred_slots[32] = {};               // > 0: a deferred copy of that many words is pending in ring entry i
     mutable int deferred_head = 0;                     // ring entry the next deferred copy goes to (entries are filled and looked at in order)
     mutable int64_t flagged_chunks = 0, rerendered_chunks = 0;
-    // where the most recent SINGLE-chunk render of the feature-reusing fast path (CuHashEmbedder mode) left its hash features in the caller's workspace: the level-major
-    // table, its column count, the keep mask by column and the merge map [n, sf] (nrf_renderer_last_features: the training backward reads them instead of encoding the
-    // fine points again).  Invalidated by every render call on entry.
-    mutable struct { const void *feats = nullptr; int64_t cols = 0; const uint8_t *keep = nullptr; const int32_t *src = nullptr; int64_t n = 0; int sf = 0; bool valid = false; } last_view;
-    mutable uint64_t chunk_serial = 0;                 // chunks rendered so far: a caller that saw serial k and still sees k knows that no render has touched the view since
-    void drop_lanes() const
-    {
-        for (auto &st : lane) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }
-        for (auto &e : lane_done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        if (lane_fork) { (void)hipEventDestroy(lane_fork); lane_fork = nullptr; }
-        lane_device = -1;
-    }
+    // where the most recent SINGLE-chunk render of the feature-reusing fast path (CuHashEmbedder mode) left its hash features in the caller's workspace
+    // (nrf_renderer_last_features; chunk_loop.h)
+    mutable nrf::FeatureView view;
     ~nrf_renderer()
     {
-        drop_lanes();
+        chunk_lanes.drop();          // first: the lanes are drained before what their kernels write is freed
         for (auto &e : deferred_ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
         if (d_flags) (void)hipFree(d_flags);
         if (h_flags) (void)hipHostFree(h_flags);
@@ -143,19 +128,6 @@ __global__ void k_gather_raw(int64_t p, const int32_t *__restrict__ src, const f
     const int64_t c = src[i];
     raw_f[i] = c < n_coarse ? raw_coarse[c] : raw_new[c - n_coarse];
 }
-
-struct Bump {
-    char *base;
-    size_t off = 0, cap;
-    Bump(void *b, size_t c) : base(static_cast<char *>(b)), cap(c) {}
-    template <class T> T *take(size_t count)
-    {
-        off = align_up(off, 256);
-        T *p = reinterpret_cast<T *>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
 
 static size_t network_ws_bytes(const nrf_renderer *r, int64_t p, int prec)
 {
@@ -618,8 +590,7 @@ namespace nrf {
 static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, const RenderParamsX *p,
                             const float *d_t, const float *d_u, const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, void *stream, uint32_t *d_flag)
 {
-    r->last_view.valid = false;          // (set again below by the feature-reusing fast path)
-    r->chunk_serial++;
+    r->view.begin_chunk();          // (set again below by the feature-reusing fast path)
     NRF_CHECK_ARG(r && p && out, "nrf_render_rays: null pointer");
     if (n == 0) return NRF_OK;
     NRF_CHECK_ARG(d_rays && d_t, "nrf_render_rays: null pointer");
@@ -791,7 +762,7 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
         PointSource psn{nullptr, d_rays, rw.z_new, ray_stride, ni};
         if (ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, psn, n * (int64_t)ni, rw.feats + n * (int64_t)s, rw.cols, rw.feats_lo ? rw.feats_lo - rw.feats : 0, rw.keep + n * (int64_t)s, st));
         else NRF_TRY(launch_hash_lm(r->desc.hash, psn, n * (int64_t)ni, rw.feats + n * (int64_t)s, rw.cols, rw.keep + n * (int64_t)s, HASH_LM_DEFAULT_VARIANT, st));
-        if (!ngp) { r->last_view.feats = rw.feats; r->last_view.cols = rw.cols; r->last_view.keep = rw.keep; r->last_view.src = rw.src; r->last_view.n = n; r->last_view.sf = sf; r->last_view.valid = true; }
+        if (!ngp) r->view.set(rw.feats, rw.cols, rw.keep, rw.src, n, sf);
         if (geo_reuse) {
             const int64_t nc = n * (int64_t)s;
             NRF_TRY(mlp_small_color_from_geo_lm(r->desc.mlp, geo_planes, nc, raw_c, dirs16, dirs_lo, s, rw.keep, nc, raw_cols, st));
@@ -848,7 +819,7 @@ static int render_lanes()
     if (v == 0) {
         const char *e = getenv("NRF_RENDER_LANES");
         v = e ? atoi(e) : 2;
-        if (v < 1 || v > NRF_MAX_LANES) v = 2;
+        if (v < 1 || v > Lanes::MAX) v = 2;
         g_render_lanes.store(v, std::memory_order_relaxed);
     }
     return v;
@@ -873,7 +844,7 @@ static int lanes_for(const nrf_renderer *r) { return r->lanes > 0 ? r->lanes : r
 
 int nrf_renderer_set_lanes(nrf_renderer *r, int lanes)
 {
-    NRF_CHECK_ARG(r && lanes >= 0 && lanes <= NRF_MAX_LANES, "nrf_renderer_set_lanes: 0 (the process-wide default) .. %d lanes", NRF_MAX_LANES);
+    NRF_CHECK_ARG(r && lanes >= 0 && lanes <= Lanes::MAX, "nrf_renderer_set_lanes: 0 (the process-wide default) .. %d lanes", Lanes::MAX);
     r->lanes = lanes;
     return NRF_OK;
 }
@@ -896,40 +867,8 @@ int nrf_get_render_lanes(void) { return render_lanes(); }
 
 int nrf_set_render_lanes(int lanes)
 {
-    NRF_CHECK_ARG(lanes >= 1 && lanes <= NRF_MAX_LANES, "nrf_set_render_lanes: 1 (single stream) .. %d", NRF_MAX_LANES);
+    NRF_CHECK_ARG(lanes >= 1 && lanes <= Lanes::MAX, "nrf_set_render_lanes: 1 (single stream) .. %d", Lanes::MAX);
     g_render_lanes.store(lanes, std::memory_order_relaxed);
-    return NRF_OK;
-}
-
-static int lanes_of(const nrf_renderer *r, int lanes, hipStream_t *st, hipEvent_t *fork, hipEvent_t *done)
-{
-    std::lock_guard<std::mutex> lk(r->lane_mu);
-    int dev = 0;
-    NRF_HIP(hipGetDevice(&dev));
-    if (r->lane_device >= 0 && r->lane_device != dev) {
-        // the renderer is now used on another device: its lanes move with it (the old ones are drained and destroyed on their own device)
-        int cur = dev;
-        (void)hipSetDevice(r->lane_device);
-        r->drop_lanes();
-        NRF_HIP(hipSetDevice(cur));
-    }
-    for (int i = 0; i < lanes; i++) {
-        if (!r->lane[i]) {
-            // NRF_LANE_CU_MASK=1 (experiment, docs/history/profiles/round4/r4z_*): lane i of L on its own 256 / L compute units (hipExtStreamCreateWithCUMask; a contiguous bit range)
-            static const int masked = [] { const char *e = getenv("NRF_LANE_CU_MASK"); return e ? atoi(e) : 0; }();
-            if (masked && lanes > 1) {
-                uint32_t bits[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                const int per = 256 / lanes;
-                for (int b = i * per; b < (i + 1) * per; b++) bits[b >> 5] |= 1u << (b & 31);
-                NRF_HIP(hipExtStreamCreateWithCUMask(&r->lane[i], 8, bits));
-            } else NRF_HIP(hipStreamCreateWithFlags(&r->lane[i], hipStreamNonBlocking));
-        }
-        if (!r->lane_done[i]) NRF_HIP(hipEventCreateWithFlags(&r->lane_done[i], hipEventDisableTiming));
-        st[i] = r->lane[i]; done[i] = r->lane_done[i];
-    }
-    if (!r->lane_fork) NRF_HIP(hipEventCreateWithFlags(&r->lane_fork, hipEventDisableTiming));
-    *fork = r->lane_fork;
-    r->lane_device = dev;
     return NRF_OK;
 }
 
@@ -972,18 +911,15 @@ static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_str
     const size_t part = lc > 0 && lc < n ? align_up(rays_ws_bytes(r, lc, p, p->normals), 256) : 0;
     if (part > 0 && (size_t)L * part <= workspace_bytes && d_workspace) {
         // fork from the caller's stream, each chunk on the least-loaded lane in that lane's slice of the workspace, join
-        hipStream_t st = as_stream(stream), lane[NRF_MAX_LANES];
-        hipEvent_t fork = nullptr, done[NRF_MAX_LANES];
-        NRF_TRY(lanes_of(r, L, lane, &fork, done));
-        int rc = NRF_OK;
-        if (hipEventRecord(fork, st) != hipSuccess) { set_error("nrf_batchify_rays: forking the lanes failed"); rc = NRF_ERR_HIP; }
-        for (int j = 0; j < L && rc == NRF_OK; j++)
-            if (hipStreamWaitEvent(lane[j], fork, 0) != hipSuccess) { set_error("nrf_batchify_rays: forking the lanes failed"); rc = NRF_ERR_HIP; }
+        hipStream_t st = as_stream(stream), lane[Lanes::MAX];
+        hipEvent_t fork = nullptr, done[Lanes::MAX];
+        NRF_TRY(r->chunk_lanes.acquire(L, true, lane, &fork, done));
+        int rc = fork_lanes(st, fork, lane, L, "nrf_batchify_rays");
         // Lane k starts with (L - k) / L of a chunk: the lanes then run out of phase (one in its encode while another is in its network) instead of doing the same
         // thing at the same time, which is what makes them share the CUs well.  The next chunk goes to the lane that has been given the fewest rays so far, and the
         // last < L chunks are cut so that all lanes end together.
-        int64_t given[NRF_MAX_LANES] = {0, 0, 0, 0};
-        bool first[NRF_MAX_LANES] = {true, true, true, true};
+        int64_t given[Lanes::MAX] = {0, 0, 0, 0};
+        bool first[Lanes::MAX] = {true, true, true, true};
         for (int64_t i = 0; i < n && rc == NRF_OK;) {                                                             // :476
             int k = 0;
             for (int j = 1; j < L; j++) if (given[j] < given[k]) k = j;
@@ -1013,14 +949,8 @@ static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_str
             given[k] += m;
             i += m;
         }
-        // join on every path: whatever was launched is ordered before the caller's next operation
-        for (int j = 0; j < L; j++) {
-            if (hipEventRecord(done[j], lane[j]) != hipSuccess || hipStreamWaitEvent(st, done[j], 0) != hipSuccess) {
-                if (rc == NRF_OK) { set_error("nrf_batchify_rays: joining the lanes failed"); rc = NRF_ERR_HIP; }
-                (void)hipStreamSynchronize(lane[j]);
-            }
-        }
-        if (done_chunks.size() != 1) r->last_view.valid = false;          // the feature view describes ONE chunk's workspace: only a single-chunk call keeps it
+        join_lanes(st, lane, done, L, "nrf_batchify_rays", rc);          // on every path
+        if (done_chunks.size() != 1) r->view.drop();          // the feature view describes ONE chunk's workspace: only a single-chunk call keeps it
         return rc == NRF_OK ? settle() : rc;
     }
     for (int64_t i = 0; i < n; i += chunk) {                                                                      // :476
@@ -1030,7 +960,7 @@ static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_str
         NRF_TRY(render_rays_impl(r, d_rays + i * ray_stride, ray_stride, m, &q, d_t, d_u, &o, d_workspace, workspace_bytes, stream, flag_of(done_chunks.size())));
         done_chunks.push_back({i, m});
     }
-    if (done_chunks.size() != 1) r->last_view.valid = false;
+    if (done_chunks.size() != 1) r->view.drop();
     return settle();
 }
 
@@ -1060,10 +990,7 @@ extern "C" NRF_API int nrf_renderer_last_features(const nrf_renderer *r, const v
                                                   uint64_t *serial)
 {
     NRF_CHECK_ARG(r && d_feats_lm && cols && d_keep_cols && d_src && n && sf, "nrf_renderer_last_features: null pointer");
-    if (serial) *serial = r->chunk_serial;
-    if (!r->last_view.valid) { set_error("nrf_renderer_last_features: the last render call left no feature view (several chunks, another path, or none yet)"); return NRF_ERR_UNSUPPORTED; }
-    *d_feats_lm = r->last_view.feats; *cols = r->last_view.cols; *d_keep_cols = r->last_view.keep; *d_src = r->last_view.src; *n = r->last_view.n; *sf = r->last_view.sf;
-    return NRF_OK;
+    return r->view.read(d_feats_lm, cols, d_keep_cols, d_src, n, sf, serial, "nrf_renderer_last_features: the last render call left no feature view (several chunks, another path, or none yet)");
 }
 
 extern "C" int nrf_view_check(const nrf_view *v, const char *who);

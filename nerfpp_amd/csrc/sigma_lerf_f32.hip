@@ -35,15 +35,6 @@ constexpr int W0_F4 = 8 * 16 * 64;                 // [mt 8][g = ks / 4, 16][lan
 constexpr int W1G_F4 = 64 * 64;                    // [g1 = ks1 / 4, 64][lane 64] float4: the geo tile
 constexpr size_t LDS_BYTES = (size_t)W0_F4 * 16 + 256 * 4;
 
-__host__ __device__ inline int row_neuron(int i) { return 2 * (4 * (i >> 3) + (i & 3)) + ((i >> 2) & 1); }
-
-__device__ __forceinline__ void split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo)
-{
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(v0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(v1));
-}
-
 // image: W0 fragments | w1 row 0 (sigma) [256] | geo tile fragments
 template <bool GEO>
 __global__ void __launch_bounds__(64 * WAVES)
@@ -191,7 +182,7 @@ int mlp_lerf_pack_sigma_f32(nrf_mlp *m, const std::vector<float> &hp)
         for (int g = 0; g < 16; g++)
             for (int lane = 0; lane < 64; lane++)
                 for (int j = 0; j < 4; j++) {
-                    const int row = 32 * mt + lsig::row_neuron(lane & 31), k = 2 * (4 * g + j) + (lane >> 5);
+                    const int row = 32 * mt + row_neuron(lane & 31), k = 2 * (4 * g + j) + (lane >> 5);
                     img.push_back(w0[(size_t)row * lerf::IN + k]);
                 }
     for (int k = 0; k < lerf::HID; k++) img.push_back(w1[k]);
@@ -219,7 +210,7 @@ __global__ void k_lsig_fill(const float *__restrict__ hp, float *__restrict__ im
     float v;
     if (idx < A) {
         const int j = idx & 3, lane = (idx >> 2) & 63, g = (idx >> 8) & 15, mt = idx >> 12;
-        const int row = 32 * mt + lsig::row_neuron(lane & 31), k = 2 * (4 * g + j) + (lane >> 5);
+        const int row = 32 * mt + row_neuron(lane & 31), k = 2 * (4 * g + j) + (lane >> 5);
         v = w0[(size_t)row * lerf::IN + k];
     } else if (idx < A + B) {
         v = w1[idx - A];

@@ -22,6 +22,7 @@
 // Resources: one wave per SIMD (4 waves, 128 points per workgroup pass).  A wave holds a layer's input and output for its 32 points in registers (2 x 128, the
 // unified VGPR + AGPR file); the 1.9 MB of fp32 weight fragments stream L2 -> LDS by LDS-DMA in chunks of one neuron tile (8 / 32 / 40 KB), one chunk ahead,
 // shared by the four waves.  Layers 1-4 and 6-7 have the same shape and run the same unrolled code (1 024 matrix instructions) in a loop.
+#include "mfma_frag.h"
 #include "mlp.h"
 
 namespace nrf {
@@ -59,10 +60,6 @@ constexpr int VIEW_BIAS_FLOATS = 128 + 4;             // merged bias [tile 4][la
 constexpr size_t LDS_BYTES = (size_t)2 * MAXG * 1024 + (BIAS_FLOATS + ALPHA_FLOATS + VIEW_BIAS_FLOATS) * 4;
 static_assert(SIGMA_GROUPS == 8 * (8 + 6 * 32 + 40) && VIEW_GROUPS <= MAXG, "image size");
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-__host__ __device__ inline int perm_row(int s, int h, int j) { return 16 * s + 8 * (j >> 2) + 4 * h + (j & 3); }      // row of a 32x32 D tile in register 8s + j of lane half h
-
-__host__ __device__ inline int row_neuron(int i) { return 2 * (4 * (i >> 3) + (i & 3)) + ((i >> 2) & 1); }
-
 struct Ctx {
     f32x4 *wbuf;                 // [2][MAXG * 64]
     const float *bias_s;         // LDS
@@ -159,13 +156,6 @@ __device__ __forceinline__ f32x16 tile(Ctx &cx, int layer, int mt, int next_ng, 
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     cx.cur ^= 1;
     return acc;
-}
-
-__device__ __forceinline__ void split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo)
-{
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(v0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(v1));
 }
 
 // registers 8s..8s+7 of an fp32 tile -> the (hi, lo) fp16 operand fragments of one k-step (v = hi + lo to 22 bits).  The asm reads VALU results only (the max).

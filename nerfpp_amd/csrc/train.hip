@@ -40,15 +40,6 @@ __global__ void k_finish_loss(int64_t count, const double *__restrict__ acc, flo
 // One wave per ray.  Forward quantities are recomputed exactly as k_raw2outputs does (same double scan for the log-transmittance);
 // the reverse pass needs suffix sums of g_L over later samples: a reverse wave scan per 64-sample block, blocks walked last to first.
 constexpr int BW_RAYS = 4;
-__device__ __forceinline__ double wave_incl_scan_d(double v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
 
 __global__ void __launch_bounds__(64 * BW_RAYS)
 k_raw2outputs_bwd(int64_t n, int s, int c, int white, const float *__restrict__ raw, const float *__restrict__ z, const float *__restrict__ dirs, int d_stride,
@@ -79,7 +70,7 @@ k_raw2outputs_bwd(int64_t n, int s, int c, int white, const float *__restrict__ 
             const float om = 1.0f - alpha;
             lg = nrf_logf(om > 1e-10f ? om : 1e-10f);
         }
-        const double incl = wave_incl_scan_d((double)lg, lane);
+        const double incl = wave_incl_scan((double)lg, lane);
         if (j < s) lt[j] = (float)(carry + (incl - (double)lg));
         carry += __shfl(incl, 63);
     }
@@ -112,7 +103,7 @@ k_raw2outputs_bwd(int64_t n, int s, int c, int white, const float *__restrict__ 
             gL = gw * alpha * nrf_expf(cl);                // g_T * dT/dL with TruncExp's clamped derivative
         }
         // suffix over LATER samples: total of this block minus the inclusive prefix, plus later blocks
-        const double incl = wave_incl_scan_d((double)gL, lane);
+        const double incl = wave_incl_scan((double)gL, lane);
         const double total = __shfl(incl, 63);
         const double later = suffix + (total - incl);
         suffix += total;

@@ -188,6 +188,18 @@ class NeRFRenderParams:               # NeRFRenderer.h:28-44 (same defaults)
     UsePredNormal: bool = False
 
 
+def _feature_view(last_features, handle):
+    """The feature view of a renderer handle through its *_last_features entry: dict(feats, cols, keep, src: device addresses; n, sf; serial) or None."""
+    if not handle:
+        return None
+    fp, kp, sp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    cols, nn, sf, ser = C.c_int64(), C.c_int64(), C.c_int(), C.c_uint64()
+    rc = last_features(handle, C.byref(fp), C.byref(cols), C.byref(kp), C.byref(sp), C.byref(nn), C.byref(sf), C.byref(ser))
+    if rc != 0:
+        return None
+    return dict(feats=fp.value, cols=int(cols.value), keep=kp.value, src=sp.value, n=int(nn.value), sf=int(sf.value), serial=int(ser.value))
+
+
 class NeRFRenderer:
     """NeRFRenderer<TEmbedder, TEmbedDirs, TNeRF> (NeRFRenderer.h:88-159)."""
 
@@ -227,14 +239,7 @@ class NeRFRenderer:
     def feature_view(self):
         """nrf_renderer_last_features: where the most recent single-chunk render of the feature-reusing fast path left the hash features of its fine depths in this
         renderer's workspace -- dict(feats, cols, keep, src: device addresses; n, sf; serial) or None.  Valid until the next render call on this renderer."""
-        if not getattr(self, "_r", None):
-            return None
-        fp, kp, sp = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        cols, nn, sf, ser = C.c_int64(), C.c_int64(), C.c_int(), C.c_uint64()
-        rc = L.lib().nrf_renderer_last_features(self._r, C.byref(fp), C.byref(cols), C.byref(kp), C.byref(sp), C.byref(nn), C.byref(sf), C.byref(ser))
-        if rc != 0:
-            return None
-        return dict(feats=fp.value, cols=int(cols.value), keep=kp.value, src=sp.value, n=int(nn.value), sf=int(sf.value), serial=int(ser.value))
+        return _feature_view(L.lib().nrf_renderer_last_features, getattr(self, "_r", None))
 
     def _workspace(self, nbytes, device):
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
@@ -718,14 +723,7 @@ class LeRFRenderer:
     def feature_view(self):
         """nrf_lerf_renderer_last_features: where the most recent one-chunk render left the language features of its fine depths in this renderer's workspace --
         dict(feats, cols, keep, src: device addresses; n, sf; serial) or None.  Valid until the next render call on this renderer (LeRFTrainer.backward reads it)."""
-        if not getattr(self, "_r", None):
-            return None
-        fp, kp, sp = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        cols, nn, sf, ser = C.c_int64(), C.c_int64(), C.c_int(), C.c_uint64()
-        rc = L.lib().nrf_lerf_renderer_last_features(self._r, C.byref(fp), C.byref(cols), C.byref(kp), C.byref(sp), C.byref(nn), C.byref(sf), C.byref(ser))
-        if rc != 0:
-            return None
-        return dict(feats=fp.value, cols=int(cols.value), keep=kp.value, src=sp.value, n=int(nn.value), sf=int(sf.value), serial=int(ser.value))
+        return _feature_view(L.lib().nrf_lerf_renderer_last_features, getattr(self, "_r", None))
 
     def _issue_single_call(self, lib, h, w, k, p, c2w, row0, rows, bb, rp, ro, res, rays_, t, u, workspace, f32, stride, n, o, d):
         if c2w is not None:

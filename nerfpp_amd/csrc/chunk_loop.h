@@ -1,28 +1,15 @@
-// chunk_loop.h -- host plumbing of a renderer's Chunk loop, shared by render.hip (nrf_renderer) and lerf_render.hip (nrf_lerf_renderer): the workspace bump
-// allocator, the lanes (auxiliary streams with their fork / join events) and the feature view a one-chunk render leaves behind.  What goes on which lane and
-// in which pieces is each renderer's own policy and stays in its file.
+// chunk_loop.h -- host plumbing of a renderer's Chunk loop, shared by render.hip (nrf_renderer) and lerf_render.hip (nrf_lerf_renderer): the lanes (auxiliary streams
+// with their fork / join events) and the feature view a one-chunk render leaves behind.  What goes on which lane and in which pieces is each renderer's own policy
+// and stays in its file.  (The workspace bump allocator both use is workspace.h's.)
 #pragma once
 
 #include "common.h"
+#include "workspace.h"
 
 #include <cstdlib>
 #include <mutex>
 
 namespace nrf {
-
-// carves 256-byte aligned pieces off a caller's workspace; `cap` is what the caller said it holds (takers compare `off` against it where they check at all)
-struct Bump {
-    char *base;
-    size_t off = 0, cap;
-    explicit Bump(void *b, size_t c = SIZE_MAX) : base(static_cast<char *>(b)), cap(c) {}
-    template <class T> T *take(size_t count)
-    {
-        off = align_up(off, 256);
-        T *p = reinterpret_cast<T *>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
 
 // The lanes of a Chunk loop: auxiliary streams and the fork / join events, created on first use on the device that is current then and re-created when a later call
 // comes on another device.  A renderer serves one device and one caller at a time (include/nerfpp_hip.h, nrf_batchify_rays).

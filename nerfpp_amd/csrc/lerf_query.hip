@@ -38,11 +38,6 @@ constexpr int64_t HEAD_SLAB = (int64_t)1 << 20;            // points per fused p
 constexpr size_t SPLIT_LE0_OFF = (size_t)2 * (8 * 8 + 2 * 16) * 1024;          // bytes of the split image before LE0 (sigma0, sigma1)
 constexpr size_t SPLIT_COPY = (size_t)(lerf::QUERY_IMAGE_FRAGS - 2 * 16) * 1024; // LE0 + Gram fragments
 
-struct Size {
-    size_t b = 0;
-    void add(size_t bytes) { b = align_up(b, 256) + bytes; }
-};
-
 // ---- the U tile ----
 // U[j][k] = sum_o W[o][j] q_k[o] in double (four partial sums, as k_lerf_gram_f64); q_0 = positives[positive_id], q_k = negatives[k - 1] (k <= n_neg), 0 beyond
 __global__ void __launch_bounds__(QSLOTS) k_query_proj_f64(const float *__restrict__ w3, const float *__restrict__ pos, const float *__restrict__ neg, int n_neg,
@@ -98,15 +93,9 @@ QueryImage take_image(Bump &b)
     QueryImage q;
     q.img = b.take<char>((size_t)lerf::QUERY_IMAGE_FRAGS * 1024);
     q.u = b.take<float>((size_t)HID * QSLOTS);
-    q.umax = b.take<uint32_t>(4);
-    q.u_scale = reinterpret_cast<float *>(q.umax + 1);
+    q.umax = b.take<uint32_t>(1);
+    q.u_scale = b.take<float>(1);
     return q;
-}
-void size_image(Size &s)
-{
-    s.add((size_t)lerf::QUERY_IMAGE_FRAGS * 1024);
-    s.add((size_t)HID * QSLOTS * 4);
-    s.add(16);
 }
 
 int build_image(const nrf_mlp *m, const QueryImage &q, const float *pos, const float *neg, int n_neg, hipStream_t st)
@@ -162,17 +151,6 @@ struct F32Bufs {
     size_t mws_bytes;
 };
 // rows: x_rows (head entry) or the features of points (point / grid entries: x == NULL here, encoded into bufs.x)
-size_t f32_bytes(const nrf_mlp *m, bool encode)
-{
-    Size s;
-    const int E = m->out_dims - 1;
-    s.add((size_t)F32_CHUNK * m->out_dims * 4);
-    s.add((size_t)F32_CHUNK * E * 4);
-    s.add((size_t)F32_CHUNK * 4);
-    if (encode) { s.add((size_t)F32_CHUNK * m->in_dims * 4); s.add((size_t)F32_CHUNK); }
-    s.add(mlp_workspace_bytes(m, F32_CHUNK, NRF_PREC_F32));
-    return align_up(s.b, 256);
-}
 F32Bufs take_f32(const nrf_mlp *m, Bump &b, bool encode)
 {
     F32Bufs f{};
@@ -282,22 +260,34 @@ int64_t slab_of(int64_t slab_points, int64_t n)
 }
 
 // workspace of the point / grid entries for slabs of `slab` points
+struct PointsWs {
+    QueryImage qi;           // fused precisions: the prompt image, ...
+    float *ptsb;             // a lattice's points (slab, or chunk of the composed path)
+    __half *x;               // ... level-major fp16 features
+    uint8_t *keep;
+    float *sig;              // sigma_le (when the caller does not want it)
+    void *geo;               // (sigma, geo32) planes
+    F32Bufs f;               // NRF_PREC_F32: the composed path's buffers
+};
+PointsWs points_layout(Bump &b, const nrf_mlp *m, int precision, int64_t slab, bool lattice)
+{
+    PointsWs w{};
+    if (fused_precision(precision)) {
+        w.qi = take_image(b);
+        if (lattice) w.ptsb = b.take<float>((size_t)slab * 3);
+        w.x = b.take<__half>((size_t)slab * IN);
+        w.keep = b.take<uint8_t>((size_t)slab);
+        w.sig = b.take<float>((size_t)slab);
+        w.geo = b.take<char>(nrf_lerf_geo_bytes(slab));
+    } else {
+        if (lattice) w.ptsb = b.take<float>((size_t)(slab < F32_CHUNK ? slab : F32_CHUNK) * 3);
+        w.f = take_f32(m, b, true);
+    }
+    return w;
+}
 size_t points_ws(const nrf_mlp *m, int precision, int64_t slab, bool lattice)
 {
-    Size s;
-    if (fused_precision(precision)) {
-        size_image(s);
-        if (lattice) s.add((size_t)slab * 12);
-        s.add((size_t)slab * IN * 2);                      // level-major fp16 features
-        s.add((size_t)slab);                               // keep
-        s.add((size_t)slab * 4);                           // sigma_le (when the caller does not want it)
-        s.add(nrf_lerf_geo_bytes(slab));                   // (sigma, geo32) planes
-    } else {
-        const int64_t c = slab < F32_CHUNK ? slab : F32_CHUNK;
-        if (lattice) s.add((size_t)c * 12);
-        s.add(f32_bytes(m, true));
-    }
-    return align_up(s.b, 256) + 256;
+    return measure([&](Bump &b) { points_layout(b, m, precision, slab, lattice); });
 }
 
 struct PointsCall {
@@ -310,16 +300,18 @@ struct PointsCall {
 
 // the point pipeline over slabs; pts_of(first, cnt, buf) gives the slab's points (the caller's array, or the lattice written into buf)
 template <class PtsOf>
-int run_points(const PointsCall &c, int64_t p, int64_t slab, bool lattice, PtsOf pts_of, float *d_sigma, float *d_rel, void *d_ws, hipStream_t st)
+int run_points(const char *who, const PointsCall &c, int64_t p, int64_t slab, bool lattice, PtsOf pts_of, float *d_sigma, float *d_rel, void *d_ws, size_t ws_bytes, hipStream_t st)
 {
-    Bump b(d_ws);
+    Bump b(d_ws, ws_bytes);
+    const PointsWs w = points_layout(b, c.m, c.precision, slab, lattice);
+    NRF_TRY(ws_check(b, points_ws(c.m, c.precision, slab, lattice), who));
+    float *const ptsb = w.ptsb;
     if (fused_precision(c.precision)) {
-        const QueryImage qi = take_image(b);
-        float *ptsb = lattice ? b.take<float>((size_t)slab * 3) : nullptr;
-        __half *x = b.take<__half>((size_t)slab * IN);
-        uint8_t *keep = b.take<uint8_t>((size_t)slab);
-        float *sig_ws = b.take<float>((size_t)slab);
-        void *geo = b.take<char>(nrf_lerf_geo_bytes(slab));
+        const QueryImage &qi = w.qi;
+        __half *x = w.x;
+        uint8_t *keep = w.keep;
+        float *sig_ws = w.sig;
+        void *geo = w.geo;
         NRF_TRY(build_image(c.m, qi, c.pos, c.neg, c.n_neg, st));
         for (int64_t first = 0; first < p; first += slab) {
             const int64_t cnt = p - first < slab ? p - first : slab;
@@ -337,8 +329,7 @@ int run_points(const PointsCall &c, int64_t p, int64_t slab, bool lattice, PtsOf
         return NRF_OK;
     }
     const int64_t cs = slab < F32_CHUNK ? slab : F32_CHUNK;
-    float *ptsb = lattice ? b.take<float>((size_t)cs * 3) : nullptr;
-    const F32Bufs f = take_f32(c.m, b, true);
+    const F32Bufs &f = w.f;
     for (int64_t first = 0; first < p; first += cs) {
         const int64_t cnt = p - first < cs ? p - first : cs;
         const float *pts = pts_of(first, cnt, ptsb);
@@ -366,21 +357,36 @@ using namespace nrf;
 
 extern "C" {
 
+namespace {
+// workspace of the head entry: slabs of up to HEAD_SLAB rows in the fused precisions
+struct HeadQueryWs {
+    QueryImage qi;
+    __half *xh, *xl;         // hi and lo feature planes
+    float *sig_split;        // split sigma (discarded)
+    void *geo;
+    F32Bufs f;               // the composed path; in the fused precisions: sigma_le in fp32 (when wanted)
+};
+HeadQueryWs head_query_layout(Bump &b, const nrf_mlp *m, int64_t p, int precision)
+{
+    HeadQueryWs w{};
+    if (fused_precision(precision)) {
+        const int64_t hs = p < HEAD_SLAB ? p : HEAD_SLAB;
+        w.qi = take_image(b);
+        w.xh = b.take<__half>((size_t)hs * IN);
+        w.xl = b.take<__half>((size_t)hs * IN);
+        w.sig_split = b.take<float>((size_t)hs);
+        w.geo = b.take<char>(nrf_lerf_geo_bytes(hs));
+    }
+    w.f = take_f32(m, b, false);
+    return w;
+}
+}  // namespace
+
 size_t nrf_lerf_head_relevancy_workspace_bytes(const nrf_mlp *m, int64_t p, int n_neg, int precision)
 {
     (void)n_neg;
     if (!m || m->family != MLP_LERF || p <= 0) return 0;
-    Size s;
-    if (fused_precision(precision)) {
-        const int64_t hs = p < HEAD_SLAB ? p : HEAD_SLAB;
-        size_image(s);
-        s.add((size_t)hs * IN * 2);                        // hi plane
-        s.add((size_t)hs * IN * 2);                        // lo plane
-        s.add((size_t)hs * 4);                             // split sigma (discarded)
-        s.add(nrf_lerf_geo_bytes(hs));
-        s.add(f32_bytes(m, false));                        // sigma_le in fp32 (when wanted)
-    } else s.add(f32_bytes(m, false));
-    return align_up(s.b, 256) + 256;
+    return measure([&](Bump &b) { head_query_layout(b, m, p, precision); });
 }
 
 int nrf_lerf_head_relevancy(const nrf_mlp *m, const float *d_x, int64_t p, const float *d_positives, int n_pos, const float *d_negatives, int n_neg, int positive_id,
@@ -396,14 +402,14 @@ int nrf_lerf_head_relevancy(const nrf_mlp *m, const float *d_x, int64_t p, const
     if (p == 0) return NRF_OK;
     NRF_CHECK_ARG(d_x && d_positives && (n_neg == 0 || d_negatives) && d_ws, "%s: null pointer", who);
     NRF_CHECK_ARG((reinterpret_cast<uintptr_t>(d_x) & 15) == 0, "%s: feature rows must be 16-byte aligned", who);
-    const size_t need = nrf_lerf_head_relevancy_workspace_bytes(m, p, n_neg, precision);
-    if (ws_bytes < need) { set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need); return NRF_ERR_WORKSPACE; }
+    Bump b(d_ws, ws_bytes);
+    const HeadQueryWs w = head_query_layout(b, m, p, precision);
+    NRF_TRY(ws_check(b, nrf_lerf_head_relevancy_workspace_bytes(m, p, n_neg, precision), who));
     hipStream_t st = as_stream(stream);
     const int E = m->out_dims - 1;
     const float *pos = d_positives + (size_t)positive_id * E;
-    Bump b(d_ws);
+    const F32Bufs &f = w.f;
     if (!fused_precision(precision)) {
-        const F32Bufs f = take_f32(m, b, false);
         for (int64_t first = 0; first < p; first += F32_CHUNK) {
             const int64_t cnt = p - first < F32_CHUNK ? p - first : F32_CHUNK;
             NRF_TRY(f32_chunk(m, d_x + first * m->in_dims, nullptr, cnt, pos, d_negatives, n_neg, d_sigma ? d_sigma + first : nullptr, d_relevancy + 2 * first, f, st));
@@ -411,12 +417,10 @@ int nrf_lerf_head_relevancy(const nrf_mlp *m, const float *d_x, int64_t p, const
         return NRF_OK;
     }
     const int64_t hs = p < HEAD_SLAB ? p : HEAD_SLAB;
-    const QueryImage qi = take_image(b);
-    __half *xh = b.take<__half>((size_t)hs * IN);
-    __half *xl = b.take<__half>((size_t)hs * IN);
-    float *sig_split = b.take<float>((size_t)hs);
-    void *geo = b.take<char>(nrf_lerf_geo_bytes(hs));
-    const F32Bufs f = take_f32(m, b, false);
+    const QueryImage &qi = w.qi;
+    __half *xh = w.xh, *xl = w.xl;
+    float *sig_split = w.sig_split;
+    void *geo = w.geo;
     NRF_TRY(build_image(m, qi, pos, d_negatives, n_neg, st));
     for (int64_t first = 0; first < p; first += hs) {
         const int64_t cnt = p - first < hs ? p - first : hs;
@@ -465,10 +469,8 @@ int nrf_lerf_point_relevancy(const nrf_lerf_renderer *r, const float *d_pts, int
     if (p == 0) return NRF_OK;
     NRF_CHECK_ARG(d_pts && d_ws, "%s: null pointer", who);
     const int64_t slab = slab_of(slab_points, p);
-    const size_t need = points_ws(c.m, precision, slab, false);
-    if (ws_bytes < need) { set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need); return NRF_ERR_WORKSPACE; }
     auto pts_of = [&](int64_t first, int64_t, float *) -> const float * { return d_pts + first * 3; };
-    return run_points(c, p, slab, false, pts_of, d_sigma, d_relevancy, d_ws, as_stream(stream));
+    return run_points(who, c, p, slab, false, pts_of, d_sigma, d_relevancy, d_ws, ws_bytes, as_stream(stream));
 }
 
 size_t nrf_lerf_relevancy_grid_workspace_bytes(const nrf_lerf_renderer *r, int nx, int ny, int nz, int precision, int64_t slab_points)
@@ -496,15 +498,13 @@ int nrf_lerf_relevancy_grid(const nrf_lerf_renderer *r, const float *bbox, int n
     if (fused_precision(precision)) NRF_TRY(fused_ok(who, c.m, c.n_neg, true));
     NRF_CHECK_ARG(d_ws, "%s: null workspace", who);
     const int64_t slab = slab_of(slab_points, g.n);
-    const size_t need = points_ws(c.m, precision, slab, true);
-    if (ws_bytes < need) { set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need); return NRF_ERR_WORKSPACE; }
     hipStream_t st = as_stream(stream);
     auto pts_of = [&](int64_t first, int64_t cnt, float *buf) -> const float * {
         hipLaunchKernelGGL(k_query_lattice_points, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, st, g, first, cnt, buf);
         if (hipGetLastError() != hipSuccess) { set_error("%s: k_query_lattice_points launch failed", who); return nullptr; }
         return buf;
     };
-    return run_points(c, g.n, slab, true, pts_of, d_sigma, d_relevancy, d_ws, st);
+    return run_points(who, c, g.n, slab, true, pts_of, d_sigma, d_relevancy, d_ws, ws_bytes, st);
 }
 
 }  // extern "C"

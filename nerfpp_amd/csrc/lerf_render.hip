@@ -178,29 +178,47 @@ static int lerf_plan(const nrf_lerf_renderer *r, const nrf_render_params *p, Ler
     return NRF_OK;
 }
 
+// One chunk's workspace.  Every piece is there whatever the caller supplies (a supplied output is written in place and its piece stays unused): one layout, one size.
+struct LerfWs {
+    float *z, *pts;                  // coarse depths and sample points
+    char *x;                         // [16][cols][8] halfs
+    uint8_t *keep;
+    float *sig;                      // sigma_le by column
+    char *geo;                       // (sigma, geo32) operand planes of the split mode, else null
+    float *w_c, *dda_c;              // coarse weights; coarse depth / disp / acc
+    float *zf;
+    int32_t *src;                    // merge map
+    float *z_new, *pts_new;          // the new samples
+    float *w_f, *dda_f;              // fine weights; fine depth / disp / acc
+    float *acc, *emb;                // un-normalised and normalised embedding
+    float *ones;
+};
+static LerfWs lerf_chunk_layout(Bump &b, const LerfPlan &pl, int64_t n)
+{
+    LerfWs w;
+    const size_t cols = (size_t)n * pl.sf, nc = (size_t)n * pl.s, nn = (size_t)n * pl.ni;
+    w.z = b.take<float>(nc);
+    w.pts = b.take<float>(nc * 3);
+    w.x = b.take<char>(cols * 256);
+    w.keep = b.take<uint8_t>(cols);
+    w.sig = b.take<float>(cols);
+    w.geo = pl.geo ? b.take<char>(nrf_lerf_geo_bytes((int64_t)cols)) : nullptr;
+    w.w_c = b.take<float>(nc);
+    w.dda_c = b.take<float>((size_t)n * 3);
+    w.zf = b.take<float>(cols);
+    w.src = b.take<int32_t>(cols);
+    w.z_new = b.take<float>(nn);
+    w.pts_new = b.take<float>(nn * 3);
+    w.w_f = b.take<float>(cols);
+    w.dda_f = b.take<float>((size_t)n * 3);
+    w.acc = b.take<float>((size_t)n * pl.E);
+    w.emb = b.take<float>((size_t)n * pl.E);
+    w.ones = b.take<float>((size_t)n);
+    return w;
+}
 static size_t lerf_chunk_ws(const LerfPlan &pl, int64_t n)
 {
-    const size_t cols = (size_t)n * pl.sf;
-    size_t b = 0;
-    auto add = [&](size_t bytes) { b = align_up(b, 256) + bytes; };
-    add((size_t)n * pl.s * 4);              // z
-    add((size_t)n * pl.s * 12);             // pts
-    add(cols * 256);                        // x: [16][cols][8] halfs
-    add(cols);                              // keep
-    add(cols * 4);                          // sigma_le by column
-    if (pl.geo) add(nrf_lerf_geo_bytes((int64_t)cols));
-    add((size_t)n * pl.s * 4);              // coarse weights
-    add((size_t)n * 4 * 3);                 // coarse depth / disp / acc
-    add((size_t)n * pl.sf * 4);             // z_fine
-    add((size_t)n * pl.sf * 4);             // merge map
-    add((size_t)n * pl.ni * 4);             // new depths
-    add((size_t)n * pl.ni * 12);            // new points
-    add((size_t)n * pl.sf * 4);             // fine weights (when the caller does not want them)
-    add((size_t)n * 4 * 3);                 // fine depth / disp / acc (likewise)
-    add((size_t)n * pl.E * 4);              // un-normalised embedding
-    add((size_t)n * pl.E * 4);              // normalised embedding (when the caller wants the relevancy only)
-    add((size_t)n * 4);                     // ones
-    return align_up(b, 256);
+    return measure([&](Bump &b) { lerf_chunk_layout(b, pl, n); });
 }
 
 static nrf_lerf_outputs slice(const nrf_lerf_outputs &o, int64_t i, int s, int sf, int E)
@@ -422,34 +440,21 @@ static int lerf_render_rays_impl(const nrf_lerf_renderer *r, const float *d_rays
     NRF_CHECK_ARG(d_rays && d_t && d_u && d_workspace, "nrf_lerf_render_rays: null pointer");
     NRF_CHECK_ARG(n * (int64_t)pl.sf < ((int64_t)1 << 31), "nrf_lerf_render_rays: %lld rays x %d samples exceed the 2^31 columns of one chunk; lower Chunk", (long long)n, pl.sf);
     NRF_CHECK_ARG(!out->d_relevancy || r->n_pos > 0, "nrf_lerf_render_rays: relevancy asked for, but no prompts are set (nrf_lerf_set_prompts)");
-    const size_t need = lerf_chunk_ws(pl, n);
-    if (workspace_bytes < need) { set_error("nrf_lerf_render_rays: workspace %zu < %zu bytes", workspace_bytes, need); return NRF_ERR_WORKSPACE; }
+    Bump b(d_workspace, workspace_bytes);
+    const LerfWs ws = lerf_chunk_layout(b, pl, n);
+    NRF_TRY(ws_check(b, lerf_chunk_ws(pl, n), "nrf_lerf_render_rays"));
     const nrf_hash *h = r->desc.lang_embed;
     const nrf_mlp *m = r->desc.lerf;
     const int s = pl.s, ni = pl.ni, sf = pl.sf, E = pl.E;
     const int64_t cols = n * (int64_t)sf, nc = n * (int64_t)s, nn = n * (int64_t)ni;
-    Bump b(d_workspace);
-    float *z = out->d_z_coarse ? out->d_z_coarse : b.take<float>((size_t)nc);
-    if (out->d_z_coarse) (void)b.take<float>((size_t)nc);
-    float *pts = b.take<float>((size_t)nc * 3);
-    char *x = b.take<char>((size_t)cols * 256);
-    uint8_t *keep = b.take<uint8_t>((size_t)cols);
-    float *sig = b.take<float>((size_t)cols);
-    char *geo = pl.geo ? b.take<char>(nrf_lerf_geo_bytes(cols)) : nullptr;
-    float *w_c_ws = b.take<float>((size_t)nc);
-    float *w_c = out->d_weights_coarse ? out->d_weights_coarse : w_c_ws;
-    float *dda_c = b.take<float>((size_t)n * 3);
-    float *zf_ws = b.take<float>((size_t)cols);
-    float *zf = out->d_z_fine ? out->d_z_fine : zf_ws;
-    int32_t *src = b.take<int32_t>((size_t)cols);
-    float *z_new = b.take<float>((size_t)nn);
-    float *pts_new = b.take<float>((size_t)nn * 3);
-    float *w_f_ws = b.take<float>((size_t)cols);
-    float *w_f = out->d_weights ? out->d_weights : w_f_ws;
-    float *dda_f = b.take<float>((size_t)n * 3);
-    float *acc = b.take<float>((size_t)n * E);
-    float *emb_ws = b.take<float>((size_t)n * E);
-    float *ones = b.take<float>((size_t)n);
+    float *z = out->d_z_coarse ? out->d_z_coarse : ws.z, *pts = ws.pts;
+    char *x = ws.x, *geo = ws.geo;
+    uint8_t *keep = ws.keep;
+    float *sig = ws.sig, *dda_c = ws.dda_c, *z_new = ws.z_new, *pts_new = ws.pts_new, *dda_f = ws.dda_f, *acc = ws.acc, *ones = ws.ones;
+    int32_t *src = ws.src;
+    float *w_c = out->d_weights_coarse ? out->d_weights_coarse : ws.w_c;
+    float *zf = out->d_z_fine ? out->d_z_fine : ws.zf;
+    float *w_f = out->d_weights ? out->d_weights : ws.w_f;
     const float *dirs = d_rays + 3;
 
     NRF_TRY(nrf_z_vals(d_rays, ray_stride, n, d_t, s, p->lindisp, z, stream));                                                 // :113-135
@@ -473,7 +478,7 @@ static int lerf_render_rays_impl(const nrf_lerf_renderer *r, const float *d_rays
         else NRF_TRY(nrf_lerf_render_embedding_lm_gather(m, x, cols, src, w_f, n, sf, acc, stream));
         // the final normalise of RenderCLIPEmbedding (LeRFRenderer.h:53): one "sample" of weight 1 per ray
         NRF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ones), 0x3f800000, (size_t)n, as_stream(stream)));
-        float *emb = out->d_embedding ? out->d_embedding : emb_ws;
+        float *emb = out->d_embedding ? out->d_embedding : ws.emb;
         NRF_TRY(nrf::launch_clip_embedding(acc, E, E, ones, n, 1, emb, as_stream(stream), d_flag));
         if (out->d_relevancy)
             NRF_TRY(nrf_lerf_relevancy(emb, n, E, r->d_pos, r->n_pos, r->d_neg, r->n_neg, 0, out->d_relevancy, stream));     // LeRFRenderer.cpp:79 (one positive phrase)
@@ -488,14 +493,33 @@ static int64_t lerf_lane_chunk(int64_t n, int chunk, int lanes)
     return chunk;
 }
 
+// The workspace of the Chunk loop: one slice of a whole chunk per lane, or the single-stream loop's one chunk (L = 0, lane[0])
+struct LerfBatchWs {
+    int L;
+    int64_t lc;
+    size_t part;
+    char *lane[Lanes::MAX];
+};
+static LerfBatchWs lerf_batchify_layout(Bump &b, const nrf_lerf_renderer *r, const LerfPlan &pl, int64_t n, int chunk)
+{
+    LerfBatchWs w{};
+    const int lanes = lerf_lanes(r);
+    w.lc = lerf_lane_chunk(n, chunk, lanes);
+    w.L = w.lc > 0 ? lanes : 0;
+    w.part = lerf_chunk_ws(pl, n < chunk ? n : (int64_t)chunk);
+    for (int k = 0; k < (w.L ? w.L : 1); k++) w.lane[k] = b.take<char>(w.part);
+    return w;
+}
+
 size_t nrf_lerf_batchify_rays_workspace_bytes(const nrf_lerf_renderer *r, int64_t n, int chunk, const nrf_render_params *p)
 {
-    if (!r || !p || chunk <= 0 || n <= 0) return 0;
-    const int lanes = lerf_lanes(r);
-    const int64_t lc = lerf_lane_chunk(n, chunk, lanes);
-    const size_t one = nrf_lerf_render_rays_workspace_bytes(r, n < chunk ? n : (int64_t)chunk, p);
-    return lc > 0 ? (size_t)lanes * one : one;
+    LerfPlan pl;
+    if (!r || !p || chunk <= 0 || n <= 0 || lerf_plan(r, p, &pl, "nrf_lerf_batchify_rays_workspace_bytes") != NRF_OK) return 0;
+    return measure([&](Bump &b) { lerf_batchify_layout(b, r, pl, n, chunk); });
 }
+
+static int lerf_batchify_run(const nrf_lerf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const LerfPlan &pl, const float *d_t,
+                             const float *d_u, const nrf_lerf_outputs *out, const LerfBatchWs &bw, void *stream);
 
 int nrf_lerf_batchify_rays(const nrf_lerf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const float *d_t,
                            const float *d_u, const nrf_lerf_outputs *out, void *d_workspace, size_t workspace_bytes, void *stream)
@@ -504,12 +528,21 @@ int nrf_lerf_batchify_rays(const nrf_lerf_renderer *r, const float *d_rays, int 
     NRF_CHECK_ARG(chunk > 0 && n >= 0, "nrf_lerf_batchify_rays: Chunk must be positive");
     LerfPlan pl;
     NRF_TRY(lerf_plan(r, p, &pl, "nrf_lerf_batchify_rays"));
+    Bump b(d_workspace, workspace_bytes);
+    const LerfBatchWs bw = lerf_batchify_layout(b, r, pl, n, chunk);
+    NRF_TRY(ws_check(b, nrf_lerf_batchify_rays_workspace_bytes(r, n, chunk, p), "nrf_lerf_batchify_rays"));
+    return lerf_batchify_run(r, d_rays, ray_stride, n, chunk, p, pl, d_t, d_u, out, bw, stream);
+}
+
+// bw: lerf_batchify_layout carved from the caller's workspace and checked by the entry
+static int lerf_batchify_run(const nrf_lerf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const LerfPlan &pl, const float *d_t,
+                             const float *d_u, const nrf_lerf_outputs *out, const LerfBatchWs &bw, void *stream)
+{
     if (n > 0) NRF_TRY(lerf_flag_begin(r, p, as_stream(stream), "nrf_lerf_batchify_rays"));
     uint32_t *const d_flag = (n > 0 && lerf_detects(p)) ? r->d_flag : nullptr;
-    const int L = lerf_lanes(r);
-    const int64_t lc = lerf_lane_chunk(n, chunk, L);
-    const size_t part = lc > 0 ? nrf_lerf_render_rays_workspace_bytes(r, lc, p) : 0;
-    if (part > 0 && (size_t)L * part <= workspace_bytes && d_workspace) {
+    const int L = bw.L;
+    const int64_t lc = bw.lc;
+    if (L > 0) {
         // the Chunk loop on lanes (as nrf_batchify_rays): consecutive chunks on L streams forked from and joined to the caller's, so that one chunk's gather-bound
         // F = 8 hash encode shares the CUs with another's matrix-bound passes.  Same kernels on the same slices: same results.
         hipStream_t st = as_stream(stream), lane[Lanes::MAX];
@@ -520,7 +553,7 @@ int nrf_lerf_batchify_rays(const nrf_lerf_renderer *r, const float *d_rays, int 
         for (int64_t i = 0; i < n && rc == NRF_OK; i += lc, k = (k + 1) % L) {                                                // :206
             const int64_t mm = n - i < lc ? n - i : lc;
             const nrf_lerf_outputs o = slice(*out, i, pl.s, pl.sf, pl.E);
-            rc = lerf_render_rays_impl(r, d_rays + i * ray_stride, ray_stride, mm, p, d_t, d_u, &o, static_cast<char *>(d_workspace) + (size_t)k * part, part, lane[k], d_flag);
+            rc = lerf_render_rays_impl(r, d_rays + i * ray_stride, ray_stride, mm, p, d_t, d_u, &o, bw.lane[k], bw.part, lane[k], d_flag);
         }
         join_lanes(st, lane, done, L, "nrf_lerf_batchify_rays", rc);
         if (n > lc) r->view.drop();          // the view describes ONE chunk's workspace
@@ -529,17 +562,31 @@ int nrf_lerf_batchify_rays(const nrf_lerf_renderer *r, const float *d_rays, int 
     for (int64_t i = 0; i < n; i += chunk) {                                                                                  // :206
         const int64_t mm = n - i < chunk ? n - i : (int64_t)chunk;
         const nrf_lerf_outputs o = slice(*out, i, pl.s, pl.sf, pl.E);
-        NRF_TRY(lerf_render_rays_impl(r, d_rays + i * ray_stride, ray_stride, mm, p, d_t, d_u, &o, d_workspace, workspace_bytes, stream, d_flag));
+        NRF_TRY(lerf_render_rays_impl(r, d_rays + i * ray_stride, ray_stride, mm, p, d_t, d_u, &o, bw.lane[0], bw.part, stream, d_flag));
     }
     if (n > chunk) r->view.drop();          // the view describes ONE chunk's workspace
     return n > 0 ? lerf_flag_end(r, p, as_stream(stream), "nrf_lerf_batchify_rays") : NRF_OK;
 }
 
+// a view's workspace: its rays (unless the caller keeps them: d_rays_out) and the Chunk loop's
+struct LerfRowsWs {
+    float *rays;
+    LerfBatchWs batch;
+};
+static LerfRowsWs lerf_rows_layout(Bump &b, const nrf_lerf_renderer *r, const LerfPlan &pl, const nrf_view *v, float *d_rays_out)
+{
+    LerfRowsWs w;
+    const int64_t n = (int64_t)v->rows * v->w;
+    w.rays = d_rays_out ? d_rays_out : b.take<float>((size_t)n * (v->use_viewdirs ? 11 : 8));
+    w.batch = lerf_batchify_layout(b, r, pl, n, v->chunk);
+    return w;
+}
+
 size_t nrf_lerf_render_rows_workspace_bytes(const nrf_lerf_renderer *r, const nrf_view *v, const nrf_render_params *p)
 {
-    if (!r || !v || !p || v->chunk <= 0 || v->rows < 0 || v->w <= 0) return 0;
-    const int64_t n = (int64_t)v->rows * v->w;
-    return align_up((size_t)n * (v->use_viewdirs ? 11 : 8) * sizeof(float), 256) + 256 + nrf_lerf_batchify_rays_workspace_bytes(r, n, v->chunk, p);
+    LerfPlan pl;
+    if (!r || !v || !p || v->chunk <= 0 || v->rows < 0 || v->w <= 0 || lerf_plan(r, p, &pl, "nrf_lerf_render_rows_workspace_bytes") != NRF_OK) return 0;
+    return measure([&](Bump &b) { lerf_rows_layout(b, r, pl, v, nullptr); });
 }
 
 int nrf_lerf_render_rows(const nrf_lerf_renderer *r, const nrf_view *v, const nrf_render_params *p, const float *d_t, const float *d_u, const nrf_lerf_outputs *out,
@@ -550,13 +597,13 @@ int nrf_lerf_render_rows(const nrf_lerf_renderer *r, const nrf_view *v, const nr
     const int64_t n = (int64_t)v->rows * v->w;
     if (n == 0) return nrf_view_rays(v, nullptr, d_near_far, stream);
     const int stride = v->use_viewdirs ? 11 : 8;
-    const size_t need = nrf_lerf_render_rows_workspace_bytes(r, v, p);
-    if (workspace_bytes < need) { set_error("nrf_lerf_render_rows: workspace %zu < %zu bytes", workspace_bytes, need); return NRF_ERR_WORKSPACE; }
-    Bump b(d_workspace);
-    float *rays = d_rays_out ? d_rays_out : b.take<float>((size_t)n * stride);
-    void *ws = b.take<char>(0);
-    NRF_TRY(nrf_view_rays(v, rays, d_near_far, stream));                                                                     // LeRFRenderer.cpp:275-305
-    return nrf_lerf_batchify_rays(r, rays, stride, n, v->chunk, p, d_t, d_u, out, ws, workspace_bytes - b.off, stream);      // :308
+    LerfPlan pl;
+    NRF_TRY(lerf_plan(r, p, &pl, "nrf_lerf_render_rows"));
+    Bump b(d_workspace, workspace_bytes);
+    const LerfRowsWs w = lerf_rows_layout(b, r, pl, v, d_rays_out);
+    NRF_TRY(ws_check(b, nrf_lerf_render_rows_workspace_bytes(r, v, p), "nrf_lerf_render_rows"));
+    NRF_TRY(nrf_view_rays(v, w.rays, d_near_far, stream));                                                                   // LeRFRenderer.cpp:275-305
+    return lerf_batchify_run(r, w.rays, stride, n, v->chunk, p, pl, d_t, d_u, out, w.batch, stream);                          // :308
 }
 
 }  // extern "C"

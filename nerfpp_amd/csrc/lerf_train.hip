@@ -12,6 +12,7 @@
 // Pinned by LibTorch autograd over the compiled LeRF.cpp / RawToOutputs weights / the reference's inline RenderCLIPEmbedding: goldens train_lerf*.
 #include "encode.h"
 #include "mlp.h"
+#include "workspace.h"
 #include "nrf_math.h"
 
 #include <atomic>
@@ -43,11 +44,12 @@ static int lt_width(const nrf_mlp *m, int s)
     return w;
 }
 static int64_t lt_chunk_pts(const nrf_mlp *m, int s) { return lerf_train_gram(m, s) ? ((int64_t)1 << NRF_LT_GRAM_CHUNK_LOG2) : LT_CHUNK_PTS; }
-// rays per backward pass: n rays in passes of at most cpts / s rays, cut EVENLY (16 384 rays at 5 461 per pass are four passes of 4 096, not three full ones and a
+// rays per backward pass: n rays in passes of at most lt_pass_cap rays, cut EVENLY (16 384 rays at 5 461 per pass are four passes of 4 096, not three full ones and a
 // one-ray tail whose products fall back to the small-shape paths)
-static int64_t lt_rays_per_pass(int64_t n, int64_t cpts, int s)
+static int64_t lt_pass_cap(const nrf_mlp *m, int s) { const int64_t cap = lt_chunk_pts(m, s) / s; return cap > 0 ? cap : 1; }
+static int64_t lt_rays_per_pass(const nrf_mlp *m, int64_t n, int s)
 {
-    const int64_t cap = cpts / s > 0 ? cpts / s : 1;
+    const int64_t cap = lt_pass_cap(m, s);
     if (n <= cap) return n < 1 ? 1 : n;
     const int64_t passes = (n + cap - 1) / cap;
     return (n + passes - 1) / passes;
@@ -458,13 +460,26 @@ __global__ void k_lt_gather_feats(int64_t c, const uint4 *__restrict__ feats, in
     if (l == 0) keep[q] = keep_cols[col];
 }
 
+// The head's workspace for n rays: row buffers of a pass's points (one per layer output + 4 gradient buffers) and the per-point norms.  Sized for the longest pass any
+// batch of up to n rays is cut into (lt_pass_cap; the even cut of lt_rays_per_pass never exceeds it), so the size does not shrink when n grows.
+struct HeadWs {
+    float *base;
+    size_t buf;          // floats per row buffer
+    float *nrm;
+};
+static HeadWs head_layout(Bump &b, const nrf_mlp *m, int64_t n, int s)
+{
+    HeadWs w;
+    const int64_t cap = lt_pass_cap(m, s);
+    const int64_t c = (n < 1 ? 1 : (n < cap ? n : cap)) * s;
+    w.buf = align_up((size_t)c * lt_width(m, s) * sizeof(float), 256) / sizeof(float);
+    w.base = b.take<float>(w.buf * (m->layers.size() + 4));
+    w.nrm = b.take<float>((size_t)c);
+    return w;
+}
 static size_t head_ws_bytes(const nrf_mlp *m, int64_t n, int s)
 {
-    const int64_t cp = lt_chunk_pts(m, s);
-    const int64_t rays = n < 1 ? 1 : (cp / s > 0 ? cp / s : 1);
-    const int64_t c = (n < rays ? (n < 1 ? 1 : n) : rays) * s;
-    const size_t buf = align_up((size_t)c * lt_width(m, s) * sizeof(float), 256);
-    return buf * (m->layers.size() + 4) + align_up((size_t)c * sizeof(float), 256) + 1024;
+    return measure([&](Bump &b) { head_layout(b, m, n, s); });
 }
 
 // one chunk of whole rays: c = rays * s points
@@ -640,15 +655,12 @@ int nrf_lerf_head_backward(const nrf_mlp *lerf, const float *d_emb, const uint8_
     if (lerf->family != MLP_LERF) { set_error("nrf_lerf_head_backward: the handle is not a LeRF head (nrf_mlp_lerf_create)"); return NRF_ERR_INVALID_ARG; }
     const int E = lerf->small.hidden_dim_color;
     if (((size_t)7 * s + (size_t)2 * E) * sizeof(float) > 60 * 1024) { set_error("nrf_lerf_head_backward: %d samples x %d embedding dims exceed the per-ray LDS image", s, E); return NRF_ERR_UNSUPPORTED; }
-    if (workspace_bytes < head_ws_bytes(lerf, n, s)) { set_error("nrf_lerf_head_backward: workspace %zu < %zu bytes", workspace_bytes, head_ws_bytes(lerf, n, s)); return NRF_ERR_WORKSPACE; }
+    Bump bump(d_workspace, workspace_bytes);
+    const HeadWs w = head_layout(bump, lerf, n, s);
+    NRF_TRY(ws_check(bump, head_ws_bytes(lerf, n, s), "nrf_lerf_head_backward"));
     if (n == 0) return NRF_OK;
     hipStream_t st = as_stream(stream);
-    const int64_t cpts = lt_chunk_pts(lerf, s);
-    const int64_t rays_per = lt_rays_per_pass(n, cpts, s);
-    const int64_t cmax = (n < rays_per ? n : rays_per) * s;
-    const size_t buf = align_up((size_t)cmax * lt_width(lerf, s) * sizeof(float), 256) / sizeof(float);
-    float *base = reinterpret_cast<float *>(d_workspace);
-    float *nrm = base + buf * (lerf->layers.size() + 4);
+    const int64_t rays_per = lt_rays_per_pass(lerf, n, s);
     const int in = lerf->small.input_ch;
     // Gram form of the last layer: G = W^T W once per call (the weights change every step), stream-ordered scratch
     float *gram = nullptr;
@@ -670,23 +682,37 @@ int nrf_lerf_head_backward(const nrf_mlp *lerf, const float *d_emb, const uint8_
         const int64_t p0 = r0 * s;
         rc = head_backward_chunk(lerf, d_emb + p0 * in, d_keep ? d_keep + p0 : nullptr, d_z + p0, d_dirs + r0 * d_stride, d_stride, d_noise ? d_noise + p0 : nullptr, noise_std,
                                  rays, s, d_g_rendered + r0 * E, d_g_params, d_g_emb ? d_g_emb + p0 * in : nullptr, d_rendered ? d_rendered + r0 * E : nullptr,
-                                 d_weights ? d_weights + p0 : nullptr, base, buf, nrm, gram, st);
+                                 d_weights ? d_weights + p0 : nullptr, w.base, w.buf, w.nrm, gram, st);
     }
     if (gram) (void)scratch_give(gram, st);
     return rc;
 }
 
 // ... with the language grid in front: pts [n, s, 3] -> nrf_hash_encode (fp32 rows) -> the head's backward -> nrf_hash_backward_rays, chunk by chunk of whole rays
+// its workspace: the head's, then one pass's feature rows, their gradient and their keep mask.  These three hold the EVEN cut's pass (lt_rays_per_pass), as they always
+// have: their size steps down where n crosses a multiple of lt_pass_cap (nothing slices this workspace; the head's share does not shrink)
+struct PointsWs {
+    void *head;
+    size_t head_bytes;
+    float *emb, *g_emb;
+    uint8_t *keep;
+};
+static PointsWs points_layout(Bump &b, const nrf_mlp *m, int in, int64_t n, int s)
+{
+    PointsWs w;
+    const size_t c = (size_t)(lt_rays_per_pass(m, n, s) * s);
+    w.head_bytes = head_ws_bytes(m, n, s);
+    w.head = b.take<char>(w.head_bytes);
+    w.emb = b.take<float>(c * in);
+    w.g_emb = b.take<float>(c * in);
+    w.keep = b.take<uint8_t>(c);
+    return w;
+}
 size_t nrf_lerf_backward_points_workspace_bytes(const nrf_lerf_renderer *r, int64_t n, int s)
 {
     if (!r || s < 1) return 0;
     const nrf_mlp *m = nrf_lerf_renderer_head(r);
-    const nrf_hash *h = nrf_lerf_renderer_lang_embed(r);
-    const int64_t cpts = lt_chunk_pts(m, s);
-    const int64_t rays_per = lt_rays_per_pass(n, cpts, s);
-    const int64_t c = (n < rays_per ? (n < 1 ? 1 : n) : rays_per) * s;
-    const int in = nrf_hash_output_dims(h);
-    return head_ws_bytes(m, n, s) + 2 * align_up((size_t)c * in * sizeof(float), 256) + align_up((size_t)c, 256) + 1024;
+    return measure([&](Bump &b) { points_layout(b, m, nrf_hash_output_dims(nrf_lerf_renderer_lang_embed(r)), n, s); });
 }
 
 static int lerf_backward_points_impl(const nrf_lerf_renderer *r, const void *d_feats_lm, int64_t cols, const uint8_t *d_keep_cols, const int32_t *d_src, const float *d_pts, const float *d_z,
@@ -718,15 +744,13 @@ static int lerf_backward_points_impl(const nrf_lerf_renderer *r, const void *d_f
     const nrf_hash *h = nrf_lerf_renderer_lang_embed(r);
     const int in = nrf_hash_output_dims(h), E = m->small.hidden_dim_color;
     if (in != m->small.input_ch) { set_error("nrf_lerf_backward_points: the grid yields %d features, the head expects %d", in, m->small.input_ch); return NRF_ERR_INVALID_ARG; }
-    if (workspace_bytes < nrf_lerf_backward_points_workspace_bytes(r, n, s)) { set_error("nrf_lerf_backward_points: workspace %zu < %zu bytes", workspace_bytes, nrf_lerf_backward_points_workspace_bytes(r, n, s)); return NRF_ERR_WORKSPACE; }
+    Bump bump(d_workspace, workspace_bytes);
+    const PointsWs w = points_layout(bump, m, in, n, s);
+    NRF_TRY(ws_check(bump, nrf_lerf_backward_points_workspace_bytes(r, n, s), "nrf_lerf_backward_points"));
     if (n == 0) return NRF_OK;
-    const int64_t cpts = lt_chunk_pts(m, s);
-    const int64_t rays_per = lt_rays_per_pass(n, cpts, s);
-    const int64_t cmax = (n < rays_per ? n : rays_per) * s;
-    char *ws = static_cast<char *>(d_workspace);
-    const size_t hb = head_ws_bytes(m, n, s), eb = align_up((size_t)cmax * in * sizeof(float), 256);
-    float *emb = reinterpret_cast<float *>(ws + align_up(hb, 256)), *g_emb = reinterpret_cast<float *>(ws + align_up(hb, 256) + eb);
-    uint8_t *keep = reinterpret_cast<uint8_t *>(ws + align_up(hb, 256) + 2 * eb);
+    const int64_t rays_per = lt_rays_per_pass(m, n, s);
+    float *emb = w.emb, *g_emb = w.g_emb;
+    uint8_t *keep = w.keep;
     for (int64_t r0 = 0; r0 < n; r0 += rays_per) {
         const int64_t rays = (n - r0) < rays_per ? (n - r0) : rays_per;
         const int64_t p0 = r0 * s, c = rays * s;
@@ -738,7 +762,7 @@ static int lerf_backward_points_impl(const nrf_lerf_renderer *r, const void *d_f
         } else
         NRF_TRY(nrf_hash_encode(h, d_pts + p0 * 3, c, emb, keep, stream));                                         // lang_embed_fn->forward (LeRFRenderer.cpp:34)
         NRF_TRY(nrf_lerf_head_backward(m, emb, keep, d_z + p0, d_dirs + r0 * d_stride, d_stride, rays, s, d_noise ? d_noise + p0 : nullptr, noise_std, d_g_rendered + r0 * E,
-                                       d_g_lerf_params, g_emb, nullptr, nullptr, d_workspace, hb, stream));
+                                       d_g_lerf_params, g_emb, nullptr, nullptr, w.head, w.head_bytes, stream));
         NRF_TRY(nrf_hash_backward_rays(h, d_pts + p0 * 3, rays, s, g_emb, d_g_table, stream));                        // CuHashEmbedderBackwardKernel's gradient (CuHashEmbedder.cu:105-216)
     }
     return NRF_OK;

@@ -14,6 +14,7 @@
 //                    id + popcount of the origin's lower mask bits
 // Every output position comes from an integer prefix sum: no atomics decide an order, so two runs give the same arrays.
 #include "common.h"
+#include "workspace.h"
 
 #include <climits>
 #include <cmath>
@@ -315,6 +316,25 @@ IsoWs iso_layout(void *ws, int64_t n)
     return w;
 }
 
+// nrf_density_grid's workspace: one slab of lattice points and renderer_density's own workspace for them
+struct GridWs {
+    int64_t slab;
+    float *pts;
+    void *density;
+    size_t density_bytes;
+};
+GridWs grid_layout(Bump &b, const nrf_renderer *r, int64_t n, int64_t slab_points)
+{
+    GridWs w;
+    w.slab = slab_points > 0 ? slab_points : DEFAULT_SLAB;
+    if (w.slab > MAX_SLAB) w.slab = MAX_SLAB;
+    if (w.slab > n) w.slab = n;
+    w.pts = b.take<float>((size_t)w.slab * 3);
+    w.density_bytes = renderer_density_ws_bytes(r, w.slab);
+    w.density = b.take<char>(w.density_bytes);
+    return w;
+}
+
 }  // namespace
 
 }  // namespace nrf
@@ -326,11 +346,7 @@ extern "C" {
 size_t nrf_density_grid_workspace_bytes(const nrf_renderer *r, int nx, int ny, int nz, int64_t slab_points)
 {
     if (!r || nx < 2 || ny < 2 || nz < 2) return 0;
-    const int64_t n = (int64_t)nx * ny * nz;
-    int64_t slab = slab_points > 0 ? slab_points : DEFAULT_SLAB;
-    if (slab > MAX_SLAB) slab = MAX_SLAB;
-    if (slab > n) slab = n;
-    return align_up((size_t)slab * 3 * sizeof(float), 256) + renderer_density_ws_bytes(r, slab) + 256;
+    return measure([&](Bump &b) { grid_layout(b, r, (int64_t)nx * ny * nz, slab_points); });
 }
 
 int nrf_density_grid(const nrf_renderer *r, const float *bbox, int nx, int ny, int nz, float *d_sigma, int64_t slab_points, void *d_workspace, size_t workspace_bytes,
@@ -341,19 +357,17 @@ int nrf_density_grid(const nrf_renderer *r, const float *bbox, int nx, int ny, i
     NRF_CHECK_ARG(slab_points <= MAX_SLAB, "nrf_density_grid: slab_points %lld above 2^30", (long long)slab_points);
     Grid g;
     NRF_TRY(make_grid("nrf_density_grid", bbox, nx, ny, nz, g));
-    const size_t need = nrf_density_grid_workspace_bytes(r, nx, ny, nz, slab_points);
-    if (workspace_bytes < need) { set_error("nrf_density_grid: workspace %zu < %zu bytes", workspace_bytes, need); return NRF_ERR_WORKSPACE; }
-    int64_t slab = slab_points > 0 ? slab_points : DEFAULT_SLAB;
-    if (slab > g.n) slab = g.n;
+    Bump bump(d_workspace, workspace_bytes);
+    const GridWs w = grid_layout(bump, r, g.n, slab_points);
+    NRF_TRY(ws_check(bump, nrf_density_grid_workspace_bytes(r, nx, ny, nz, slab_points), "nrf_density_grid"));
+    const int64_t slab = w.slab;
     hipStream_t st = as_stream(stream);
-    float *pts = static_cast<float *>(d_workspace);
-    const size_t pts_bytes = align_up((size_t)slab * 3 * sizeof(float), 256);
-    void *ws = static_cast<char *>(d_workspace) + pts_bytes;
+    float *pts = w.pts;
     for (int64_t first = 0; first < g.n; first += slab) {
         const int64_t cnt = g.n - first < slab ? g.n - first : slab;
         hipLaunchKernelGGL(k_lattice_points, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, st, g, first, cnt, pts);
         NRF_LAUNCH_CHECK();
-        NRF_TRY(renderer_density(r, pts, cnt, d_sigma + first, ws, workspace_bytes - pts_bytes, st));
+        NRF_TRY(renderer_density(r, pts, cnt, d_sigma + first, w.density, w.density_bytes, st));
     }
     return NRF_OK;
 }

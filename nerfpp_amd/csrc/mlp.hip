@@ -6,6 +6,7 @@
 // from 0 -- the exact order the oracle restates, so NRF_PREC_F32 output equals the oracle bit for bit.
 // The matrix-core paths (NRF_PREC_F16_MFMA) are in mlp_small_mfma.hip / mlp_nerf_mfma.hip.
 #include "mlp.h"
+#include "workspace.h"
 
 #include <thread>
 
@@ -101,19 +102,24 @@ int run_linear(int64_t npts, Seg a, Seg b, const LinearLayer &L, int relu, float
 
 static const int64_t F32_CHUNK = 1 << 18;   // points per pass of the generic path (bounds the scratch)
 
+// scratch of the generic fp32 forward: three row buffers of one pass's points (the matrix-core precisions need none)
+struct ForwardWs { float *A, *B, *C; };
+static ForwardWs forward_layout(Bump &b, const nrf_mlp *m, int64_t p, int prec)
+{
+    ForwardWs w{};
+    if (prec != NRF_PREC_F32) return w;
+    const size_t rows = (size_t)(p < F32_CHUNK ? p : F32_CHUNK) * m->max_width;
+    w.A = b.take<float>(rows); w.B = b.take<float>(rows); w.C = b.take<float>(rows);
+    return w;
+}
 size_t mlp_workspace_bytes(const nrf_mlp *m, int64_t p, int prec)
 {
-    if (prec == NRF_PREC_F32) {
-        const int64_t c = p < F32_CHUNK ? p : F32_CHUNK;
-        return align_up((size_t)c * m->max_width * sizeof(float), 256) * 3;
-    }
-    return 256;
+    return measure([&](Bump &b) { forward_layout(b, m, p, prec); });
 }
 
-static int forward_f32(const nrf_mlp *m, const float *x, int xs, int64_t p, float *out, int os, float *ws, hipStream_t st)
+static int forward_f32(const nrf_mlp *m, const float *x, int xs, int64_t p, float *out, int os, const ForwardWs &ws, hipStream_t st)
 {
-    const size_t buf_elems = align_up((size_t)(p < F32_CHUNK ? p : F32_CHUNK) * m->max_width * sizeof(float), 256) / sizeof(float);
-    float *A = ws, *B = ws + buf_elems, *C = ws + 2 * buf_elems;
+    float *A = ws.A, *B = ws.B, *C = ws.C;
     const int W = m->max_width;
     const Seg none{nullptr, 0, 0, 0};
     if (m->family == MLP_SMALL) {
@@ -218,10 +224,12 @@ int mlp_forward(const nrf_mlp *m, const float *d_x, int x_stride, int64_t p, int
     if (p == 0) return NRF_OK;
     ProfScope prof(NRF_PROF_MLP, st);
     if (prec == NRF_PREC_F32) {
-        if (ws_bytes < mlp_workspace_bytes(m, p, prec)) { set_error("mlp_forward: workspace %zu < %zu bytes", ws_bytes, mlp_workspace_bytes(m, p, prec)); return NRF_ERR_WORKSPACE; }
+        Bump bump(d_ws, ws_bytes);
+        const ForwardWs w = forward_layout(bump, m, p, prec);
+        NRF_TRY(ws_check(bump, mlp_workspace_bytes(m, p, prec), "mlp_forward"));
         for (int64_t p0 = 0; p0 < p; p0 += F32_CHUNK) {
             const int64_t c = (p - p0) < F32_CHUNK ? (p - p0) : F32_CHUNK;
-            NRF_TRY(forward_f32(m, d_x + p0 * x_stride, x_stride, c, d_out + p0 * out_stride, out_stride, reinterpret_cast<float *>(d_ws), st));
+            NRF_TRY(forward_f32(m, d_x + p0 * x_stride, x_stride, c, d_out + p0 * out_stride, out_stride, w, st));
         }
         return NRF_OK;
     }
@@ -329,10 +337,25 @@ int run_backprop(int64_t npts, Seg g, const nrf_mlp *m, const LinearLayer &L, fl
 #endif
 static const int64_t BWD_CHUNK = (int64_t)1 << NRF_BWD_CHUNK_LOG2;          // points per pass of the fp32 backward (bounds the scratch; docs/history/profiles/round5/r5X_*)
 
+// Scratch of the fp32 backwards: `count` row buffers of one pass's points, W floats per row.  buf[i] is the i-th; the families say what each holds.
+struct RowBufs {
+    float *base;
+    size_t stride;          // floats from one buffer to the next
+    float *operator[](size_t i) const { return base + i * stride; }
+};
+static RowBufs row_bufs_layout(Bump &b, int64_t p, int W, size_t count)
+{
+    RowBufs w;
+    w.stride = align_up((size_t)(p < BWD_CHUNK ? p : BWD_CHUNK) * W * sizeof(float), 256) / sizeof(float);
+    w.base = b.take<float>(w.stride * count);
+    return w;
+}
+
+// NeRFSmall: one buffer per layer (the predicted-normals head's included: with_head recomputes its hidden outputs there and keeps its input gradient) + 3 gradient buffers
+static RowBufs small_backward_layout(Bump &b, const nrf_mlp *m, int64_t p) { return row_bufs_layout(b, p, m->max_width, m->layers.size() + 3); }
 size_t mlp_backward_workspace_bytes(const nrf_mlp *m, int64_t p)
 {
-    const int64_t c = p < BWD_CHUNK ? p : BWD_CHUNK;
-    return align_up((size_t)c * m->max_width * sizeof(float), 256) * (m->layers.size() + 3);
+    return measure([&](Bump &b) { small_backward_layout(b, m, p); });
 }
 
 static int run_sum_cols(int64_t npts, int n, const float *a, int a_stride, int a_off, const float *b, int b_stride, int b_off, float *y, int y_stride, hipStream_t st,
@@ -342,7 +365,9 @@ int mlp_small_backward(const nrf_mlp *m, const float *x, int xs, const float *g_
                        void *ws, size_t ws_bytes, hipStream_t st, bool with_head)
 {
     if (m->family != MLP_SMALL) { set_error("nrf_mlp_backward: built for the NeRFSmall family"); return NRF_ERR_UNSUPPORTED; }
-    if (ws_bytes < mlp_backward_workspace_bytes(m, p)) { set_error("nrf_mlp_backward: workspace %zu < %zu bytes", ws_bytes, mlp_backward_workspace_bytes(m, p)); return NRF_ERR_WORKSPACE; }
+    Bump bump(ws, ws_bytes);
+    const RowBufs bufs = small_backward_layout(bump, m, p);
+    NRF_TRY(ws_check(bump, mlp_backward_workspace_bytes(m, p), "nrf_mlp_backward"));
     const auto &d = m->small;
     // (a predicted-normals head, if the handle has one, sits behind these layers.  Without with_head it receives no gradient: the training loss reads RGBMap only,
     // NeRFExecutor.h:882-887, and nothing else reads the normals -- its parameters' gradient stays zero, as in the reference's autograd.  with_head: g_out[:, 4:7] is
@@ -350,15 +375,13 @@ int mlp_small_backward(const nrf_mlp *m, const float *x, int xs, const float *g_
     const int W = m->max_width, nl = d.num_layers + d.num_layers_color;
     const int nn = with_head ? d.num_layers_normals : 0;
     if (with_head && (!d.use_pred_normal || gos < 7)) { set_error("internal: mlp_small_backward: with_head needs the predicted-normals head and 7 gradient columns"); return NRF_ERR_INVALID_ARG; }
-    const size_t buf = align_up((size_t)(p < BWD_CHUNK ? p : BWD_CHUNK) * W * sizeof(float), 256) / sizeof(float);
-    float *base = reinterpret_cast<float *>(ws);
     std::vector<float *> H(nl);
-    for (int l = 0; l < nl; l++) H[l] = base + (size_t)l * buf;
-    float *G[3] = {base + (size_t)nl * buf, base + (size_t)(nl + 1) * buf, base + (size_t)(nl + 2) * buf};
-    // the head's share of the workspace (one buffer per head layer, mlp_backward_workspace_bytes): its nn - 1 hidden outputs and its input gradient
+    for (int l = 0; l < nl; l++) H[l] = bufs[l];
+    float *G[3] = {bufs[nl], bufs[nl + 1], bufs[nl + 2]};
+    // the head's share of the workspace (one buffer per head layer): its nn - 1 hidden outputs and its input gradient
     std::vector<float *> HN(nn > 0 ? nn - 1 : 0);
-    for (int l = 0; l + 1 < nn; l++) HN[l] = base + (size_t)(nl + 3 + l) * buf;
-    float *GNIN = nn > 0 ? base + (size_t)(nl + 3 + nn - 1) * buf : nullptr;          // d loss / d cat[sigma, geo_feat, input_pts] through the head
+    for (int l = 0; l + 1 < nn; l++) HN[l] = bufs[nl + 3 + l];
+    float *GNIN = nn > 0 ? bufs[nl + 3 + nn - 1] : nullptr;          // d loss / d cat[sigma, geo_feat, input_pts] through the head
     const Seg none{nullptr, 0, 0, 0};
     for (int64_t p0 = 0; p0 < p; p0 += BWD_CHUNK) {
         const int64_t c = (p - p0) < BWD_CHUNK ? (p - p0) : BWD_CHUNK;
@@ -521,28 +544,33 @@ static int run_grad_wb_fast(int64_t npts, Seg g, Seg a, Seg b, int out, int in, 
     return run_grad_b(npts, g, out, db, st);
 }
 
+// classic NeRF: row stride of every scratch buffer: the widest row (cat[input_pts, h] / cat[feature, views]), rounded up to 8 floats so that every row starts 32-byte
+// aligned (the matrix-core products of gemm_bf16x3.hip load rows with 16-byte vectors)
+static int nerf_backward_width(const nrf_mlp *m)
+{
+    const int in = m->nerf.input_ch, iv = m->nerf.input_ch_views;
+    return (m->max_width + (in > iv ? in : iv) + 7) & ~7;
+}
+// ... and its buffers: the depth hidden outputs, FEAT, HV and 5 gradient buffers
+static RowBufs nerf_backward_layout(Bump &b, const nrf_mlp *m, int64_t p) { return row_bufs_layout(b, p, nerf_backward_width(m), (size_t)m->nerf.depth + 7); }
 static size_t mlp_nerf_backward_workspace_bytes(const nrf_mlp *m, int64_t p)
 {
-    const int64_t c = p < BWD_CHUNK ? p : BWD_CHUNK;
-    const int pad = m->nerf.input_ch > m->nerf.input_ch_views ? m->nerf.input_ch : m->nerf.input_ch_views;
-    return align_up((size_t)c * (size_t)((m->max_width + pad + 7) & ~7) * sizeof(float), 256) * (m->nerf.depth + 7);
+    return measure([&](Bump &b) { nerf_backward_layout(b, m, p); });
 }
 
 int mlp_nerf_backward(const nrf_mlp *m, const float *x, int xs, const float *g_out, int gos, int64_t p, float *g_params, float *g_x, int gxs, void *ws, size_t ws_bytes,
                       hipStream_t st)
 {
-    if (ws_bytes < mlp_nerf_backward_workspace_bytes(m, p)) { set_error("nrf_mlp_backward: workspace %zu < %zu bytes", ws_bytes, mlp_nerf_backward_workspace_bytes(m, p)); return NRF_ERR_WORKSPACE; }
+    Bump bump(ws, ws_bytes);
+    const RowBufs bufs = nerf_backward_layout(bump, m, p);
+    NRF_TRY(ws_check(bump, mlp_nerf_backward_workspace_bytes(m, p), "nrf_mlp_backward"));
     const auto &d = m->nerf;
     const int D = d.depth, Wd = d.width, in = d.input_ch, iv = d.input_ch_views;
-    // row stride of every scratch buffer: the widest row (cat[input_pts, h] / cat[feature, views]), rounded up to 8 floats so that every row starts 32-byte aligned (the
-    // matrix-core products of gemm_bf16x3.hip load rows with 16-byte vectors)
-    const int W = (m->max_width + (in > iv ? in : iv) + 7) & ~7;
-    const size_t buf = align_up((size_t)(p < BWD_CHUNK ? p : BWD_CHUNK) * W * sizeof(float), 256) / sizeof(float);
-    float *base = reinterpret_cast<float *>(ws);
+    const int W = nerf_backward_width(m);
     std::vector<float *> H(D);
-    for (int l = 0; l < D; l++) H[l] = base + (size_t)l * buf;
-    float *FEAT = base + (size_t)D * buf, *HV = base + (size_t)(D + 1) * buf;
-    float *G[5] = {base + (size_t)(D + 2) * buf, base + (size_t)(D + 3) * buf, base + (size_t)(D + 4) * buf, base + (size_t)(D + 5) * buf, base + (size_t)(D + 6) * buf};
+    for (int l = 0; l < D; l++) H[l] = bufs[l];
+    float *FEAT = bufs[D], *HV = bufs[D + 1];
+    float *G[5] = {bufs[D + 2], bufs[D + 3], bufs[D + 4], bufs[D + 5], bufs[D + 6]};
     const Seg none{nullptr, 0, 0, 0};
     auto bias_of = [&](const LinearLayer &L) { return g_params + L.w_off + (size_t)L.in * L.out; };
     for (int64_t p0 = 0; p0 < p; p0 += BWD_CHUNK) {

@@ -20,6 +20,7 @@
 // Arithmetic: fp16 operands, fp32 accumulation.  Gradients are multiplied by a power of two S chosen from max|g_out| (read
 // on the device, no host sync) so that they sit in the middle of the fp16 range, and divided out in fp32 at the end.
 #include "mlp.h"
+#include "workspace.h"
 
 namespace nrf {
 
@@ -636,10 +637,22 @@ static const int64_t BWD_MFMA_CHUNK = 1 << 22;       // points per launch; every
 
 static size_t h_frags_of(const nrf_mlp_small_desc &d) { return 2 + 4 * (d.num_layers - 1) + 2 + 4 * (d.num_layers_color - 1); }
 
+// the flag words the *_flags entries read at the head of the workspace, then one fragment slot per resident wave (256 persistent workgroups), whatever the batch
+struct BwdMfmaWs {
+    uint32_t *absmax;          // [0] max |g_out| bits, [1] non-finite input flag, [2] non-finite result flag
+    half8 *scratch;
+};
+static BwdMfmaWs bwd_mfma_layout(Bump &b, const nrf_mlp *m)
+{
+    BwdMfmaWs w;
+    w.absmax = b.take<uint32_t>(4);
+    w.scratch = b.take<half8>((size_t)256 * (BW_BLOCK_PTS / 32) * h_frags_of(m->small) * (1024 / sizeof(half8)));
+    return w;
+}
 size_t mlp_small_backward_mfma_workspace_bytes(const nrf_mlp *m, int64_t p)
 {
-    (void)p;                                       // one fragment slot per resident wave (256 persistent workgroups), whatever the batch
-    return 256 + (size_t)256 * (BW_BLOCK_PTS / 32) * h_frags_of(m->small) * 1024;
+    (void)p;
+    return measure([&](Bump &b) { bwd_mfma_layout(b, m); });
 }
 
 static int backward_mfma_impl(const nrf_mlp *m, const float *x, int xs, const __half2 *feats_lm, const __half *dirs, int s_per_ray, const float *g_out, int gos, int64_t p,
@@ -668,11 +681,13 @@ static int backward_mfma_impl(const nrf_mlp *m, const float *x, int xs, const __
         set_error("nrf_mlp_backward_f16: NeRFSmall shape outside the built matrix-core family (in 32, views 16, 64-wide, geo 15, 2-3 + 3-4 layers, no bias); use nrf_mlp_backward");
         return NRF_ERR_UNSUPPORTED;
     }
-    if (ws_bytes < mlp_small_backward_mfma_workspace_bytes(m, p)) { set_error("nrf_mlp_backward_f16: workspace %zu < %zu bytes", ws_bytes, mlp_small_backward_mfma_workspace_bytes(m, p)); return NRF_ERR_WORKSPACE; }
+    Bump bump(ws, ws_bytes);
+    const BwdMfmaWs w = bwd_mfma_layout(bump, m);
+    NRF_TRY(ws_check(bump, mlp_small_backward_mfma_workspace_bytes(m, p), "nrf_mlp_backward_f16"));
     if (g_x && ((gxs % 4) != 0 || (reinterpret_cast<uintptr_t>(g_x) & 15))) { set_error("nrf_mlp_backward_f16: d_g_x rows must be 16-byte aligned"); return NRF_ERR_INVALID_ARG; }
-    uint32_t *absmax = reinterpret_cast<uint32_t *>(ws);
-    half8 *scratch = reinterpret_cast<half8 *>(reinterpret_cast<unsigned char *>(ws) + 256);
-    NRF_HIP(hipMemsetAsync(absmax, 0, 16, st));           // [0] max |g_out| bits, [1] non-finite input flag, [2] non-finite result flag
+    uint32_t *absmax = w.absmax;
+    half8 *scratch = w.scratch;
+    NRF_HIP(hipMemsetAsync(absmax, 0, 16, st));
     {
         const int64_t n = p * gos;
         hipLaunchKernelGGL(k_absmax, dim3((unsigned)(ceil_div(n, (int64_t)256) < 1024 ? ceil_div(n, (int64_t)256) : 1024)), dim3(256), 0, st, n, g_out, absmax);

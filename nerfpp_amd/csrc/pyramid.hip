@@ -8,6 +8,7 @@
 // the kernel's, one wave per pixel, so each is wave-uniform.  Arithmetic is the reference's ATen fp32 sequence, one rounding per op (-ffp-contract=off,
 // correctly rounded fp32 division), so results equal the LibTorch CPU path bit for bit, NaN rows included.
 #include "common.h"
+#include "workspace.h"
 
 #include <cmath>
 #include <vector>
@@ -390,14 +391,23 @@ int nrf_pyramid_pixel_values(const nrf_pyramid *p, int img_id, float scale, cons
     return pyr_launch(c, d_x, d_y, n, 1, 0, d_out, out_stride, as_stream(stream));
 }
 
-static size_t pyr_preview_row_bytes(const nrf_pyramid *p, int w) { return align_up((size_t)w * p->d * sizeof(float), 256) + align_up((size_t)w * 2 * sizeof(float), 256); }
+// the preview's workspace for `rows` image rows at a time: their embeddings and relevancies
+struct PreviewWs { float *emb, *rel; };
+static PreviewWs preview_layout(Bump &b, const nrf_pyramid *p, int w, int rows)
+{
+    PreviewWs ws;
+    ws.emb = b.take<float>((size_t)rows * w * p->d);
+    ws.rel = b.take<float>((size_t)rows * w * 2);
+    return ws;
+}
+static size_t pyr_preview_bytes(const nrf_pyramid *p, int w, int rows) { return measure([&](Bump &b) { preview_layout(b, p, w, rows); }); }
 
 size_t nrf_pyramid_relevancy_preview_workspace_bytes(const nrf_pyramid *p, int img_id, int rows)
 {
     if (!p || img_id < 0 || img_id >= p->n_images || rows < 1) return 0;
     const int w = p->wh[2 * img_id], h = p->wh[2 * img_id + 1];
     if (rows > h) rows = h;
-    return align_up((size_t)rows * w * p->d * sizeof(float), 256) + align_up((size_t)rows * w * 2 * sizeof(float), 256);
+    return pyr_preview_bytes(p, w, rows);
 }
 
 int nrf_pyramid_relevancy_preview(const nrf_pyramid *p, int img_id, float scale, const float *d_positives, int n_pos, const float *d_negatives, int n_neg, int positive_id,
@@ -409,15 +419,17 @@ int nrf_pyramid_relevancy_preview(const nrf_pyramid *p, int img_id, float scale,
     NRF_CHECK_ARG(n_pos >= 1 && n_neg >= 1 && positive_id >= 0 && positive_id < n_pos && (size_t)(1 + n_neg) * p->d * sizeof(float) <= 64 * 1024,
                   "nrf_pyramid_relevancy_preview: phrases as nrf_lerf_relevancy takes them (P %d, Q %d, id %d, D %d)", n_pos, n_neg, positive_id, p->d);
     const int w = p->wh[2 * img_id], h = p->wh[2 * img_id + 1];
-    // rows of row_bytes each fit: align_up(rows * a, 256) <= rows * align_up(a, 256)
-    const int rows = (int)std::min<size_t>((size_t)h, workspace_bytes / pyr_preview_row_bytes(p, w));
+    // the caller's bytes decide how many rows go at a time.  rows of one row's bytes each fit: align_up(rows * a, 256) <= rows * align_up(a, 256)
+    const int rows = (int)std::min<size_t>((size_t)h, workspace_bytes / pyr_preview_bytes(p, w, 1));
     if (rows < 1) {
-        set_error("nrf_pyramid_relevancy_preview: a workspace of %zu bytes holds no row (%zu bytes per row)", workspace_bytes, pyr_preview_row_bytes(p, w));
+        set_error("nrf_pyramid_relevancy_preview: a workspace of %zu bytes holds no row (%zu bytes per row)", workspace_bytes, pyr_preview_bytes(p, w, 1));
         return NRF_ERR_WORKSPACE;
     }
+    Bump bump(d_workspace, workspace_bytes);
+    const PreviewWs ws = preview_layout(bump, p, w, rows);
+    NRF_TRY(ws_check(bump, 0, "nrf_pyramid_relevancy_preview"));
     hipStream_t st = as_stream(stream);
-    float *emb = reinterpret_cast<float *>(d_workspace);
-    float *rel = reinterpret_cast<float *>(reinterpret_cast<char *>(d_workspace) + align_up((size_t)rows * w * p->d * sizeof(float), 256));
+    float *emb = ws.emb, *rel = ws.rel;
     // NeRFExecutor.h:809-827 pixel by pixel; here rows [r0, r0 + rows) at a time: GetPixelValue(i, j) -> Relevancy -> saturate_cast<uchar>(rel[0, 0] * 255)
     for (int r0 = 0; r0 < h; r0 += rows) {
         const int64_t m = (int64_t)std::min(rows, h - r0) * w;

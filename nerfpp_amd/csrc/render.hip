@@ -129,14 +129,27 @@ __global__ void k_gather_raw(int64_t p, const int32_t *__restrict__ src, const f
     raw_f[i] = c < n_coarse ? raw_coarse[c] : raw_new[c - n_coarse];
 }
 
+// scratch of the generic row-major network (run_network) over p points
+struct NetWs {
+    float *x;            // concatenated MLP input [p, in_ch + in_views]
+    uint8_t *keep;       // keep mask
+    float *pts;          // explicit points (PE path)
+    void *mlp;           // mlp_forward's own scratch
+    size_t mlp_bytes;
+};
+static NetWs network_layout(Bump &b, const nrf_renderer *r, int64_t p, int prec)
+{
+    NetWs w;
+    w.x = b.take<float>((size_t)p * (r->in_ch + r->in_views));
+    w.keep = b.take<uint8_t>((size_t)p);
+    w.pts = b.take<float>((size_t)p * 3);
+    w.mlp_bytes = mlp_workspace_bytes(r->desc.mlp, p, prec);
+    w.mlp = b.take<char>(w.mlp_bytes);
+    return w;
+}
 static size_t network_ws_bytes(const nrf_renderer *r, int64_t p, int prec)
 {
-    size_t b = 0;
-    b += align_up((size_t)p * (r->in_ch + r->in_views) * sizeof(float), 256);    // concatenated MLP input
-    b += align_up((size_t)p, 256);                                               // keep mask
-    b += align_up((size_t)p * 3 * sizeof(float), 256);                           // explicit points (PE path)
-    b += align_up(mlp_workspace_bytes(r->desc.mlp, p, prec), 256) + 1024;
-    return b;
+    return measure([&](Bump &b) { network_layout(b, r, p, prec); });
 }
 
 // The fast path (matrix-core precisions, a hash grid of either encoder with F = 2 and 16 levels, SH directions, NeRFSmall in the built
@@ -163,42 +176,42 @@ static bool fast_path(const nrf_renderer *r, int prec)
            mlp_small_mfma_available(r->desc.mlp);
 }
 
-static size_t fast_ws_bytes(const nrf_renderer *r, int64_t n, int64_t p)
+// scratch of the fast path's network (run_network_fast) and of its sigma-only twin (run_sigma_fast) over up to p points: the level-major feature table and the keep mask
+struct FastWs {
+    __half2 *feats;      // [planes][16][p]: HashEmbedder features travel as two planes (hi + lo in split precision, one fp32 plane for the exact sigma kernel)
+    uint8_t *keep;
+};
+static FastWs fast_layout(Bump &b, const nrf_renderer *r, int64_t p)
 {
-    return align_up((size_t)p * 16 * sizeof(__half2), 256) * 2 + align_up((size_t)p, 256) + align_up((size_t)n * r->in_views * sizeof(__half), 256) + 1024;
+    FastWs w;
+    w.feats = b.take<__half2>((size_t)p * 16 * (r->desc.hash->desc.mode == NRF_HASH_NGP ? 2 : 1));
+    w.keep = b.take<uint8_t>((size_t)p);
+    return w;
 }
 
 // dirs_f16: per-ray direction features [n, V] prepared once per chunk (nullptr: computed here from `viewdirs`)
-static int run_network_fast(const nrf_renderer *r, const PointSource &ps, const __half *dirs_f16, const __half *dirs_lo, int64_t n, int s, float *raw, void *ws,
-                            size_t ws_bytes, hipStream_t st)
+static int run_network_fast(const nrf_renderer *r, const PointSource &ps, const __half *dirs_f16, const __half *dirs_lo, int64_t n, int s, float *raw, const FastWs &w,
+                            hipStream_t st)
 {
     const int64_t p = n * s;
     if (p == 0) return NRF_OK;
-    Bump bump(ws, ws_bytes);
     const bool ngp = r->desc.hash->desc.mode == NRF_HASH_NGP;
     const bool want_lo = ngp && dirs_lo != nullptr;                       // split precision on fp32-valued features
-    __half2 *feats = bump.take<__half2>((size_t)p * 16 * (want_lo ? 2 : 1));
-    uint8_t *keep = bump.take<uint8_t>((size_t)p);
-    if (bump.off > ws_bytes) { set_error("run_network_fast: workspace too small"); return NRF_ERR_WORKSPACE; }
-    if (ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, p, feats, p, want_lo ? p * 16 : 0, keep, st));
-    else NRF_TRY(launch_hash_lm(r->desc.hash, ps, p, feats, p, keep, HASH_LM_DEFAULT_VARIANT, st));
-    return mlp_small_forward_mfma_lm(r->desc.mlp, feats, want_lo ? feats + p * 16 : nullptr, p, dirs_f16, dirs_lo, s, keep, p, raw, st);
+    if (ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, p, w.feats, p, want_lo ? p * 16 : 0, w.keep, st));
+    else NRF_TRY(launch_hash_lm(r->desc.hash, ps, p, w.feats, p, w.keep, HASH_LM_DEFAULT_VARIANT, st));
+    return mlp_small_forward_mfma_lm(r->desc.mlp, w.feats, want_lo ? w.feats + p * 16 : nullptr, p, dirs_f16, dirs_lo, s, w.keep, p, raw, st);
 }
 
 // Coarse pass of a hierarchical render on the fast path: sigma only, exact fp32 on the matrix cores (sigma_small_f32.hip).  The features are the
 // fast path's own (CuHashEmbedder: level-major fp16, exact; HashEmbedder: one level-major fp32 plane), so sigma equals NRF_PREC_F32's bit for bit.
-static int run_sigma_fast(const nrf_renderer *r, const PointSource &ps, int64_t n, int s, float *sigma, void *ws, size_t ws_bytes, hipStream_t st)
+static int run_sigma_fast(const nrf_renderer *r, const PointSource &ps, int64_t n, int s, float *sigma, const FastWs &w, hipStream_t st)
 {
     const int64_t p = n * s;
     if (p == 0) return NRF_OK;
-    Bump bump(ws, ws_bytes);
     const bool ngp = r->desc.hash->desc.mode == NRF_HASH_NGP;
-    __half2 *feats = bump.take<__half2>((size_t)p * 16 * (ngp ? 2 : 1));
-    uint8_t *keep = bump.take<uint8_t>((size_t)p);
-    if (bump.off > ws_bytes) { set_error("run_sigma_fast: workspace too small"); return NRF_ERR_WORKSPACE; }
-    if (ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, p, feats, p, 0, keep, st, true));
-    else NRF_TRY(launch_hash_lm(r->desc.hash, ps, p, feats, p, keep, HASH_LM_DEFAULT_VARIANT, st));
-    return mlp_small_sigma_f32_lm(r->desc.mlp, feats, ngp ? 1 : 0, p, keep, p, sigma, st);
+    if (ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, p, w.feats, p, 0, w.keep, st, true));
+    else NRF_TRY(launch_hash_lm(r->desc.hash, ps, p, w.feats, p, w.keep, HASH_LM_DEFAULT_VARIANT, st));
+    return mlp_small_sigma_f32_lm(r->desc.mlp, w.feats, ngp ? 1 : 0, p, w.keep, p, sigma, st);
 }
 
 // Feature reuse across the two passes of a hierarchical render (both hash encoders' fast paths, deterministic sample points): the fine pass evaluates the network at
@@ -216,9 +229,9 @@ struct ReuseWs {
     int64_t cols;
 };
 
-static int reuse_layout(void *ws, size_t ws_bytes, int64_t n, int s, int ni, bool want_lo, bool want_f32, ReuseWs &w)
+static ReuseWs reuse_layout(Bump &bump, int64_t n, int s, int ni, bool want_lo, bool want_f32)
 {
-    Bump bump(ws, ws_bytes);
+    ReuseWs w;
     w.cols = n * (int64_t)(s + ni);
     w.feats = bump.take<__half2>((size_t)w.cols * 16);
     w.feats_lo = want_lo ? bump.take<__half2>((size_t)w.cols * 16) : nullptr;
@@ -226,24 +239,18 @@ static int reuse_layout(void *ws, size_t ws_bytes, int64_t n, int s, int ni, boo
     w.keep = bump.take<uint8_t>((size_t)w.cols);
     w.src = bump.take<int32_t>((size_t)w.cols);
     w.z_new = bump.take<float>((size_t)n * ni);
-    if (bump.off > ws_bytes) { set_error("nrf_render_rays: workspace too small for the feature-reuse layout"); return NRF_ERR_WORKSPACE; }
-    return NRF_OK;
+    return w;
 }
 
-// RunNetwork over p = n*s points given either explicit points or (rays, z).
+// RunNetwork over p = n*s points given either explicit points or (rays, z); w: network_layout for at least p points
 static int run_network(const nrf_renderer *r, const PointSource &ps, const float *viewdirs, int vd_stride, int64_t n, int s, int prec,
-                       float *raw, void *ws, size_t ws_bytes, hipStream_t st)
+                       float *raw, const NetWs &w, hipStream_t st)
 {
     const int64_t p = n * s;
     if (p == 0) return NRF_OK;
-    if (ws_bytes < network_ws_bytes(r, p, prec)) { set_error("run_network: workspace %zu < %zu bytes", ws_bytes, network_ws_bytes(r, p, prec)); return NRF_ERR_WORKSPACE; }
-    Bump bump(ws, ws_bytes);
     const int xd = r->in_ch + r->in_views;
-    float *x = bump.take<float>((size_t)p * xd);
-    uint8_t *keep = bump.take<uint8_t>((size_t)p);
-    float *pts = bump.take<float>((size_t)p * 3);
-    void *mws = bump.take<char>(0);
-    const size_t mws_bytes = ws_bytes - bump.off;
+    float *x = w.x, *pts = w.pts;
+    uint8_t *keep = w.keep;
     // embed_fn->forward(inputs_flat)                                            (NeRFRenderer.h:175)
     if (r->desc.hash) {
         NRF_TRY(launch_hash(r->desc.hash, ps, p, x, xd, keep, st));
@@ -266,7 +273,7 @@ static int run_network(const nrf_renderer *r, const PointSource &ps, const float
         else NRF_TRY(launch_sh(viewdirs, vd_stride, p, r->desc.dirs_param, r->desc.dirs_encoder == NRF_DIRS_SH_CUDA ? NRF_SH_CUDA : NRF_SH_LIBTORCH, s, x + r->in_ch, xd, st));
     }
     // fn->forward(embedded)                                                     (NeRFRenderer.h:184)
-    NRF_TRY(mlp_forward(r->desc.mlp, x, xd, p, prec, raw, r->desc.mlp->out_dims, mws, mws_bytes, st));
+    NRF_TRY(mlp_forward(r->desc.mlp, x, xd, p, prec, raw, r->desc.mlp->out_dims, w.mlp, w.mlp_bytes, st));
     // outputs_flat[~keep_mask, -1] = 0                                          (NeRFRenderer.h:187-188)
     if (r->desc.hash) {
         hipLaunchKernelGGL(k_mask_sigma, dim3((unsigned)ceil_div(p, 256)), dim3(256), 0, st, p, r->desc.mlp->out_dims, keep, raw);
@@ -391,7 +398,10 @@ int nrf_run_network(const nrf_renderer *r, const float *d_pts, const float *d_vi
 {
     NRF_CHECK_ARG(r && d_pts && d_raw && n >= 0 && s >= 1, "nrf_run_network: bad argument");
     PointSource ps{d_pts, nullptr, nullptr, 0, s};
-    return run_network(r, ps, d_viewdirs, 3, n, s, precision, d_raw, d_workspace, workspace_bytes, as_stream(stream));   // generic boundary: row-major path
+    Bump bump(d_workspace, workspace_bytes);
+    const NetWs w = network_layout(bump, r, n * s, precision);
+    NRF_TRY(ws_check(bump, nrf_run_network_workspace_bytes(r, n, s), "nrf_run_network"));
+    return run_network(r, ps, d_viewdirs, 3, n, s, precision, d_raw, w, as_stream(stream));   // generic boundary: row-major path
 }
 
 size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p) { return rays_ws_bytes(r, n, p, 0); }
@@ -399,33 +409,127 @@ size_t nrf_render_rays_normals_workspace_bytes(const nrf_renderer *r, int64_t n,
 
 }  // extern "C"
 
-size_t nrf::rays_ws_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p, int normals)
+namespace nrf {
+
+// Which kernels render one chunk.  Everything follows from the renderer, the params and the ray count, except sigma_only: a caller that wants the coarse rows
+// (out->d_raw_coarse) gets the whole network in the coarse pass.
+struct Path {
+    bool fast;             // hash grid + NeRFSmall on the matrix cores (fast_path)
+    bool fast_classic;     // classic NeRF fast path: PE(10) positions / PE(4) directions + the 8x256 matrix-core kernel with the PE fused in
+    bool classic_split;
+    // ... and its coarse pass: the density branch (eight 256-wide layers + alpha_linear) in exact fp32 on the matrix cores, followed in the same kernel by the colour
+    // branch on the exact h8 in split precision (sigma_nerf_f32.hip).  Sigma -- hence the coarse weights and the fine sample set -- equals NRF_PREC_F32's bit for bit, and
+    // the coarse pass still leaves whole (rgb, sigma) rows for the fine pass to reuse at its S coarse depths.  2 x the time of NRF_COARSE_FULL.
+    bool exact_classic;
+    bool sigma_only;       // the coarse pass only supplies SamplePDF's weights: sigma net alone, in the parity arithmetic (see nrf_render_params.coarse_mode)
+    bool split;            // fast, split precision: per-ray direction features and HashEmbedder features travel as (hi, lo)
+    bool ngp;              // fast on a HashEmbedder grid: fp32-valued features
+    // Where the coarse pass runs the WHOLE network in the fine pass's own arithmetic (the classic NeRF fast path in either matrix-core precision; HashNeRF with
+    // NRF_COARSE_FULL), the fine pass's S coarse depths need no evaluation at all: their outputs exist.  The network then runs on the N_importance new samples and
+    // k_gather_raw assembles raw_f through the merge map: a quarter of the frame's network evaluations (64 of 256 per ray) is not done; same kernel on the same
+    // inputs, so the result is unchanged bit for bit.
+    bool reuse_raw;
+    bool reuse;            // otherwise (the default split mode: coarse pass = sigma net alone) the coarse hash features are kept for the fine pass (see ReuseWs)
+    // The default HashNeRF mode (split precision, exact sigma-only coarse pass): the coarse kernel also leaves the sigma net's whole output (sigma, geo_feat) as the colour
+    // net's operand fragment, so the fine pass runs the colour net alone at its S coarse depths -- 44 of the 116 matrix instructions per 32 points and 144 of the 336
+    // conversions per point are not repeated there, and what it uses is the EXACT sigma-net output instead of a split-precision repeat.  Both network launches of the
+    // fine pass then walk feature COLUMNS in order (coarse columns, new columns: coalesced loads, no merge-map indirection) and write by column; the compositing
+    // kernel reads through the merge map (one ray's samples lie in two contiguous runs).
+    bool geo_reuse;
+};
+
+static Path choose_path(const nrf_renderer *r, const nrf_render_params *p, int64_t n, bool raw_coarse_supplied)
+{
+    Path a{};
+    const int ni = p->n_importance, sf = p->n_samples + ni, c = r->desc.mlp->out_dims;
+    const bool cone = p->has_cone != 0, precond = p->precond_alpha > 0.0f;
+    a.fast = fast_path(r, p->precision);
+    a.sigma_only = ni > 0 && a.fast && !raw_coarse_supplied && mlp_small_sigma_f32_available(r->desc.mlp) &&
+                   (p->coarse_mode == NRF_COARSE_SIGMA_F32 || (p->coarse_mode == NRF_COARSE_AUTO && p->precision == NRF_PREC_F16_SPLIT));
+    a.classic_split = p->precision == NRF_PREC_F16_SPLIT;
+    a.fast_classic = (p->precision == NRF_PREC_F16_MFMA || a.classic_split) && !r->desc.hash && r->desc.pe_freqs == 10 && r->desc.dirs_encoder == NRF_DIRS_PE &&
+                     r->desc.dirs_param == 4 && (a.classic_split ? mlp_nerf_split_available(r->desc.mlp) : mlp_nerf_mfma_available(r->desc.mlp));
+    a.exact_classic = ni > 0 && a.fast_classic && mlp_nerf_sigma_f32_available(r->desc.mlp) && c == 4 &&
+                      (p->coarse_mode == NRF_COARSE_SIGMA_F32 || (p->coarse_mode == NRF_COARSE_AUTO && a.classic_split));
+    a.split = a.fast && p->precision == NRF_PREC_F16_SPLIT;
+    a.ngp = a.fast && r->desc.hash->desc.mode == NRF_HASH_NGP;
+    a.reuse_raw = (a.fast || a.fast_classic) && ni > 0 && !a.sigma_only && !cone && !precond && c == 4 && n * (int64_t)sf < ((int64_t)1 << 31);
+    a.reuse = !a.reuse_raw && a.fast && ni > 0 && !cone && !precond && n * (int64_t)sf < ((int64_t)1 << 31);
+    a.geo_reuse = a.reuse && a.sigma_only && a.split && r->desc.mlp->small.geo_feat_dim <= 15;
+    return a;
+}
+
+// The network's scratch of one chunk: each path carves the same region with its own pieces, and a chunk reserves the largest (chunk_layout).
+struct PathWs {
+    NetWs net;                             // generic: the row-major network, sized for the pass with the most points
+    FastWs fw;                             // fast without feature reuse (likewise)
+    ReuseWs rw;                            // reuse
+    void *geo_planes; float *raw_cols;     // geo_reuse: operand fragments of the coarse columns, network outputs by column
+    int32_t *rr_src; float *rr_znew, *rr_rawnew;      // reuse_raw: merge map, new-sample depths and their network outputs
+};
+static PathWs path_layout(Bump &b, const nrf_renderer *r, const Path &a, int64_t n, int s, int ni, int prec)
+{
+    PathWs w{};
+    const int sf = s + ni;
+    const int64_t pmax = n * (int64_t)(a.reuse_raw ? (s > ni ? s : ni) : sf);          // points of the largest network pass
+    if (a.reuse) {
+        w.rw = reuse_layout(b, n, s, ni, a.ngp && a.split, a.ngp && a.sigma_only);
+        if (a.geo_reuse) { w.geo_planes = b.take<char>((size_t)n * s * 64); w.raw_cols = b.take<float>((size_t)n * sf * 4); }
+    } else if (a.fast) w.fw = fast_layout(b, r, pmax);
+    else if (!a.fast_classic) w.net = network_layout(b, r, pmax, prec);
+    if (a.reuse_raw) {
+        w.rr_src = b.take<int32_t>((size_t)n * sf);
+        w.rr_znew = b.take<float>((size_t)n * ni);
+        w.rr_rawnew = b.take<float>((size_t)n * ni * 4);
+    }
+    return w;
+}
+
+// One chunk's workspace.  out: the caller's outputs (null: none supplied, what the size functions measure -- every buffer a caller supplies is one piece less).
+struct ChunkWs {
+    float *z_c, *w_c, *raw_c, *z_f, *raw_f;
+    __half *dirs16, *dirs_lo;              // per-ray direction features of the fast paths (hi, lo)
+    float *z_plain;                        // un-jittered depths
+    float *pts;                            // explicit sample points
+    float *nrm_w, *nrm_g;                  // normals: the final weights when the caller does not keep them, the density gradients of the final samples
+    void *net; size_t net_bytes;           // the path's scratch (path_layout)
+};
+static ChunkWs chunk_layout(Bump &b, const nrf_renderer *r, int64_t n, const nrf_render_params *p, int normals, const RenderOutputsX *out)
+{
+    ChunkWs w{};
+    const int s = p->n_samples, ni = p->n_importance, sf = s + ni, so = ni > 0 ? sf : s;
+    const int c = r->desc.mlp->out_dims;
+    w.z_c = out && out->d_z_coarse ? out->d_z_coarse : b.take<float>((size_t)n * s);
+    w.w_c = out && out->d_weights_coarse ? out->d_weights_coarse : b.take<float>((size_t)n * s);
+    w.raw_c = out && out->d_raw_coarse ? out->d_raw_coarse : ((out && ni == 0 && out->d_raw) ? out->d_raw : b.take<float>((size_t)n * s * c));
+    if (ni > 0) {
+        w.z_f = out && out->d_z_fine ? out->d_z_fine : b.take<float>((size_t)n * sf);
+        w.raw_f = out && out->d_raw ? out->d_raw : b.take<float>((size_t)n * sf * c);
+    }
+    const Path full = choose_path(r, p, n, true), sig = choose_path(r, p, n, false);          // the two that a caller's outputs can select
+    const int dv = full.fast ? r->in_views : (full.fast_classic ? 32 : 0);
+    if (dv) w.dirs16 = b.take<__half>((size_t)n * dv);
+    if (dv && p->precision == NRF_PREC_F16_SPLIT) w.dirs_lo = b.take<__half>((size_t)n * dv);
+    if (p->perturb > 0.0f) w.z_plain = b.take<float>((size_t)n * s);
+    if (p->has_cone || p->precond_alpha > 0.0f) w.pts = b.take<float>((size_t)n * sf * 3);
+    if (normals && !(out && out->d_weights)) w.nrm_w = b.take<float>((size_t)n * so);
+    if (normals & NRF_NORMALS_DENSITY) w.nrm_g = b.take<float>((size_t)n * so * 3);
+    // ... each also as a short chunk selects it (one ray: the reuse paths are open only below 2^31 columns, and a lane slice holds every shorter chunk too)
+    for (const Path &a : {full, sig, choose_path(r, p, 1, true), choose_path(r, p, 1, false)}) {
+        const size_t m = measure([&](Bump &mb) { path_layout(mb, r, a, n, s, ni, p->precision); });
+        if (m > w.net_bytes) w.net_bytes = m;
+    }
+    w.net = b.take<char>(w.net_bytes);
+    return w;
+}
+
+static size_t rays_ws_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p, int normals)
 {
     if (!r || !p) return 0;
-    const int s = p->n_samples, sf = p->n_samples + p->n_importance;
-    const int c = r->desc.mlp->out_dims;
-    size_t b = 0;
-    b += align_up((size_t)n * s * 4, 256) * 2;            // z_coarse, weights_coarse
-    b += align_up((size_t)n * s * c * 4, 256);            // raw_coarse
-    b += align_up((size_t)n * sf * 4, 256);               // z_fine
-    b += align_up((size_t)n * sf * c * 4, 256);           // raw_fine
-    // the network's scratch: the generic row-major path of all S + N_importance depths, or the feature-reuse layout of the hash fast paths (reuse_layout), whichever is
-    // larger -- with few importance samples the HashEmbedder layout (two feature planes of every column + the fp32 plane of the S coarse ones) passes the first
-    const size_t reuse = align_up((size_t)n * sf * 16 * sizeof(__half2), 256) * 2 + align_up((size_t)n * s * 16 * sizeof(float2), 256) + align_up((size_t)n * sf, 256) +
-                         align_up((size_t)n * sf * 4, 256) + align_up((size_t)n * (sf - s) * 4, 256) + 2048;
-    const size_t generic = network_ws_bytes(r, n * sf, p->precision);
-    b += (generic > reuse ? generic : reuse) + 4096;
-    b += align_up((size_t)n * 64 * sizeof(__half), 256) * 2;  // per-ray direction features of the fast path (hi, lo)
-    b += align_up((size_t)n * sf * 4, 256) + align_up((size_t)n * (sf - s) * 4, 256) + 1024;   // feature reuse: merge map + new-sample depths
-    b += align_up((size_t)n * sf * 4, 256) + align_up((size_t)n * (sf - s) * 4, 256) + align_up((size_t)n * (sf - s) * 16, 256);   // raw reuse: map, depths, outputs of the new samples
-    b += align_up((size_t)n * s * 64, 256) + align_up((size_t)n * sf * 16, 256);                 // geo hand-over: operand fragments of the coarse columns, outputs by column
-    if (p->perturb > 0.0f) b += align_up((size_t)n * s * 4, 256);                             // un-jittered depths
-    if (p->has_cone || p->precond_alpha > 0.0f) b += align_up((size_t)n * sf * 12, 256);     // explicit sample points
-    const int so = p->n_importance > 0 ? sf : s;
-    if (normals) b += align_up((size_t)n * so * 4, 256);                                        // normals: the final weights when the caller does not keep them
-    if (normals & NRF_NORMALS_DENSITY) b += align_up((size_t)n * so * 12, 256);                 // ... and the density gradients of the final samples
-    return b;
+    return measure([&](Bump &b) { chunk_layout(b, r, n, p, normals, nullptr); });
 }
+
+}  // namespace nrf
 
 namespace nrf {
 
@@ -602,73 +706,35 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
     NRF_CHECK_ARG(p->precond_alpha == 0.0f || p->has_bbox, "nrf_render_rays: stochastic preconditioning reflects at the bounding box (NeRFRenderer.h:436-442): bbox required");
     NRF_CHECK_ARG(p->perturb == 0.0f || p->n_samples >= 2, "nrf_render_rays: Perturb > 0 needs n_samples >= 2");
     NRF_CHECK_ARG(p->coarse_mode >= NRF_COARSE_AUTO && p->coarse_mode <= NRF_COARSE_SIGMA_F32, "nrf_render_rays: coarse_mode %d is not an NRF_COARSE_* value", p->coarse_mode);
-    if (workspace_bytes < rays_ws_bytes(r, n, p, p->normals)) {
-        set_error("nrf_render_rays: workspace %zu < %zu bytes", workspace_bytes, rays_ws_bytes(r, n, p, p->normals));
-        return NRF_ERR_WORKSPACE;
-    }
-    hipStream_t st = as_stream(stream);
-    if (p->precision == NRF_PREC_F16_SPLIT) NRF_TRY(ensure_scales(r, st));          // (a no-op inside a Chunk loop: nrf_batchify_rays did it before its lanes forked)
     const int s = p->n_samples, ni = p->n_importance, sf = s + ni;
     const int c = r->desc.mlp->out_dims;
+    // the chunk's pieces and, in the network's region, those of the path that runs: all carved and checked here, before the first launch
+    const Path path = choose_path(r, p, n, out->d_raw_coarse != nullptr);
+    Bump bump(d_workspace, workspace_bytes);
+    const ChunkWs cw = chunk_layout(bump, r, n, p, p->normals, out);
+    NRF_TRY(ws_check(bump, rays_ws_bytes(r, n, p, p->normals), "nrf_render_rays"));
+    Bump net(cw.net, cw.net_bytes);
+    const PathWs pw = path_layout(net, r, path, n, s, ni, p->precision);          // (fits: net_bytes is the largest measure of the paths a call can take)
+    hipStream_t st = as_stream(stream);
+    if (p->precision == NRF_PREC_F16_SPLIT) NRF_TRY(ensure_scales(r, st));          // (a no-op inside a Chunk loop: nrf_batchify_rays did it before its lanes forked)
     // the FINAL compositing of the matrix-core precisions uses hardware exp / log / rcp and fp32 scans (composite.hip); NRF_PREC_F32, and the coarse pass whose
     // weights feed SamplePDF (a moved CDF bin is a visibly different sample set), keep the oracle's arithmetic
     const bool fastc = p->precision != NRF_PREC_F32;
-    Bump bump(d_workspace, workspace_bytes);
-    float *z_c = out->d_z_coarse ? out->d_z_coarse : bump.take<float>((size_t)n * s);
-    float *w_c = out->d_weights_coarse ? out->d_weights_coarse : bump.take<float>((size_t)n * s);
-    float *raw_c = out->d_raw_coarse ? out->d_raw_coarse : ((ni == 0 && out->d_raw) ? out->d_raw : bump.take<float>((size_t)n * s * c));
-    float *z_f = nullptr, *raw_f = nullptr;
-    if (ni > 0) {
-        z_f = out->d_z_fine ? out->d_z_fine : bump.take<float>((size_t)n * sf);
-        raw_f = out->d_raw ? out->d_raw : bump.take<float>((size_t)n * sf * c);
-    }
-    const bool fast = fast_path(r, p->precision);
-    // the coarse pass only supplies SamplePDF's weights: sigma net alone, in the parity arithmetic (see nrf_render_params.coarse_mode)
-    const bool sigma_only_hash = ni > 0 && fast && !out->d_raw_coarse && mlp_small_sigma_f32_available(r->desc.mlp) &&
-                                 (p->coarse_mode == NRF_COARSE_SIGMA_F32 || (p->coarse_mode == NRF_COARSE_AUTO && p->precision == NRF_PREC_F16_SPLIT));
-    // classic NeRF fast path: PE(10) positions / PE(4) directions + the 8x256 matrix-core kernel with the PE fused in
-    const bool classic_split = p->precision == NRF_PREC_F16_SPLIT;
-    const bool fast_classic = (p->precision == NRF_PREC_F16_MFMA || classic_split) && !r->desc.hash && r->desc.pe_freqs == 10 && r->desc.dirs_encoder == NRF_DIRS_PE &&
-                              r->desc.dirs_param == 4 && (classic_split ? mlp_nerf_split_available(r->desc.mlp) : mlp_nerf_mfma_available(r->desc.mlp));
-    // ... and its coarse pass: the density branch (eight 256-wide layers + alpha_linear) in exact fp32 on the matrix cores, followed in the same kernel by the colour
-    // branch on the exact h8 in split precision (sigma_nerf_f32.hip).  Sigma -- hence the coarse weights and the fine sample set -- equals NRF_PREC_F32's bit for bit, and
-    // the coarse pass still leaves whole (rgb, sigma) rows for the fine pass to reuse at its S coarse depths.  2 x the time of NRF_COARSE_FULL.
-    const bool exact_classic = ni > 0 && fast_classic && mlp_nerf_sigma_f32_available(r->desc.mlp) && c == 4 &&
-                               (p->coarse_mode == NRF_COARSE_SIGMA_F32 || (p->coarse_mode == NRF_COARSE_AUTO && classic_split));
-    const bool sigma_only = sigma_only_hash;
-    __half *dirs16 = nullptr;
-    __half *dirs_lo = nullptr;
-    if (fast) dirs16 = bump.take<__half>((size_t)n * r->in_views);
-    if (fast && p->precision == NRF_PREC_F16_SPLIT) dirs_lo = bump.take<__half>((size_t)n * r->in_views);
-    if (fast_classic) dirs16 = bump.take<__half>((size_t)n * 32);
-    if (fast_classic && classic_split) dirs_lo = bump.take<__half>((size_t)n * 32);
-    // merge map, new-sample depths and their network outputs of the raw-reuse fine pass (see reuse_raw below)
-    int32_t *rr_src = ni > 0 ? bump.take<int32_t>((size_t)n * sf) : nullptr;
-    float *rr_znew = ni > 0 ? bump.take<float>((size_t)n * ni) : nullptr;
-    float *rr_rawnew = ni > 0 ? bump.take<float>((size_t)n * ni * 4) : nullptr;
-    void *geo_planes = ni > 0 ? static_cast<void *>(bump.take<char>((size_t)n * s * 64)) : nullptr;      // see geo_reuse below
-    float *raw_cols = ni > 0 ? bump.take<float>((size_t)n * sf * 4) : nullptr;
-    float *z_plain = p->perturb > 0.0f ? bump.take<float>((size_t)n * s) : nullptr;
-    float *bump_pts = (p->has_cone || p->precond_alpha > 0.0f) ? bump.take<float>((size_t)n * sf * 3) : nullptr;
     const int so = ni > 0 ? sf : s;
-    float *nrm_w = (p->normals && !out->d_weights) ? bump.take<float>((size_t)n * so) : nullptr;
-    float *nrm_g = (p->normals & NRF_NORMALS_DENSITY) ? bump.take<float>((size_t)n * so * 3) : nullptr;
-    void *nws = bump.take<char>(0);
-    const size_t nws_bytes = workspace_bytes - bump.off;
     const float *viewdirs = r->in_views > 0 ? d_rays + 8 : nullptr;
-    if (fast) NRF_TRY(launch_dirs_f16(d_rays, ray_stride, n, r->desc.dirs_param, r->desc.dirs_encoder == NRF_DIRS_SH_CUDA ? NRF_SH_CUDA : NRF_SH_LIBTORCH, dirs16, dirs_lo, st));
-    if (fast_classic && classic_split) NRF_TRY(launch_dirs_pe_split(d_rays, ray_stride, n, dirs16, dirs_lo, st));
-    else if (fast_classic) NRF_TRY(launch_dirs_pe_f16(d_rays, ray_stride, n, dirs16, st));
+    if (path.fast) NRF_TRY(launch_dirs_f16(d_rays, ray_stride, n, r->desc.dirs_param, r->desc.dirs_encoder == NRF_DIRS_SH_CUDA ? NRF_SH_CUDA : NRF_SH_LIBTORCH, cw.dirs16, cw.dirs_lo, st));
+    if (path.fast_classic && path.classic_split) NRF_TRY(launch_dirs_pe_split(d_rays, ray_stride, n, cw.dirs16, cw.dirs_lo, st));
+    else if (path.fast_classic) NRF_TRY(launch_dirs_pe_f16(d_rays, ray_stride, n, cw.dirs16, st));
     auto network = [&](const PointSource &src, int ns_, float *raw_out) -> int {
-        if (fast) return run_network_fast(r, src, dirs16, dirs_lo, n, ns_, raw_out, nws, nws_bytes, st);
-        if (fast_classic && classic_split) return mlp_nerf_forward_split_fused(r->desc.mlp, src.pts, src.rays, src.ray_stride, src.z, ns_, dirs16, dirs_lo, n * (int64_t)ns_, raw_out, st);
-        if (fast_classic) return mlp_nerf_forward_mfma_fused(r->desc.mlp, src.pts, src.rays, src.ray_stride, src.z, ns_, dirs16, n * (int64_t)ns_, raw_out, st);
-        return run_network(r, src, viewdirs, ray_stride, n, ns_, p->precision, raw_out, nws, nws_bytes, st);
+        if (path.fast) return run_network_fast(r, src, cw.dirs16, cw.dirs_lo, n, ns_, raw_out, pw.fw, st);
+        if (path.fast_classic && path.classic_split) return mlp_nerf_forward_split_fused(r->desc.mlp, src.pts, src.rays, src.ray_stride, src.z, ns_, cw.dirs16, cw.dirs_lo, n * (int64_t)ns_, raw_out, st);
+        if (path.fast_classic) return mlp_nerf_forward_mfma_fused(r->desc.mlp, src.pts, src.rays, src.ray_stride, src.z, ns_, cw.dirs16, n * (int64_t)ns_, raw_out, st);
+        return run_network(r, src, viewdirs, ray_stride, n, ns_, p->precision, raw_out, pw.net, st);
     };
     // ---- stochastic branches: all off on the render path ----
     const RngRef rng{p->seed, p->ray_base};
     const bool jitter = p->perturb > 0.0f, cone = p->has_cone != 0, precond = p->precond_alpha > 0.0f;
-    float *pts = (cone || precond) ? bump_pts : nullptr;
+    float *pts = (cone || precond) ? cw.pts : nullptr;
     SigmaNoise nz{};
     nz.on = p->raw_noise_std > 0.0f; nz.std = p->raw_noise_std; nz.g = rng;
     StochPoints sp{};
@@ -678,8 +744,8 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
     // and the predicted-normals columns of the F32 network's rows (the only precision the head has: raw holds every row in depth order)
     auto normals_tail = [&](const PointSource &src, const float *wts, const float *raw_rows) -> int {
         if (p->normals & NRF_NORMALS_DENSITY) {
-            NRF_TRY(density_grad_launch(r->desc.hash, r->desc.mlp, src, n * (int64_t)so, wts, nullptr, nrm_g, st));
-            NRF_TRY(normals_composite(n, so, nrm_g, 3, 0, nullptr, -1.0f, wts, out->d_normals, st));
+            NRF_TRY(density_grad_launch(r->desc.hash, r->desc.mlp, src, n * (int64_t)so, wts, nullptr, cw.nrm_g, st));
+            NRF_TRY(normals_composite(n, so, cw.nrm_g, 3, 0, nullptr, -1.0f, wts, out->d_normals, st));
         }
         if (p->normals & NRF_NORMALS_PREDICTED) NRF_TRY(normals_composite(n, so, raw_rows, c, 4, nullptr, 1.0f, wts, out->d_pred_normals, st));
         return NRF_OK;
@@ -687,99 +753,84 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
 
     // z_vals; pts = o + d*z formed inside the encoder                           (NeRFRenderer.h:393-419)
     if (jitter) {
-        NRF_TRY(nrf_z_vals(d_rays, ray_stride, n, d_t, s, p->lindisp, z_plain, st));
-        NRF_TRY(launch_jitter_z(z_plain, nullptr, rng, n, s, z_c, st));                                             // :404-417
-    } else NRF_TRY(nrf_z_vals(d_rays, ray_stride, n, d_t, s, p->lindisp, z_c, st));
-    PointSource ps{nullptr, d_rays, z_c, ray_stride, s};
+        NRF_TRY(nrf_z_vals(d_rays, ray_stride, n, d_t, s, p->lindisp, cw.z_plain, st));
+        NRF_TRY(launch_jitter_z(cw.z_plain, nullptr, rng, n, s, cw.z_c, st));                                             // :404-417
+    } else NRF_TRY(nrf_z_vals(d_rays, ray_stride, n, d_t, s, p->lindisp, cw.z_c, st));
+    PointSource ps{nullptr, d_rays, cw.z_c, ray_stride, s};
     if (cone) {                                                                                                    // :420
         sp.precond = 0; sp.stream_r = NRF_RNG_R_COARSE; sp.stream_theta = NRF_RNG_THETA_COARSE;
-        NRF_TRY(launch_stoch_points(nullptr, d_rays, ray_stride, z_c, n, s, sp, rng, pts, st));
+        NRF_TRY(launch_stoch_points(nullptr, d_rays, ray_stride, cw.z_c, n, s, sp, rng, pts, st));
         ps.pts = pts;
     }
-    // Where the coarse pass runs the WHOLE network in the fine pass's own arithmetic (the classic NeRF fast path in either matrix-core precision; HashNeRF with
-    // NRF_COARSE_FULL), the fine pass's S coarse depths need no evaluation at all: their outputs exist.  The network then runs on the N_importance new samples and
-    // k_gather_raw assembles raw_f through the merge map: a quarter of the frame's network evaluations (64 of 256 per ray) is not done; same kernel on the same
-    // inputs, so the result is unchanged bit for bit.
-    const bool reuse_raw = (fast || fast_classic) && ni > 0 && !sigma_only && !cone && !precond && c == 4 && n * (int64_t)sf < ((int64_t)1 << 31);
-    // otherwise (the default split mode: coarse pass = sigma net alone) the coarse hash features are kept for the fine pass (see ReuseWs)
-    const bool reuse = !reuse_raw && fast && ni > 0 && !cone && !precond && n * (int64_t)sf < ((int64_t)1 << 31);
-    const bool ngp = fast && r->desc.hash->desc.mode == NRF_HASH_NGP;       // HashEmbedder: fp32-valued features, (hi, lo) planes in split precision
-    // The default HashNeRF mode (split precision, exact sigma-only coarse pass): the coarse kernel also leaves the sigma net's whole output (sigma, geo_feat) as the colour
-    // net's operand fragment, so the fine pass runs the colour net alone at its S coarse depths -- 44 of the 116 matrix instructions per 32 points and 144 of the 336
-    // conversions per point are not repeated there, and what it uses is the EXACT sigma-net output instead of a split-precision repeat.  Both network launches of the
-    // fine pass then walk feature COLUMNS in order (coarse columns, new columns: coalesced loads, no merge-map indirection) and write by column; the compositing
-    // kernel reads through the merge map (one ray's samples lie in two contiguous runs).
-    const bool geo_reuse = reuse && sigma_only && dirs_lo != nullptr && r->desc.mlp->small.geo_feat_dim <= 15;
-    ReuseWs rw{};
-    if (reuse) {
-        NRF_TRY(reuse_layout(nws, nws_bytes, n, s, ni, ngp && dirs_lo, ngp && sigma_only, rw));
+    const ReuseWs &rw = pw.rw;
+    if (path.reuse) {
         // HashEmbedder mode: the exact coarse kernel reads the unrounded fp32 features; the (hi, lo) planes of the coarse columns are read only by a fine pass that
         // runs the whole network there -- not when the coarse kernel hands (sigma, geo_feat) over
-        if (ngp && geo_reuse) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, n * (int64_t)s, reinterpret_cast<__half2 *>(rw.f32), n * (int64_t)s, 0, rw.keep, st, true, nullptr, 0));
-        else if (ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, n * (int64_t)s, rw.feats, rw.cols, rw.feats_lo ? rw.feats_lo - rw.feats : 0, rw.keep, st, false, rw.f32, n * (int64_t)s));
+        if (path.ngp && path.geo_reuse) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, n * (int64_t)s, reinterpret_cast<__half2 *>(rw.f32), n * (int64_t)s, 0, rw.keep, st, true, nullptr, 0));
+        else if (path.ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, ps, n * (int64_t)s, rw.feats, rw.cols, rw.feats_lo ? rw.feats_lo - rw.feats : 0, rw.keep, st, false, rw.f32, n * (int64_t)s));
         else NRF_TRY(launch_hash_lm(r->desc.hash, ps, n * (int64_t)s, rw.feats, rw.cols, rw.keep, HASH_LM_DEFAULT_VARIANT, st));
-        if (sigma_only) NRF_TRY(mlp_small_sigma_f32_lm(r->desc.mlp, ngp ? static_cast<const void *>(rw.f32) : rw.feats, ngp ? 1 : 0, ngp ? n * (int64_t)s : rw.cols, rw.keep, n * (int64_t)s, raw_c, st,
-                                                       geo_reuse ? geo_planes : nullptr, n * (int64_t)s));
-        else NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats, rw.feats_lo, rw.cols, dirs16, dirs_lo, s, rw.keep, n * (int64_t)s, raw_c, st));
-    } else if (exact_classic) NRF_TRY(mlp_nerf_exact_coarse(r->desc.mlp, ps.pts, ps.rays, ps.ray_stride, ps.z, s, dirs16, dirs_lo, n * (int64_t)s, raw_c, st));
-    else if (sigma_only) NRF_TRY(run_sigma_fast(r, ps, n, s, raw_c, nws, nws_bytes, st));                         // raw_c holds sigma [n,s] only
-    else NRF_TRY(network(ps, s, raw_c));                                                                           // :422
+        if (path.sigma_only) NRF_TRY(mlp_small_sigma_f32_lm(r->desc.mlp, path.ngp ? static_cast<const void *>(rw.f32) : rw.feats, path.ngp ? 1 : 0, path.ngp ? n * (int64_t)s : rw.cols, rw.keep, n * (int64_t)s, cw.raw_c, st,
+                                                       path.geo_reuse ? pw.geo_planes : nullptr, n * (int64_t)s));
+        else NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats, rw.feats_lo, rw.cols, cw.dirs16, cw.dirs_lo, s, rw.keep, n * (int64_t)s, cw.raw_c, st));
+    } else if (path.exact_classic) NRF_TRY(mlp_nerf_exact_coarse(r->desc.mlp, ps.pts, ps.rays, ps.ray_stride, ps.z, s, cw.dirs16, cw.dirs_lo, n * (int64_t)s, cw.raw_c, st));
+    else if (path.sigma_only) NRF_TRY(run_sigma_fast(r, ps, n, s, cw.raw_c, pw.fw, st));                         // raw_c holds sigma [n,s] only
+    else NRF_TRY(network(ps, s, cw.raw_c));                                                                           // :422
     nz.stream = NRF_RNG_NOISE_COARSE;
     if (ni == 0) {
         // a caller that asked for both the coarse intermediates and Raw gets the same rows in both (raw_c is the coarse buffer then: Raw was left unwritten -- a training
         // step with N_importance = 0 differentiated garbage; found by tools/scratch/train_fuzz.py)
-        if (out->d_raw && raw_c != out->d_raw) NRF_HIP(hipMemcpyAsync(out->d_raw, raw_c, (size_t)n * s * c * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (out->d_raw && cw.raw_c != out->d_raw) NRF_HIP(hipMemcpyAsync(out->d_raw, cw.raw_c, (size_t)n * s * c * sizeof(float), hipMemcpyDeviceToDevice, st));
         // the reference leaves result.Outputs UNDEFINED in this case (:423 vs :448); the coarse maps are what a caller wants
-        NRF_TRY(launch_raw2outputs(raw_c, z_c, d_rays + 3, ray_stride, n, s, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
-                                   out->d_weights ? out->d_weights : w_c, out->d_depth, nz, st, fastc, nullptr, nullptr, 0, d_flag));
-        return p->normals ? normals_tail(ps, out->d_weights ? out->d_weights : w_c, raw_c) : NRF_OK;
+        NRF_TRY(launch_raw2outputs(cw.raw_c, cw.z_c, d_rays + 3, ray_stride, n, s, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
+                                   out->d_weights ? out->d_weights : cw.w_c, out->d_depth, nz, st, fastc, nullptr, nullptr, 0, d_flag));
+        return p->normals ? normals_tail(ps, out->d_weights ? out->d_weights : cw.w_c, cw.raw_c) : NRF_OK;
     }
-    NRF_TRY(launch_raw2outputs(raw_c, z_c, d_rays + 3, ray_stride, n, s, sigma_only ? 1 : c, sigma_only ? 0 : 3, p->white_bkgr, nullptr, nullptr, nullptr, w_c, nullptr, nz,
+    NRF_TRY(launch_raw2outputs(cw.raw_c, cw.z_c, d_rays + 3, ray_stride, n, s, path.sigma_only ? 1 : c, path.sigma_only ? 0 : 3, p->white_bkgr, nullptr, nullptr, nullptr, cw.w_c, nullptr, nz,
                                st, false));   // :423  always the exact arithmetic: these weights choose the fine samples
-    NRF_TRY(launch_fine_depths(z_c, w_c, n, s, jitter ? nullptr : d_u, 0, rng, ni, p->sum_vec, z_f, st, reuse_raw ? rr_src : (reuse ? rw.src : nullptr),
-                               reuse_raw ? rr_znew : (reuse ? rw.z_new : nullptr)));                                // :427-431 (det = perturb == 0)
-    PointSource psf{nullptr, d_rays, z_f, ray_stride, sf};
-    const float *raw_final = raw_f;
+    NRF_TRY(launch_fine_depths(cw.z_c, cw.w_c, n, s, jitter ? nullptr : d_u, 0, rng, ni, p->sum_vec, cw.z_f, st, path.reuse_raw ? pw.rr_src : (path.reuse ? rw.src : nullptr),
+                               path.reuse_raw ? pw.rr_znew : (path.reuse ? rw.z_new : nullptr)));                                // :427-431 (det = perturb == 0)
+    PointSource psf{nullptr, d_rays, cw.z_f, ray_stride, sf};
+    const float *raw_final = cw.raw_f;
     const int32_t *src_final = nullptr;          // compositing reads sample i's network output at row src_final[i] (NULL: i) of raw_final | raw2_final (launch_raw2outputs)
     const float *raw2_final = nullptr;
     int64_t split_final = 0;
     if (cone || precond) {                                                                                         // :433-445
         sp.precond = precond; sp.stream_r = NRF_RNG_R_FINE; sp.stream_theta = NRF_RNG_THETA_FINE;
-        NRF_TRY(launch_stoch_points(nullptr, d_rays, ray_stride, z_f, n, sf, sp, rng, pts, st));
+        NRF_TRY(launch_stoch_points(nullptr, d_rays, ray_stride, cw.z_f, n, sf, sp, rng, pts, st));
         psf.pts = pts;
     }
-    if (reuse_raw) {
+    if (path.reuse_raw) {
         // the network on the N_importance new samples only; the S coarse depths take the coarse pass's outputs (same kernel, same inputs: same bits)
-        PointSource psn{nullptr, d_rays, rr_znew, ray_stride, ni};
-        NRF_TRY(network(psn, ni, rr_rawnew));
+        PointSource psn{nullptr, d_rays, pw.rr_znew, ray_stride, ni};
+        NRF_TRY(network(psn, ni, pw.rr_rawnew));
         if (out->d_raw) {          // the caller wants raw in depth order
-            hipLaunchKernelGGL(k_gather_raw, dim3((unsigned)ceil_div(n * (int64_t)sf, 256)), dim3(256), 0, st, n * (int64_t)sf, rr_src, reinterpret_cast<const float4 *>(raw_c),
-                               reinterpret_cast<const float4 *>(rr_rawnew), n * (int64_t)s, reinterpret_cast<float4 *>(raw_f));
+            hipLaunchKernelGGL(k_gather_raw, dim3((unsigned)ceil_div(n * (int64_t)sf, 256)), dim3(256), 0, st, n * (int64_t)sf, pw.rr_src, reinterpret_cast<const float4 *>(cw.raw_c),
+                               reinterpret_cast<const float4 *>(pw.rr_rawnew), n * (int64_t)s, reinterpret_cast<float4 *>(cw.raw_f));
             NRF_LAUNCH_CHECK();
-        } else { raw_final = raw_c; raw2_final = rr_rawnew; split_final = n * (int64_t)s; src_final = rr_src; }          // the compositing kernel reads through the merge map
-    } else if (reuse) {
+        } else { raw_final = cw.raw_c; raw2_final = pw.rr_rawnew; split_final = n * (int64_t)s; src_final = pw.rr_src; }          // the compositing kernel reads through the merge map
+    } else if (path.reuse) {
         // the hash encode of the N_importance new samples only; the MLP gathers every depth's column through the merge map
         PointSource psn{nullptr, d_rays, rw.z_new, ray_stride, ni};
-        if (ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, psn, n * (int64_t)ni, rw.feats + n * (int64_t)s, rw.cols, rw.feats_lo ? rw.feats_lo - rw.feats : 0, rw.keep + n * (int64_t)s, st));
+        if (path.ngp) NRF_TRY(launch_hash_ngp_lm(r->desc.hash, psn, n * (int64_t)ni, rw.feats + n * (int64_t)s, rw.cols, rw.feats_lo ? rw.feats_lo - rw.feats : 0, rw.keep + n * (int64_t)s, st));
         else NRF_TRY(launch_hash_lm(r->desc.hash, psn, n * (int64_t)ni, rw.feats + n * (int64_t)s, rw.cols, rw.keep + n * (int64_t)s, HASH_LM_DEFAULT_VARIANT, st));
-        if (!ngp) r->view.set(rw.feats, rw.cols, rw.keep, rw.src, n, sf);
-        if (geo_reuse) {
+        if (!path.ngp) r->view.set(rw.feats, rw.cols, rw.keep, rw.src, n, sf);
+        if (path.geo_reuse) {
             const int64_t nc = n * (int64_t)s;
-            NRF_TRY(mlp_small_color_from_geo_lm(r->desc.mlp, geo_planes, nc, raw_c, dirs16, dirs_lo, s, rw.keep, nc, raw_cols, st));
-            NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats + nc, rw.feats_lo ? rw.feats_lo + nc : nullptr, rw.cols, dirs16, dirs_lo, ni, rw.keep + nc, n * (int64_t)ni,
-                                              raw_cols + nc * 4, st));
+            NRF_TRY(mlp_small_color_from_geo_lm(r->desc.mlp, pw.geo_planes, nc, cw.raw_c, cw.dirs16, cw.dirs_lo, s, rw.keep, nc, pw.raw_cols, st));
+            NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats + nc, rw.feats_lo ? rw.feats_lo + nc : nullptr, rw.cols, cw.dirs16, cw.dirs_lo, ni, rw.keep + nc, n * (int64_t)ni,
+                                              pw.raw_cols + nc * 4, st));
             if (out->d_raw) {          // the caller wants raw in depth order
-                hipLaunchKernelGGL(k_gather_raw, dim3((unsigned)ceil_div(n * (int64_t)sf, 256)), dim3(256), 0, st, n * (int64_t)sf, rw.src, reinterpret_cast<const float4 *>(raw_cols),
-                                   reinterpret_cast<const float4 *>(raw_cols) + nc, nc, reinterpret_cast<float4 *>(raw_f));
+                hipLaunchKernelGGL(k_gather_raw, dim3((unsigned)ceil_div(n * (int64_t)sf, 256)), dim3(256), 0, st, n * (int64_t)sf, rw.src, reinterpret_cast<const float4 *>(pw.raw_cols),
+                                   reinterpret_cast<const float4 *>(pw.raw_cols) + nc, nc, reinterpret_cast<float4 *>(cw.raw_f));
                 NRF_LAUNCH_CHECK();
-            } else { raw_final = raw_cols; src_final = rw.src; }
-        } else NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats, rw.feats_lo, rw.cols, dirs16, dirs_lo, sf, rw.keep, n * (int64_t)sf, raw_f, st, rw.src));
-    } else NRF_TRY(network(psf, sf, raw_f));                                                                       // :447
+            } else { raw_final = pw.raw_cols; src_final = rw.src; }
+        } else NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats, rw.feats_lo, rw.cols, cw.dirs16, cw.dirs_lo, sf, rw.keep, n * (int64_t)sf, cw.raw_f, st, rw.src));
+    } else NRF_TRY(network(psf, sf, cw.raw_f));                                                                       // :447
     nz.stream = NRF_RNG_NOISE_FINE;
-    float *w_final = out->d_weights ? out->d_weights : nrm_w;
-    NRF_TRY(launch_raw2outputs(raw_final, z_f, d_rays + 3, ray_stride, n, sf, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
+    float *w_final = out->d_weights ? out->d_weights : cw.nrm_w;
+    NRF_TRY(launch_raw2outputs(raw_final, cw.z_f, d_rays + 3, ray_stride, n, sf, c, 3, p->white_bkgr, out->d_rgb, out->d_disp, out->d_acc,
                                w_final, out->d_depth, nz, st, fastc, src_final, raw2_final, split_final, d_flag));     // :448
-    return p->normals ? normals_tail(psf, w_final, raw_f) : NRF_OK;
+    return p->normals ? normals_tail(psf, w_final, cw.raw_f) : NRF_OK;
 }
 
 }  // namespace nrf
@@ -849,13 +900,30 @@ int nrf_renderer_set_lanes(nrf_renderer *r, int lanes)
     return NRF_OK;
 }
 
+// The workspace of a Chunk loop: one slice of a whole chunk per lane (L lanes of lc rays), or the single-stream loop's one chunk (L = 0, lane[0]).
+struct BatchWs {
+    int L;
+    int64_t lc;
+    size_t part;                    // bytes of one slice: rays_ws_bytes of the largest chunk the loop cuts
+    char *lane[Lanes::MAX];
+    size_t rest;                    // the caller's bytes from lane[0] on (an F32 re-render may use all of them)
+};
+static BatchWs batchify_layout(Bump &b, const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p, int normals)
+{
+    BatchWs w{};
+    const int lanes = lanes_for(r);
+    w.lc = lane_chunk(n, chunk, lanes);
+    w.L = w.lc > 0 && w.lc < n ? lanes : 0;
+    w.part = rays_ws_bytes(r, w.L ? w.lc : (n < chunk ? n : (int64_t)chunk), p, normals);
+    const size_t first = align_up(b.off, 256);          // where lane[0] starts
+    for (int k = 0; k < (w.L ? w.L : 1); k++) w.lane[k] = b.take<char>(w.part);
+    w.rest = b.cap > first ? b.cap - first : 0;
+    return w;
+}
 static size_t batchify_ws_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p, int normals)
 {
     if (!r || !p || chunk <= 0) return 0;
-    const int lanes = lanes_for(r);
-    const int64_t lc = lane_chunk(n, chunk, lanes);
-    if (lc > 0 && lc < n) return (size_t)lanes * align_up(rays_ws_bytes(r, lc, p, normals), 256);
-    return rays_ws_bytes(r, n < chunk ? n : (int64_t)chunk, p, normals);
+    return measure([&](Bump &b) { batchify_layout(b, r, n, chunk, p, normals); });
 }
 size_t nrf_batchify_rays_workspace_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p) { return batchify_ws_bytes(r, n, chunk, p, 0); }
 size_t nrf_batchify_rays_normals_workspace_bytes(const nrf_renderer *r, int64_t n, int chunk, const nrf_render_params *p, int bits)
@@ -872,12 +940,12 @@ int nrf_set_render_lanes(int lanes)
     return NRF_OK;
 }
 
-static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const RenderParamsX *p, const float *d_t,
-                         const float *d_u, const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, void *stream)
+// bw: batchify_layout carved from the caller's workspace and checked by the entry
+static int batchify_run(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const RenderParamsX *p, const float *d_t,
+                        const float *d_u, const RenderOutputsX *out, const BatchWs &bw, void *stream)
 {
-    NRF_TRY(normals_check(r, p, out, "nrf_batchify_rays"));
-    NRF_CHECK_ARG(chunk > 0 && n >= 0, "nrf_batchify_rays: Chunk must be positive");
-    NRF_CHECK_ARG(p->overflow_policy >= NRF_OVERFLOW_AUTO && p->overflow_policy <= NRF_OVERFLOW_IGNORE, "nrf_batchify_rays: overflow_policy %d is not an NRF_OVERFLOW_* value", p->overflow_policy);
+    void *const d_workspace = bw.lane[0];
+    const size_t workspace_bytes = bw.rest;          // (the F32 re-render's)
     const int s = p->n_samples, sf = p->n_samples + p->n_importance, so = p->n_importance > 0 ? sf : s;
     const int c = r->desc.mlp->out_dims;
     RenderParamsX q = *p;
@@ -906,10 +974,9 @@ static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_str
             return NRF_OK;
         });
     };
-    const int L = lanes_for(r);
-    const int64_t lc = lane_chunk(n, chunk, L);
-    const size_t part = lc > 0 && lc < n ? align_up(rays_ws_bytes(r, lc, p, p->normals), 256) : 0;
-    if (part > 0 && (size_t)L * part <= workspace_bytes && d_workspace) {
+    const int L = bw.L;
+    const int64_t lc = bw.lc;
+    if (L > 0) {
         // fork from the caller's stream, each chunk on the least-loaded lane in that lane's slice of the workspace, join
         hipStream_t st = as_stream(stream), lane[Lanes::MAX];
         hipEvent_t fork = nullptr, done[Lanes::MAX];
@@ -944,7 +1011,7 @@ static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_str
             if (m > rem) m = rem;
             q.ray_base = p->ray_base + i;
             const RenderOutputsX o = slice_outputs(*out, i, s, so, sf, c);
-            rc = render_rays_impl(r, d_rays + i * ray_stride, ray_stride, m, &q, d_t, d_u, &o, static_cast<char *>(d_workspace) + (size_t)k * part, part, lane[k], flag_of(done_chunks.size()));
+            rc = render_rays_impl(r, d_rays + i * ray_stride, ray_stride, m, &q, d_t, d_u, &o, bw.lane[k], bw.part, lane[k], flag_of(done_chunks.size()));
             done_chunks.push_back({i, m});
             given[k] += m;
             i += m;
@@ -957,11 +1024,30 @@ static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_str
         const int64_t m = n - i < chunk ? n - i : (int64_t)chunk;
         q.ray_base = p->ray_base + i;
         const RenderOutputsX o = slice_outputs(*out, i, s, so, sf, c);
-        NRF_TRY(render_rays_impl(r, d_rays + i * ray_stride, ray_stride, m, &q, d_t, d_u, &o, d_workspace, workspace_bytes, stream, flag_of(done_chunks.size())));
+        NRF_TRY(render_rays_impl(r, d_rays + i * ray_stride, ray_stride, m, &q, d_t, d_u, &o, bw.lane[0], bw.part, stream, flag_of(done_chunks.size())));
         done_chunks.push_back({i, m});
     }
     if (done_chunks.size() != 1) r->view.drop();
     return settle();
+}
+
+// the argument checks of the Chunk loop's entries (who: the entry), before its workspace is carved
+static int batchify_check(const nrf_renderer *r, int64_t n, int chunk, const RenderParamsX *p, const RenderOutputsX *out, const char *who)
+{
+    NRF_TRY(normals_check(r, p, out, who));
+    NRF_CHECK_ARG(chunk > 0 && n >= 0, "%s: Chunk must be positive", who);
+    NRF_CHECK_ARG(p->overflow_policy >= NRF_OVERFLOW_AUTO && p->overflow_policy <= NRF_OVERFLOW_IGNORE, "%s: overflow_policy %d is not an NRF_OVERFLOW_* value", who, p->overflow_policy);
+    return NRF_OK;
+}
+
+static int batchify_impl(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const RenderParamsX *p, const float *d_t,
+                         const float *d_u, const RenderOutputsX *out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_TRY(batchify_check(r, n, chunk, p, out, "nrf_batchify_rays"));
+    Bump bump(d_workspace, workspace_bytes);
+    const BatchWs bw = batchify_layout(bump, r, n, chunk, p, p->normals);
+    NRF_TRY(ws_check(bump, batchify_ws_bytes(r, n, chunk, p, p->normals), "nrf_batchify_rays"));
+    return batchify_run(r, d_rays, ray_stride, n, chunk, p, d_t, d_u, out, bw, stream);
 }
 
 int nrf_batchify_rays(const nrf_renderer *r, const float *d_rays, int ray_stride, int64_t n, int chunk, const nrf_render_params *p, const float *d_t,
@@ -995,11 +1081,23 @@ extern "C" NRF_API int nrf_renderer_last_features(const nrf_renderer *r, const v
 
 extern "C" int nrf_view_check(const nrf_view *v, const char *who);
 
+// a view's workspace: its rays (unless the caller keeps them: d_rays_out) and the Chunk loop's
+struct RowsWs {
+    float *rays;
+    BatchWs batch;
+};
+static RowsWs rows_layout(Bump &b, const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, int normals, float *d_rays_out)
+{
+    RowsWs w;
+    const int64_t n = (int64_t)v->rows * v->w;
+    w.rays = d_rays_out ? d_rays_out : b.take<float>((size_t)n * (v->use_viewdirs ? 11 : 8));
+    w.batch = batchify_layout(b, r, n, v->chunk, p, normals);
+    return w;
+}
 static size_t rows_ws_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, int normals)
 {
     if (!r || !v || !p || v->chunk <= 0 || v->rows < 0 || v->w <= 0) return 0;
-    const int64_t n = (int64_t)v->rows * v->w;
-    return align_up((size_t)n * (v->use_viewdirs ? 11 : 8) * sizeof(float), 256) + 256 + batchify_ws_bytes(r, n, v->chunk, p, normals);
+    return measure([&](Bump &b) { rows_layout(b, r, v, p, normals, nullptr); });
 }
 size_t nrf_render_rows_workspace_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p) { return rows_ws_bytes(r, v, p, 0); }
 size_t nrf_render_rows_normals_workspace_bytes(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, int bits) { return rows_ws_bytes(r, v, p, bits); }
@@ -1015,17 +1113,14 @@ static int render_rows_impl(const nrf_renderer *r, const nrf_view *v, const Rend
     const int64_t n = (int64_t)v->rows * v->w;
     if (n == 0) return nrf_view_rays(v, nullptr, d_near_far, stream);        // an empty tile: only Near / Far (= +inf / -inf) are defined
     const int stride = v->use_viewdirs ? 11 : 8;
-    if (workspace_bytes < rows_ws_bytes(r, v, p, p->normals)) {
-        set_error("nrf_render_rows: workspace %zu < %zu bytes", workspace_bytes, rows_ws_bytes(r, v, p, p->normals));
-        return NRF_ERR_WORKSPACE;
-    }
+    NRF_TRY(batchify_check(r, n, v->chunk, p, out, "nrf_render_rows"));
     Bump bump(d_workspace, workspace_bytes);
-    float *rays = d_rays_out ? d_rays_out : bump.take<float>((size_t)n * stride);
-    void *ws = bump.take<char>(0);
-    NRF_TRY(nrf_view_rays(v, rays, d_near_far, stream));                                                          // :541-583, :602-603
+    const RowsWs w = rows_layout(bump, r, v, p, p->normals, d_rays_out);
+    NRF_TRY(ws_check(bump, rows_ws_bytes(r, v, p, p->normals), "nrf_render_rows"));
+    NRF_TRY(nrf_view_rays(v, w.rays, d_near_far, stream));                                                        // :541-583, :602-603
     RenderParamsX q = *p;
     q.ray_base = p->ray_base + (int64_t)v->row0 * v->w;
-    return batchify_impl(r, rays, stride, n, v->chunk, &q, d_t, d_u, out, ws, workspace_bytes - bump.off, stream);   // :586-590
+    return batchify_run(r, w.rays, stride, n, v->chunk, &q, d_t, d_u, out, w.batch, stream);                      // :586-590
 }
 
 int nrf_render_rows(const nrf_renderer *r, const nrf_view *v, const nrf_render_params *p, const float *d_t, const float *d_u, const nrf_render_outputs *out,
@@ -1067,34 +1162,47 @@ static bool density_classic_exact(const nrf_renderer *r)
            mlp_nerf_sigma_f32_available(r->desc.mlp);
 }
 
+// renderer_density's workspace, by the kernels that serve the renderer
+struct DensityWs {
+    FastWs sig;          // hash-exact: the sigma path's own scratch
+    float *raw;          // otherwise: the network's rows [p, c]
+    __half *dirs;        // classic-exact: one direction row
+    float *vd;           // generic: one view direction, and the network's scratch
+    NetWs net;
+};
+static DensityWs density_layout(Bump &b, const nrf_renderer *r, int64_t p)
+{
+    DensityWs w{};
+    if (density_hash_exact(r)) { w.sig = fast_layout(b, r, p); return w; }
+    w.raw = b.take<float>((size_t)p * r->desc.mlp->out_dims);
+    if (density_classic_exact(r)) w.dirs = b.take<__half>(32);
+    else { w.vd = b.take<float>(3); w.net = network_layout(b, r, p, NRF_PREC_F32); }
+    return w;
+}
 size_t renderer_density_ws_bytes(const nrf_renderer *r, int64_t p)
 {
-    if (density_hash_exact(r)) return align_up((size_t)p * 16 * sizeof(__half2), 256) * 2 + align_up((size_t)p, 256) + 1024;          // run_sigma_fast's layout
-    if (density_classic_exact(r)) return align_up((size_t)p * 4 * sizeof(float), 256) + align_up(32 * sizeof(__half), 256) + 1024;       // raw rows + one direction row
-    return align_up((size_t)p * r->desc.mlp->out_dims * sizeof(float), 256) + align_up(3 * sizeof(float), 256) + network_ws_bytes(r, p, NRF_PREC_F32) + 1024;
+    return measure([&](Bump &b) { density_layout(b, r, p); });
 }
 
 int renderer_density(const nrf_renderer *r, const float *pts, int64_t p, float *sigma, void *ws, size_t ws_bytes, hipStream_t st)
 {
     if (p <= 0) return NRF_OK;
-    if (ws_bytes < renderer_density_ws_bytes(r, p)) { set_error("renderer_density: workspace %zu < %zu bytes", ws_bytes, renderer_density_ws_bytes(r, p)); return NRF_ERR_WORKSPACE; }
-    // hash grid + NeRFSmall: level-major encode + mlp_small_sigma_f32_lm, keep mask applied by the kernel (the coarse pass's sigma, equal to NRF_PREC_F32's)
-    if (density_hash_exact(r)) return run_sigma_fast(r, PointSource{pts, nullptr, nullptr, 0, 1}, p, 1, sigma, ws, ws_bytes, st);
     Bump bump(ws, ws_bytes);
+    const DensityWs w = density_layout(bump, r, p);
+    NRF_TRY(ws_check(bump, renderer_density_ws_bytes(r, p), "renderer_density"));
+    // hash grid + NeRFSmall: level-major encode + mlp_small_sigma_f32_lm, keep mask applied by the kernel (the coarse pass's sigma, equal to NRF_PREC_F32's)
+    if (density_hash_exact(r)) return run_sigma_fast(r, PointSource{pts, nullptr, nullptr, 0, 1}, p, 1, sigma, w.sig, st);
     const int c = r->desc.mlp->out_dims;
-    float *raw = bump.take<float>((size_t)p * c);
+    float *raw = w.raw;
     if (density_classic_exact(r)) {
         // the classic coarse kernel: exact-fp32 density branch; its fused split-precision colour tail reads one zero direction row (all points are "ray 0": s = p) and
         // its rgb columns are dropped
-        __half *dirs = bump.take<__half>(32);
-        NRF_HIP(hipMemsetAsync(dirs, 0, 32 * sizeof(__half), st));
-        NRF_TRY(mlp_nerf_exact_coarse(r->desc.mlp, pts, nullptr, 0, nullptr, (int)p, dirs, nullptr, p, raw, st));
+        NRF_HIP(hipMemsetAsync(w.dirs, 0, 32 * sizeof(__half), st));
+        NRF_TRY(mlp_nerf_exact_coarse(r->desc.mlp, pts, nullptr, 0, nullptr, (int)p, w.dirs, nullptr, p, raw, st));
     } else {
         // any other renderer: the F32 network over the points (one ray of p samples: a single zero view direction; sigma does not read it)
-        float *vd = bump.take<float>(3);
-        NRF_HIP(hipMemsetAsync(vd, 0, 3 * sizeof(float), st));
-        void *nws = bump.take<char>(0);
-        NRF_TRY(run_network(r, PointSource{pts, nullptr, nullptr, 0, (int)p}, r->in_views > 0 ? vd : nullptr, 3, 1, (int)p, NRF_PREC_F32, raw, nws, ws_bytes - bump.off, st));
+        NRF_HIP(hipMemsetAsync(w.vd, 0, 3 * sizeof(float), st));
+        NRF_TRY(run_network(r, PointSource{pts, nullptr, nullptr, 0, (int)p}, r->in_views > 0 ? w.vd : nullptr, 3, 1, (int)p, NRF_PREC_F32, raw, w.net, st));
     }
     hipLaunchKernelGGL(k_take_column, dim3((unsigned)ceil_div(p, 256)), dim3(256), 0, st, p, c, 3, raw, sigma);
     NRF_LAUNCH_CHECK();

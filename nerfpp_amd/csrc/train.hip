@@ -6,6 +6,7 @@
 //   Adam(lr, betas (0.9, 0.99), eps 1e-15)      :539               nrf_adam_step
 // Gradients flow only through the fine pass (z_samples are detached, NeRFRenderer.h:429).
 #include "encode.h"
+#include "workspace.h"
 
 namespace nrf {
 
@@ -824,7 +825,31 @@ int nrf_hash_backward_rays(const nrf_hash *h, const float *d_pts, int64_t n, int
     return NRF_OK;
 }
 
-size_t nrf_hash_backward_packed_workspace_bytes(const nrf_hash *h) { return h ? 1024 + (size_t)nrf_hash_table_elems(h) / 2 * 8 : 0; }
+// workspace of the packed form: a 1 KB head (level masses, the pass's scale) and one 64-bit word per table entry
+struct PackedHead {
+    double mass[64];
+    unsigned char pad[256];
+    float qs[64];
+};
+static_assert(sizeof(PackedHead) == 1024, "the packed form's head is 1 KB");
+struct PackedWs {
+    PackedHead *head;
+    unsigned long long *q;          // [entries]
+};
+static PackedWs packed_layout(Bump &b, const nrf_hash *h)
+{
+    PackedWs w;
+    w.head = b.take<PackedHead>(1);
+    w.q = b.take<unsigned long long>((size_t)(nrf_hash_table_elems(h) / 2));
+    return w;
+}
+size_t nrf_hash_backward_packed_workspace_bytes(const nrf_hash *h)
+{
+    if (!h) return 0;
+    Bump b;
+    packed_layout(b, h);
+    return b.off;          // (to the byte, as before: the words end where they end)
+}
 
 int nrf_hash_backward_rays_packed(const nrf_hash *h, const float *d_pts, int64_t n, int s, const float *d_g_emb, float *d_g_table, void *d_workspace,
                                   size_t workspace_bytes, void *stream)
@@ -832,16 +857,18 @@ int nrf_hash_backward_rays_packed(const nrf_hash *h, const float *d_pts, int64_t
     NRF_CHECK_ARG(h && d_pts && d_g_emb && d_g_table && d_workspace && n >= 0 && s >= 1, "nrf_hash_backward_rays_packed: bad argument");
     NRF_CHECK_ARG(h->desc.mode == NRF_HASH_NGP || h->primes_set, "nrf_hash_backward_rays_packed: CuHashEmbedder-mode grid without primes");
     if (h->desc.n_features != 2) { set_error("nrf_hash_backward_rays_packed: built for 2 features per level (a table entry = one 64-bit word); use nrf_hash_backward_rays"); return NRF_ERR_UNSUPPORTED; }
-    if (workspace_bytes < nrf_hash_backward_packed_workspace_bytes(h)) { set_error("nrf_hash_backward_rays_packed: workspace %zu < %zu bytes", workspace_bytes, nrf_hash_backward_packed_workspace_bytes(h)); return NRF_ERR_WORKSPACE; }
+    Bump bump(d_workspace, workspace_bytes);
+    const PackedWs w = packed_layout(bump, h);
+    NRF_TRY(ws_check(bump, nrf_hash_backward_packed_workspace_bytes(h), "nrf_hash_backward_rays_packed"));
     if ((reinterpret_cast<uintptr_t>(d_workspace) & 255) || (reinterpret_cast<uintptr_t>(d_g_table) & 7)) { set_error("nrf_hash_backward_rays_packed: workspace must be 256-byte, g_table 8-byte aligned"); return NRF_ERR_INVALID_ARG; }
     if (n == 0) return NRF_OK;
     const int L = h->desc.n_levels;
     hipStream_t st = as_stream(stream);
-    double *mass = reinterpret_cast<double *>(d_workspace);                                         // [L] (<= 64 levels = 512 bytes)
-    float *qs = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(d_workspace) + 768);
-    unsigned long long *q = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(d_workspace) + 1024);
+    double *mass = w.head->mass;
+    float *qs = w.head->qs;
+    unsigned long long *q = w.q;
     const int64_t entries = nrf_hash_table_elems(h) / 2;
-    NRF_HIP(hipMemsetAsync(d_workspace, 0, 1024 + (size_t)entries * 8, st));
+    NRF_HIP(hipMemsetAsync(d_workspace, 0, bump.off, st));
     float *qt = reinterpret_cast<float *>(q);                        // the kernel indexes its table in floats: entry e = floats 2e, 2e+1 = word e
     const bool ngp = h->desc.mode == NRF_HASH_NGP;
     // The bound behind the scale is a sum over ALL points of a pass while a typical entry sees a handful, so the resolution relative to one addend
@@ -852,7 +879,7 @@ int nrf_hash_backward_rays_packed(const nrf_hash *h, const float *d_pts, int64_t
         const int64_t nr = (n - r0) < rays_per_group ? (n - r0) : rays_per_group;
         const int64_t p = nr * s;
         const float *gp = d_g_emb + r0 * s * (int64_t)(L * 2), *pp = d_pts + r0 * s * 3;
-        if (r0) NRF_HIP(hipMemsetAsync(mass, 0, 512, st));
+        if (r0) NRF_HIP(hipMemsetAsync(mass, 0, sizeof(w.head->mass), st));
         hipLaunchKernelGGL(k_level_mass, dim3((unsigned)(ceil_div(p, 16) < 2048 ? ceil_div(p, 16) : 2048)), dim3(256), 0, st, p, L, 2, gp, mass, ngp ? pp : (const float *)nullptr,
                            h->params.bbox, (float)h->desc.finest_resolution, p);
         hipLaunchKernelGGL(k_qscale, dim3(1), dim3(1), 0, st, L, ngp ? 0 : 1, mass, qs);
@@ -866,42 +893,48 @@ int nrf_hash_backward_rays_packed(const nrf_hash *h, const float *d_pts, int64_t
     return NRF_OK;
 }
 
-// workspace of the binned form: header (64 KB: mass [passes][L], scale [passes][2]) | gcount [nbins + 1] | start [nbins + 1] | cursor [nbins] | wg_hist | records
+// workspace of the binned form: header (64 KB: mass [passes][L], scale [passes][2]) | overflow counter | side list | gcount [nbins + 1] | start [nbins + 1] |
+// cursor [nbins] | wg_hist | records
 constexpr size_t BIN_HDR = 65536;
-constexpr size_t BIN_OVF_BYTES = 256 + ((size_t)BIN_OVF_PER_LEVEL * NRF_MAX_LEVELS * sizeof(BinOvf) + 255) / 256 * 256;      // counter | side list, behind the header
+struct BinnedWs {
+    int64_t nbins, rays_per_group, nwg;
+    unsigned char *hdr;
+    uint32_t *ovf_count;            // (one word, in a 256-byte piece of its own)
+    BinOvf *ovf;
+    uint32_t *gcount, *start, *cursor, *wg_hist;
+    BinRec *rec;
+};
 // n_rays < 0: the worst case (a whole group of 2^18 points per pass); otherwise the pass never holds more than n_rays rays and the record buffer is sized for that
-static void binned_layout(const nrf_hash *h, int s, int64_t n_rays, int64_t *nbins, int64_t *rays_per_group, int64_t *nwg, size_t *off_hist, size_t *off_rec, size_t *total)
+static BinnedWs binned_layout(Bump &b, const nrf_hash *h, int s, int64_t n_rays)
 {
+    BinnedWs w;
     const int L = h->desc.n_levels;
     const int64_t entries = nrf_hash_table_elems(h) / 2;
-    *nbins = ceil_div(entries, (int64_t)BIN_WORDS);
-    *rays_per_group = (PACKED_GROUP_PTS / s) > 0 ? (PACKED_GROUP_PTS / s) : 1;
-    const int64_t held = (n_rays >= 0 && n_rays < *rays_per_group) ? (n_rays > 0 ? n_rays : 1) : *rays_per_group;      // rays a pass can hold at most
+    w.nbins = ceil_div(entries, (int64_t)BIN_WORDS);
+    w.rays_per_group = (PACKED_GROUP_PTS / s) > 0 ? (PACKED_GROUP_PTS / s) : 1;
+    const int64_t held = (n_rays >= 0 && n_rays < w.rays_per_group) ? (n_rays > 0 ? n_rays : 1) : w.rays_per_group;      // rays a pass can hold at most
     const int64_t threads = held * ((s + BWD_SEG - 1) / BWD_SEG);
-    *nwg = ceil_div(threads, (int64_t)256);
-    size_t o = BIN_HDR + BIN_OVF_BYTES + align_up((size_t)(*nbins + 1) * 4, 256) * 2 + align_up((size_t)*nbins * 4, 256);
-    *off_hist = o;
-    o += align_up((size_t)L * *nwg * BIN_MAX_PER_LEVEL * 4, 256);
-    *off_rec = o;
-    o += (size_t)held * s * 8 * L * sizeof(BinRec);                    // every sample may flush eight records per level
-    *total = o;
+    w.nwg = ceil_div(threads, (int64_t)256);
+    w.hdr = b.take<unsigned char>(BIN_HDR);
+    w.ovf_count = b.take<uint32_t>(64);
+    w.ovf = b.take<BinOvf>((size_t)BIN_OVF_PER_LEVEL * NRF_MAX_LEVELS);
+    w.gcount = b.take<uint32_t>((size_t)w.nbins + 1);
+    w.start = b.take<uint32_t>((size_t)w.nbins + 1);
+    w.cursor = b.take<uint32_t>((size_t)w.nbins);
+    w.wg_hist = b.take<uint32_t>((size_t)L * w.nwg * BIN_MAX_PER_LEVEL);
+    w.rec = b.take<BinRec>((size_t)held * s * 8 * L);                    // every sample may flush eight records per level
+    return w;
+}
+static size_t binned_bytes(const nrf_hash *h, int s, int64_t n_rays)
+{
+    Bump b;
+    binned_layout(b, h, s, n_rays);
+    return b.off;          // (to the byte, as before: the records end where they end)
 }
 
-size_t nrf_hash_backward_binned_workspace_bytes(const nrf_hash *h, int s)
-{
-    if (!h || s < 1) return 0;
-    int64_t nbins, rpg, nwg; size_t oh, orr, total;
-    binned_layout(h, s, -1, &nbins, &rpg, &nwg, &oh, &orr, &total);
-    return total;
-}
+size_t nrf_hash_backward_binned_workspace_bytes(const nrf_hash *h, int s) { return (!h || s < 1) ? 0 : binned_bytes(h, s, -1); }
 
-size_t nrf_hash_backward_binned_workspace_bytes_for(const nrf_hash *h, int64_t n, int s)
-{
-    if (!h || s < 1 || n < 0) return 0;
-    int64_t nbins, rpg, nwg; size_t oh, orr, total;
-    binned_layout(h, s, n, &nbins, &rpg, &nwg, &oh, &orr, &total);
-    return total;
-}
+size_t nrf_hash_backward_binned_workspace_bytes_for(const nrf_hash *h, int64_t n, int s) { return (!h || s < 1 || n < 0) ? 0 : binned_bytes(h, s, n); }
 
 int nrf_hash_backward_rays_binned(const nrf_hash *h, const float *d_pts, int64_t n, int s, const float *d_g_emb, float *d_g_table, void *d_workspace,
                                   size_t workspace_bytes, void *stream)
@@ -910,24 +943,22 @@ int nrf_hash_backward_rays_binned(const nrf_hash *h, const float *d_pts, int64_t
     NRF_CHECK_ARG(h->desc.mode == NRF_HASH_NGP || h->primes_set, "nrf_hash_backward_rays_binned: CuHashEmbedder-mode grid without primes");
     if (h->desc.n_features != 2) { set_error("nrf_hash_backward_rays_binned: built for 2 features per level (a table entry = one 64-bit word); use nrf_hash_backward_rays"); return NRF_ERR_UNSUPPORTED; }
     if (h->desc.log2_hashmap_size > 19) { set_error("nrf_hash_backward_rays_binned: a level of 2^%d words touches more than %d bins; use nrf_hash_backward_rays_packed", h->desc.log2_hashmap_size, BIN_MAX_PER_LEVEL); return NRF_ERR_UNSUPPORTED; }
-    int64_t nbins, rays_per_group, nwg; size_t off_hist, off_rec, total;
-    binned_layout(h, s, n, &nbins, &rays_per_group, &nwg, &off_hist, &off_rec, &total);       // sized for THIS call's rays: any workspace of nrf_hash_backward_binned_workspace_bytes[_for] fits
-    if (workspace_bytes < total) { set_error("nrf_hash_backward_rays_binned: workspace %zu < %zu bytes", workspace_bytes, total); return NRF_ERR_WORKSPACE; }
+    Bump bump(d_workspace, workspace_bytes);
+    const BinnedWs w = binned_layout(bump, h, s, n);       // sized for THIS call's rays: any workspace of nrf_hash_backward_binned_workspace_bytes[_for] fits
+    NRF_TRY(ws_check(bump, binned_bytes(h, s, n), "nrf_hash_backward_rays_binned"));
+    const int64_t nbins = w.nbins, rays_per_group = w.rays_per_group;
     if ((reinterpret_cast<uintptr_t>(d_workspace) & 255) || (reinterpret_cast<uintptr_t>(d_g_table) & 7)) { set_error("nrf_hash_backward_rays_binned: workspace must be 256-byte, g_table 8-byte aligned"); return NRF_ERR_INVALID_ARG; }
     if (n == 0) return NRF_OK;
     const int L = h->desc.n_levels;
     hipStream_t st = as_stream(stream);
-    unsigned char *ws = reinterpret_cast<unsigned char *>(d_workspace);
+    unsigned char *ws = w.hdr;
     // The level masses and scales of ALL passes come first, in two launches (a launch of 2^18 points is latency-bound: 30 us for 33 MB, thirteen of them per
     // training step, plus the scale kernel and a memset per pass: docs/history/profiles/round4/r5c_*); same per-pass sums, same scales, same table gradient bits.
     const int64_t pass_cap = (int64_t)(BIN_HDR / ((size_t)L * 8 + 8));                          // passes whose masses and scales the header holds
     double *mass = reinterpret_cast<double *>(ws);
     float *qs = reinterpret_cast<float *>(ws + (size_t)pass_cap * L * 8);
-    const size_t cnt_bytes = align_up((size_t)(nbins + 1) * 4, 256);
-    unsigned char *cb = ws + BIN_HDR + BIN_OVF_BYTES;
-    uint32_t *gcount = reinterpret_cast<uint32_t *>(cb), *start = reinterpret_cast<uint32_t *>(cb + cnt_bytes), *cursor = reinterpret_cast<uint32_t *>(cb + 2 * cnt_bytes);
-    BinSink sink{reinterpret_cast<uint32_t *>(ws + off_hist), gcount, cursor, reinterpret_cast<BinRec *>(ws + off_rec),
-                 reinterpret_cast<uint32_t *>(ws + BIN_HDR), reinterpret_cast<BinOvf *>(ws + BIN_HDR + 256), (uint32_t)(BIN_OVF_PER_LEVEL * L)};
+    uint32_t *gcount = w.gcount, *start = w.start, *cursor = w.cursor;
+    BinSink sink{w.wg_hist, gcount, cursor, w.rec, w.ovf_count, w.ovf, (uint32_t)(BIN_OVF_PER_LEVEL * L)};
     const int64_t entries = nrf_hash_table_elems(h) / 2;
     const bool ngp = h->desc.mode == NRF_HASH_NGP;
     static PerDeviceOnce attr_set;          // idempotent one-time setup per device (common.h)
@@ -944,7 +975,7 @@ int nrf_hash_backward_rays_binned(const nrf_hash *h, const float *d_pts, int64_t
             // leaves them zeroed
             const int64_t rays_left = n - r0, passes = ceil_div(rays_left, rays_per_group) < pass_cap ? ceil_div(rays_left, rays_per_group) : pass_cap;
             const int64_t pts_here = (rays_left < passes * rays_per_group ? rays_left : passes * rays_per_group) * s;
-            NRF_HIP(hipMemsetAsync(ws, 0, pass == 0 ? BIN_HDR + BIN_OVF_BYTES + cnt_bytes : BIN_HDR, st));
+            NRF_HIP(hipMemsetAsync(ws, 0, pass == 0 ? (size_t)(reinterpret_cast<unsigned char *>(start) - ws) : BIN_HDR, st));          // first: header, overflow list and bin counts
             const int64_t blocks = ceil_div(group_pts < pts_here ? group_pts : pts_here, 16);
             hipLaunchKernelGGL(k_level_mass, dim3((unsigned)(blocks < 2048 ? blocks : 2048), (unsigned)passes), dim3(256), 0, st, pts_here, L, 2, gp, mass, ngp ? pp : (const float *)nullptr,
                                h->params.bbox, (float)h->desc.finest_resolution, group_pts);

@@ -564,6 +564,26 @@ NRF_API int nrf_isosurface_emit(const float *d_sigma, int nx, int ny, int nz, co
                                 int64_t n_verts, int64_t n_tris, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Connected components (components.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* Which faces of a mesh, which set points of a lattice belong together.  A lock-free union-find on the device whose result is
+ * canonical: components are numbered 0 .. K-1 in ascending order of their smallest member index (vertex id / linear lattice index), so two runs, and any correct
+ * implementation, give the same array.  Both entries SYNCHRONISE the stream once to return *n_components (as nrf_isosurface_count does for its counts).
+ *   nrf_mesh_components: d_faces [F,3] int32 over V vertices -> d_labels [V] int32: vertices that share a face share a label, a vertex used by no face gets -1; the
+ *   component of a face is the label of its first vertex.  Degenerate ((a,a,b), (a,a,a)) and duplicate faces are legal; 0 <= V, F < 2^31.  A vertex index outside
+ *   [0, V) gives NRF_ERR_INVALID_ARG: such a face is skipped (nothing is read or written at the index) and the labels are unspecified.
+ *   nrf_lattice_components: d_mask [nz][ny][nx] uint8 (x fastest, non-zero = set) -> d_labels of the same shape, -1 where the mask is 0.  connectivity 6 (faces),
+ *   26 (faces, edges, corners) or 14: the 7 edge types of the isosurface's Kuhn split, (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), and their negatives
+ *   -- the components of sigma > iso under 14 are exactly the solids whose surfaces nrf_isosurface_* emits.  Any other value is NRF_ERR_INVALID_ARG.  Neighbours
+ *   never wrap across a row or a plane; nx, ny, nz >= 1, nx * ny * nz < 2^31. */
+NRF_API size_t nrf_mesh_components_workspace_bytes(int64_t n_verts, int64_t n_tris);
+NRF_API int nrf_mesh_components(const int32_t *d_faces, int64_t n_verts, int64_t n_tris, int32_t *d_labels, int64_t *n_components, void *d_workspace,
+                                size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_lattice_components_workspace_bytes(int nx, int ny, int nz);
+NRF_API int nrf_lattice_components(const uint8_t *d_mask, int nx, int ny, int nz, int connectivity, int32_t *d_labels, int64_t *n_components, void *d_workspace,
+                                   size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Density gradient (normals.hip; the reference's calculate_normals, never finished there)
  * ------------------------------------------------------------------------------------------- */
 /* d_sigma [p] (may be NULL) = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at d_pts [p,3], bit for bit (keep mask of NeRFRenderer.h:187-188 included: it writes

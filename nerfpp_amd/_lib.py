@@ -174,6 +174,10 @@ _ABI = """
     nrf_isosurface_workspace_bytes(iii)->z
     nrf_isosurface_count(piiipfppppzp)
     nrf_isosurface_emit(piiipfpppllpzp)
+    nrf_mesh_components_workspace_bytes(ll)->z
+    nrf_mesh_components(pllpppzp)
+    nrf_lattice_components_workspace_bytes(iii)->z
+    nrf_lattice_components(piiiipppzp)
     nrf_density_grad_workspace_bytes(pl)->z
     nrf_density_grad(pplpppzp)
     nrf_render_rays_workspace_bytes(plp)->z

@@ -14,6 +14,7 @@
 //                    id + popcount of the origin's lower mask bits
 // Every output position comes from an integer prefix sum: no atomics decide an order, so two runs give the same arrays.
 #include "common.h"
+#include "scan.h"
 #include "workspace.h"
 
 #include <climits>
@@ -50,25 +51,6 @@ __device__ __forceinline__ void coords(const Grid &g, int64_t i, int &x, int &y,
 }
 
 __device__ __forceinline__ float lattice_coord(const Grid &g, int axis, int i) { return g.bmin[axis] + (float)i * g.step[axis]; }
-
-// exclusive scan over the block (Hillis-Steele in LDS); `total` = the block's sum
-template <class T, int B>
-__device__ __forceinline__ T block_exclusive_scan(T v, T *sh, T &total)
-{
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < B; off <<= 1) {
-        const T t = tid >= off ? sh[tid - off] : T(0);
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    total = sh[B - 1];
-    const T incl = sh[tid];
-    __syncthreads();
-    return incl - v;
-}
 
 // inside bits of the 8 corners of the cell at (x, y, z) (corners outside the lattice: 0) and which corners exist
 __device__ __forceinline__ void cell_corners(const Grid &g, const float *__restrict__ f, int64_t i, int x, int y, int z, float iso, unsigned &inside, unsigned &exists)

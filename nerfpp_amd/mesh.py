@@ -1,4 +1,5 @@
-"""Mesh export: DensityGrid, Isosurface, ExtractMesh and SavePLY over the C ABI (include/nerfpp_hip.h, mesh.hip).
+"""Mesh export: DensityGrid, Isosurface, ExtractMesh, MeshComponents, FilterComponents and SavePLY over the C ABI (include/nerfpp_hip.h, mesh.hip,
+components.hip).
 
 The reference has no mesh export; the names follow the mirror's style.  The density lattice is the exact-fp32 sigma of the renderer's network
 (== RunNetwork(..., NRF_PREC_F32)[..., 3] bit for bit); the isosurface is marching tetrahedra on the Kuhn split of each cell, in an order fixed by integer
@@ -112,16 +113,21 @@ def _safe_normalize(v, eps=1e-8):
     return v / torch.linalg.vector_norm(v, dim=-1, keepdim=True).clamp_min(eps)
 
 
-def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, precision=L.NRF_PREC_F32, normals="lattice"):
+def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, precision=L.NRF_PREC_F32, normals="lattice", keep_largest=None,
+                min_component_faces=0):
     """DensityGrid -> Isosurface -> per-vertex colour: sigmoid of RunNetwork's rgb at the vertex seen along -normal (a ray hitting the surface head-on), in chunks.
     normals="lattice": the isosurface's central-difference normals; "field": -safe_normalize(DensityGradient(vertices)), the field's own analytic normal
-    (also the colour's view direction)."""
+    (also the colour's view direction).  keep_largest / min_component_faces: FilterComponents on the bare isosurface, before the field normals and the colours,
+    so a dropped floater costs no network evaluation."""
     if normals not in ("lattice", "field"):
         raise L.NrfError(f"ExtractMesh: normals must be 'lattice' or 'field', got {normals!r}")
     bb = _bbox(renderer, bbox)
     sigma = DensityGrid(renderer, bb, resolution)
     verts, faces, lattice_normals = Isosurface(sigma, bb, threshold)
     del sigma
+    if keep_largest is not None or min_component_faces > 0:
+        kept = FilterComponents(Mesh(verts, faces, lattice_normals), keep_largest, min_component_faces)
+        verts, faces, lattice_normals = kept.Vertices, kept.Faces, kept.Normals
     normals = lattice_normals if normals == "lattice" else -_safe_normalize(DensityGradient(renderer, verts)[1])
     rgb = None
     if colors:
@@ -131,6 +137,59 @@ def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, pre
             raw = renderer.RunNetwork(v[:, None, :], (-normals[i:i + COLOR_CHUNK]).contiguous(), precision)
             rgb[i:i + COLOR_CHUNK] = torch.sigmoid(raw[:, 0, :3])          # RawToOutputs's rgb (NeRFRenderer.h:250)
     return Mesh(verts, faces, normals, rgb)
+
+
+def _submesh(mesh, keep_faces, relevancy=None):
+    """The sub-mesh of the faces keep_faces [F] bool: the vertices they use in ascending original order, faces re-indexed; normals, colours and `relevancy` [V, ...]
+    follow their vertices.  Any torch device."""
+    faces = mesh.Faces.to(torch.int64)[keep_faces]
+    used = torch.zeros((mesh.Vertices.shape[0],), dtype=torch.bool, device=faces.device)
+    used[faces.reshape(-1)] = True
+    old = torch.nonzero(used).reshape(-1)
+    remap = torch.full((used.shape[0],), -1, dtype=torch.int64, device=faces.device)
+    remap[old] = torch.arange(old.numel(), dtype=torch.int64, device=faces.device)
+
+    def sub(t):
+        return None if t is None else t[old]
+    return Mesh(mesh.Vertices[old], remap[faces].to(mesh.Faces.dtype), mesh.Normals[old], sub(mesh.Colors), sub(relevancy))
+
+
+def MeshComponents(mesh_or_faces, n_verts=None):
+    """nrf_mesh_components: (labels [V] int32, K) of a Mesh or of faces [F, 3] over n_verts vertices (default: the largest index + 1).  Vertices that share a face
+    share a label, a vertex used by no face gets -1; components are numbered 0 .. K-1 by their smallest vertex id, so the labels are the same on every run.  The
+    component of a face is the label of its first vertex.  An index outside [0, n_verts) raises."""
+    if isinstance(mesh_or_faces, Mesh):
+        faces, v = mesh_or_faces.Faces, int(mesh_or_faces.Vertices.shape[0]) if n_verts is None else int(n_verts)
+    else:
+        faces = torch.as_tensor(mesh_or_faces)
+        v = (int(faces.max()) + 1 if faces.numel() else 0) if n_verts is None else int(n_verts)
+    dev = faces.device if faces.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    faces = faces.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    lib = L.lib()
+    labels = torch.empty((v,), device=dev, dtype=torch.int32)
+    ws = torch.empty((max(1, int(lib.nrf_mesh_components_workspace_bytes(v, faces.shape[0]))),), device=dev, dtype=torch.uint8)
+    k = C.c_int64()
+    L.check(lib.nrf_mesh_components(_ptr(faces), v, faces.shape[0], _ptr(labels), C.byref(k), _ptr(ws), ws.numel(), _stream()))
+    return labels, int(k.value)
+
+
+def FilterComponents(mesh, keep_largest=None, min_faces=0, labels=None):
+    """The sub-mesh of whole connected components; the size of a component is its face count.  keep_largest=k keeps the k largest (ties: the lower label first),
+    min_faces drops the smaller ones; given both, a component must pass both.  Kept vertices stay in ascending original order, faces are re-indexed, normals,
+    colours and relevancy follow their vertices.  labels: MeshComponents(mesh)[0] when not given; with labels the function runs on any torch device and calls no
+    kernel of the library."""
+    labels = MeshComponents(mesh)[0] if labels is None else torch.as_tensor(labels)
+    labels = labels.to(device=mesh.Faces.device, dtype=torch.int64)
+    face_label = labels[mesh.Faces[:, 0].to(torch.int64)]
+    sizes = torch.bincount(face_label, minlength=int(labels.max()) + 1 if labels.numel() else 0)
+    keep = sizes >= int(min_faces)
+    if keep_largest is not None:
+        # stable descending sort of the sizes (in label order): equal sizes keep the lower label first
+        top = torch.sort(sizes, descending=True, stable=True).indices[:max(int(keep_largest), 0)]
+        largest = torch.zeros_like(keep)
+        largest[top] = True
+        keep &= largest
+    return _submesh(mesh, keep[face_label], mesh.Relevancy)
 
 
 def SavePLY(path, mesh):

@@ -1,4 +1,5 @@
-"""LeRF relevancy in 3D: PointRelevancy, RelevancyGrid, LocateQuery, VertexRelevancy and SegmentMesh over the C ABI (include/nerfpp_hip.h, lerf_query.hip).
+"""LeRF relevancy in 3D: PointRelevancy, RelevancyGrid, LocateQuery, VertexRelevancy, SegmentMesh, LatticeComponents and LocateObject over the C ABI
+(include/nerfpp_hip.h, lerf_query.hip, components.hip).
 
 The reference reads its language field through rendered images only (LeRFRenderer::Render -> Relevancy).  Here a point set, a lattice or a mesh is labelled by
 Relevancy(normalize(le(x)), positive, negatives) of every point -- the formula of nrf_lerf_relevancy -- with LeRF's own density sigma_le beside it.  The fused
@@ -10,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .mesh import Mesh, _resolution
+from .mesh import Mesh, _lattice_points_at, _resolution, _submesh
 from .modules import _ptr, _stream, _dev_f32
 
 
@@ -99,7 +100,6 @@ def LocateQuery(lerf_renderer, bbox=None, resolution=128, sigma_threshold=1.0, t
         idx = idx[order]
     else:
         idx = idx[:0]
-    from .mesh import _lattice_points_at
     return dict(positions=_lattice_points_at(bb, nx, ny, nz, idx), relevancy=r[idx], indices=idx.to(torch.int64))
 
 
@@ -115,13 +115,47 @@ def SegmentMesh(mesh, vertex_relevancy, threshold):
     keep_v = rel.reshape(-1, 2)[:, 0] >= threshold
     faces = mesh.Faces.to(torch.int64)
     keep_f = keep_v[faces].all(dim=1) if faces.numel() else torch.zeros((0,), dtype=torch.bool, device=faces.device)
-    faces = faces[keep_f]
-    used = torch.zeros_like(keep_v)
-    used[faces.reshape(-1)] = True
-    old = torch.nonzero(used).reshape(-1)
-    remap = torch.full((keep_v.shape[0],), -1, dtype=torch.int64, device=faces.device)
-    remap[old] = torch.arange(old.numel(), dtype=torch.int64, device=faces.device)
+    return _submesh(mesh, keep_f, rel.reshape(-1, 2))
 
-    def sub(t):
-        return None if t is None else t[old]
-    return Mesh(mesh.Vertices[old], remap[faces].to(mesh.Faces.dtype), mesh.Normals[old], sub(mesh.Colors), rel.reshape(-1, 2)[old])
+
+def LatticeComponents(mask, connectivity=14):
+    """nrf_lattice_components: (labels [nz, ny, nx] int32, K) of the set (non-zero) points of mask [nz, ny, nx] (x fastest); -1 where the mask is 0.  connectivity 6,
+    14 (the isosurface's Kuhn edges: the components of sigma > iso are the solids whose surfaces Isosurface emits) or 26; neighbours never wrap.  Components are
+    numbered 0 .. K-1 by their smallest flat index, so the labels are the same on every run."""
+    m = torch.as_tensor(mask)
+    if m.dim() != 3:
+        raise L.NrfError(f"LatticeComponents: mask must be [nz, ny, nx], got {tuple(m.shape)}")
+    dev = m.device if m.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    m = (m.to(dev) != 0).to(torch.uint8).contiguous()
+    nz, ny, nx = (int(v) for v in m.shape)
+    lib = L.lib()
+    labels = torch.empty((nz, ny, nx), device=dev, dtype=torch.int32)
+    ws = torch.empty((max(1, int(lib.nrf_lattice_components_workspace_bytes(nx, ny, nz))),), device=dev, dtype=torch.uint8)
+    k = C.c_int64()
+    L.check(lib.nrf_lattice_components(_ptr(m), nx, ny, nz, int(connectivity), _ptr(labels), C.byref(k), _ptr(ws), ws.numel(), _stream()))
+    return labels, int(k.value)
+
+
+def LocateObject(lerf_renderer, bbox=None, resolution=128, sigma_threshold=1.0, relevancy_threshold=0.5, positive_id=0, precision=L.NRF_PREC_F16_SPLIT,
+                 connectivity=14):
+    """The region the positive prompt points at, not just its best point: of the lattice points of RelevancyGrid with sigma_le >= sigma_threshold and
+    rel[..., 0] >= relevancy_threshold (0.5: the positive prompt beats every negative in the pairwise softmax), the connected component (LatticeComponents) of the
+    seed, the masked point of highest rel[..., 0] (ties: the lowest flat index -- LocateQuery's rule).  Returns dict(mask [nz, ny, nx] bool, count, seed_index (flat,
+    into [nz, ny, nx]), seed_position [3], relevancy [2] of the seed, bbox [6]: the world box of the component's index extents, ready for ExtractMesh(bbox=...)).
+    When no point passes: count 0, an empty mask, and None for the rest."""
+    nx, ny, nz = _resolution(resolution)
+    bb = _lerf_bbox(lerf_renderer, bbox)
+    rel, sigma = RelevancyGrid(lerf_renderer, bb, (nx, ny, nz), positive_id, precision)
+    mask = (sigma >= sigma_threshold) & (rel[..., 0] >= relevancy_threshold)
+    idx = torch.nonzero(mask.reshape(-1)).reshape(-1)
+    if idx.numel() == 0:
+        return dict(mask=mask, count=0, seed_index=None, seed_position=None, relevancy=None, bbox=None)
+    r = rel.reshape(-1, 2)
+    seed = idx[torch.sort(r[idx, 0], descending=True, stable=True).indices[0]]          # candidates in ascending index order: equal scores keep the lower index
+    labels, _ = LatticeComponents(mask, connectivity)
+    comp = labels == labels.reshape(-1)[seed]
+    zyx = torch.nonzero(comp)
+    lo, hi = zyx.min(dim=0).values, zyx.max(dim=0).values
+    corners = torch.stack([(lo[0] * ny + lo[1]) * nx + lo[2], (hi[0] * ny + hi[1]) * nx + hi[2]])
+    return dict(mask=comp, count=int(zyx.shape[0]), seed_index=int(seed), seed_position=_lattice_points_at(bb, nx, ny, nz, seed), relevancy=r[seed],
+                bbox=_lattice_points_at(bb, nx, ny, nz, corners).reshape(6))

@@ -22,10 +22,10 @@ def mfma_roofline(kernel, units, flop_per_unit, seconds, launches, issued_flop_p
 # source files whose contents decide a kernel's HBM traffic: the PMC summary records their hashes, and a summary taken from other sources is not reported
 PMC_KERNEL_SOURCES = {
     "hash_encode (k_hash_cu_lm)": ["hash_fast.hip", "hash_fast.h", "encode.h"],
-    "mlp_small (k_mlp_small_mfma)": ["mlp_small_mfma.hip"],
-    "sigma_small_f32 (k_sigma_small_f32)": ["sigma_small_f32.hip"],
-    "mlp_nerf_split (k_mlp_nerf_split)": ["mlp_nerf_split_mfma.hip", "mlp_nerf_net.h"],
-    "mlp_nerf (k_mlp_nerf_mfma)": ["mlp_nerf_mfma.hip", "mlp_nerf_net.h"],
+    "mlp_small (k_mlp_small_mfma)": ["mlp_small_mfma.hip", "mfma_frag.h"],
+    "sigma_small_f32 (k_sigma_small_f32)": ["sigma_small_f32.hip", "mfma_frag.h"],
+    "mlp_nerf_split (k_mlp_nerf_split)": ["mlp_nerf_split_mfma.hip", "mlp_nerf_net.h", "mfma_frag.h"],
+    "mlp_nerf (k_mlp_nerf_mfma)": ["mlp_nerf_mfma.hip", "mlp_nerf_net.h", "mfma_frag.h"],
 }
 
 

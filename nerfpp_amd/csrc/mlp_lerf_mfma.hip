@@ -27,37 +27,6 @@
 namespace nrf {
 namespace lerf {
 
-// Chunk CI of the weight image -> LDS buffer `dst` by LDS-DMA (global_load_lds_dwordx4, one 1-KB fragment per wave-instruction, wave w takes fragments
-// w, w + NW, ...): same scheme as mlp_nerf_mfma.hip -- three LDS buffers, requested two chunks ahead, no staging registers.
-template <class N, int CI>
-__device__ __forceinline__ void stage_dma(half8 *__restrict__ dst, const half8 *__restrict__ packed, int wave, int lane)
-{
-    constexpr int ci = CI % N::total_chunks();
-    constexpr int nf = N::chunk_frags(ci);
-    constexpr int base = N::chunk_off(ci);
-#pragma unroll
-    for (int q = 0; q < (nf + NW - 1) / NW; q++) {
-        // SGPR base with the fragment's constant offset added on the scalar side, then made opaque (not hoistable out of the persistent loop), + lane * 16: the
-        // saddr form of the DMA; with the offset added behind the opaque point the compiler forms a 64-bit per-lane address (two v_lshl_add_u64 per DMA)
-        const half8 *pk = packed + (size_t)wave * 64;
-        asm volatile("" : "+s"(pk));                     // not hoistable out of the persistent loop ...
-        pk += (size_t)(base + q * NW) * 64;
-        asm volatile("" : "+s"(pk));                     // ... and the offset added here, on the scalar side
-        if (q * NW + wave < nf)                          // wave-uniform
-            __builtin_amdgcn_global_load_lds(pk + lane, (__attribute__((address_space(3))) void *)(dst + (q * NW + wave) * 64), 16, 0, 0);
-    }
-}
-
-template <bool RELU>
-__device__ __forceinline__ half8 tile_to_frag(const f32x16 &acc, int s)
-{
-    half8 r;
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = (_Float16)acc[8 * s + j];
-    if (RELU) r = __builtin_elementwise_max(r, half8{0, 0, 0, 0, 0, 0, 0, 0});
-    return r;
-}
-
 struct Ctx {
     half8 *wbuf;                       // [3][MAXF*64]
     const half8 *packed;
@@ -68,7 +37,7 @@ struct Ctx {
 // One chunk: fetch the following chunk, run this chunk's MFMAs out of LDS, hand each finished tile to `hook(tile, acc)`, publish the
 // fetched chunk.  All indices are template constants.
 // w / dma_dst are __restrict__ parameters so that, inlined, the LDS reads and the DMA's LDS write carry alias scopes: otherwise every LDS read issued
-// while an LDS-DMA is pending waits for vmcnt(0) (see mlp_nerf_mfma.hip).
+// while an LDS-DMA is pending waits for vmcnt(0) (see mfma_frag.h, the weight stream).
 template <class N, int L, int C, int NN, int NC, class Hook>
 __device__ __forceinline__ void chunk_body(const Ctx &cx, const half8 *__restrict__ w, half8 *__restrict__ dma_dst, const half8 (&bn)[NN], const half8 (&bc)[NC], Hook &hook)
 {
@@ -78,7 +47,7 @@ __device__ __forceinline__ void chunk_body(const Ctx &cx, const half8 *__restric
     constexpr int TILE0 = (L == 1) ? C : 2 * C;
     constexpr bool NATF = N::nat_first(L);
     static_assert(KSN <= NN && KSC <= NC, "operand fragment arrays too small");
-    stage_dma<N, CI + 2>(dma_dst, cx.packed, cx.wave, cx.lane);
+    stage_dma<N, NW, CI + 2>(dma_dst, cx.packed, cx.wave, cx.lane);
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int t = 0; t < NT; t++) {
@@ -190,8 +159,8 @@ k_lerf_mfma(int64_t npts, Args in, const half8 *__restrict__ packed)
     half8 *wbuf = reinterpret_cast<half8 *>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    stage_dma<N, 0>(wbuf, packed, wave, lane);
-    stage_dma<N, 1>(wbuf + MAXF * 64, packed, wave, lane);
+    stage_dma<N, NW, 0>(wbuf, packed, wave, lane);
+    stage_dma<N, NW, 1>(wbuf + MAXF * 64, packed, wave, lane);
     __syncthreads();                               // vmcnt(0): chunks 0 and 1 are in place
     int cur = 0;
     const int64_t nblocks = (npts + NBLK - 1) / NBLK;
@@ -517,7 +486,7 @@ static int launch_lerf(const nrf_mlp *m, const Args &a_in, int64_t p, hipStream_
     const size_t lds = (size_t)3 * MAXF * 1024;
     const int64_t nblocks = ceil_div(p, NBLK);
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);       // persistent: one 8-wave workgroup per CU (216 VGPRs: two waves per SIMD)
-    hipLaunchKernelGGL((k_lerf_mfma<NL>), dim3(grid), dim3(64 * NW), lds, st, p, a, reinterpret_cast<const lerf::half8 *>(m->d_packed_f16));
+    hipLaunchKernelGGL((k_lerf_mfma<NL>), dim3(grid), dim3(64 * NW), lds, st, p, a, reinterpret_cast<const half8 *>(m->d_packed_f16));
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
@@ -536,7 +505,7 @@ static int lerf_embedding_passes(const nrf_mlp *m, lerf::Args a, int64_t n, int 
         rc = launch_lerf<4>(m, a, n * (int64_t)s, st);
         if (rc == NRF_OK) {
             hipLaunchKernelGGL(lerf::k_lerf_embed, dim3((unsigned)ceil_div(ceil_div(n, (int64_t)32), (int64_t)4)), dim3(256), 0, st, n, (const float *)asum,
-                               reinterpret_cast<const lerf::half8 *>(m->d_packed_f16), d_out);
+                               reinterpret_cast<const half8 *>(m->d_packed_f16), d_out);
             if (hipGetLastError() != hipSuccess) { set_error("k_lerf_embed launch failed"); rc = NRF_ERR_HIP; }
         }
     }

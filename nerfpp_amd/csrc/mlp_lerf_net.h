@@ -7,10 +7,6 @@
 namespace nrf {
 namespace lerf {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int NW = 8;              // waves per workgroup
 constexpr int NBLK = 32 * NW;      // points per workgroup iteration (one 32-point tile per wave)
 constexpr int MAXF = 32;           // fragments (1 KB each) in the largest chunk
@@ -82,10 +78,6 @@ struct QueryArgs {
 
 // kernel of the query: precision split (hi + lo in LE0 and the U tile) or not (fp16 operands); img: the query image above
 int lerf_split_query(const nrf_mlp *m, const lerf::QueryArgs &a, int64_t p, const void *img, bool split, hipStream_t st);
-
-namespace lerf {
-
-}  // namespace lerf
 
 // split-precision passes (mlp_lerf_split_mfma.hip); same arguments as the fp16 launchers
 int lerf_split_available(const nrf_mlp *m);

@@ -76,43 +76,17 @@ static_assert(NetS<4, 2>::total_chunks() == 16 && NetS<4, 2>::chunk_off(0) == 2 
 static_assert(NetS<2>::total_chunks() == 10 && NetS<4>::total_chunks() == 26, "chunk counts");
 static_assert(NetS<4>::chunk_off(26) == 2 * LE1_FRAG0, "the split image doubles the fp16 image");
 
+// the weight stream of mfma_frag.h at this file's wave count; NRF_LERF_ABLATE & 1: no stream
 template <class N, int CI, int Q>
 __device__ __forceinline__ void stage_piece(half8 *__restrict__ dst, const half8 *__restrict__ packed, int wave, int lane)
 {
-    constexpr int ci = CI % N::total_chunks();
-    constexpr int nf = N::dma_frags(ci);
-    constexpr int STEP = N::hi_only(ci) ? 2 : 1;          // hi-only chunks: every second fragment of the image, into its usual slot
-    static_assert(nf % SNW == 0, "fragments per chunk must divide by the wave count");
-    if constexpr (Q * SNW < nf && !((NRF_LERF_ABLATE) & 1)) {
-        constexpr int base = N::chunk_off(ci);
-        // the fragment's address = SGPR base (its constant offset added on the scalar side, then made opaque) + lane * 16: the saddr form of the DMA.  With the offset
-        // added after the opaque point the compiler forms a 64-bit per-lane address instead -- two v_lshl_add_u64 per DMA, ~1 070 per iteration of the classic kernel
-        const half8 *pk = packed + (size_t)wave * (64 * STEP);
-        asm volatile("" : "+s"(pk));                          // opaque: the addresses derived from it cannot be hoisted out of the persistent loop (533 SGPR pairs would spill)
-        constexpr int F0 = 2 * N::k0_dma(ci);                 // first fragment of the chunk that travels (block-triangular Gram tiles skip their leading k-steps)
-        pk += (size_t)(base + F0 + STEP * Q * SNW) * 64;
-        asm volatile("" : "+s"(pk));                          // the offset is added HERE, on the scalar side (s_add_u32 / s_addc_u32)
-        __builtin_amdgcn_global_load_lds(pk + lane, (__attribute__((address_space(3))) void *)(dst + (F0 + STEP * (Q * SNW + wave)) * 64), 16, 0, 0);
-    }
+    if constexpr (!((NRF_LERF_ABLATE) & 1)) nrf::stage_piece<N, SNW, CI, Q>(dst, packed, wave, lane);
 }
 
 template <class N, int CI, int... Qs>
-__device__ __forceinline__ void stage_all(half8 *__restrict__ dst, const half8 *__restrict__ packed, int wave, int lane, std::integer_sequence<int, Qs...>)
+__device__ __forceinline__ void stage_all(half8 *__restrict__ dst, const half8 *__restrict__ packed, int wave, int lane, std::integer_sequence<int, Qs...> qs)
 {
-    (stage_piece<N, CI, Qs>(dst, packed, wave, lane), ...);
-}
-
-// registers 8s..8s+7 of a finished tile -> the (hi, lo) operand fragments of k-step s.  The asm reads VALU results only (the max / the add).
-template <bool RELU>
-__device__ __forceinline__ void tile_to_frag2(const f32x16 &t, int s, half8 &hi, half8 &lo)
-{
-    union { half8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const float lim = RELU ? 0.0f : -3.402823466e38f;          // max with -FLT_MAX: the identity on every finite value, and a VALU result for the asm to read
-        split_pair(fmaxf(t[8 * s + 2 * j], lim), fmaxf(t[8 * s + 2 * j + 1], lim), h.u[j], l.u[j]);
-    }
-    hi = h.v; lo = l.v;
+    if constexpr (!((NRF_LERF_ABLATE) & 1)) nrf::stage_all<N, SNW, CI>(dst, packed, wave, lane, qs);
 }
 
 struct CtxS {
@@ -930,7 +904,7 @@ int lerf_split_embedding_passes(const nrf_mlp *m, lerf::Args a, int64_t n, int s
         rc = lerf::launch_lerf_split<4>(m, a, n * (int64_t)s, st);
         if (rc == NRF_OK) {
             hipLaunchKernelGGL(lerf::k_lerf_embed_split, dim3((unsigned)ceil_div(ceil_div(n, (int64_t)32), (int64_t)4)), dim3(256), 0, st, n, (const float *)asum,
-                               reinterpret_cast<const lerf::half8 *>(m->d_packed_split), d_out);
+                               reinterpret_cast<const half8 *>(m->d_packed_split), d_out);
             if (hipGetLastError() != hipSuccess) { set_error("k_lerf_embed_split launch failed"); rc = NRF_ERR_HIP; }
         }
     }

@@ -42,42 +42,6 @@
 
 namespace nrf {
 
-// Chunk CI of the weight image -> LDS buffer `dst` by LDS-DMA (global_load_lds_dwordx4): one wave-instruction moves one 1-KB fragment
-// (64 lanes x 16 B, lane-linear on both sides -- exactly the fragment layout), wave w takes fragments w, w + NW, ...  No staging registers
-// (the register-staged version carried 20 VGPRs per thread in a kernel at the 256-VGPR cap) and no ds_write pass; the data is in flight
-// while the chunk's MFMAs run and is retired by the vmcnt(0) that __syncthreads() emits at the end of the chunk.
-// The fragment's address is a pinned SGPR base + lane * 16: left to itself the compiler hoists 40 chunks x 5 lane addresses out of the
-// persistent loop as 64-bit VGPR pairs.
-template <int CI>
-__device__ __forceinline__ void stage_dma(half8 *__restrict__ dst, const half8 *__restrict__ packed, int wave, int lane)
-{
-    constexpr int ci = CI % NerfNet::total_chunks();
-    constexpr int nf = NerfNet::chunk_frags(ci);
-    constexpr int base = NerfNet::chunk_off(ci);
-#pragma unroll
-    for (int q = 0; q < (nf + NW - 1) / NW; q++) {
-        // SGPR base with the fragment's constant offset added on the scalar side, then made opaque (not hoistable out of the persistent loop), + lane * 16: the
-        // saddr form of the DMA; with the offset added behind the opaque point the compiler forms a 64-bit per-lane address (two v_lshl_add_u64 per DMA)
-        const half8 *pk = packed + (size_t)wave * 64;
-        asm volatile("" : "+s"(pk));                     // not hoistable out of the persistent loop ...
-        pk += (size_t)(base + q * NW) * 64;
-        asm volatile("" : "+s"(pk));                     // ... and the offset added here, on the scalar side
-        if (q * NW + wave < nf)                          // wave-uniform
-            __builtin_amdgcn_global_load_lds(pk + lane, (__attribute__((address_space(3))) void *)(dst + (q * NW + wave) * 64), 16, 0, 0);
-    }
-}
-
-template <bool RELU>
-__device__ __forceinline__ half8 nerf_tile_to_frag(const f32x16 &acc, int s)
-{
-    half8 r;
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = (_Float16)acc[8 * s + j];
-    // ReLU after the (monotonic) rounding: max(round(x), 0) == round(max(x, 0)); packed, 4 v_pk_max_f16 instead of 8 v_max_f32
-    if (RELU) r = __builtin_elementwise_max(r, half8{0, 0, 0, 0, 0, 0, 0, 0});
-    return r;
-}
-
 struct Ctx {
     half8 *wbuf;            // [2][MAXF*64]
     const float *bias_s;    // LDS
@@ -94,9 +58,7 @@ template <int L, int C, bool RELU, int NN, int NC, int NOUT>
 __device__ __forceinline__ void nerf_chunk_body(const Ctx &cx, const half8 *__restrict__ w, half8 *__restrict__ dma_dst, const float *__restrict__ bias_s,
                                                 const half8 (&bn)[NPT][NN], const half8 (&bc)[NPT][NC], half8 (&bout)[NPT][NOUT], f32x16 (&last)[NPT])
 {
-    // w / dma_dst / bias_s are __restrict__ PARAMETERS on purpose: inlining turns that into alias-scope metadata on the LDS reads and on the DMA's LDS
-    // write, which is what lets the compiler see that this chunk's reads do not touch the look-ahead's destination.  Without it every LDS read issued
-    // while an LDS-DMA is pending is preceded by s_waitcnt vmcnt(0) and the look-ahead is drained at the top of the chunk.
+    // w / dma_dst / bias_s are __restrict__ PARAMETERS on purpose: alias scopes that keep this chunk's LDS reads clear of the look-ahead DMA (mfma_frag.h, the weight stream)
     constexpr int KSN = NerfNet::ks_nat(L), KSC = NerfNet::ks_ch(L), KS = KSN + KSC;
     constexpr int CI = NerfNet::first_chunk(L) + C;
     constexpr int NT = NerfNet::chunk_tiles(L, C);
@@ -104,7 +66,7 @@ __device__ __forceinline__ void nerf_chunk_body(const Ctx &cx, const half8 *__re
     constexpr int NTILES = NerfNet::tiles(L);
     constexpr bool NATF = NerfNet::nat_first(L);
     static_assert(KSN <= NN && KSC <= NC, "operand fragment arrays too small");
-    stage_dma<CI + 2>(dma_dst, cx.packed, cx.wave, cx.lane);
+    stage_dma<NerfNet, NW, CI + 2>(dma_dst, cx.packed, cx.wave, cx.lane);
 #pragma unroll
     for (int t = 0; t < NT; t++) {
         const int tile = 2 * C + t;
@@ -133,8 +95,8 @@ __device__ __forceinline__ void nerf_chunk_body(const Ctx &cx, const half8 *__re
 #pragma unroll
         for (int pt = 0; pt < NPT; pt++) {
             if (2 * tile + 1 < NOUT) {
-                bout[pt][2 * tile] = nerf_tile_to_frag<RELU>(acc[pt], 0);
-                bout[pt][2 * tile + 1] = nerf_tile_to_frag<RELU>(acc[pt], 1);
+                bout[pt][2 * tile] = tile_to_frag<RELU>(acc[pt], 0);
+                bout[pt][2 * tile + 1] = tile_to_frag<RELU>(acc[pt], 1);
             }
             if (tile == NTILES - 1) last[pt] = acc[pt];
         }
@@ -182,8 +144,8 @@ k_mlp_nerf_mfma(int64_t npts, NerfInput in, const half8 *__restrict__ packed, co
     const int r = lane & 31, h = lane >> 5;
     for (int i = tid; i < NBIAS; i += 64 * NW) bias_s[i] = biases[i];
     // three LDS buffers, weights requested TWO chunks ahead of their use: a chunk's MFMAs take 1-2 us, an L2 round trip under this load about as long
-    stage_dma<0>(wbuf, packed, wave, lane);
-    stage_dma<1>(wbuf + MAXF * 64, packed, wave, lane);
+    stage_dma<NerfNet, NW, 0>(wbuf, packed, wave, lane);
+    stage_dma<NerfNet, NW, 1>(wbuf + MAXF * 64, packed, wave, lane);
     __syncthreads();                               // vmcnt(0): chunks 0 and 1 are in place
     int cur = 0;
     const int64_t nblocks = (npts + NBLK - 1) / NBLK;
@@ -344,7 +306,7 @@ bool nerf_f16_images_host(const nrf_mlp_nerf_desc &d, const float *hp, const flo
 
     img.clear(); img2.clear();
     bias.assign(NBIAS, 0.0f);
-    auto chained = [](int k, int h, int j) { return 32 * (k >> 1) + nerf_perm_row(k & 1, h, j); };
+    auto chained = [](int k, int h, int j) { return 32 * (k >> 1) + perm_row(k & 1, h, j); };
     auto natural = [](int k, int h, int j) { return 16 * k + 8 * h + j; };
     // value of the weight that multiplies operand element (kstep, h, j) for output row `row` of kernel-layer L (-> 0 if padding)
     auto wval = [&](int L, int row, int kstep, int h, int j) -> float {

@@ -1,12 +1,10 @@
 // mlp_nerf_net.h -- layer plan and fragment bookkeeping of the classic 8 x 256 NeRF on the matrix cores, shared by mlp_nerf_mfma.hip
 // (NRF_PREC_F16_MFMA) and mlp_nerf_split_mfma.hip (NRF_PREC_F16_SPLIT).  See mlp_nerf_mfma.hip for the formulation.
 #pragma once
+#include "mfma_frag.h"
 #include "mlp.h"
 
 namespace nrf {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Measured on MI355X (bench --workload classic): 8 waves x 1 point tile = 1021 TFLOP/s (40.9 % of the 2.5 PF dense fp16 peak);
 // 4 waves x 2 tiles (one wave per SIMD, half the LDS fragment reads) = 779 TFLOP/s: with a single wave per SIMD nothing
@@ -20,8 +18,6 @@ constexpr int NPT = NRF_NERF_NPT;      // 32-point tiles per wave (every weight 
 constexpr int NBLK = 32 * NPT * NW;    // points per workgroup iteration
 constexpr int MAXF = 40;               // fragments (1 KB each) in the largest chunk
 constexpr int NBIAS = 8 * 256 + 160 + 32;
-
-__host__ __device__ inline int nerf_perm_row(int s, int h, int j) { return 16 * s + 8 * (j >> 2) + 4 * h + (j & 3); }
 
 struct NerfNet {
     static constexpr int NLAYER = 10;

@@ -35,42 +35,13 @@ struct NerfNetS {
     static constexpr int chunk_frags(int ci) { return 2 * NerfNet::ks(layer_of(ci)); }
     static constexpr int chunk_off(int ci) { int n = 0; for (int i = 0; i < ci; i++) n += chunk_frags(i); return n; }
     static constexpr int total_frags() { return chunk_off(total_chunks()); }
+    // what the shared weight stream (mfma_frag.h, stage_piece) asks of a chunk table: every fragment of a chunk travels, from its first k-step on
+    static constexpr int dma_frags(int ci) { return chunk_frags(ci); }
+    static constexpr bool hi_only(int) { return false; }
+    static constexpr int k0_dma(int) { return 0; }
 };
 static_assert(NerfNetS::total_chunks() == 70, "chunk count");
 static_assert(NerfNetS::total_frags() == 2 * NerfNet::total_frags(), "the split image is twice the fp16 image");
-
-// piece Q (0 .. pieces per wave) of chunk CI -> LDS buffer `dst`: wave w moves fragments w, w + SNW, ... (every chunk's fragment count is a multiple of SNW)
-template <int CI, int Q>
-__device__ __forceinline__ void stage_piece(half8 *__restrict__ dst, const half8 *__restrict__ packed, int wave, int lane)
-{
-    constexpr int ci = CI % NerfNetS::total_chunks();
-    constexpr int nf = NerfNetS::chunk_frags(ci);
-    static_assert(nf % SNW == 0, "fragments per chunk must divide by the wave count");
-    if constexpr (Q * SNW < nf) {
-        constexpr int base = NerfNetS::chunk_off(ci);
-        // the fragment's address = SGPR base (its constant offset added on the scalar side, then made opaque) + lane * 16: the saddr form of the DMA.  With the offset
-        // added after the opaque point the compiler forms a 64-bit per-lane address instead -- two v_lshl_add_u64 per DMA, ~1 070 per iteration of the classic kernel
-        const half8 *pk = packed + (size_t)wave * 64;
-        asm volatile("" : "+s"(pk));                          // opaque: the addresses derived from it cannot be hoisted out of the persistent loop (533 SGPR pairs would spill)
-        pk += (size_t)(base + Q * SNW) * 64;
-        asm volatile("" : "+s"(pk));                          // the offset is added HERE, on the scalar side (s_add_u32 / s_addc_u32)
-        __builtin_amdgcn_global_load_lds(pk + lane, (__attribute__((address_space(3))) void *)(dst + (Q * SNW + wave) * 64), 16, 0, 0);
-    }
-}
-
-template <int CI, int... Qs>
-__device__ __forceinline__ void stage_all(half8 *__restrict__ dst, const half8 *__restrict__ packed, int wave, int lane, std::integer_sequence<int, Qs...>)
-{
-    (stage_piece<CI, Qs>(dst, packed, wave, lane), ...);
-}
-
-// (hi, lo) of two fp32 values, packed: hi = RNE(v), lo = RNE(v - hi) through one mixed-precision FMA each (see mlp_small_mfma.hip, split_pair)
-__device__ __forceinline__ void nerf_split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo)
-{
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(v0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(v1));
-}
 
 #ifdef NRF_NERF_TRACE
 // diagnostic build only (tools/scratch/classic_trace.py): cycle stamps of wave 0 of every workgroup, summed per section: [0] tile loops, [2] end-of-chunk wait +
@@ -91,8 +62,6 @@ struct CtxS {
 #endif
 };
 
-typedef uint32_t nerf_u32x4 __attribute__((ext_vector_type(4)));
-
 // One conversion unit of a finished tile: values 8s + 2j, 8s + 2j + 1 (s = u >> 2, j = u & 3) of its accumulator -> ReLU -> the (hi, lo) words j of the next layer's
 // B fragments 2 PT + s.  Seven vector instructions (two AGPR reads, two v_max, one v_cvt_pk, two v_fma_mix).
 template <int PT, int NB>
@@ -100,14 +69,14 @@ __device__ __forceinline__ void nerf_conv_unit(const f32x16 &tile, int u, half8 
 {
     const int s = u >> 2, j = u & 3;
     uint32_t hi, lo;
-    nerf_split_pair(fmaxf(tile[8 * s + 2 * j], 0.0f), fmaxf(tile[8 * s + 2 * j + 1], 0.0f), hi, lo);
-    nerf_u32x4 hv = __builtin_bit_cast(nerf_u32x4, tgt[2 * PT + s][0]), lv = __builtin_bit_cast(nerf_u32x4, tgt[2 * PT + s][1]);
+    split_pair(fmaxf(tile[8 * s + 2 * j], 0.0f), fmaxf(tile[8 * s + 2 * j + 1], 0.0f), hi, lo);
+    u32x4 hv = __builtin_bit_cast(u32x4, tgt[2 * PT + s][0]), lv = __builtin_bit_cast(u32x4, tgt[2 * PT + s][1]);
     hv[j] = hi; lv[j] = lo;
     tgt[2 * PT + s][0] = __builtin_bit_cast(half8, hv); tgt[2 * PT + s][1] = __builtin_bit_cast(half8, lv);
 }
 
 // One chunk = neuron tile T of layer L.  w / dma_dst / bias_s are __restrict__ PARAMETERS on purpose (alias-scope metadata after inlining: this chunk's
-// LDS reads do not touch the look-ahead's destination, so no vmcnt(0) is inserted before them -- see mlp_nerf_mfma.hip).
+// LDS reads do not touch the look-ahead's destination, so no vmcnt(0) is inserted before them -- see mfma_frag.h, the weight stream).
 //
 // What a single wave per SIMD has to hide by itself (cycle stamps of a diagnostic build, per 16-step tile = 1536 matrix-pipe cycles; numbers in DESIGN section 9):
 //   * the conversion of a finished tile into the next layer's operands -- ~180 vector instructions = ~700 cycles during which the pipe sat idle when the
@@ -147,7 +116,7 @@ __device__ __forceinline__ void nerf_chunk_body_s(const CtxS &cx, const half8 *_
 #ifdef NRF_NERF_TRACE
     const unsigned long long t0_ = NRF_STAMP();
 #endif
-    stage_all<CI + 2>(dma_dst, cx.packed, cx.wave, cx.lane, std::make_integer_sequence<int, LEAD>{});
+    stage_all<NerfNetS, SNW, CI + 2>(dma_dst, cx.packed, cx.wave, cx.lane, std::make_integer_sequence<int, LEAD>{});
     half8 fa[3][2];
     const uint32_t waddr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)(w + cx.lane);
     auto read_pair = [&](int kk, int slot) {
@@ -193,7 +162,7 @@ __device__ __forceinline__ void nerf_chunk_body_s(const CtxS &cx, const half8 *_
             // the next piece of the look-ahead chunk, in the shadow of this k-step's matrix instructions (q is a compile-time value after unrolling)
             const int qq = q;
             switch (qq) {
-#define NRF_PIECE(Q) case Q: stage_piece<CI + 2, Q>(dma_dst, cx.packed, cx.wave, cx.lane); break;
+#define NRF_PIECE(Q) case Q: stage_piece<NerfNetS, SNW, CI + 2, Q>(dma_dst, cx.packed, cx.wave, cx.lane); break;
                 NRF_PIECE(0) NRF_PIECE(1) NRF_PIECE(2) NRF_PIECE(3) NRF_PIECE(4) NRF_PIECE(5) NRF_PIECE(6) NRF_PIECE(7) NRF_PIECE(8) NRF_PIECE(9)
 #undef NRF_PIECE
             }
@@ -253,8 +222,8 @@ k_mlp_nerf_split(int64_t npts, NerfInput in, const half8 *__restrict__ packed, c
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     for (int i = tid; i < NBIAS; i += 64 * SNW) bias_s[i] = biases[i];
-    stage_all<0>(wbuf, packed, wave, lane, std::make_integer_sequence<int, NerfNetS::chunk_frags(0) / SNW>{});
-    stage_all<1>(wbuf + SMAXF * 64, packed, wave, lane, std::make_integer_sequence<int, NerfNetS::chunk_frags(1) / SNW>{});
+    stage_all<NerfNetS, SNW, 0>(wbuf, packed, wave, lane, std::make_integer_sequence<int, NerfNetS::chunk_frags(0) / SNW>{});
+    stage_all<NerfNetS, SNW, 1>(wbuf + SMAXF * 64, packed, wave, lane, std::make_integer_sequence<int, NerfNetS::chunk_frags(1) / SNW>{});
     __syncthreads();                               // vmcnt(0): chunks 0 and 1 are in place
     int cur = 0;
     const int64_t nblocks = (npts + SNBLK - 1) / SNBLK;

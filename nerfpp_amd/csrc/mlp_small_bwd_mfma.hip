@@ -19,13 +19,11 @@
 //
 // Arithmetic: fp16 operands, fp32 accumulation.  Gradients are multiplied by a power of two S chosen from max|g_out| (read
 // on the device, no host sync) so that they sit in the middle of the fp16 range, and divided out in fp32 at the end.
+#include "mfma_frag.h"
 #include "mlp.h"
 #include "workspace.h"
 
 namespace nrf {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -41,8 +39,6 @@ constexpr int BW = 4;                   // waves per workgroup: one per SIMD, 51
 constexpr int BPT = 1;                  // 32-point tiles per wave (two would need 180 working registers on top of the 320 accumulators)
 constexpr int BW_BLOCK_PTS = 32 * BPT * BW;
 constexpr int IN_KS = 2, V = 16, GEO = 15;      // 32 hash features, 16 direction features, 15 geometry features (NeRF.h:215)
-
-__host__ __device__ inline int prow(int s, int h, int j) { return 16 * s + 8 * (j >> 2) + 4 * h + (j & 3); }   // see mlp_small_mfma.hip
 
 template <int NL, int NLC>
 struct BwdPlan {
@@ -82,16 +78,6 @@ struct LmInput { const __half2 *feats; int64_t pstride; const __half *dirs; int 
 
 __device__ __forceinline__ f32x16 mfma(const half8 &a, const half8 &b, const f32x16 &c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
-template <bool RELU>
-__device__ __forceinline__ half8 to_frag(const f32x16 &acc, int s)
-{
-    half8 r;
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = (_Float16)acc[8 * s + j];
-    if (RELU) r = __builtin_elementwise_max(r, half8{0, 0, 0, 0, 0, 0, 0, 0});
-    return r;
-}
-
 // acc[pt][mt] = sum_ks A[mt][ks] . b[pt][ks]; A fragments read from LDS
 template <int MT, int KS>
 __device__ __forceinline__ void gemm(const half8 *__restrict__ frags, int lane, const half8 (&b)[BPT][KS], f32x16 (&acc)[BPT][MT])
@@ -122,7 +108,7 @@ __device__ __forceinline__ void mask_to_frags(const f32x16 (&acc)[BPT][2], const
     for (int pt = 0; pt < BPT; pt++)
 #pragma unroll
         for (int f = 0; f < 4; f++) {
-            half8 v = to_frag<false>(acc[pt][f >> 1], f & 1);
+            half8 v = tile_to_frag<false>(acc[pt][f >> 1], f & 1);
 #pragma unroll
             for (int j = 0; j < 8; j++) v[j] = hf[pt][f][j] > (_Float16)0 ? v[j] : (_Float16)0;
             g[pt][f] = v;
@@ -194,11 +180,11 @@ k_small_bwd(int64_t npts, const float *__restrict__ x, int xs, const float *__re
     half8 sel0, sel1, nat0, nat1, selgeo;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-        sel0[j] = prow(0, h, j) == r ? (_Float16)1 : (_Float16)0;               // ... neuron r of a chained fragment pair (registers of a D tile)
-        sel1[j] = prow(1, h, j) == r ? (_Float16)1 : (_Float16)0;
+        sel0[j] = perm_row(0, h, j) == r ? (_Float16)1 : (_Float16)0;               // ... neuron r of a chained fragment pair (registers of a D tile)
+        sel1[j] = perm_row(1, h, j) == r ? (_Float16)1 : (_Float16)0;
         nat0[j] = 8 * h + j == r ? (_Float16)1 : (_Float16)0;                   // ... element r of a pair loaded in natural order
         nat1[j] = 16 + 8 * h + j == r ? (_Float16)1 : (_Float16)0;
-        const int row = prow(0, h, j);                                          // ... geo feature row - 1 as colour-net input V + row - 1
+        const int row = perm_row(0, h, j);                                          // ... geo feature row - 1 as colour-net input V + row - 1
         selgeo[j] = (row >= 1 && row <= GEO && V + row - 1 == r) ? (_Float16)1 : (_Float16)0;
     }
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -207,12 +193,12 @@ k_small_bwd(int64_t npts, const float *__restrict__ x, int xs, const float *__re
     auto transpose = [&](const half8 &a0, const half8 &s0, const half8 &a1, const half8 &s1, half8 (&t)[2]) {
         f32x16 d = mfma(a0, s0, zero);
         d = mfma(a1, s1, d);
-        t[0] = to_frag<false>(d, 0); t[1] = to_frag<false>(d, 1);
+        t[0] = tile_to_frag<false>(d, 0); t[1] = tile_to_frag<false>(d, 1);
         __builtin_amdgcn_sched_barrier(0);       // unfenced, every product of a layer is issued before the first conversion: 16 live D tiles
     };
     auto transpose1 = [&](const half8 &a0, const half8 &s0, half8 (&t)[2]) {
         const f32x16 d = mfma(a0, s0, zero);
-        t[0] = to_frag<false>(d, 0); t[1] = to_frag<false>(d, 1);
+        t[0] = tile_to_frag<false>(d, 0); t[1] = tile_to_frag<false>(d, 1);
         __builtin_amdgcn_sched_barrier(0);
     };
     // both 32-neuron groups' products are issued before the first conversion (two live D tiles): the second pair of matrix instructions runs while the first result lands
@@ -226,8 +212,8 @@ k_small_bwd(int64_t npts, const float *__restrict__ x, int xs, const float *__re
                 f32x16 d0 = mfma(f[pt][0], sel0, zero), d1 = mfma(f[pt][2], sel0, zero);
                 d0 = mfma(f[pt][1], sel1, d0); d1 = mfma(f[pt][3], sel1, d1);
                 __builtin_amdgcn_sched_barrier(0);
-                t[0][pt][0] = to_frag<false>(d0, 0); t[0][pt][1] = to_frag<false>(d0, 1);
-                t[1][pt][0] = to_frag<false>(d1, 0); t[1][pt][1] = to_frag<false>(d1, 1);
+                t[0][pt][0] = tile_to_frag<false>(d0, 0); t[0][pt][1] = tile_to_frag<false>(d0, 1);
+                t[1][pt][0] = tile_to_frag<false>(d1, 0); t[1][pt][1] = tile_to_frag<false>(d1, 1);
                 __builtin_amdgcn_sched_barrier(0);
             } else {
 #pragma unroll
@@ -339,13 +325,13 @@ k_small_bwd(int64_t npts, const float *__restrict__ x, int xs, const float *__re
 #pragma unroll
                 for (int pt = 0; pt < BPT; pt++)
 #pragma unroll
-                    for (int f = 0; f < 4; f++) { bh[pt][f] = to_frag<true>(acc2[pt][f >> 1], f & 1); hstore(pt, P::h_sigma(l) + f, bh[pt][f]); }
+                    for (int f = 0; f < 4; f++) { bh[pt][f] = tile_to_frag<true>(acc2[pt][f >> 1], f & 1); hstore(pt, P::h_sigma(l) + f, bh[pt][f]); }
                 if (l < NL - 1) { gemm<2, 4>(fr, lane, bh, acc2); }
                 else {
                     f32x16 sig[BPT][1];
                     gemm<1, 4>(fr, lane, bh, sig);
 #pragma unroll
-                    for (int pt = 0; pt < BPT; pt++) { bc[pt][1] = to_frag<false>(sig[pt][0], 0); hstore(pt, P::h_color(0) + 1, bc[pt][1]); }
+                    for (int pt = 0; pt < BPT; pt++) { bc[pt][1] = tile_to_frag<false>(sig[pt][0], 0); hstore(pt, P::h_color(0) + 1, bc[pt][1]); }
                 }
                 fr += P::sigma_frags(l) * 64;
             }
@@ -355,7 +341,7 @@ k_small_bwd(int64_t npts, const float *__restrict__ x, int xs, const float *__re
 #pragma unroll
                 for (int pt = 0; pt < BPT; pt++)
 #pragma unroll
-                    for (int f = 0; f < 4; f++) { bh[pt][f] = to_frag<true>(acc2[pt][f >> 1], f & 1); hstore(pt, P::h_color(l) + f, bh[pt][f]); }
+                    for (int f = 0; f < 4; f++) { bh[pt][f] = tile_to_frag<true>(acc2[pt][f >> 1], f & 1); hstore(pt, P::h_color(l) + f, bh[pt][f]); }
                 if (l < NLC - 1) { gemm<2, 4>(fr, lane, bh, acc2); fr += P::color_frags(l) * 64; }
             }
         }
@@ -433,7 +419,7 @@ k_small_bwd(int64_t npts, const float *__restrict__ x, int xs, const float *__re
 #pragma unroll
             for (int pt = 0; pt < BPT; pt++) {
                 if (h == 0) a1[pt][0][0] += gsig[pt];
-                g3[pt][0] = to_frag<false>(a1[pt][0], 0);
+                g3[pt][0] = tile_to_frag<false>(a1[pt][0], 0);
             }
         }
         NRF_BSTAMP(9);
@@ -589,7 +575,7 @@ bool mlp_small_bwd_image_host(const nrf_mlp *m, const std::vector<float> &hp, st
     if (!ok) return false;
     const int G = d.geo_feat_dim;
     auto natural = [](int ks, int h, int j) { return 16 * ks + 8 * h + j; };
-    auto chained = [](int ks, int h, int j) { return 32 * (ks >> 1) + prow(ks & 1, h, j); };
+    auto chained = [](int ks, int h, int j) { return 32 * (ks >> 1) + perm_row(ks & 1, h, j); };
     auto transposed = [&](const nrf::LinearLayer &L) {          // [in][out]
         std::vector<float> t((size_t)L.in * L.out);
         for (int o = 0; o < L.out; o++)

@@ -22,15 +22,14 @@
 // fp16 in the reference itself (CuHashEmbedder.cu:95), so the first layer needs only two.  Result: fp32-grade pixels
 // (render-vs-oracle PSNR > 90 dB where the plain fp16 mode gives ~45 dB on the adversarial synthetic scene) at 3x the MFMA
 // work of a kernel that was not MFMA-bound to begin with.  The doubled weight image (80 KB) is shared by 8 waves per workgroup.
+#include "mfma_frag.h"
 #include "mlp.h"
 
 #include <type_traits>
 
 namespace nrf {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #ifdef NRF_SMALL_TRACE
 // diagnostic build only (tools/scratch/small_trace.py): cycle stamps of wave 0 of every workgroup of the split kernel, summed per section:
@@ -53,39 +52,10 @@ constexpr int PT = NRF_SMALL_PT; // 32-point tiles per wave
 constexpr int waves_of(bool split) { return split ? NRF_SPLIT_WAVES : 4; }
 constexpr int block_pts_of(bool split) { return 32 * PT * waves_of(split); }
 
-// neuron (row of a D tile / k of the next layer) held by element j of lane-half h in k-step s of a 32-row tile
-__host__ __device__ inline int perm_row(int s, int h, int j) { return 16 * s + 8 * (j >> 2) + 4 * h + (j & 3); }
-
 #ifndef NRF_SPLIT_RTZ
 #define NRF_SPLIT_RTZ 0             // split mode, hidden layers: 1 = ReLU folded into a truncating (hi, lo) split (2 instructions per value instead of 2.5);
                                     // measured 11.65 vs 11.79 ms (same box, warm) with the frame's max error vs fp32 5.2e-6 instead of 3.5e-6: off
 #endif
-
-// D tile registers 8s..8s+7 -> fp16 B fragment (round to nearest even), optional ReLU
-template <bool RELU>
-__device__ __forceinline__ half8 tile_to_frag(const f32x16 &acc, int s)
-{
-    half8 r;
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = (_Float16)acc[8 * s + j];
-    // ReLU after the (monotonic) rounding: max(round(x), 0) == round(max(x, 0)); packed, 4 v_pk_max_f16 instead of 8 v_max_f32
-    if (RELU) r = __builtin_elementwise_max(r, half8{0, 0, 0, 0, 0, 0, 0, 0});
-    return r;
-}
-
-// D tile registers 8s..8s+7 -> (hi, lo) fp16 pair of B fragments: v = hi + lo to 22 bits.
-// VALU cost matters here (the split kernel converts as many values as it multiplies tiles), so the hidden-layer form is 2.5
-// instructions per value: one v_max_f32 (this file is built with -fno-honor-nans, otherwise fmaxf first canonicalises the MFMA
-// result), half a v_cvt_pk_f16_f32 (RNE), and lo = f16(v - hi) as ONE mixed-precision FMA that reads hi as a half and writes a
-// half (v_fma_mixlo/mixhi_f16: fma(f32(hi), -1, v), exact difference, rounded once) -- which the compiler does not select by
-// itself (it emits cvt + sub + cvt).  The asm only ever reads compiler-produced VALU results, never an MFMA result directly,
-// so the MFMA -> VALU hazard handling stays with the compiler.
-__device__ __forceinline__ void split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo)
-{
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(v0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(v1));
-}
 
 // ReLU folded into the split, 2 instructions per value: hi' = f16(v) rounded TOWARD ZERO (v_cvt_pkrtz_f16_f32, two values per instruction), so that the
 // residual v - hi' is zero or has the sign of v; then relu(v) = max(hi', 0) + max(v - hi', 0) exactly: the first max is one packed v_pk_max_f16 per pair,
@@ -103,32 +73,20 @@ __device__ __forceinline__ void split_pair_relu(float v0, float v1, uint32_t &hi
     hi = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(f16x2, pre), f16x2{0, 0}));
 }
 
+// tile_to_frag2 (mfma_frag.h), except that NRF_SPLIT_RTZ takes the hidden layers' conversion through split_pair_relu
 template <bool RELU>
-__device__ __forceinline__ void tile_to_frag2(const f32x16 &acc, int s, half8 &hi, half8 &lo)
+__device__ __forceinline__ void small_tile_to_frag2(const f32x16 &acc, int s, half8 &hi, half8 &lo)
 {
+#if NRF_SPLIT_RTZ
     if constexpr (RELU) {
         union { half8 v; uint32_t u[4]; } h, l;
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-#if NRF_SPLIT_RTZ
-            split_pair_relu(acc[8 * s + 2 * j], acc[8 * s + 2 * j + 1], h.u[j], l.u[j]);
-#else
-            split_pair(fmaxf(acc[8 * s + 2 * j], 0.0f), fmaxf(acc[8 * s + 2 * j + 1], 0.0f), h.u[j], l.u[j]);
-#endif
-        }
+        for (int j = 0; j < 4; j++) split_pair_relu(acc[8 * s + 2 * j], acc[8 * s + 2 * j + 1], h.u[j], l.u[j]);
         hi = h.v; lo = l.v;
-    } else {
-        // same two roundings (hi = RNE(v), lo = RNE(v - hi)) through the 1.5-instruction-per-value path
-        union { half8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            // split_pair's asm must read VALU results, never the matrix instruction's destination directly (the MFMA -> VALU hazard handling is the compiler's and
-            // does not look into asm): a max with -FLT_MAX is the cheapest instruction that is the identity on every finite value
-            const float v0 = fmaxf(acc[8 * s + 2 * j], -3.402823466e38f), v1 = fmaxf(acc[8 * s + 2 * j + 1], -3.402823466e38f);
-            split_pair(v0, v1, h.u[j], l.u[j]);
-        }
-        hi = h.v; lo = l.v;
+        return;
     }
+#endif
+    tile_to_frag2<RELU>(acc, s, hi, lo);
 }
 
 // acc[pt][mt] += A[mt][ks] . B[pt][ks] over all k-steps; A fragments stream from LDS in consumption order.
@@ -446,13 +404,12 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
         // item i in 0..3 of tile t: point tile i >> 1, register half i & 1 -> operand fragment 2t + (i & 1) of buffer `buf`
         auto conv_item = [&](int buf, int t, int i) {
             const int pt = i >> 1, sh = i & 1;
-            if constexpr (SPLIT) tile_to_frag2<true>(acc2[pt][t], sh, bh[buf][pt][2 * t + sh][0], bh[buf][pt][2 * t + sh][NP - 1]);
+            if constexpr (SPLIT) small_tile_to_frag2<true>(acc2[pt][t], sh, bh[buf][pt][2 * t + sh][0], bh[buf][pt][2 * t + sh][NP - 1]);
             else bh[buf][pt][2 * t + sh][0] = tile_to_frag<true>(acc2[pt][t], sh);
         };
         // The same conversion in HALF-QUAD units for the fine-grained schedule (split mode): quad q of item i = values 4q..4q+3 of the 8-register half tile.
         // Part 0: four ReLUs and the two packed roundings to fp16 (hi); part 1: the four residuals lo = f16(v - hi).  Two value pairs advance together so that
         // no instruction reads the result of the one right before it (a v_cvt_pk followed by the v_fma_mix that reads it costs an s_nop).
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         float qm[4];
         uint32_t qc[2];
         auto conv_half = [&](int buf, int t, int i, int q, int part, bool need_lo) __attribute__((always_inline)) {
@@ -599,7 +556,7 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
                 for (int q = 0; q < NP; q++) bc[pt][s][q] = bv[pt][s][q];
             // rows 0..15 of the sigma tile: sigma (zero weight) + geo
             if constexpr (GEOIN) { bc[pt][V_KS][0] = bg[pt][0]; bc[pt][V_KS][NP - 1] = bg[pt][NP - 1]; }
-            else if constexpr (SPLIT) tile_to_frag2<false>(sig[pt][0], 0, bc[pt][V_KS][0], bc[pt][V_KS][NP - 1]);
+            else if constexpr (SPLIT) small_tile_to_frag2<false>(sig[pt][0], 0, bc[pt][V_KS][0], bc[pt][V_KS][NP - 1]);
             else bc[pt][V_KS][0] = tile_to_frag<false>(sig[pt][0], 0);
         }
         NRF_TSTAMP(3);

@@ -14,20 +14,14 @@
 //     both parities of point l, and the lane runs fmaf over k = 32 mt .. 32 mt + 31 in ascending order before the next m-tile arrives;
 //   * geo (output rows 1..32, optional) accumulates in ONE matrix tile per point tile: the 16 k-steps a finished m-tile supplies are issued right away, so the
 //     tile's own sum also runs in ascending k.  Its rows are ordered [geo31, geo0 .. geo30]: registers 8s..8s+7 then hold exactly the values of operand fragment s of
-//     LE0's chained input cat[sigma, geo0..30] (mlp_lerf_net.h: perm_row), with sigma patched into the slot of row 0 and geo31 moved to fragment 2 -- the (hi, lo)
+//     LE0's chained input cat[sigma, geo0..30] (mfma_frag.h: perm_row), with sigma patched into the slot of row 0 and geo31 moved to fragment 2 -- the (hi, lo)
 //     planes kernel B of mlp_lerf_split_mfma.hip reads (Args::geo), here from exact fp32 values instead of split-arithmetic ones.
 // W0 (128 KB of fp32 fragments) lives in LDS for the life of a persistent 8-wave workgroup (two waves per SIMD: one's vector work under the other's matrix
 // chain); the geo tile's 32 KB of fragments are read from global memory (L1 / L2 resident) four k-steps per load.
 #include "mlp_lerf_net.h"
 
 namespace nrf {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace lsig {
-
-using lerf::f32x16;
-using lerf::half8;
 
 constexpr int WAVES = 8;
 constexpr int BLOCK_PTS = 64 * WAVES;
@@ -65,8 +59,7 @@ k_lerf_sigma_f32(int64_t npts, const _Float16 *__restrict__ x_lm, int64_t pstrid
             for (int lv = 0; lv < 16; lv++) {
                 // word j of the 16 bytes holds features 2 j (low half) and 2 j + 1 (high half): the lane half's one is shifted down and converted -- two instructions per
                 // value.  Written as `hh ? v[2 j + 1] : v[2 j]` the compiler builds a dynamic vector-element extract: seven v_cndmask per value, 870 per iteration.
-                typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                const u32x4_t v = *reinterpret_cast<const u32x4_t *>(x_lm + ((int64_t)lv * pstride + p) * 8);
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(x_lm + ((int64_t)lv * pstride + p) * 8);
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const uint32_t bits = v[j] >> (16 * hh);
@@ -139,14 +132,7 @@ k_lerf_sigma_f32(int64_t npts, const _Float16 *__restrict__ x_lm, int64_t pstrid
                 if (hh == 0) t[0] = pt == 0 ? a : a_t1;              // row 0 of LE0's chained operand: sigma (unmasked, as kernel A hands it over)
                 union { half8 v; uint32_t u[4]; } fh[3], fl[3];
 #pragma unroll
-                for (int s = 0; s < 2; s++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        // through a compiler-visible vector instruction (identity on finite values): the asm of split_pair must never read a matrix result directly --
-                        // the compiler's hazard padding does not look into it (the other sigma kernels do the same)
-                        const float lim = -3.402823466e38f;
-                        split_pair(fmaxf(t[8 * s + 2 * j], lim), fmaxf(t[8 * s + 2 * j + 1], lim), fh[s].u[j], fl[s].u[j]);
-                    }
+                for (int s = 0; s < 2; s++) tile_to_frag2<false>(t, s, fh[s].v, fl[s].v);
                 split_pair(hh == 0 ? g31 : 0.0f, 0.0f, fh[2].u[0], fl[2].u[0]);
 #pragma unroll
                 for (int j = 1; j < 4; j++) { fh[2].u[j] = 0; fl[2].u[j] = 0; }
@@ -260,9 +246,9 @@ int nrf_lerf_sigma_exact_lm_strided(const nrf_mlp *m, const void *d_feats_lm, in
     const float *img = reinterpret_cast<const float *>(m->d_packed_sigma_f32);
     const _Float16 *x = reinterpret_cast<const _Float16 *>(d_feats_lm);
     if (d_geo) hipLaunchKernelGGL((lsig::k_lerf_sigma_f32<true>), dim3(grid), dim3(64 * lsig::WAVES), lsig::LDS_BYTES, st, p, x, pstride, d_keep, img, d_sigma,
-                                  reinterpret_cast<lerf::half8 *>(d_geo), geo_stride);
+                                  reinterpret_cast<half8 *>(d_geo), geo_stride);
     else hipLaunchKernelGGL((lsig::k_lerf_sigma_f32<false>), dim3(grid), dim3(64 * lsig::WAVES), lsig::LDS_BYTES, st, p, x, pstride, d_keep, img, d_sigma,
-                            static_cast<lerf::half8 *>(nullptr), (int64_t)0);
+                            static_cast<half8 *>(nullptr), (int64_t)0);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

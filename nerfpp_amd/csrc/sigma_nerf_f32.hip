@@ -27,11 +27,7 @@
 
 namespace nrf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace nsig {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int NW = 4;
 constexpr int BLK = 32 * NW;
@@ -59,7 +55,6 @@ constexpr int ALPHA_FLOATS = 256 + 4;                 // alpha_linear.weight [25
 constexpr int VIEW_BIAS_FLOATS = 128 + 4;             // merged bias [tile 4][lane half 2][16] | rgb bias [3] | pad
 constexpr size_t LDS_BYTES = (size_t)2 * MAXG * 1024 + (BIAS_FLOATS + ALPHA_FLOATS + VIEW_BIAS_FLOATS) * 4;
 static_assert(SIGMA_GROUPS == 8 * (8 + 6 * 32 + 40) && VIEW_GROUPS <= MAXG, "image size");
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 struct Ctx {
     f32x4 *wbuf;                 // [2][MAXG * 64]
     const float *bias_s;         // LDS
@@ -156,15 +151,6 @@ __device__ __forceinline__ f32x16 tile(Ctx &cx, int layer, int mt, int next_ng, 
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     cx.cur ^= 1;
     return acc;
-}
-
-// registers 8s..8s+7 of an fp32 tile -> the (hi, lo) fp16 operand fragments of one k-step (v = hi + lo to 22 bits).  The asm reads VALU results only (the max).
-__device__ __forceinline__ void tile_to_frag2(const f32x16 &t, int s, float lim, half8 &hi, half8 &lo)
-{
-    union { half8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-    for (int j = 0; j < 4; j++) split_pair(fmaxf(t[8 * s + 2 * j], lim), fmaxf(t[8 * s + 2 * j + 1], lim), h.u[j], l.u[j]);
-    hi = h.v; lo = l.v;
 }
 
 // One tile of the colour branch in split precision (mlp_nerf_split_mfma.hip's arithmetic: Wl.xh + Wh.xl + Wh.xh per k-step into one fp32 accumulator): KS k-steps,
@@ -335,7 +321,7 @@ k_sigma_nerf_f32(int64_t npts, const float *__restrict__ pts, const float *__res
         for (int ck = 0; ck < 4; ck++)
             views_chunk<VIEW_CHUNK_KS>(cx, ck < 3 ? VIEW_GROUPS : VIEW_LAST_GROUPS, ck == 0, [&](int k, half8 &bh, half8 &bl) {
                 const int c = 4 * ck + k;                        // chained k-step 0..15
-                tile_to_frag2(hin[c >> 1], c & 1, 0.0f, bh, bl);
+                tile_to_frag2<true>(hin[c >> 1], c & 1, bh, bl);
             }, vacc);
         {
             // PE(4) of the view direction, one row per ray: natural order, element j of k-step s = dirs[16 s + 8 h + j]
@@ -357,7 +343,7 @@ k_sigma_nerf_f32(int64_t npts, const float *__restrict__ pts, const float *__res
                 for (int e = 0; e < 4; e++) v[4 * q4 + e] = v[4 * q4 + e] + bv[e];
             }
 #pragma unroll
-            for (int sp = 0; sp < 2; sp++) tile_to_frag2(v, sp, 0.0f, bb[2 * t + sp][0], bb[2 * t + sp][1]);           // ReLU inside the split
+            for (int sp = 0; sp < 2; sp++) tile_to_frag2<true>(v, sp, bb[2 * t + sp][0], bb[2 * t + sp][1]);           // ReLU inside the split
         }
         const f32x16 c = tile16<RGB_KS>(cx, groups(0), [&](int k, int part) { return bb[k][part]; });
         const int64_t p = p0 + r;

@@ -27,7 +27,7 @@
 // so they are formed the same way: the exact hidden values split into (hi, lo) fp16 fragments, registers 8u..8u+7 of tile t = k-step (t, u) of a 32x32x16 product
 // (any assignment of k inside a k-step is fine as long as the weight fragment uses the same one), three matrix instructions per k-step, 12 per 32 points beside the
 // 192 fp32 ones.  Natural row order: register q of lane half h of the result is row 8(q/4) + 4h + q%4, which IS element q of the colour net's geo operand fragment
-// (perm_row(0, h, q) in mlp_small_mfma.hip) -- split once more and stored as that fragment, planes [hi | lo][column][lane half] of 16 bytes.
+// (perm_row(0, h, q), mfma_frag.h) -- split once more and stored as that fragment, planes [hi | lo][column][lane half] of 16 bytes.
 //
 // Tried and measured (round 3, docs/history/profiles/round3/r3z_sigma_two_crews_ab.log): the packed fp32 FMA of the vector ALUs has the same peak rate as the fp32 matrix
 // instruction (157 TFLOP/s each) and the counters of this kernel show the matrix pipe busy 0.81 of the cycles with NO vector co-execution, so half of the waves
@@ -37,43 +37,20 @@
 // points instead of 512 packed FMAs per 64).  Not kept.  A registers-only probe settles why (tools/scratch/coexec_probe.hip, docs/history/profiles/round3/
 // r3z_fp32_mfma_vs_pk_fma_coexec_probe.log): four matrix waves alone 3.4 ms, four packed-FMA waves alone 4.7 ms, the eight together 8.2 ms -- on this chip the fp32
 // matrix instruction and the packed fp32 FMA execute on the same lanes; 157 TFLOP/s is the ceiling of their SUM.
+#include "mfma_frag.h"
 #include "mlp.h"
 
 namespace nrf {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 sg_half8 __attribute__((ext_vector_type(8)));
-
-// two fp32 values -> packed (hi, lo) fp16 pairs, v = hi + lo to 22 bits (see split_pair in mlp_small_mfma.hip)
-__device__ __forceinline__ void sg_split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo)
+// tile_to_frag2 (mfma_frag.h) of the values times a power of two (the range scale of the split-precision operands, mlp.h): the multiply is also the VALU result
+// the asm of split_pair may read
+__device__ __forceinline__ void sg_frag_scaled(const f32x16 &t, int s, float scale, half8 &hi, half8 &lo)
 {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(v0), "v"(v1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(v0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(v1));
-}
-// registers q0..q0+7 of a tile -> one (hi, lo) operand fragment.  The asm reads VALU results only (the max / a copy), never a matrix result directly.
-__device__ __forceinline__ void sg_frag(const f32x16 &t, int q0, sg_half8 &hi, sg_half8 &lo)
-{
-    union { sg_half8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-    for (int j = 0; j < 4; j++) sg_split_pair(fmaxf(t[q0 + 2 * j], -3.402823466e38f), fmaxf(t[q0 + 2 * j + 1], -3.402823466e38f), h.u[j], l.u[j]);
-    hi = h.v; lo = l.v;
-}
-// ... of the values times a power of two (the range scale of the split-precision operands, mlp.h): the multiply is also the VALU result the asm may read
-__device__ __forceinline__ void sg_frag_scaled(const f32x16 &t, int q0, float scale, sg_half8 &hi, sg_half8 &lo)
-{
-    union { sg_half8 v; uint32_t u[4]; } h, l;
-#pragma unroll
-    for (int j = 0; j < 4; j++) sg_split_pair(t[q0 + 2 * j] * scale, t[q0 + 2 * j + 1] * scale, h.u[j], l.u[j]);
-    hi = h.v; lo = l.v;
+    tile_to_frag2_of(t, s, [scale](float v) { return v * scale; }, hi, lo);
 }
 
 constexpr int SIG_WAVES = 8;                     // 2 per SIMD: one's vector work (ReLU, swaps, the last layer) under the other's matrix chain
 constexpr int SIG_BLOCK_PTS = 64 * SIG_WAVES;    // two 32-point tiles per wave
-
-// neuron carried by row i of an m-tile (see above)
-__host__ __device__ inline int sigma_row_neuron(int i) { return 2 * (4 * (i >> 3) + (i & 3)) + ((i >> 2) & 1); }
 
 // acc[pt][mt] = sum over KS k-steps; A fragments from LDS as [mt][ks / 4][lane][4] floats (one ds_read_b128 per four k-steps, shared by
 // both point tiles); bfn(pt, ks) yields the B operand
@@ -115,16 +92,16 @@ __device__ __forceinline__ void relu_tiles(f32x16 (&acc)[2][2])
 template <int NL, bool F32IN, bool GEO, bool A32>
 __global__ void __launch_bounds__(64 * SIG_WAVES)
 k_sigma_small_f32(int64_t npts, const void *__restrict__ feats, int64_t pstride, const uint8_t *__restrict__ keep, const float *__restrict__ image,
-                  float *__restrict__ sigma, sg_half8 *__restrict__ geo, int64_t geo_stride, const float *__restrict__ scales)
+                  float *__restrict__ sigma, half8 *__restrict__ geo, int64_t geo_stride, const float *__restrict__ scales)
 {
     constexpr int W0_F4 = 2 * 4 * 64, W1_F4 = NL == 3 ? 2 * 8 * 64 : 0;
     __shared__ f32x4 wl[W0_F4 + W1_F4];
     __shared__ float wlast[64];
-    __shared__ sg_half8 wg[GEO ? 4 * 2 * 64 : 1];
+    __shared__ half8 wg[GEO ? 4 * 2 * 64 : 1];
     for (int i = threadIdx.x; i < W0_F4 + W1_F4; i += blockDim.x) wl[i] = reinterpret_cast<const f32x4 *>(image)[i];
     if (threadIdx.x < 64) wlast[threadIdx.x] = image[(W0_F4 + W1_F4) * 4 + threadIdx.x];
     if constexpr (GEO) {
-        const sg_half8 *gi = reinterpret_cast<const sg_half8 *>(image + (W0_F4 + W1_F4) * 4 + 64);
+        const half8 *gi = reinterpret_cast<const half8 *>(image + (W0_F4 + W1_F4) * 4 + 64);
         for (int i = threadIdx.x; i < 4 * 2 * 64; i += blockDim.x) wg[i] = gi[i];
     }
     __syncthreads();
@@ -209,15 +186,15 @@ k_sigma_small_f32(int64_t npts, const void *__restrict__ feats, int64_t pstride,
                 for (int t = 0; t < 2; t++)
 #pragma unroll
                     for (int u = 0; u < 2; u++) {
-                        sg_half8 xh, xl;
-                        sg_frag_scaled(hl[pt][t], 8 * u, hscale, xh, xl);
-                        const sg_half8 ah = wg[((2 * t + u) * 2 + 0) * 64 + lane], al = wg[((2 * t + u) * 2 + 1) * 64 + lane];
+                        half8 xh, xl;
+                        sg_frag_scaled(hl[pt][t], u, hscale, xh, xl);
+                        const half8 ah = wg[((2 * t + u) * 2 + 0) * 64 + lane], al = wg[((2 * t + u) * 2 + 1) * 64 + lane];
                         g = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, xh, g, 0, 0, 0);
                         g = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xl, g, 0, 0, 0);
                         g = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, xh, g, 0, 0, 0);
                     }
-                sg_half8 gh, gl;
-                sg_frag(g, 0, gh, gl);
+                half8 gh, gl;
+                tile_to_frag2<false>(g, 0, gh, gl);
                 const int64_t pp = blk * SIG_BLOCK_PTS + wave * 64 + pt * 32 + r;
                 if (pp < npts) { geo[(pp << 1) + hh] = gh; geo[((geo_stride + pp) << 1) + hh] = gl; }
             }
@@ -257,7 +234,7 @@ bool mlp_small_sigma_image_host(const nrf_mlp_small_desc &d, const std::vector<f
             for (int g = 0; g < ks_count / 4; g++)
                 for (int lane = 0; lane < 64; lane++)
                     for (int j = 0; j < 4; j++) {
-                        const int row = 32 * mt + sigma_row_neuron(lane & 31), k = 2 * (4 * g + j) + (lane >> 5);
+                        const int row = 32 * mt + row_neuron(lane & 31), k = 2 * (4 * g + j) + (lane >> 5);
                         img.push_back(w[(size_t)row * in + k]);
                     }
         off += (size_t)in * out;
@@ -308,7 +285,7 @@ int mlp_small_sigma_f32_lm(const nrf_mlp *m, const void *feats, int f32_in, int6
     const float *img = reinterpret_cast<const float *>(m->d_packed_sigma_f32);
     const int nl = m->small.num_layers;
     if (geo && (m->small.geo_feat_dim > 15 || m->small.hidden_dim != 64)) { set_error("internal: geo hand-over outside the built NeRFSmall family"); return NRF_ERR_UNSUPPORTED; }
-    sg_half8 *g = static_cast<sg_half8 *>(geo);
+    half8 *g = static_cast<half8 *>(geo);
     const bool a32 = (p >> 26) == 0 && (pstride >> 26) == 0;          // the 16 level planes within 4 GB: 32-bit byte offsets
 #define NRF_GO(NL_, F_)                                                                                                                                              \
     do {                                                                                                                                                             \

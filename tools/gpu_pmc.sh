@@ -1,6 +1,10 @@
 #!/bin/bash
-# PMC passes for the dominant kernels (separate passes per counter group, no trace domains besides kernel dispatch)
-set -u
+# PMC passes for the dominant kernels (separate passes per counter group, no trace domains besides kernel dispatch).
+# The first pass that fails, faults or runs into its time limit ends the script with that pass's status: nothing more is started on the card.
+set -euo pipefail
+# a pass that ignores its time limit's TERM is killed 10 s later; a failed pass is named on stderr before set -e ends the script with its status
+timeout() { command timeout -k 10 "$@"; }
+trap 'echo "gpu_pmc.sh: pass ${name:-?} ended with status $?" >&2' ERR
 tag=${1:-pmc}
 ROOTD=$PWD
 mkdir -p gpurun_out

@@ -1,6 +1,9 @@
 #!/bin/bash
-# clock held under load + matrix-pipe busy cycles of the dominant kernels (separate --pmc passes, kernel dispatch only)
-set -u
+# clock held under load + matrix-pipe busy cycles of the dominant kernels (separate --pmc passes, kernel dispatch only); the first pass that fails ends the script
+set -euo pipefail
+# a pass that ignores its time limit's TERM is killed 10 s later; a failed pass is named on stderr before set -e ends the script with its status
+timeout() { command timeout -k 10 "$@"; }
+trap 'echo "gpu_pmc_clock.sh: pass ${name:-?} ended with status $?" >&2' ERR
 # counters are per dispatch: the Chunk loop on ONE stream, so that no two kernels run at the same time (the variable is inherited; nothing stands between rocprofv3's -- and python3)
 export NRF_RENDER_LANES=1
 tag=${1:-pmcclk}

@@ -584,6 +584,36 @@ NRF_API int nrf_lattice_components(const uint8_t *d_mask, int nx, int ny, int nz
                                    size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Image metrics (image_metrics.hip; the reference has only the training loop's PSNR, NeRFExecutor.h:893)
+ * ------------------------------------------------------------------------------------------- */
+/* How good a frame is, on the device and in fp64 (in fp32 the variances E[x^2] - mu^2 cancel against c2: a flat pair 0.25 / 0.75 is off by 1.19e-4).  Images are
+ * [b,h,w,c] fp32 contiguous (the layout of RGBMap), c in 1..4, h and w >= 11, b * c <= 65535; data_range L finite and > 0.
+ *   nrf_ssim_window: HOST.  The 11 weights every kernel here uses: g[k] = exp(-(k-5)^2 / 4.5) (sigma 1.5) divided by the sum of the 11 values added in order k = 0..10.
+ *   nrf_ssim: Wang et al. 2004 over the VALID region (h-10) x (w-10), per channel, every op a double op rounded once, in this order:
+ *     c1 = (0.01 L) * (0.01 L), c2 = (0.03 L) * (0.03 L); the five planes x, y, x*x, y*y, x*y are filtered along the row first, then along the column, each 11-tap sum
+ *     as acc = g[0] * a[0]; acc = acc + g[k] * a[k], k = 1..10 -> mx, my, exx, eyy, exy;
+ *     mxx = mx*mx, myy = my*my, mxy = mx*my; sxx = exx - mxx, syy = eyy - myy, sxy = exy - mxy;
+ *     cs = (2*sxy + c2) / ((sxx + syy) + c2); lum = (2*mxy + c1) / ((mxx + myy) + c1); ssim = lum * cs.
+ *     d_means [b,c,2]: the mean of ssim and the mean of cs over the valid region.  d_map (optional) [b,h-10,w-10,c]: ssim per pixel -- a numpy float64 restatement of
+ *     the order above equals it bit for bit.  The sums are fp64 tile partials in the workspace combined in one ordered pass, no atomics: two runs give the same bits, an
+ *     image's means do not depend on the batch it came in, and they are the same with and without d_map.
+ *   nrf_image_mse: d_mse [b] = the mean over an image's elems_per_image values of ((double)x - (double)y)^2; the same ordered reduction.
+ *   nrf_ms_ssim: d_means [scales,b,c,2], 1 <= scales <= 5 and min(h, w) >> (scales - 1) >= 11.  Scale 0 is nrf_ssim's computation; each further scale first pools both
+ *     images 2 x 2 in double, ((a00 + a01) + (a10 + a11)) * 0.25 (an odd trailing row or column is dropped; the pooled planes stay in the workspace as doubles), then
+ *     runs the same computation on them.  Combining the scales is the caller's (nerfpp_amd/metrics.py: MSSSIM).
+ * A bad shape, c, data_range, scales or a null pointer: NRF_ERR_INVALID_ARG; a workspace below the *_workspace_bytes twin: NRF_ERR_WORKSPACE.  A refusal
+ * launches nothing and writes nothing.  No entry synchronises. */
+NRF_API int nrf_ssim_window(double *out11);
+NRF_API size_t nrf_ssim_workspace_bytes(int b, int h, int w, int c);
+NRF_API int nrf_ssim(const float *d_x, const float *d_y, int b, int h, int w, int c, double data_range, double *d_means, double *d_map, void *d_workspace,
+                     size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_image_mse_workspace_bytes(int b, int64_t elems_per_image);
+NRF_API int nrf_image_mse(const float *d_x, const float *d_y, int b, int64_t elems_per_image, double *d_mse, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_ms_ssim_workspace_bytes(int b, int h, int w, int c, int scales);
+NRF_API int nrf_ms_ssim(const float *d_x, const float *d_y, int b, int h, int w, int c, double data_range, int scales, double *d_means, void *d_workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Density gradient (normals.hip; the reference's calculate_normals, never finished there)
  * ------------------------------------------------------------------------------------------- */
 /* d_sigma [p] (may be NULL) = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at d_pts [p,3], bit for bit (keep mask of NeRFRenderer.h:187-188 included: it writes

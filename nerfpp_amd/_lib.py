@@ -178,6 +178,13 @@ _ABI = """
     nrf_mesh_components(pllpppzp)
     nrf_lattice_components_workspace_bytes(iii)->z
     nrf_lattice_components(piiiipppzp)
+    nrf_ssim_window(p)
+    nrf_ssim_workspace_bytes(iiii)->z
+    nrf_ssim(ppiiiidpppzp)
+    nrf_image_mse_workspace_bytes(il)->z
+    nrf_image_mse(ppilppzp)
+    nrf_ms_ssim_workspace_bytes(iiiii)->z
+    nrf_ms_ssim(ppiiiidippzp)
     nrf_density_grad_workspace_bytes(pl)->z
     nrf_density_grad(pplpppzp)
     nrf_render_rays_workspace_bytes(plp)->z

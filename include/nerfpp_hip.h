@@ -481,7 +481,9 @@ typedef struct nrf_render_params {
  *   NRF_OVERFLOW_DEFERRED          no synchronisation: the words are copied to pinned host memory behind the call's work and looked at by the first LATER render call on
  *                                  this renderer that finds the copy complete, which then returns NRF_ERR_NONFINITE before doing anything (or by nrf_renderer_nonfinite).
  *                                  Up to 32 calls' words may be in flight; the 33rd call waits for the oldest copy.  For pipelines that keep several frames in flight.
- *   NRF_OVERFLOW_IGNORE            no detection at all (the compositing kernel skips the test). */
+ *   NRF_OVERFLOW_IGNORE            no detection at all (the compositing kernel skips the test).
+ * With nrf_set_live_colour on (the default) the fine pass does not evaluate the colour net at coarse depths whose sigma is not positive; their rows read (0, 0, 0, sigma).
+ * A non-finite COLOUR at such a depth -- which met a zero weight and never reached a pixel -- therefore no longer sets the word; a non-finite sigma there still does. */
 enum { NRF_OVERFLOW_AUTO = 0, NRF_OVERFLOW_RERENDER = 1, NRF_OVERFLOW_ERROR = 2, NRF_OVERFLOW_DEFERRED = 3, NRF_OVERFLOW_IGNORE = 4 };
 
 typedef struct nrf_render_outputs {   /* NeRFRendererOutputs / NeRFRenderResult (NeRFRenderer.h:12-26); NULL = not wanted */
@@ -1005,6 +1007,18 @@ enum { NRF_PROF_HASH = 0, NRF_PROF_MLP = 1, NRF_PROF_COMPOSITE = 2, NRF_PROF_SAM
  * loop (also: NRF_RENDER_LANES=1..4).  Process-wide setting, read at every call; the workspace query and the call must see the same value. */
 NRF_API int nrf_set_render_lanes(int lanes);
 NRF_API int nrf_get_render_lanes(void);
+/* The fine pass of the default hierarchical HashNeRF render (NRF_PREC_F16_SPLIT with the exact coarse pass) evaluates the colour net at a coarse depth only where that
+ * depth's density is positive: relu(sigma) = 0 gives alpha = 0 and a weight of exactly 0, so the colour there cannot change a bit of RGB, depth, disparity, acc or the
+ * weights.  Renders that return Raw or add sigma noise evaluate every colour whatever the switch says.  on = 1 (the default; also NRF_LIVE_COLOUR=0 in the environment
+ * turns it off) / 0: the colour net at every coarse depth.  Process-wide, read at every call; workspace sizes do not depend on it. */
+NRF_API int nrf_set_live_colour(int on);
+NRF_API int nrf_get_live_colour(void);
+/* The compaction behind it, on its own: d_list [p] int32 receives the indices i with d_sigma[i] > 0.0f in ascending order (NaN, +-0 and negatives are not listed; entries
+ * from *d_count on are left as they were), d_count [1] int32 their number, and -- unless NULL -- d_raw_rows [p, 4] (16-byte aligned) the row (0, 0, 0, d_sigma[i]) of
+ * every index that is NOT listed, the sigma word copied bit for bit; rows of listed indices are not written.  1 <= p < 2^31.  Deterministic, no atomics, no host
+ * synchronisation. */
+NRF_API size_t nrf_live_points_workspace_bytes(int64_t p);
+NRF_API int nrf_live_points(const float *d_sigma, int64_t p, int32_t *d_list, int32_t *d_count, float *d_raw_rows, void *d_workspace, size_t workspace_bytes, void *stream);
 /* ... per renderer: 1-4 lanes for this renderer's calls whatever the process-wide setting; 0 returns it to that setting (two renderers of one process need not share it). */
 NRF_API int nrf_renderer_set_lanes(nrf_renderer *r, int lanes);
 /* 1 when the fp32 layer products of the training paths (classic and LeRF backward, NeRFSmall's fp32 backward) run as rocBLAS GEMMs on the fp32 matrix cores (the library is

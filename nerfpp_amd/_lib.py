@@ -274,6 +274,10 @@ _ABI = """
     nrf_scratch_trim()->z
     nrf_set_render_lanes(i)
     nrf_get_render_lanes()
+    nrf_set_live_colour(i)
+    nrf_get_live_colour()
+    nrf_live_points_workspace_bytes(l)->z
+    nrf_live_points(plppppzp)
     nrf_renderer_set_lanes(pi)
     nrf_fp32_gemm_available()
     nrf_get_train_gemm()

@@ -140,6 +140,9 @@ int mlp_small_forward_mfma_lm(const nrf_mlp *m, const __half2 *feats, const __ha
                               const uint8_t *keep, int64_t p, float *out, hipStream_t st, const int32_t *src = nullptr);
 int mlp_small_color_from_geo_lm(const nrf_mlp *m, const void *geo, int64_t geo_stride, const float *sigma, const __half *dirs, const __half *dirs_lo, int s,
                                 const uint8_t *keep, int64_t p, float *out, hipStream_t st);
+bool mlp_small_color_list_ok(const nrf_mlp *m, int64_t p, int s);          // the listed launch's 32-bit addressing holds p columns of s-sample rays
+int mlp_small_color_from_geo_list_lm(const nrf_mlp *m, const void *geo, int64_t geo_stride, const float *sigma, const __half *dirs, const __half *dirs_lo, int s,
+                                     int64_t p, const int32_t *list, const int32_t *count, float *out, hipStream_t st);
 int mlp_small_pack_sigma_f32(nrf_mlp *m, const std::vector<float> &host_params);
 int mlp_small_sigma_f32_available(const nrf_mlp *m);
 int mlp_small_sigma_f32_lm(const nrf_mlp *m, const void *feats, int f32_in, int64_t pstride, const uint8_t *keep, int64_t p, float *sigma, hipStream_t st, void *geo = nullptr,

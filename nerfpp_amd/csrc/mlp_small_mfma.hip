@@ -173,14 +173,15 @@ struct SmallPlan {
 // dirs[ray][V] (fp16) shared by the `s` samples of a ray (NeRFRenderer.h:179), and the embedder's keep mask, which is
 // applied to sigma in the epilogue (NeRFRenderer.h:187-188).
 struct SmallInput {
-    const float *x; int x_stride; int in_ch;          // row-major fp32 input
+    union { const float *x; const int32_t *count; };  // row-major fp32 input | LIST (level-major, so x is free): the number of listed points, a device word
+    int x_stride; int in_ch;
     const __half2 *feats; int64_t pstride;            // level-major fp16 input
     const __half *dirs; int s;
     const uint8_t *keep;
     const __half *dirs_lo;                            // split mode: lo parts of the direction features, same layout
     const __half2 *feats_lo;                          // split mode, fp32-valued features (HashEmbedder): lo plane, same layout as feats
     const int32_t *src;                               // optional: point i reads column src[i] of feats / keep (the renderer's feature reuse: the fine pass's coarse depths
-                                                      // point at the coarse pass's columns); NULL: column i
+                                                      // point at the coarse pass's columns); NULL: column i.  LIST: the listed columns
     // GEOIN (colour net only): the sigma net's output comes from the coarse pass's exact kernel (sigma_small_f32.hip, GEO) -- the (sigma, geo_feat) operand fragment of
     // point i as planes [hi | lo][geo_stride][2 lane halves] of 16 bytes, and sigma itself (keep mask applied) as [p] floats.  feats is not read.
     const half8 *geo; int64_t geo_stride;
@@ -220,11 +221,21 @@ constexpr int small_drop_of(int id) { return (int)((((unsigned long long)NRF_SMA
 // LMLO: the level-major features come as (hi, lo) planes (fp32-valued features of the LibTorch HashEmbedder); without it they are exact
 // fp16 numbers (CuHashEmbedder rounds its output to fp16 itself, CuHashEmbedder.cu:95) and the layer-0 operand has no lo part.
 // A32 (level-major input without a merge map, < 2^26 points, planes < 2^27 columns: every launch of the renderer's default mode): 32-bit addressing, see load_inputs
-template <int IN_KS, int V_KS, int NL, int NLC, bool LM, bool SPLIT, bool LMLO = false, bool GEOIN = false, bool A32 = false>
+// LIST (the GEOIN, A32 kernel only): point j of the launch is column col = in.src[j] of the coarse pass -- geo fragments, sigma, the ray (col / s) and the output row
+// all come from col -- and the point count is the device word *in.count (live_points.hip), read once before the loop; the npts argument is only the upper bound the
+// grid was sized from.  The list travels one iteration ahead of the operands (load_cols), like a merge map.  Listed points have sigma > 0, which a masked point never
+// has, so the keep byte is not fetched.  (The parameter is the last one and SmallInput keeps its layout: the other instantiations compile to the code they compiled to.)
+template <int IN_KS, int V_KS, int NL, int NLC, bool LM, bool SPLIT, bool LMLO = false, bool GEOIN = false, bool A32 = false, bool LIST = false>
 __global__ void __launch_bounds__(64 * waves_of(SPLIT), SPLIT ? NRF_SPLIT_MINWAVES : 2)
 k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, float *__restrict__ out, int out_stride)
 {
     using Plan = SmallPlan<IN_KS, V_KS, NL, NLC>;
+    static_assert(!LIST || (GEOIN && A32), "the list mode exists for the colour-only kernel with 32-bit addressing");
+    if constexpr (LIST) {
+        const int32_t cnt = *in.count;
+        npts = cnt < npts ? cnt : npts;          // (count <= the bound by construction; the clamp keeps a wrong word from becoming an address)
+        if ((int64_t)blockIdx.x * block_pts_of(SPLIT) >= npts) return;          // workgroup-uniform, before the barrier: count == 0 runs no iteration and dereferences nothing
+    }
     constexpr int NP = SPLIT ? 2 : 1;
     constexpr int BLOCK_PTS = block_pts_of(SPLIT);
     constexpr bool IN_LO = SPLIT && (!LM || LMLO);
@@ -263,6 +274,16 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
     // So the columns travel one iteration AHEAD of the operands (load_cols for block i + 2 while block i computes), and the keep byte is fetched with the operands.
     static_assert(!A32 || (LM && SPLIT), "32-bit addressing is instantiated for the split-precision level-major kernels");
     auto load_cols = [&](int64_t blk_, int32_t (&cols)[PT]) {
+        if constexpr (LIST) {
+            const uint32_t q0 = (uint32_t)blk_ * (uint32_t)BLOCK_PTS + (uint32_t)(wave * (32 * PT));
+#pragma unroll
+            for (int pt = 0; pt < PT; pt++) {
+                uint32_t q = q0 + (uint32_t)(pt * 32 + r);
+                q = q < (uint32_t)npts ? q : (uint32_t)npts - 1u;          // npts >= 1 here: a workgroup with nothing to do has left
+                cols[pt] = in.src[q];
+            }
+            return;
+        }
         if (A32 || !(LM && in.src)) return;
         const int64_t p0_ = blk_ * BLOCK_PTS + wave * (32 * PT);
 #pragma unroll
@@ -285,7 +306,8 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
                     // the ray index by a multiply -- the generic path below spends ~150 vector instructions per iteration on 64-bit indices and two divisions
                     uint32_t pu = (uint32_t)p0_ + (uint32_t)(pt * 32 + r);
                     pu = pu < (uint32_t)npts ? pu : (uint32_t)npts - 1u;
-                    if (in.keep) kpv[pt] = in.keep[pu];
+                    if constexpr (LIST) pu = (uint32_t)cols[pt];          // the column of list position pu (clamped by load_cols)
+                    else if (in.keep) kpv[pt] = in.keep[pu];
                     if constexpr (GEOIN) {
                         const uint32_t goff = (pu * 2u + (uint32_t)h) * 16u;
                         bg[pt][0] = *reinterpret_cast<const half8 *>(reinterpret_cast<const char *>(in.geo) + goff);
@@ -364,6 +386,7 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
     // PREFETCH: the operands of the NEXT block iteration are requested right after this iteration's first layer has consumed its own, and
     // arrive while the rest of the network runs (the loads' latency, ~2 us under load, is otherwise exposed once per ~10 us iteration)
     constexpr bool PREFETCH = LM && (SPLIT ? (NRF_SMALL_PREFETCH_SPLIT != 0) : (NRF_SMALL_PREFETCH_F16 != 0));
+    static_assert(!LIST || PREFETCH, "the list mode hands its columns over with the prefetched operands");
     half8 bx[PT][IN_KS][NP];
     half8 bv[PT][V_KS][NP];
     half8 bxn[PREFETCH ? PT : 1][IN_KS][NP];
@@ -373,14 +396,20 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
     (void)bg; (void)bgn; (void)sgv; (void)sgn;
     uint8_t kp[PT], kpn[PT];
     int32_t cols_next[PT];                                   // columns of the block after the one whose operands are being prefetched
+    int32_t cols_cur[PT], cols_pre[PT];                      // LIST: the columns of this iteration's points (its output rows) and of the prefetched operands
+    (void)cols_cur; (void)cols_pre;
 #pragma unroll
-    for (int pt = 0; pt < PT; pt++) { kp[pt] = 1; kpn[pt] = 1; cols_next[pt] = 0; }
+    for (int pt = 0; pt < PT; pt++) { kp[pt] = 1; kpn[pt] = 1; cols_next[pt] = 0; cols_cur[pt] = 0; cols_pre[pt] = 0; }
     if constexpr (PREFETCH) {
         if ((int64_t)blockIdx.x < nblocks) {
             int32_t c0[PT];
             load_cols(blockIdx.x, c0);
             if ((int64_t)blockIdx.x + gridDim.x < nblocks) load_cols((int64_t)blockIdx.x + gridDim.x, cols_next);
             load_inputs(blockIdx.x, c0, bx, bv, kp, bg, sgv);
+            if constexpr (LIST) {
+#pragma unroll
+                for (int pt = 0; pt < PT; pt++) cols_cur[pt] = c0[pt];
+            }
         }
     }
 #ifdef NRF_SMALL_TRACE
@@ -519,6 +548,10 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
             if constexpr (PREFETCH) {
                 if (more) {
                     load_inputs(blk + gridDim.x, cols_next, bxn, bvn, kpn, bgn, sgn);             // cols_next arrived an iteration ago
+                    if constexpr (LIST) {
+#pragma unroll
+                        for (int pt = 0; pt < PT; pt++) cols_pre[pt] = cols_next[pt];
+                    }
                     if (blk + 2 * (int64_t)gridDim.x < nblocks) load_cols(blk + 2 * (int64_t)gridDim.x, cols_next);
                 }
             }
@@ -594,8 +627,9 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
         if (h == 0) {
 #pragma unroll
             for (int pt = 0; pt < PT; pt++) {
-                const int64_t p = p0 + pt * 32 + r;
+                int64_t p = p0 + pt * 32 + r;
                 if (p < npts) {
+                    if constexpr (LIST) p = cols_cur[pt];          // the output row of a listed point is its column
                     float sg;
                     if constexpr (GEOIN) sg = sgv[pt]; else if constexpr (SPLIT) sg = sig[pt][0][0] * inv_sigma; else sg = sig[pt][0][0];
                     if constexpr (LM) { if (!kp[pt]) sg = 0.0f; }                                    // the embedder's keep mask (NeRFRenderer.h:187-188), fetched with the operands
@@ -620,6 +654,7 @@ k_mlp_small_mfma(int64_t npts, SmallInput in, const half8 *__restrict__ packed, 
                         for (int q = 0; q < NP; q++) bv[pt][s][q] = bvn[pt][s][q];
                     kp[pt] = kpn[pt];
                     if constexpr (GEOIN) { bg[pt][0] = bgn[pt][0]; bg[pt][NP - 1] = bgn[pt][NP - 1]; sgv[pt] = sgn[pt]; }
+                    if constexpr (LIST) cols_cur[pt] = cols_pre[pt];
                 }
             }
         }
@@ -751,7 +786,7 @@ int mlp_small_pack_f16(nrf_mlp *m, const std::vector<float> &hp)
 }
 
 template <int V_KS, int NL, int NLC>
-static int launch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool split, int64_t p, float *out, int os, hipStream_t st)
+static int launch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool split, int64_t p, float *out, int os, hipStream_t st, bool listed)
 {
     using Plan = SmallPlan<2, V_KS, NL, NLC>;
     const size_t lds = (size_t)Plan::total() * 1024 * (split ? 2 : 1);
@@ -769,11 +804,15 @@ static int launch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool sp
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * waves_of(SP_)), lds, st, p, in, img, out, os);                                          \
     } while (0)
     // 32-bit byte offsets: points, feature planes (4 levels apart), geo fragments and the per-ray direction rows all below 4 GB
-    const bool a32 = lm && split && !in.src && (p >> 26) == 0 && (in.pstride >> 27) == 0 && (in.geo_stride >> 26) == 0 && in.ray_mul != 0 &&
+    const bool a32 = lm && split && (!in.src || listed) && (p >> 26) == 0 && (in.pstride >> 27) == 0 && (in.geo_stride >> 26) == 0 && in.ray_mul != 0 &&
                      (((uint64_t)(p / (in.s > 0 ? in.s : 1)) + 1) * (uint64_t)(32 * V_KS)) >> 32 == 0;
     if (in.geo) {
         if (!lm || !split) { set_error("internal: the colour-only NeRFSmall kernel is split precision, level-major"); return NRF_ERR_INVALID_ARG; }
-        if (a32) NRF_GO(true, true, false, true, true); else NRF_GO(true, true, false, true);
+        if (listed) {
+            // p is the bound the grid is sized from; the kernel reads the count itself
+            if (!a32 || !in.src || !in.count) { set_error("internal: the listed colour-only launch needs 32-bit addressing ranges (%lld points)", (long long)p); return NRF_ERR_INVALID_ARG; }
+            NRF_GO(true, true, false, true, true, true);
+        } else if (a32) NRF_GO(true, true, false, true, true); else NRF_GO(true, true, false, true);
     } else if (lm) {
         if (split) {
             if (in.feats_lo) { if (a32) NRF_GO(true, true, true, false, true); else NRF_GO(true, true, true); }
@@ -786,7 +825,7 @@ static int launch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool sp
     return NRF_OK;
 }
 
-static int dispatch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool split, int64_t p, float *out, int os, hipStream_t st);
+static int dispatch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool split, int64_t p, float *out, int os, hipStream_t st, bool listed = false);
 
 int mlp_small_mfma_available(const nrf_mlp *m) { return m && m->family == MLP_SMALL && m->d_packed_f16 != nullptr && m->d_packed_split != nullptr; }
 
@@ -797,7 +836,7 @@ int mlp_small_forward_mfma_lm(const nrf_mlp *m, const __half2 *feats, const __ha
 {
     if (!mlp_small_mfma_available(m)) { set_error("internal: matrix-core NeRFSmall image missing"); return NRF_ERR_UNSUPPORTED; }
     ProfScope prof(NRF_PROF_MLP, st);
-    SmallInput in{nullptr, 0, m->small.input_ch, feats, pstride, dirs, s, keep, dirs_lo, dirs_lo ? feats_lo : nullptr, src, nullptr, 0, nullptr};
+    SmallInput in{{nullptr}, 0, m->small.input_ch, feats, pstride, dirs, s, keep, dirs_lo, dirs_lo ? feats_lo : nullptr, src, nullptr, 0, nullptr};
     return dispatch_small(m, in, true, dirs_lo != nullptr, p, out, 4, st);
 }
 
@@ -809,8 +848,27 @@ int mlp_small_color_from_geo_lm(const nrf_mlp *m, const void *geo, int64_t geo_s
     if (!mlp_small_mfma_available(m)) { set_error("internal: matrix-core NeRFSmall image missing"); return NRF_ERR_UNSUPPORTED; }
     if (!geo || !sigma || !dirs_lo) { set_error("internal: colour-only pass without geo planes / sigma / split direction features"); return NRF_ERR_INVALID_ARG; }
     ProfScope prof(NRF_PROF_MLP_COLOUR, st);
-    SmallInput in{nullptr, 0, m->small.input_ch, nullptr, 0, dirs, s, keep, dirs_lo, nullptr, nullptr, static_cast<const half8 *>(geo), geo_stride, sigma};
+    SmallInput in{{nullptr}, 0, m->small.input_ch, nullptr, 0, dirs, s, keep, dirs_lo, nullptr, nullptr, static_cast<const half8 *>(geo), geo_stride, sigma};
     return dispatch_small(m, in, true, true, p, out, 4, st);
+}
+
+// The same over the listed columns only: list[0 .. *count) of the p columns (live_points.hip; ascending, both on the device), out row = the column.  Rows of columns
+// that are not listed are not written.  Callers ask mlp_small_color_list_ok first.
+bool mlp_small_color_list_ok(const nrf_mlp *m, int64_t p, int s)
+{
+    // the ranges of launch_small's 32-bit addressing for this launch: points, geo fragments and per-ray direction rows below 4 GB
+    const int v_ks = m->small.input_ch_views / 16;
+    return s >= 1 && p >= 1 && (p >> 26) == 0 && (((uint64_t)(p / s) + 1) * (uint64_t)(32 * v_ks)) >> 32 == 0;
+}
+
+int mlp_small_color_from_geo_list_lm(const nrf_mlp *m, const void *geo, int64_t geo_stride, const float *sigma, const __half *dirs, const __half *dirs_lo, int s,
+                                     int64_t p, const int32_t *list, const int32_t *count, float *out, hipStream_t st)
+{
+    if (!mlp_small_mfma_available(m)) { set_error("internal: matrix-core NeRFSmall image missing"); return NRF_ERR_UNSUPPORTED; }
+    if (!geo || !sigma || !dirs_lo || !list || !count) { set_error("internal: listed colour-only pass without geo planes / sigma / split direction features / list"); return NRF_ERR_INVALID_ARG; }
+    SmallInput in{{nullptr}, 0, m->small.input_ch, nullptr, 0, dirs, s, nullptr, dirs_lo, nullptr, list, static_cast<const half8 *>(geo), geo_stride, sigma};
+    in.count = count;
+    return dispatch_small(m, in, true, true, p, out, 4, st, true);
 }
 
 int mlp_small_forward_mfma(const nrf_mlp *m, const float *x, int xs, int64_t p, int split, float *out, int os, hipStream_t st)
@@ -822,11 +880,11 @@ int mlp_small_forward_mfma(const nrf_mlp *m, const float *x, int xs, int64_t p, 
         return NRF_ERR_UNSUPPORTED;
     }
     if ((xs % 4) != 0 || (reinterpret_cast<uintptr_t>(x) & 15)) { set_error("NRF_PREC_F16_MFMA: input rows must be 16-byte aligned"); return NRF_ERR_INVALID_ARG; }
-    SmallInput in{x, xs, d.input_ch, nullptr, 0, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
+    SmallInput in{{x}, xs, d.input_ch, nullptr, 0, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     return dispatch_small(m, in, false, split != 0, p, out, os, st);
 }
 
-static int dispatch_small(const nrf_mlp *m, const SmallInput &in_, bool lm, bool split, int64_t p, float *out, int os, hipStream_t st)
+static int dispatch_small(const nrf_mlp *m, const SmallInput &in_, bool lm, bool split, int64_t p, float *out, int os, hipStream_t st, bool listed)
 {
     const auto &d = m->small;
     SmallInput in = in_;
@@ -841,7 +899,7 @@ static int dispatch_small(const nrf_mlp *m, const SmallInput &in_, bool lm, bool
         else { in.ray_mul = (uint32_t)((((uint64_t)1 << (31 + L)) + (uint64_t)in.s - 1) / (uint64_t)in.s); in.ray_shift = L - 1; }
     }
     const int v = d.input_ch_views / 16;
-#define NRF_CASE(V, NL, NLC) if (v == V && d.num_layers == NL && d.num_layers_color == NLC) return launch_small<V, NL, NLC>(m, in, lm, split, p, out, os, st);
+#define NRF_CASE(V, NL, NLC) if (v == V && d.num_layers == NL && d.num_layers_color == NLC) return launch_small<V, NL, NLC>(m, in, lm, split, p, out, os, st, listed);
     NRF_CASE(1, 3, 4) NRF_CASE(1, 3, 3) NRF_CASE(1, 3, 2) NRF_CASE(1, 2, 4) NRF_CASE(1, 2, 3) NRF_CASE(1, 2, 2)
     NRF_CASE(4, 3, 4) NRF_CASE(4, 3, 3) NRF_CASE(4, 3, 2) NRF_CASE(4, 2, 4) NRF_CASE(4, 2, 3) NRF_CASE(4, 2, 2)
 #undef NRF_CASE

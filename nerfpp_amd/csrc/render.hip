@@ -10,6 +10,7 @@
 #include "chunk_loop.h"
 #include "encode.h"
 #include "hash_fast.h"
+#include "live_points.h"
 #include "mlp.h"
 #include "stoch.h"
 
@@ -465,6 +466,7 @@ struct PathWs {
     FastWs fw;                             // fast without feature reuse (likewise)
     ReuseWs rw;                            // reuse
     void *geo_planes; float *raw_cols;     // geo_reuse: operand fragments of the coarse columns, network outputs by column
+    int32_t *live_list, *live_count; LiveWs live;      // geo_reuse: the coarse columns with sigma > 0, their number, the compaction's scratch (live_points.hip)
     int32_t *rr_src; float *rr_znew, *rr_rawnew;      // reuse_raw: merge map, new-sample depths and their network outputs
 };
 static PathWs path_layout(Bump &b, const nrf_renderer *r, const Path &a, int64_t n, int s, int ni, int prec)
@@ -474,7 +476,11 @@ static PathWs path_layout(Bump &b, const nrf_renderer *r, const Path &a, int64_t
     const int64_t pmax = n * (int64_t)(a.reuse_raw ? (s > ni ? s : ni) : sf);          // points of the largest network pass
     if (a.reuse) {
         w.rw = reuse_layout(b, n, s, ni, a.ngp && a.split, a.ngp && a.sigma_only);
-        if (a.geo_reuse) { w.geo_planes = b.take<char>((size_t)n * s * 64); w.raw_cols = b.take<float>((size_t)n * sf * 4); }
+        if (a.geo_reuse) {
+            w.geo_planes = b.take<char>((size_t)n * s * 64); w.raw_cols = b.take<float>((size_t)n * sf * 4);
+            // (carved whatever nrf_set_live_colour says: the size a caller asked for does not depend on a switch that may move before the call)
+            w.live_list = b.take<int32_t>((size_t)n * s); w.live_count = b.take<int32_t>(1); w.live = live_points_layout(b, n * (int64_t)s);
+        }
     } else if (a.fast) w.fw = fast_layout(b, r, pmax);
     else if (!a.fast_classic) w.net = network_layout(b, r, pmax, prec);
     if (a.reuse_raw) {
@@ -816,7 +822,13 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
         if (!path.ngp) r->view.set(rw.feats, rw.cols, rw.keep, rw.src, n, sf);
         if (path.geo_reuse) {
             const int64_t nc = n * (int64_t)s;
-            NRF_TRY(mlp_small_color_from_geo_lm(r->desc.mlp, pw.geo_planes, nc, cw.raw_c, cw.dirs16, cw.dirs_lo, s, rw.keep, nc, pw.raw_cols, st));
+            // The colour of a coarse depth with sigma <= 0 (or NaN) meets a weight of exactly 0 in the compositing below: the colour net runs over the live columns only,
+            // and the dead ones get the row (0, 0, 0, sigma).  Not when the caller takes Raw (every colour is wanted there) or when sigma noise may lift a dead sigma.
+            if (!out->d_raw && !nz.on && live_colour_on() && mlp_small_color_list_ok(r->desc.mlp, nc, s)) {
+                ProfScope prof(NRF_PROF_MLP_COLOUR, st);
+                NRF_TRY(live_points_launch(cw.raw_c, nc, pw.live_list, pw.live_count, pw.raw_cols, pw.live, st));
+                NRF_TRY(mlp_small_color_from_geo_list_lm(r->desc.mlp, pw.geo_planes, nc, cw.raw_c, cw.dirs16, cw.dirs_lo, s, nc, pw.live_list, pw.live_count, pw.raw_cols, st));
+            } else NRF_TRY(mlp_small_color_from_geo_lm(r->desc.mlp, pw.geo_planes, nc, cw.raw_c, cw.dirs16, cw.dirs_lo, s, rw.keep, nc, pw.raw_cols, st));
             NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats + nc, rw.feats_lo ? rw.feats_lo + nc : nullptr, rw.cols, cw.dirs16, cw.dirs_lo, ni, rw.keep + nc, n * (int64_t)ni,
                                               pw.raw_cols + nc * 4, st));
             if (out->d_raw) {          // the caller wants raw in depth order

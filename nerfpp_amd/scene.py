@@ -103,10 +103,12 @@ def synth_hash_table(n_levels, log2_t, n_feat, base_seed=5000, amp=0.5):
 
 
 def make_hash_scene(mode="cu", n_levels=16, n_feat=2, log2_t=19, base=16, finest=512, sh_degree=4, num_layers_color=4, seed=5000,
-                    table_amp=0.5, sigma_scale=30.0, bbox=LEGO_BBOX, num_layers=3, geo=15):
+                    table_amp=0.5, sigma_scale=30.0, bbox=LEGO_BBOX, num_layers=3, geo=15, table=None, dense_budget=None):
     """HashNeRF (BASELINE config 3/4): hash grid + SH + NeRFSmall.  mode 'cu' = CuHashEmbedder + CuSHEncoder (the named
-    plugin), 'ngp' = HashEmbedder + SHEncoder (the LibTorch CPU twin the oracle/_ref pins)."""
-    table = synth_hash_table(n_levels, log2_t, n_feat, seed, table_amp)
+    plugin), 'ngp' = HashEmbedder + SHEncoder (the LibTorch CPU twin the oracle/_ref pins).
+    table / dense_budget: the caller's table instead of the synthetic one, and a bake budget in force from the first bake on (the image is baked once)."""
+    if table is None:
+        table = synth_hash_table(n_levels, log2_t, n_feat, seed, table_amp)
     if mode == "cu":
         emb = CuHashEmbedder("embedder", bbox, n_levels, n_feat, log2_t, base, finest)
         primes = np.array(CU_PRIMES[:3 * n_levels], np.int32)
@@ -116,6 +118,8 @@ def make_hash_scene(mode="cu", n_levels=16, n_feat=2, log2_t=19, base=16, finest
         emb = HashEmbedder("embedder", bbox, n_levels, n_feat, log2_t, base, finest)
         primes = None
         dirs = SHEncoder("embeddirs", 3, sh_degree)
+    if dense_budget is not None:
+        emb.set_dense_budget(dense_budget)          # before the table completes the handle: takes effect at its first bake
     emb.set_table(table)
     in_ch, in_views = n_levels * n_feat, sh_degree * sh_degree
     params = synth_linear_stack(small_shapes(in_ch, in_views, num_layers, 64, geo, num_layers_color, 64), seed + 1000, 1.6, 0.0,

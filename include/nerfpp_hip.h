@@ -65,11 +65,17 @@ NRF_API int nrf_ndc_rays(int h, int w, float focal, float near_plane, const floa
  * nrf_precrop_bounds : CalculateBounds (:44-65), host only; out = {h_start, h_end, w_start, w_end}, inclusive.
  * nrf_rand_pixels    : the batch's pixel coordinates (:154-155 draws torch::randint): counter-based, element k of iteration `iter` is
  *                      lo + floor(u32(seed, stream, iter*n + k) * range / 2^32), streams 16 (rows) / 17 (columns) of include/nrf_rng.h.
+ * nrf_rand_patches   : n_patches square patches of patch x patch pixels inside the same (inclusive) crop, for losses over neighbourhoods (nrf_ssim_loss): patch k's
+ *                      origin row is h_start + floor(u32(seed, 19, iter*n_patches + k) * (h_end - h_start - patch + 2) / 2^32), its column the same with stream 20 and
+ *                      the w bounds; element k*patch*patch + i*patch + j is pixel (oy + i, ox + j).  d_rand_h / d_rand_w [n_patches * patch * patch] feed nrf_ray_batch /
+ *                      nrf_gather_pixels unchanged.  patch < 1, patch > 4096 or a crop smaller than the patch: NRF_ERR_INVALID_ARG, nothing launched.
  * nrf_ray_batch      : GetRayBatch (:109-145): rays through pixels (rand_h[k], rand_w[k]); cone_angle = (1/fx + 1/fy)/2 to host.
  * nrf_gather_pixels  : target_s = CurrentImage.index({rand_h, rand_w}) (:156); image [h, w, c] fp32 on the device. */
 NRF_API int nrf_precrop_bounds(int h, int w, int iter, int precrop_iters, float precrop_frac, int *out);
 NRF_API int nrf_rand_pixels(uint64_t seed, int64_t iter, int h_start, int h_end, int w_start, int w_end, int64_t n, int64_t *d_rand_h,
                             int64_t *d_rand_w, void *stream);
+NRF_API int nrf_rand_patches(uint64_t seed, int64_t iter, int h_start, int h_end, int w_start, int w_end, int64_t n_patches, int patch, int64_t *d_rand_h,
+                             int64_t *d_rand_w, void *stream);
 NRF_API int nrf_ray_batch(const float *K, const float *c2w, const int64_t *d_rand_h, const int64_t *d_rand_w, int64_t n, float *d_o, float *d_d,
                           float *cone_angle, void *stream);
 NRF_API int nrf_gather_pixels(const float *d_image, int h, int w, int c, const int64_t *d_rand_h, const int64_t *d_rand_w, int64_t n, float *d_out,
@@ -614,6 +620,21 @@ NRF_API int nrf_image_mse(const float *d_x, const float *d_y, int b, int64_t ele
 NRF_API size_t nrf_ms_ssim_workspace_bytes(int b, int h, int w, int c, int scales);
 NRF_API int nrf_ms_ssim(const float *d_x, const float *d_y, int b, int h, int w, int c, double data_range, int scales, double *d_means, void *d_workspace,
                         size_t workspace_bytes, void *stream);
+
+/* SSIM as a training loss: d_loss [2] = {1 - m, m}, m = the mean of nrf_ssim's ssim over ALL n = b * (h-10) * (w-10) * c valid values, and the gradient of
+ * 1 - m with respect to x.  Images as above (the domain of nrf_ssim); weight finite and >= 0.  d_g_x [b,h,w,c] fp32 is ACCUMULATED into; d_grad64 (optional)
+ * [b,h,w,c] is written.  Every op is a double op rounded once, in this order:
+ *   1. mx, my, exx, eyy, exy, mxx, myy, mxy, sxx, syy, sxy, cs, lum, ssim as nrf_ssim states them; cd = (sxx + syy) + c2 and ld = (mxx + myy) + c1 are its denominators;
+ *   2. per valid pixel  A = cs * (2*(my - lum*mx)/ld) + lum * (2*(cs*mx - my)/cd),  B = -(ssim/cd),  Cc = 2*lum/cd;
+ *   3. the transposed window T(M) along one axis, M padded with 10 zeros on both sides: acc = g[0]*M[p]; acc = acc + g[k]*M[p-k], k = 1..10 -- along the column
+ *      (image rows) first, then along the row: [h-10, w-10] -> [h, w];
+ *   4. grad64 = -(((T(A) + 2*x*T(B)) + y*T(Cc))) / n, n as a double;  g_x[i] = g_x[i] + (float)(weight * grad64[i]); weight == 0 leaves g_x alone.
+ * A numpy float64 restatement of this order equals d_grad64 by value (tests/ssim_loss_ref.py).  No atomics: the sum is fp64 workgroup partials in the workspace added in
+ * one ordered pass, every gradient element has one writer; two runs give the same bits, the result is the same with and without d_grad64, and an image's
+ * grad64 * n does not depend on the other images of the batch.  Refusals and the workspace as for the entries above. */
+NRF_API size_t nrf_ssim_loss_workspace_bytes(int b, int h, int w, int c);
+NRF_API int nrf_ssim_loss(const float *d_x, const float *d_y, int b, int h, int w, int c, double data_range, double weight, double *d_loss, float *d_g_x,
+                          double *d_grad64, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Density gradient (normals.hip; the reference's calculate_normals, never finished there)

@@ -87,6 +87,7 @@ _ABI = """
     nrf_ndc_rays(iiffpplppp)
     nrf_precrop_bounds(iiiifp)
     nrf_rand_pixels(qliiiilppp)
+    nrf_rand_patches(qliiiilippp)
     nrf_ray_batch(pppplpppp)
     nrf_gather_pixels(piiipplpp)
     nrf_aabb(ppplfppp)
@@ -185,6 +186,8 @@ _ABI = """
     nrf_image_mse(ppilppzp)
     nrf_ms_ssim_workspace_bytes(iiiii)->z
     nrf_ms_ssim(ppiiiidippzp)
+    nrf_ssim_loss_workspace_bytes(iiii)->z
+    nrf_ssim_loss(ppiiiiddppppzp)
     nrf_density_grad_workspace_bytes(pl)->z
     nrf_density_grad(pplpppzp)
     nrf_render_rays_workspace_bytes(plp)->z

@@ -18,6 +18,7 @@
 //   it came in.
 // k_pool2<T>: ((a00 + a01) + (a10 + a11)) * 0.25 in double, an odd trailing row / column dropped; the pooled planes are doubles in the workspace.
 // k_mse: 4096 elements per block, lane t takes t, t + 256, ... in ascending order; the same partials and k_finish.
+// k_ssim_loss<CT> / k_ssim_loss_finish: 1 - mean SSIM as a training loss and its gradient d loss / d x (nrf_ssim_loss); described where they stand.
 #include "workspace.h"
 
 #include <cmath>
@@ -259,6 +260,169 @@ template <class T> int pool_launch(const T *in, int b, int h, int w, int c, doub
 
 inline bool range_ok(double data_range) { return std::isfinite(data_range) && data_range > 0.0; }
 
+// ---- SSIM as a training loss: 1 - mean SSIM and its gradient with respect to x (nrf_ssim_loss; the operation order is in include/nerfpp_hip.h) ----
+// k_ssim_loss<CT>: one workgroup of 256 lanes per 32 x 32 tile of the GRADIENT (= of the image) of one channel of one image, everything between the inputs and the
+// gradient in LDS.  A gradient pixel p collects the coefficient maps at the valid pixels o = p - 10 .. p, and those need the inputs o .. o + 10: per axis the tile
+// holds the coefficient pixels [max(g0 - 10, 0), min(g0 + 32, h - 10)) -- at most CT of them -- and 10 more input pixels.  Beyond that range the coefficient maps
+// are the padded zeros of the definition: their taps are skipped (acc starts at 0.0 and takes the remaining taps in the order k = 0..10; 0.0 + a == a and a + 0.0 == a,
+// so the values are the definition's).
+//   CT = 42: the tiles of a large image (inputs 52 x 52).  LDS 21.6 KB inputs + 87.4 KB row-pass moments + 42.3 KB coefficient maps = 151.3 KB, one workgroup per CU.
+//   CT = 22: a whole image of h, w <= 32 in one workgroup -- the training patches.  8.2 + 28.2 + 11.6 = 48.0 KB, three workgroups per CU.
+//   1. inputs -> LDS;  2. row pass of the five moments (k_ssim's order);  3. column pass, the SSIM formula, A / B / Cc -> LDS, and the sum of ssim over the valid
+//   pixels INSIDE the gradient tile (each valid pixel lies in exactly one);  4. transposed window along the column into the moments' LDS (dead by then);  5. along
+//   the row, the combination with x and y, grad64 and the accumulation into g_x: one lane per element, no atomics.
+//   The sums: lane, wave shuffle tree, four wave sums in order -> one fp64 partial per workgroup; k_ssim_loss_finish adds them in k_finish's fixed order.
+constexpr int SL_CT_TILE = SS_TILE + SS_APRON, SL_CT_WHOLE = SS_TILE - SS_APRON;
+
+inline int64_t ssim_loss_tiles(int h, int w) { return ceil_div(h, SS_TILE) * ceil_div(w, SS_TILE); }
+
+inline bool ssim_loss_shape_ok(int b, int h, int w, int c) { return ssim_shape_ok(b, h, w, c) && ssim_loss_tiles(h, w) < ((int64_t)1 << 31); }
+
+template <int CT>
+__global__ void __launch_bounds__(IM_THREADS)
+k_ssim_loss(const float *__restrict__ x, const float *__restrict__ y, int h, int w, int c, int tiles_x, SsimWindow win, double c1, double c2, double n_valid,
+            double weight, float *__restrict__ g_x, double *__restrict__ grad64, double *__restrict__ partials)
+{
+    constexpr int IT = CT + SS_APRON, GT = SS_TILE;
+    static_assert(3 * GT <= 5 * IT, "the column pass of the transposed window reuses the moments' LDS");
+    __shared__ double s_m[5 * IT * CT];          // [5][IT][CT] moments after the row pass; from step 4 on [3][GT][CT]: T along the column
+    __shared__ double s_c[3 * CT * CT];          // [3][CT][CT] A, B, Cc
+    __shared__ float s_x[IT * IT], s_y[IT * IT];
+    __shared__ double s_sum[IM_THREADS / 64];
+    const int t = threadIdx.x;
+    const int gy0 = (int)(blockIdx.x / (unsigned)tiles_x) * GT, gx0 = (int)(blockIdx.x % (unsigned)tiles_x) * GT;
+    const int img = (int)(blockIdx.y / (unsigned)c), ch = (int)(blockIdx.y % (unsigned)c);
+    const int64_t base = (int64_t)img * h * w * c + ch;
+    const int oh = h - SS_APRON, ow = w - SS_APRON;
+    const int cy0 = gy0 > SS_APRON ? gy0 - SS_APRON : 0, cx0 = gx0 > SS_APRON ? gx0 - SS_APRON : 0;
+    const int n_cy = (gy0 + GT < oh ? gy0 + GT : oh) - cy0, n_cx = (gx0 + GT < ow ? gx0 + GT : ow) - cx0;          // 1 .. CT coefficient pixels per axis
+    const int n_iy = n_cy + SS_APRON, n_ix = n_cx + SS_APRON;                                                      // input pixels: all inside the image
+    const int n_gy = h - gy0 < GT ? h - gy0 : GT, n_gx = w - gx0 < GT ? w - gx0 : GT;
+    for (int e = t; e < n_iy * n_ix; e += IM_THREADS) {
+        const int r = e / n_ix, q = e - r * n_ix;
+        const int64_t at = base + ((int64_t)(cy0 + r) * w + (cx0 + q)) * c;
+        s_x[r * IT + q] = x[at]; s_y[r * IT + q] = y[at];
+    }
+    __syncthreads();
+    for (int e = t; e < n_iy * n_cx; e += IM_THREADS) {
+        const int r = e / n_cx, q = e - r * n_cx;
+        const float *ax = s_x + r * IT + q, *ay = s_y + r * IT + q;
+        double a = (double)ax[0], b = (double)ay[0];
+        double mx = win.g[0] * a, my = win.g[0] * b, exx = win.g[0] * (a * a), eyy = win.g[0] * (b * b), exy = win.g[0] * (a * b);
+#pragma unroll
+        for (int k = 1; k < SS_TAPS; k++) {
+            a = (double)ax[k]; b = (double)ay[k];
+            mx = mx + win.g[k] * a;
+            my = my + win.g[k] * b;
+            exx = exx + win.g[k] * (a * a);
+            eyy = eyy + win.g[k] * (b * b);
+            exy = exy + win.g[k] * (a * b);
+        }
+        double *m = s_m + r * CT + q;
+        m[0] = mx; m[IT * CT] = my; m[2 * IT * CT] = exx; m[3 * IT * CT] = eyy; m[4 * IT * CT] = exy;
+    }
+    __syncthreads();
+    double sum_ssim = 0.0;
+    for (int e = t; e < n_cy * n_cx; e += IM_THREADS) {
+        const int r = e / n_cx, q = e - r * n_cx;
+        const double *m = s_m + r * CT + q;
+        double mx = win.g[0] * m[0], my = win.g[0] * m[IT * CT], exx = win.g[0] * m[2 * IT * CT], eyy = win.g[0] * m[3 * IT * CT], exy = win.g[0] * m[4 * IT * CT];
+#pragma unroll
+        for (int k = 1; k < SS_TAPS; k++) {
+            mx = mx + win.g[k] * m[k * CT];
+            my = my + win.g[k] * m[IT * CT + k * CT];
+            exx = exx + win.g[k] * m[2 * IT * CT + k * CT];
+            eyy = eyy + win.g[k] * m[3 * IT * CT + k * CT];
+            exy = exy + win.g[k] * m[4 * IT * CT + k * CT];
+        }
+        const double mxx = mx * mx, myy = my * my, mxy = mx * my;
+        const double sxx = exx - mxx, syy = eyy - myy, sxy = exy - mxy;
+        const double cd = (sxx + syy) + c2, ld = (mxx + myy) + c1;
+        const double cs = (2.0 * sxy + c2) / cd;
+        const double lum = (2.0 * mxy + c1) / ld;
+        const double ssim = lum * cs;
+        if (cy0 + r >= gy0 && cx0 + q >= gx0) sum_ssim += ssim;
+        double *co = s_c + r * CT + q;
+        co[0] = cs * (2.0 * (my - lum * mx) / ld) + lum * (2.0 * (cs * mx - my) / cd);
+        co[CT * CT] = -(ssim / cd);
+        co[2 * CT * CT] = 2.0 * lum / cd;
+    }
+    sum_ssim = wave_sum(sum_ssim);
+    if ((t & 63) == 0) s_sum[t >> 6] = sum_ssim;
+    __syncthreads();
+    if (t == 0) {
+        double a = s_sum[0];
+#pragma unroll
+        for (int k = 1; k < IM_THREADS / 64; k++) a += s_sum[k];
+        partials[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = a;
+    }
+    for (int e = t; e < n_gy * n_cx; e += IM_THREADS) {
+        const int gr = e / n_cx, q = e - gr * n_cx;
+        const int r0 = gy0 + gr - cy0;          // the coefficient row of tap 0; tap k reads row r0 - k
+        double ta = 0.0, tb = 0.0, tc = 0.0;
+#pragma unroll
+        for (int k = 0; k < SS_TAPS; k++) {
+            const int r = r0 - k;
+            if (r >= 0 && r < n_cy) {
+                const double *co = s_c + r * CT + q;
+                ta = ta + win.g[k] * co[0];
+                tb = tb + win.g[k] * co[CT * CT];
+                tc = tc + win.g[k] * co[2 * CT * CT];
+            }
+        }
+        double *o = s_m + gr * CT + q;
+        o[0] = ta; o[GT * CT] = tb; o[2 * GT * CT] = tc;
+    }
+    __syncthreads();
+    for (int e = t; e < n_gy * n_gx; e += IM_THREADS) {
+        const int gr = e / n_gx, gq = e - gr * n_gx;
+        const int q0 = gx0 + gq - cx0;
+        const double *row = s_m + gr * CT;
+        double ta = 0.0, tb = 0.0, tc = 0.0;
+#pragma unroll
+        for (int k = 0; k < SS_TAPS; k++) {
+            const int q = q0 - k;
+            if (q >= 0 && q < n_cx) {
+                ta = ta + win.g[k] * row[q];
+                tb = tb + win.g[k] * row[GT * CT + q];
+                tc = tc + win.g[k] * row[2 * GT * CT + q];
+            }
+        }
+        const int li = (gy0 + gr - cy0) * IT + q0;
+        const double xv = (double)s_x[li], yv = (double)s_y[li];
+        const double g = -((ta + (2.0 * xv) * tb) + yv * tc) / n_valid;
+        const int64_t at = base + ((int64_t)(gy0 + gr) * w + (gx0 + gq)) * c;
+        if (grad64) grad64[at] = g;
+        if (weight != 0.0) g_x[at] = g_x[at] + (float)(weight * g);
+    }
+}
+
+// loss[1] = (sum of the partials) / n, loss[0] = 1 - loss[1]: one block; thread t adds k = t, t + 256, ... in ascending order, then k_finish's tree
+__global__ void __launch_bounds__(IM_THREADS) k_ssim_loss_finish(int64_t count, const double *__restrict__ partials, double n_valid, double *__restrict__ loss)
+{
+    __shared__ double s_a[IM_THREADS];
+    const int t = threadIdx.x;
+    double a = 0.0;
+    for (int64_t k = t; k < count; k += IM_THREADS) a += partials[k];
+    s_a[t] = a;
+    __syncthreads();
+    for (int off = IM_THREADS / 2; off > 0; off >>= 1) {
+        if (t < off) s_a[t] += s_a[t + off];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double mean = s_a[0] / n_valid;
+        loss[1] = mean;
+        loss[0] = 1.0 - mean;
+    }
+}
+
+struct SsimLossWs {
+    double *partials;          // [b * c][tiles]
+};
+
+void ssim_loss_layout(Bump &bp, int b, int h, int w, int c, SsimLossWs &ws) { ws.partials = bp.take<double>((size_t)b * c * ssim_loss_tiles(h, w)); }
+
 }  // namespace
 
 }  // namespace nrf
@@ -294,6 +458,43 @@ int nrf_ssim(const float *d_x, const float *d_y, int b, int h, int w, int c, dou
     NRF_TRY(ws_check(bp, nrf_ssim_workspace_bytes(b, h, w, c), "nrf_ssim"));
     const double k1 = 0.01 * data_range, k2 = 0.03 * data_range;
     return ssim_launch(d_x, d_y, b, h, w, c, ssim_window(), k1 * k1, k2 * k2, d_means, d_map, ws.partials, as_stream(stream));
+}
+
+size_t nrf_ssim_loss_workspace_bytes(int b, int h, int w, int c)
+{
+    if (!ssim_loss_shape_ok(b, h, w, c)) return 0;
+    return measure([&](Bump &bp) { SsimLossWs ws; ssim_loss_layout(bp, b, h, w, c, ws); });
+}
+
+int nrf_ssim_loss(const float *d_x, const float *d_y, int b, int h, int w, int c, double data_range, double weight, double *d_loss, float *d_g_x, double *d_grad64,
+                  void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(d_x && d_y && d_loss && d_g_x && d_workspace, "nrf_ssim_loss: null pointer");
+    NRF_CHECK_ARG(ssim_loss_shape_ok(b, h, w, c), "nrf_ssim_loss: images [%d, %d, %d, %d]: b >= 1, h and w >= 11, c in 1..4, b * c <= 65535", b, h, w, c);
+    NRF_CHECK_ARG(range_ok(data_range), "nrf_ssim_loss: data_range must be finite and > 0");
+    NRF_CHECK_ARG(std::isfinite(weight) && weight >= 0.0, "nrf_ssim_loss: the weight must be finite and >= 0");
+    NRF_CHECK_ARG((reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_ssim_loss: the workspace must be 8-byte aligned");
+    Bump bp(d_workspace, workspace_bytes);
+    SsimLossWs ws;
+    ssim_loss_layout(bp, b, h, w, c, ws);
+    NRF_TRY(ws_check(bp, nrf_ssim_loss_workspace_bytes(b, h, w, c), "nrf_ssim_loss"));
+    hipStream_t st = as_stream(stream);
+    const double k1 = 0.01 * data_range, k2 = 0.03 * data_range;
+    const double n_valid = (double)((int64_t)b * (h - SS_APRON) * (w - SS_APRON) * c);
+    const SsimWindow win = ssim_window();
+    const bool whole = h <= SS_TILE && w <= SS_TILE;          // one workgroup per image channel: the training patches
+    const int tiles_x = whole ? 1 : (int)ceil_div(w, SS_TILE);
+    const int64_t tiles = whole ? 1 : ssim_loss_tiles(h, w);
+    if (whole)
+        hipLaunchKernelGGL(k_ssim_loss<SL_CT_WHOLE>, dim3(1, (unsigned)(b * c)), dim3(IM_THREADS), 0, st, d_x, d_y, h, w, c, tiles_x, win, k1 * k1, k2 * k2, n_valid,
+                           weight, d_g_x, d_grad64, ws.partials);
+    else
+        hipLaunchKernelGGL(k_ssim_loss<SL_CT_TILE>, dim3((unsigned)tiles, (unsigned)(b * c)), dim3(IM_THREADS), 0, st, d_x, d_y, h, w, c, tiles_x, win, k1 * k1,
+                           k2 * k2, n_valid, weight, d_g_x, d_grad64, ws.partials);
+    NRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ssim_loss_finish, dim3(1), dim3(IM_THREADS), 0, st, (int64_t)b * c * tiles, (const double *)ws.partials, n_valid, d_loss);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
 }
 
 size_t nrf_image_mse_workspace_bytes(int b, int64_t elems_per_image)

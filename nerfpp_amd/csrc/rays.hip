@@ -304,6 +304,20 @@ __global__ void k_rand_pixels(int64_t n, uint64_t seed, uint64_t idx0, int h0, u
     rw[k] = w0 + (int64_t)(((uint64_t)nrf_rng_u32(seed, 17u, idx0 + (uint64_t)k) * rw_range) >> 32);
 }
 
+// patch-shaped batches (the SSIM loss needs 11 x 11 neighbourhoods): patch k's origin from streams 19 (row) / 20 (column), element k * patch^2 + i * patch + j = (oy + i, ox + j)
+__global__ void k_rand_patches(int64_t total, int patch, uint64_t seed, uint64_t idx0, int h0, uint64_t rh_range, int w0, uint64_t rw_range, int64_t *__restrict__ rh,
+                               int64_t *__restrict__ rw)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const int64_t pp = (int64_t)patch * patch;
+    const int64_t k = e / pp;
+    const int in = (int)(e - k * pp);
+    const int i = in / patch, j = in - i * patch;
+    rh[e] = h0 + (int64_t)(((uint64_t)nrf_rng_u32(seed, 19u, idx0 + (uint64_t)k) * rh_range) >> 32) + i;
+    rw[e] = w0 + (int64_t)(((uint64_t)nrf_rng_u32(seed, 20u, idx0 + (uint64_t)k) * rw_range) >> 32) + j;
+}
+
 // N4: (depth - near) / span (NeRFExecutor.h:690)
 __global__ void k_normalize_depth(int64_t n, float near_, float span, const float *__restrict__ depth, float *__restrict__ out)
 {
@@ -506,6 +520,23 @@ int nrf_rand_pixels(uint64_t seed, int64_t iter, int h_start, int h_end, int w_s
     if (n == 0) return NRF_OK;
     hipLaunchKernelGGL(k_rand_pixels, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, as_stream(stream), n, seed, (uint64_t)iter * (uint64_t)n, h_start,
                        (uint64_t)(h_end - h_start + 1), w_start, (uint64_t)(w_end - w_start + 1), d_rand_h, d_rand_w);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
+int nrf_rand_patches(uint64_t seed, int64_t iter, int h_start, int h_end, int w_start, int w_end, int64_t n_patches, int patch, int64_t *d_rand_h, int64_t *d_rand_w,
+                     void *stream)
+{
+    NRF_CHECK_ARG(d_rand_h && d_rand_w && n_patches >= 0 && iter >= 0, "nrf_rand_patches: bad argument");
+    NRF_CHECK_ARG(patch >= 1 && patch <= 4096, "nrf_rand_patches: patch = %d (1 .. 4096)", patch);
+    const int64_t rh_range = (int64_t)h_end - h_start - patch + 2, rw_range = (int64_t)w_end - w_start - patch + 2;          // origins that keep the patch inside the crop
+    NRF_CHECK_ARG(rh_range >= 1 && rw_range >= 1, "nrf_rand_patches: the crop [%d, %d] x [%d, %d] is smaller than a %d x %d patch", h_start, h_end, w_start, w_end, patch,
+                  patch);
+    NRF_CHECK_ARG(n_patches < ((int64_t)1 << 31), "nrf_rand_patches: too many patches");
+    const int64_t total = n_patches * patch * patch;
+    if (total == 0) return NRF_OK;
+    hipLaunchKernelGGL(k_rand_patches, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, as_stream(stream), total, patch, seed, (uint64_t)iter * (uint64_t)n_patches,
+                       h_start, (uint64_t)rh_range, w_start, (uint64_t)rw_range, d_rand_h, d_rand_w);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

@@ -69,8 +69,13 @@ class NeRFDataset:
     with torch::randint from the global generator; here they are a pure function of (seed, iteration, element) (include/nrf_rng.h), so
     a training run is reproducible and a batch can be regenerated from its iteration number alone."""
 
-    def __init__(self, views, batch_size, precorp_iters=0, precorp_frac=0.5, seed=0, lerf: Optional[LeRFDataParams] = None):
+    def __init__(self, views, batch_size, precorp_iters=0, precorp_frac=0.5, seed=0, lerf: Optional[LeRFDataParams] = None, patch_size=0):
         self.Views, self.BatchSize, self.PrecorpIters, self.PrecorpFrac, self.Seed = list(views), int(batch_size), int(precorp_iters), float(precorp_frac), int(seed)
+        # patch_size P > 0: the batch is BatchSize / P^2 square patches of P x P neighbouring pixels (nrf_rand_patches), what a loss over neighbourhoods needs
+        # (Trainer(ssim_loss_weight, patch_size)); 0: independent pixels, as the reference draws them
+        self.PatchSize = int(patch_size)
+        if self.PatchSize < 0 or (self.PatchSize > 0 and (self.BatchSize % (self.PatchSize * self.PatchSize) != 0 or self.BatchSize == 0)):
+            raise L.NrfError(f"NeRFDataset: batch_size {self.BatchSize} is not a positive multiple of patch_size^2 = {self.PatchSize * self.PatchSize}")
         self.CurrentIter, self.CurrentImageIdx = 0, 0
         self.LeRFParams = lerf
         if lerf is not None:
@@ -89,7 +94,11 @@ class NeRFDataset:
         h0, h1, w0, w1 = CalculateBounds(v.H, v.W, self.CurrentIter, self.PrecorpIters, self.PrecorpFrac)
         n = self.BatchSize
         rh = torch.empty((n,), device="cuda", dtype=torch.int64); rw = torch.empty_like(rh)
-        L.check(L.lib().nrf_rand_pixels(self.Seed, self.CurrentIter, h0, h1, w0, w1, n, _ptr(rh), _ptr(rw), _stream()))
+        if self.PatchSize > 0:
+            P = self.PatchSize
+            L.check(L.lib().nrf_rand_patches(self.Seed, self.CurrentIter, h0, h1, w0, w1, n // (P * P), P, _ptr(rh), _ptr(rw), _stream()))
+        else:
+            L.check(L.lib().nrf_rand_pixels(self.Seed, self.CurrentIter, h0, h1, w0, w1, n, _ptr(rh), _ptr(rw), _stream()))
         target = None
         if v.Image is not None:
             img = _dev_f32(v.Image)
@@ -98,6 +107,8 @@ class NeRFDataset:
             L.check(L.lib().nrf_gather_pixels(_ptr(img), v.H, v.W, c, _ptr(rh), _ptr(rw), n, _ptr(target), _stream()))
         o, d, cone = GetRayBatch(rh, rw, v.H, v.W, v.K, v.Pose)
         out = dict(rays_o=o, rays_d=d, cone_angle=cone, Near=v.Near, Far=v.Far, target_s=target, rand_h=rh, rand_w=rw)
+        if self.PatchSize > 0:
+            out["patch_size"] = self.PatchSize
         if self.LeRFParams is not None:
             # :180-193: GetPixelValue(rand_h, rand_w, 0.5f, CurrentImageIdx, ..., Size(W, H)) per pixel -- the row as x, as the reference passes it
             out["target_lang_embedding"] = self.LeRFParams.pyramid.GetPixelValue(rh, rw, 0.5, self.CurrentImageIdx)

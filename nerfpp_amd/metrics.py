@@ -1,4 +1,4 @@
-"""Image metrics on the device: MSE, PSNR, SSIM, MSSSIM and EvaluateViews over the C ABI (include/nerfpp_hip.h, image_metrics.hip).
+"""Image metrics on the device: MSE, PSNR, SSIM, MSSSIM, SSIMLoss and EvaluateViews over the C ABI (include/nerfpp_hip.h, image_metrics.hip).
 
 The reference measures a frame only inside its training loop (-10 log10(mse), NeRFExecutor.h:893; scene.psnr restates it on the host).  Here a render is scored
 where it lies: the kernels compute in fp64 in a stated operation order (the header gives it), so a numpy float64 restatement equals the SSIM map bit for bit, the
@@ -75,6 +75,24 @@ def SSIM(x, y, data_range=1.0, per_channel=False, return_map=False):
         out = out[0]
         smap = smap[0] if return_map else None
     return (out, smap) if return_map else out
+
+
+def SSIMLoss(x, y, data_range=1.0, weight=1.0, grad=None, return_grad64=False):
+    """nrf_ssim_loss: 1 - the mean SSIM over every valid value of the batch, as a training loss of x against y -> (loss [2] float64 on the device: {1 - mean, mean},
+    grad).  `grad` (fp32, x's shape) is accumulated into, grad += float32(weight * d(1 - mean)/dx); None starts from zeros.  With return_grad64 the result is
+    (loss, grad, grad64): the unweighted float64 gradient."""
+    x, y, _ = _pair(x, y, "SSIMLoss")
+    b, h, w, c = (int(v) for v in x.shape)
+    if grad is None:
+        grad = torch.zeros_like(x)
+    elif grad.dtype != torch.float32 or not grad.is_cuda or not grad.is_contiguous() or grad.numel() != x.numel():
+        raise L.NrfError(f"SSIMLoss: grad must be a contiguous fp32 device tensor of {x.numel()} elements")
+    lib = L.lib()
+    loss = torch.empty((2,), device=x.device, dtype=torch.float64)
+    g64 = torch.empty(x.shape, device=x.device, dtype=torch.float64) if return_grad64 else None
+    ws = _workspace(lib.nrf_ssim_loss_workspace_bytes(b, h, w, c), x.device)
+    L.check(lib.nrf_ssim_loss(_ptr(x), _ptr(y), b, h, w, c, float(data_range), float(weight), _ptr(loss), _ptr(grad), _ptr(g64), _ptr(ws), ws.numel(), _stream()))
+    return (loss, grad, g64) if return_grad64 else (loss, grad)
 
 
 def MsSsimScaleMeans(x, y, data_range=1.0, scales=5):

@@ -22,7 +22,8 @@ from .renderer import NeRFRenderer, NeRFRenderParams, RngFill, StochasticPrecond
 class Trainer:
     def __init__(self, embedder: _HashBase, embeddirs, mlp: NeRFSmall, table, mlp_blob, learning_rate=5e-4, betas=(0.9, 0.99), eps=1e-15,
                  tv_loss_weight=0.0, seed=0, mlp_backward="f32", hash_backward="f32", grad_sync=None, train_dense_budget=256 << 20,
-                 pred_normal_loss_weight=0.0, orientation_loss_weight=0.0, distortion_loss_weight=0.0, sparsity_loss_weight=0.0):
+                 pred_normal_loss_weight=0.0, orientation_loss_weight=0.0, distortion_loss_weight=0.0, sparsity_loss_weight=0.0,
+                 ssim_loss_weight=0.0, patch_size=0):
         # two configurations of the reference's train loop (NeRFExecutor.h:862-995): hash grid + NeRFSmall (main.cpp:220-221) and the classic PE(10) / PE(4) + NeRF 8x256
         # (NeRFImpl is a legal TNeRF of the same loop; its embedders have no parameters: `table` is None / empty there)
         self.has_table = isinstance(embedder, _HashBase)
@@ -71,6 +72,16 @@ class Trainer:
             raise L.NrfError("distortion_loss_weight / sparsity_loss_weight must be finite and >= 0")
         self.ray_losses = torch.zeros((2,), device=dev)             # [L_dist, L_sparse] of the last step, unweighted, on the device
         self._rws = None
+        # The structural term of the usual (1 - l) L1 + l (1 - SSIM) image loss, on batches of patch_size x patch_size patches (NeRFDataset(patch_size)): one kernel
+        # (nrf_ssim_loss) adds w * d(1 - mean SSIM) / d rgb to g_rgb right after the Huber term, so every backward path below is served; the step's loss is
+        # huber + w * ssim_loss[0].  Weight 0 (the default): no call is issued
+        self.ssim_loss_weight, self.patch_size = float(ssim_loss_weight), int(patch_size)
+        if not (0.0 <= self.ssim_loss_weight < math.inf):
+            raise L.NrfError("ssim_loss_weight must be finite and >= 0")
+        if self.ssim_loss_weight > 0 and self.patch_size < 11:
+            raise L.NrfError("ssim_loss_weight > 0 needs patch_size >= 11 (the SSIM window is 11 x 11)")
+        self.ssim_loss = torch.zeros((2,), device=dev, dtype=torch.float64)          # [1 - mean SSIM, mean SSIM] of the last step, unweighted, on the device
+        self._sws = None
         # "f32": one float atomic per feature; "packed": both features of an entry in one 64-bit fixed-point atomic (nrf_hash_backward_rays_packed);
         # "binned": the same fixed-point contributions merged per table range in LDS before they reach memory (nrf_hash_backward_rays_binned; equals "packed" bit for bit)
         if hash_backward not in ("f32", "packed", "binned"):
@@ -129,6 +140,17 @@ class Trainer:
         tgt = _dev_f32(target).reshape(n, 3)
         loss_mse = torch.empty((2,), device=rgb.device); g_rgb = torch.empty_like(rgb)
         L.check(lib.nrf_huber_loss(_ptr(rgb), _ptr(tgt), rgb.numel(), _ptr(loss_mse), _ptr(g_rgb), _stream()))
+        if self.ssim_loss_weight > 0:
+            # the batch is n / P^2 patches, element k * P^2 + i * P + j = pixel (i, j) of patch k (nrf_rand_patches): rgb / tgt viewed as [n / P^2, P, P, 3]
+            P = self.patch_size
+            if n % (P * P) != 0:
+                raise L.NrfError(f"Trainer.backward: ssim_loss_weight > 0 needs a batch of whole {P} x {P} patches, got {n} rays")
+            tgt = tgt.contiguous()
+            nbs = lib.nrf_ssim_loss_workspace_bytes(n // (P * P), P, P, 3)
+            if self._sws is None or self._sws.numel() < nbs:
+                self._sws = torch.empty((max(1, int(nbs)),), device="cuda", dtype=torch.uint8)
+            L.check(lib.nrf_ssim_loss(_ptr(rgb), _ptr(tgt), n // (P * P), P, P, 3, 1.0, self.ssim_loss_weight, _ptr(self.ssim_loss), _ptr(g_rgb), None,
+                                      _ptr(self._sws), self._sws.numel(), _stream()))
         raw = res.Raw; s = n_samples_out
         z = res.Extras["z_fine"] if "z_fine" in res.Extras else res.Extras["z_coarse"]
         c = int(self.mlp.GetOutputDims())                  # 4, or 7 with the predicted-normals head

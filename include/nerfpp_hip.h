@@ -1040,6 +1040,19 @@ NRF_API int nrf_get_live_colour(void);
  * synchronisation. */
 NRF_API size_t nrf_live_points_workspace_bytes(int64_t p);
 NRF_API int nrf_live_points(const float *d_sigma, int64_t p, int32_t *d_list, int32_t *d_count, float *d_raw_rows, void *d_workspace, size_t workspace_bytes, void *stream);
+/* The default hierarchical HashNeRF render (the path of nrf_set_live_colour, sigma noise off, at most 256 + 256 samples) turns a chunk's exact coarse sigma into the fine
+ * depths in ONE kernel -- coarse weights, SamplePDF, the stable merge and the per-ray masks of sigma > 0 from which the live list is made -- instead of one launch per
+ * stage.  The same device functions in the same order: every output is bit for bit what the stage-wise chain gives.  on = 1 (the default; NRF_FUSED_RESAMPLE=0 in the
+ * environment turns it off) / 0: one launch per stage.  Process-wide, read at every call; workspace sizes do not depend on it. */
+NRF_API int nrf_set_fused_resample(int on);
+NRF_API int nrf_get_fused_resample(void);
+/* Debug entry, for tests: that kernel pair on its own.  d_sigma [n, s] -> d_z_fine [n, s + ns], d_src [n, s + ns], d_z_new [n, ns] as nrf_raw2weights (c = 1) followed by
+ * nrf_fine_depths_merge give them; d_u: the shared table [ns] (u_stride 0), per-ray rows (u_stride ns) or NULL (draws generated from seed / ray_base as the renderer's
+ * Perturb > 0 does); d_weights [n, s] or NULL: the coarse weights.  With d_counts (16-byte aligned, 4 ceil(n / 4) + ceil(n / 64) int32: every ray's number of
+ * sigma > 0, then the list offsets of the groups of 64 rays) also d_list, d_count and d_raw_rows [n * s, 4] exactly as nrf_live_points writes them.  2 <= s <= 256, 1 <= ns <= 256, n (s + ns) < 2^31. */
+NRF_API int nrf_dbg_resample(const float *d_sigma, const float *d_z, const float *d_dirs, int d_stride, int64_t n, int s, const float *d_u, int64_t u_stride, uint64_t seed,
+                             int64_t ray_base, int ns, int sum_vec, float *d_z_fine, int32_t *d_src, float *d_z_new, float *d_weights, int32_t *d_counts, int32_t *d_list,
+                             int32_t *d_count, float *d_raw_rows, void *stream);
 /* ... per renderer: 1-4 lanes for this renderer's calls whatever the process-wide setting; 0 returns it to that setting (two renderers of one process need not share it). */
 NRF_API int nrf_renderer_set_lanes(nrf_renderer *r, int lanes);
 /* 1 when the fp32 layer products of the training paths (classic and LeRF backward, NeRFSmall's fp32 backward) run as rocBLAS GEMMs on the fp32 matrix cores (the library is

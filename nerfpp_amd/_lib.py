@@ -281,6 +281,9 @@ _ABI = """
     nrf_get_live_colour()
     nrf_live_points_workspace_bytes(l)->z
     nrf_live_points(plppppzp)
+    nrf_set_fused_resample(i)
+    nrf_get_fused_resample()
+    nrf_dbg_resample(pppiliplqliippppppppp)
     nrf_renderer_set_lanes(pi)
     nrf_fp32_gemm_available()
     nrf_get_train_gemm()

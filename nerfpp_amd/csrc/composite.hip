@@ -9,6 +9,7 @@
 // the CPU oracle and here), which makes the whole stage -- and with it the fine-pass sample set -- reproducible.  The pdf normaliser sum(w) is evaluated in ATen's own lane
 // order (sum_vec) because it feeds searchsorted: the sample INDICES are bit-exact against the oracle.
 #include "common.h"
+#include "live_points.h"
 #include "stoch.h"
 
 #include <type_traits>
@@ -339,6 +340,159 @@ k_fine_depths(int64_t n, int s, int ns, int sum_vec, const float *__restrict__ z
             if (srcp) srcp[rank] = i < s ? src_z + i : src_new + (i - s);
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The renderer's exact coarse weights + fine depths as ONE kernel (k_resample): what k_raw2outputs<false> (weights only, sigma rows of one channel, no noise) followed by
+// k_fine_depths computes, by the same device functions on the same values in the same order -- the weights go from the wave that made them to SamplePDF through LDS
+// instead of HBM, nothing is reduced that nobody reads, the ray index is wave-uniform (scalar row bases, 32-bit lane offsets) and LDS is sized by the instantiation.
+// ------------------------------------------------------------------------------------------------
+// The !FAST body of k_raw2outputs reduced to the weights: w[j] = alpha_j * exp(sum_{i<j} log(1 - alpha_i)) of one ray.  z: the ray's depths (LDS), sg[b]: sigma of
+// sample b * 64 + lane as stored (0 past s).  weights[1:-1] go to wts (LDS, SamplePDF's operand), the whole row to w_out unless NULL.
+template <int NB>
+__device__ __forceinline__ void coarse_weights_wave(const float *z, const float (&sg)[NB], float nrm, int s, float *wts, float *__restrict__ w_out, int lane)
+{
+    double carry = 0;                                              // sum of log(1-alpha) over previous 64-sample blocks
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const int base = b * 64;
+        if (base >= s) break;                                      // wave-uniform
+        const int j = base + lane;
+        const bool live = j < s;
+        float lg = 0.0f, alpha = 0.0f;
+        if (live) {
+            const float zj = z[j];
+            float dist = (j + 1 < s) ? (z[j + 1] - zj) : 1e10f;    // NeRFRenderer.h:239-240
+            dist = dist * nrm;                                      // :241
+            const float sig = sg[b] > 0.0f ? sg[b] : 0.0f;          // relu
+            alpha = -(nrf_expf(-sig * dist)) + 1.0f;                // :234
+            const float om = 1.0f - alpha;
+            lg = nrf_logf(om > 1e-10f ? om : 1e-10f);               // :265
+        }
+        const double incl = wave_incl_scan_t<double>((double)lg, lane);
+        const double excl = carry + (incl - (double)lg);           // exclusive prefix: cat[0, cumsum][:-1] (:263-266)
+        carry += __shfl(incl, 63);
+        if (live) {
+            const float trans = nrf_expf((float)excl);              // TruncExp forward = exp (:267)
+            const float w = alpha * trans;
+            if (j >= 1 && j + 1 < s) wts[j - 1] = w;
+            if (w_out) w_out[j] = w;
+        }
+    }
+}
+
+// the stable merge of k_fine_depths: cat(z[0..s), smp[0..ns)) ascending into outp, the origin of every slot into srcp
+__device__ __forceinline__ void merge_depths_wave(const float *zl, const float *smp, int s, int ns, float *__restrict__ outp, int32_t *__restrict__ srcp, int32_t src_z,
+                                                  int32_t src_new, int lane)
+{
+    bool bad = false;
+    for (int k = lane; k + 1 < s; k += 64) bad |= zl[k] > zl[k + 1];
+    for (int k = lane; k + 1 < ns; k += 64) bad |= smp[k] > smp[k + 1];
+    if (!__any(bad)) {
+        for (int i = lane; i < s; i += 64) {             // rank(z_i) = i + #{samples < z_i}   (z precedes samples on ties)
+            const float v = zl[i];
+            int lo = 0, hi = ns;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (smp[mid] < v) lo = mid + 1; else hi = mid; }
+            outp[i + lo] = v;
+            srcp[i + lo] = src_z + i;
+        }
+        for (int j = lane; j < ns; j += 64) {            // rank(sample_j) = j + #{z <= sample_j}
+            const float v = smp[j];
+            int lo = 0, hi = s;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (zl[mid] <= v) lo = mid + 1; else hi = mid; }
+            outp[j + lo] = v;
+            srcp[j + lo] = src_new + j;
+        }
+    } else {
+        const int tot = s + ns;
+        for (int i = lane; i < tot; i += 64) {
+            const float v = i < s ? zl[i] : smp[i - s];
+            int rank = 0;
+            for (int k = 0; k < tot; k++) {
+                const float o = k < s ? zl[k] : smp[k - s];
+                rank += (o < v) || (o == v && k < i);
+            }
+            outp[rank] = v;
+            srcp[rank] = i < s ? src_z + i : src_new + (i - s);
+        }
+    }
+}
+
+template <int SMAX, int NSMAX>
+struct ResampleLds {
+    float bins[SMAX];
+    float wts[SMAX];
+    float cdf[SMAX + 4];
+    float smp[NSMAX];
+    float scratch[64];
+    float zs[SMAX];
+};
+
+// One wave per ray.  sigma [n, s] as the exact coarse kernel stored it; zf / src / z_new as k_fine_depths writes them (n (s + ns) < 2^31: src is int32).  w_out: the
+// coarse weights [n, s] or NULL.  counts != NULL: the live part -- counts[ray] = #{sigma > 0} (the predicate of live_points.hip: NaN is dead) and the ray's
+// ceil(s / 64) 64-bit masks of them in the first bytes of the ray's own block of rows [n * s, 4] (live_points.hip expands them and then writes the dead rows there).
+template <int SMAX, int NSMAX>
+__global__ void __launch_bounds__(64 * RAYS_PER_BLOCK)
+k_resample(int64_t n, int s, int ns, int sum_vec, const float *__restrict__ z, const float *__restrict__ sigma, const float *__restrict__ dirs, int d_stride,
+           const float *__restrict__ u, int64_t u_stride, RngRef g, float *__restrict__ zf, int32_t *__restrict__ src, float *__restrict__ z_new,
+           float *__restrict__ w_out, int32_t *__restrict__ counts, float *__restrict__ rows)
+{
+    constexpr int NB = SMAX / 64;
+    __shared__ ResampleLds<SMAX, NSMAX> lds[RAYS_PER_BLOCK];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));          // wave-uniform: the row bases below are scalar
+    const int64_t ray = (int64_t)blockIdx.x * RAYS_PER_BLOCK + wv;
+    if (ray >= n) return;
+    ResampleLds<SMAX, NSMAX> &L = lds[wv];
+    float *zl = L.zs;
+    const float *zr = z + ray * s, *sr = sigma + ray * s;
+    float sg[NB];
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const int j = b * 64 + lane;
+        if (j < s) zl[j] = zr[j];
+        sg[b] = j < s ? sr[j] : 0.0f;
+    }
+    const float *dv = dirs + ray * d_stride;
+    float nn = dv[0] * dv[0]; nn = nn + dv[1] * dv[1]; nn = nn + dv[2] * dv[2];
+    const float nrm = sqrtf(nn);                                   // torch::norm(rays_d, 2, -1)
+    if (counts) {
+        int32_t cnt = 0;
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            if (b * 64 >= s) break;
+            const uint64_t m = __ballot(sg[b] > 0.0f);             // (lanes past s hold 0)
+            cnt += __popcll(m);
+            if (lane == 0) reinterpret_cast<uint64_t *>(rows + ray * s * 4)[b] = m;
+        }
+        if (lane == 0) counts[ray] = cnt;
+    }
+    wave_sync();
+    coarse_weights_wave<NB>(zl, sg, nrm, s, L.wts, w_out ? w_out + ray * s : nullptr, lane);
+    const int nb = s - 1;
+    for (int k = lane; k < nb; k += 64) L.bins[k] = 0.5f * (zl[k + 1] + zl[k]);                  // :427
+    wave_sync();
+    float *smp = L.smp;                     // samples [ns]
+    sample_pdf_wave(L.bins, L.wts, nb, u ? u + ray * u_stride : nullptr, g.seed, (uint64_t)((g.ray_base + ray) * ns), ns, sum_vec, L.cdf, smp, L.scratch, nullptr, lane);
+    float *zn = z_new + ray * ns;
+    for (int j = lane; j < ns; j += 64) zn[j] = smp[j];
+    merge_depths_wave(zl, smp, s, ns, zf + ray * (s + ns), src + ray * (s + ns), (int32_t)(ray * s), (int32_t)(n * s + ray * ns), lane);
+}
+
+int launch_resample(const float *z, const float *sigma, const float *dirs, int d_stride, int64_t n, int s, const float *u, int64_t u_stride, const RngRef &g, int ns,
+                    int sum_vec, float *zf, int32_t *src, float *z_new, float *w_out, int32_t *counts, float *rows, hipStream_t st)
+{
+    NRF_CHECK_ARG(s >= 2 && s <= MAX_S && ns >= 1 && ns <= MAX_S, "resample: n_samples %d / n_importance %d outside the built range [2,%d] / [1,%d]", s, ns, MAX_S, MAX_S);
+    NRF_CHECK_ARG(sum_vec == 0 || sum_vec == 4 || sum_vec == 8 || sum_vec == 16, "resample: sum_vec must be 0, 4, 8 or 16");
+    NRF_CHECK_ARG(n * (int64_t)(s + ns) < ((int64_t)1 << 31), "resample: n (s + ns) must fit the int32 column map");
+    NRF_CHECK_ARG(!counts || (rows && (reinterpret_cast<uintptr_t>(rows) & 15) == 0), "resample: the live masks travel in the 16-byte aligned rows");
+    if (n == 0) return NRF_OK;
+    ProfScope prof(NRF_PROF_SAMPLE, st);
+    const dim3 grid((unsigned)ceil_div(n, RAYS_PER_BLOCK)), block(64 * RAYS_PER_BLOCK);
+    if (s <= 64 && ns <= 128) hipLaunchKernelGGL((k_resample<64, 128>), grid, block, 0, st, n, s, ns, sum_vec, z, sigma, dirs, d_stride, u, u_stride, g, zf, src, z_new, w_out, counts, rows);
+    else hipLaunchKernelGGL((k_resample<256, 256>), grid, block, 0, st, n, s, ns, sum_vec, z, sigma, dirs, d_stride, u, u_stride, g, zf, src, z_new, w_out, counts, rows);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
 }
 
 // RenderCLIPEmbedding (LeRFRenderer.h:45-54): out = normalize(sum_s w_s * e_s, eps 1e-8).  One workgroup per ray; thread = embedding

@@ -14,6 +14,7 @@
 // consecutive points (all loads issued before the first is used); a lane's position in the list is the popcount of the live lanes below it.
 #include "live_points.h"
 #include "scan.h"
+#include "stoch.h"
 
 namespace nrf {
 
@@ -115,6 +116,118 @@ int live_points_launch(const float *sigma, int64_t p, int32_t *list, int32_t *co
     return NRF_OK;
 }
 
+// ---- the same list from per-ray masks ----
+// k_resample (composite.hip) had every coarse sigma of a ray in one wave's lanes: it leaves counts[ray] = #{sigma > 0} and the ray's ceil(s / 64) ballot masks in the
+// first bytes of the ray's own rows [ray * s .. ray * s + s).  One workgroup turns the n counts into the offsets of the groups of 64 rays (no second pass over sigma, no
+// atomics, no read-back; behind the counts, see ray_counts_len); then a wave per ray adds the counts of the rays before it in its group, expands the masks into the
+// ascending columns ray * s + i and writes the rows of the ray's dead columns -- after it has read the masks out of them.
+constexpr int RAY_SCAN_B = 1024;
+constexpr int RAY_GROUP = 64;                                                   // rays per scanned group: one coalesced load and one wave sum
+static inline int64_t ray_groups_at(int64_t n) { return (n + 3) / 4 * 4; }     // the group offsets' place in the counts array (16-byte aligned like the counts)
+
+// goffs[g] <- sum of counts[0 .. 64 g).  A thread loads four consecutive counts (a wave 1 KB in a row), sixteen lanes sum a group, and the block scans RAY_SCAN_B group
+// sums at a time (scan.h).  The counts array is a multiple of four words long (ray_groups_at): the last load stays inside it, and what lies past n is not added.
+__global__ void __launch_bounds__(RAY_SCAN_B)
+k_ray_scan(int32_t n, const int32_t *__restrict__ counts, int32_t *__restrict__ goffs)
+{
+    constexpr int STEPS = RAY_GROUP / 4;          // loads per thread and piece: RAY_SCAN_B groups x 64 rays / (RAY_SCAN_B threads x 4 rays)
+    __shared__ int32_t sh[RAY_SCAN_B], gsum[RAY_SCAN_B];
+    const int32_t ng = (n + RAY_GROUP - 1) / RAY_GROUP;
+    int32_t carry = 0;
+    for (int32_t g0 = 0; g0 < ng; g0 += RAY_SCAN_B) {
+        int4 v[STEPS];
+#pragma unroll
+        for (int k = 0; k < STEPS; k++) {          // every load is issued before the first sum
+            const int64_t i = ((int64_t)g0 * RAY_GROUP / 4 + k * RAY_SCAN_B + threadIdx.x) * 4;
+            v[k] = i < n ? *reinterpret_cast<const int4 *>(counts + i) : int4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int k = 0; k < STEPS; k++) {
+            const int64_t i = ((int64_t)g0 * RAY_GROUP / 4 + k * RAY_SCAN_B + threadIdx.x) * 4;
+            int32_t t = v[k].x + (i + 1 < n ? v[k].y : 0) + (i + 2 < n ? v[k].z : 0) + (i + 3 < n ? v[k].w : 0);
+#pragma unroll
+            for (int off = 8; off > 0; off >>= 1) t += __shfl_xor(t, off);
+            if ((threadIdx.x & 15) == 0) gsum[k * (RAY_SCAN_B / 16) + (threadIdx.x >> 4)] = t;
+        }
+        __syncthreads();
+        int32_t total;
+        const int32_t ex = block_exclusive_scan<int32_t, RAY_SCAN_B>(gsum[threadIdx.x], sh, total);
+        if (g0 + (int32_t)threadIdx.x < ng) goffs[g0 + threadIdx.x] = carry + ex;
+        carry += total;
+        __syncthreads();
+    }
+}
+
+constexpr int MASK_WAVES = 4;         // waves per workgroup
+constexpr int MASK_RPW = 4;           // consecutive rays per wave: their masks and counts are requested before the first row is written
+constexpr int MASK_WORDS = 4;         // s <= 256
+
+__global__ void __launch_bounds__(64 * MASK_WAVES)
+k_mask_scatter(int32_t n, int s, const float *__restrict__ sigma, const int32_t *__restrict__ counts, const int32_t *__restrict__ goffs, int32_t *__restrict__ list,
+               int32_t *__restrict__ count, float4 *rows)
+{
+    const int lane = threadIdx.x & 63;
+    const int32_t r0 = ((int32_t)blockIdx.x * MASK_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * MASK_RPW;          // (a multiple of 4: one group)
+    if (r0 >= n) return;
+    const int32_t g = r0 / RAY_GROUP, gr = g * RAY_GROUP;
+    // this lane's ray of the group, counted only where it precedes r0; the wave's rays follow from their own counts
+    int32_t before = (gr + lane < r0) ? counts[gr + lane] : 0;
+    float4 q0[MASK_RPW], q1[MASK_RPW];
+    float sgv[MASK_RPW][MASK_WORDS];
+    // the masks, read as the rows they lie in (the type the stores below have: none of them can move above these loads), and with them the rays' sigma: one round of
+    // loads, then one of stores
+#pragma unroll
+    for (int q = 0; q < MASK_RPW; q++) {
+        const int32_t ray = r0 + q < n ? r0 + q : n - 1;
+        q0[q] = rows[(int64_t)ray * s];
+        q1[q] = s > 128 ? rows[(int64_t)ray * s + 1] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int b = 0; b < MASK_WORDS; b++) sgv[q][b] = b * 64 + lane < s ? sigma[(int64_t)ray * s + b * 64 + lane] : 0.0f;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+    int32_t at = goffs[g] + before;
+    const uint64_t below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int q = 0; q < MASK_RPW; q++) {
+        const int32_t ray = r0 + q;
+        if (ray >= n) break;
+        uint64_t mask[MASK_WORDS];
+        mask[0] = (uint64_t)__float_as_uint(q0[q].x) | ((uint64_t)__float_as_uint(q0[q].y) << 32);
+        mask[1] = s > 64 ? (uint64_t)__float_as_uint(q0[q].z) | ((uint64_t)__float_as_uint(q0[q].w) << 32) : 0ull;
+        mask[2] = (uint64_t)__float_as_uint(q1[q].x) | ((uint64_t)__float_as_uint(q1[q].y) << 32);
+        mask[3] = s > 192 ? (uint64_t)__float_as_uint(q1[q].z) | ((uint64_t)__float_as_uint(q1[q].w) << 32) : 0ull;
+        float4 *rr = rows + (int64_t)ray * s;
+        const int32_t col0 = ray * s;
+#pragma unroll
+        for (int b = 0; b < MASK_WORDS; b++) {
+            if (b * 64 >= s) break;
+            const int j = b * 64 + lane;
+            if ((mask[b] >> lane) & 1ull) list[at + __popcll(mask[b] & below)] = col0 + j;          // (a live lane has j < s: the ballot was taken over the ray's samples only)
+            else if (j < s) rr[j] = float4{0.0f, 0.0f, 0.0f, sgv[q][b]};
+            at += __popcll(mask[b]);
+        }
+        if (ray == n - 1 && lane == 0) *count = at;
+    }
+}
+
+// the counts array of launch_resample / live_from_masks_launch: n per-ray counts, then (16-byte aligned) the offsets of the groups of 64 rays
+int64_t ray_counts_len(int64_t n) { return ray_groups_at(n) + ceil_div(n, RAY_GROUP); }
+
+int live_from_masks_launch(const float *sigma, int64_t n, int s, int32_t *counts, int32_t *list, int32_t *count, float *rows, hipStream_t st)
+{
+    if (n <= 0 || s < 1 || s > 64 * MASK_WORDS || n * (int64_t)s >= ((int64_t)1 << 31) || !rows || (reinterpret_cast<uintptr_t>(counts) & 15)) {
+        set_error("internal: live list from masks of %lld rays x %d samples", (long long)n, s);
+        return NRF_ERR_INVALID_ARG;
+    }
+    int32_t *goffs = counts + ray_groups_at(n);
+    hipLaunchKernelGGL(k_ray_scan, dim3(1), dim3(RAY_SCAN_B), 0, st, (int32_t)n, counts, goffs);
+    hipLaunchKernelGGL(k_mask_scatter, dim3((unsigned)ceil_div(n, MASK_WAVES * MASK_RPW)), dim3(64 * MASK_WAVES), 0, st, (int32_t)n, s, sigma, counts, goffs, list, count,
+                       reinterpret_cast<float4 *>(rows));
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
 // ---- the switch: NRF_LIVE_COLOUR=0 / nrf_set_live_colour(0) keeps the colour launch over every coarse depth ----
 static std::atomic<int> g_live_colour{-1};          // -1: not decided yet (environment, default on)
 int live_colour_on()
@@ -128,9 +241,43 @@ int live_colour_on()
     return v;
 }
 
+// ---- the switch: NRF_FUSED_RESAMPLE=0 / nrf_set_fused_resample(0) keeps the stage-wise chain (exact weights, fine depths, count / scan / scatter) ----
+static std::atomic<int> g_fused_resample{-1};          // -1: not decided yet (environment, default on)
+int fused_resample_on()
+{
+    int v = g_fused_resample.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char *e = getenv("NRF_FUSED_RESAMPLE");
+        v = (e && strcmp(e, "0") == 0) ? 0 : 1;
+        g_fused_resample.store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
+
 }  // namespace nrf
 
 extern "C" {
+
+int nrf_set_fused_resample(int on)
+{
+    NRF_CHECK_ARG(on == 0 || on == 1, "nrf_set_fused_resample: 0 (one launch per stage) or 1 (one resampling kernel per chunk)");
+    nrf::g_fused_resample.store(on, std::memory_order_relaxed);
+    return NRF_OK;
+}
+
+int nrf_get_fused_resample(void) { return nrf::fused_resample_on(); }
+
+int nrf_dbg_resample(const float *d_sigma, const float *d_z, const float *d_dirs, int d_stride, int64_t n, int s, const float *d_u, int64_t u_stride, uint64_t seed,
+                     int64_t ray_base, int ns, int sum_vec, float *d_z_fine, int32_t *d_src, float *d_z_new, float *d_weights, int32_t *d_counts, int32_t *d_list,
+                     int32_t *d_count, float *d_raw_rows, void *stream)
+{
+    NRF_CHECK_ARG(d_sigma && d_z && d_dirs && d_z_fine && d_src && d_z_new && n >= 0 && d_stride >= 3, "nrf_dbg_resample: bad argument");
+    NRF_CHECK_ARG(!d_counts || (d_list && d_count && d_raw_rows && (reinterpret_cast<uintptr_t>(d_counts) & 15) == 0), "nrf_dbg_resample: the live part needs list, count, rows and 16-byte aligned counts");
+    NRF_TRY(nrf::launch_resample(d_z, d_sigma, d_dirs, d_stride, n, s, d_u, u_stride, nrf::RngRef{seed, ray_base}, ns, sum_vec, d_z_fine, d_src, d_z_new, d_weights, d_counts,
+                                 d_raw_rows, nrf::as_stream(stream)));
+    if (!d_counts || n == 0) return NRF_OK;
+    return nrf::live_from_masks_launch(d_sigma, n, s, d_counts, d_list, d_count, d_raw_rows, nrf::as_stream(stream));
+}
 
 int nrf_set_live_colour(int on)
 {

@@ -791,10 +791,20 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
                                    out->d_weights ? out->d_weights : cw.w_c, out->d_depth, nz, st, fastc, nullptr, nullptr, 0, d_flag));
         return p->normals ? normals_tail(ps, out->d_weights ? out->d_weights : cw.w_c, cw.raw_c) : NRF_OK;
     }
-    NRF_TRY(launch_raw2outputs(cw.raw_c, cw.z_c, d_rays + 3, ray_stride, n, s, path.sigma_only ? 1 : c, path.sigma_only ? 0 : 3, p->white_bkgr, nullptr, nullptr, nullptr, cw.w_c, nullptr, nz,
-                               st, false));   // :423  always the exact arithmetic: these weights choose the fine samples
-    NRF_TRY(launch_fine_depths(cw.z_c, cw.w_c, n, s, jitter ? nullptr : d_u, 0, rng, ni, p->sum_vec, cw.z_f, st, path.reuse_raw ? pw.rr_src : (path.reuse ? rw.src : nullptr),
-                               path.reuse_raw ? pw.rr_znew : (path.reuse ? rw.z_new : nullptr)));                                // :427-431 (det = perturb == 0)
+    // The default HashNeRF path (raw_c = the exact sigma [n, s]): weights, SamplePDF and merge as one kernel (composite.hip: k_resample), which also leaves the per-ray
+    // counts and masks of sigma > 0 when the colour launch below runs over the live list.  The counts lie where the new samples' network outputs are written later
+    // (one ray with one new sample has no room for them: that chunk counts by launch).
+    const bool list_colour = path.geo_reuse && !out->d_raw && !nz.on && live_colour_on() && mlp_small_color_list_ok(r->desc.mlp, n * (int64_t)s, s);
+    const bool fused = path.reuse && path.geo_reuse && path.sigma_only && !nz.on && s >= 2 && s <= 256 && ni <= 256 && fused_resample_on();
+    int32_t *ray_counts = fused && list_colour && ray_counts_len(n) <= n * (int64_t)ni * 4 ? reinterpret_cast<int32_t *>(pw.raw_cols + n * (int64_t)s * 4) : nullptr;
+    if (fused) NRF_TRY(launch_resample(cw.z_c, cw.raw_c, d_rays + 3, ray_stride, n, s, jitter ? nullptr : d_u, 0, rng, ni, p->sum_vec, cw.z_f, rw.src, rw.z_new,
+                                       out->d_weights_coarse ? cw.w_c : nullptr, ray_counts, pw.raw_cols, st));
+    else {
+        NRF_TRY(launch_raw2outputs(cw.raw_c, cw.z_c, d_rays + 3, ray_stride, n, s, path.sigma_only ? 1 : c, path.sigma_only ? 0 : 3, p->white_bkgr, nullptr, nullptr, nullptr, cw.w_c, nullptr, nz,
+                                   st, false));   // :423  always the exact arithmetic: these weights choose the fine samples
+        NRF_TRY(launch_fine_depths(cw.z_c, cw.w_c, n, s, jitter ? nullptr : d_u, 0, rng, ni, p->sum_vec, cw.z_f, st, path.reuse_raw ? pw.rr_src : (path.reuse ? rw.src : nullptr),
+                                   path.reuse_raw ? pw.rr_znew : (path.reuse ? rw.z_new : nullptr)));                                // :427-431 (det = perturb == 0)
+    }
     PointSource psf{nullptr, d_rays, cw.z_f, ray_stride, sf};
     const float *raw_final = cw.raw_f;
     const int32_t *src_final = nullptr;          // compositing reads sample i's network output at row src_final[i] (NULL: i) of raw_final | raw2_final (launch_raw2outputs)
@@ -824,9 +834,10 @@ static int render_rays_impl(const nrf_renderer *r, const float *d_rays, int ray_
             const int64_t nc = n * (int64_t)s;
             // The colour of a coarse depth with sigma <= 0 (or NaN) meets a weight of exactly 0 in the compositing below: the colour net runs over the live columns only,
             // and the dead ones get the row (0, 0, 0, sigma).  Not when the caller takes Raw (every colour is wanted there) or when sigma noise may lift a dead sigma.
-            if (!out->d_raw && !nz.on && live_colour_on() && mlp_small_color_list_ok(r->desc.mlp, nc, s)) {
+            if (list_colour) {
                 ProfScope prof(NRF_PROF_MLP_COLOUR, st);
-                NRF_TRY(live_points_launch(cw.raw_c, nc, pw.live_list, pw.live_count, pw.raw_cols, pw.live, st));
+                if (ray_counts) NRF_TRY(live_from_masks_launch(cw.raw_c, n, s, ray_counts, pw.live_list, pw.live_count, pw.raw_cols, st));
+                else NRF_TRY(live_points_launch(cw.raw_c, nc, pw.live_list, pw.live_count, pw.raw_cols, pw.live, st));
                 NRF_TRY(mlp_small_color_from_geo_list_lm(r->desc.mlp, pw.geo_planes, nc, cw.raw_c, cw.dirs16, cw.dirs_lo, s, nc, pw.live_list, pw.live_count, pw.raw_cols, st));
             } else NRF_TRY(mlp_small_color_from_geo_lm(r->desc.mlp, pw.geo_planes, nc, cw.raw_c, cw.dirs16, cw.dirs_lo, s, rw.keep, nc, pw.raw_cols, st));
             NRF_TRY(mlp_small_forward_mfma_lm(r->desc.mlp, rw.feats + nc, rw.feats_lo ? rw.feats_lo + nc : nullptr, rw.cols, cw.dirs16, cw.dirs_lo, ni, rw.keep + nc, n * (int64_t)ni,

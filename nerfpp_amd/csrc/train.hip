@@ -170,6 +170,18 @@ __global__ void k_hash_ngp_bwd(HashParams hp, const float *__restrict__ pts, int
     }
 }
 
+// fp16(g * w) as the reference forms it, (T)(float * float) (CuHashEmbedder.cu:197): the product rounded to fp32, then to fp16.  Left to itself the compiler folds the
+// conversion into the multiplication (v_fma_mixlo_f16: k_hash_cu_bwd, and four products per sample of k_hash_bwd_ray<4>, <8>), which rounds the exact product ONCE -- one
+// fp16 ulp from the reference in ~4e-5 of the addends.  The empty statement keeps the fp32 product a value of its own.  The F = 1, 2 walks and k_hash_bwd_ray_fl convert
+// their products two at a time (v_cvt_pk_f16_f32), were never folded and keep the plain form and their instruction stream; tests/test_hash_backward_gpu.py holds every one
+// of them to the two-rounding addends.
+__device__ __forceinline__ float cu_addend_f16(float g, float w)
+{
+    float p = g * w;
+    asm("" : "+v"(p));
+    return __half2float(__float2half_rn(p));
+}
+
 // CuHashEmbedder (CuHashEmbedder.cu:105-216): grad_in = fp16(g * 128) (:297), each corner adds fp16(grad_in * w) (:196-197) into the
 // level's slice of the pool at the forward's (quirky) element offset, result / 128 (:323).  The reference accumulates with fp16
 // atomics (order-dependent, saturating); here the per-corner contributions are rounded exactly as there but ACCUMULATED IN FP32.
@@ -206,7 +218,7 @@ __global__ void k_hash_cu_bwd(HashParams hp, const float *__restrict__ pts, int6
         const uint32_t ps = ((lsz & (lsz - 1u)) == 0u) ? ((hx ^ hy ^ hz) & (lsz - 1u)) : ((hx ^ hy ^ hz) % lsz);       // local_size is a power of two for T >= 4
         const float w = ((k & 4) ? a : 1.0f - a) * ((k & 2) ? b : 1.0f - b) * ((k & 1) ? c : 1.0f - c);
 #pragma unroll
-        for (int f = 0; f < F; f++) unsafeAtomicAdd(tl + (size_t)ps * F + f, __half2float(__float2half_rn(g[f] * w)) * (1.0f / 128.0f));
+        for (int f = 0; f < F; f++) unsafeAtomicAdd(tl + (size_t)ps * F + f, cu_addend_f16(g[f], w) * (1.0f / 128.0f));
     }
 }
 
@@ -417,7 +429,8 @@ __device__ __forceinline__ void hash_bwd_walk(const HashParams &hp, const float 
             const float wx = ((k >> 2) & 1) ? w[0] : 1.0f - w[0], wy = ((k >> 1) & 1) ? w[1] : 1.0f - w[1], wz = (k & 1) ? w[2] : 1.0f - w[2];
 #pragma unroll
             for (int f = 0; f < F; f++) {
-                if constexpr (CU) acc[k][f] += __half2float(__float2half_rn(g[f] * (wx * wy * wz))) * (1.0f / 128.0f);
+                if constexpr (CU && F > 2) acc[k][f] += cu_addend_f16(g[f], wx * wy * wz) * (1.0f / 128.0f);          // (the F = 4, 8 instances had four products folded)
+                else if constexpr (CU) acc[k][f] += __half2float(__float2half_rn(g[f] * (wx * wy * wz))) * (1.0f / 128.0f);
                 else acc[k][f] += ((g[f] * wz) * wy) * wx;
             }
         }

@@ -281,7 +281,10 @@ NRF_API int nrf_raw2weights_gather(const float *d_raw, int c, int sigma_ch, cons
  *   nrf_lerf_render_embedding : out[n, 768] = sum_s weights[n,s] * normalize(le(x[n,s]))  (LeRF.cpp:96-108 + the sum of LeRFRenderer.h:45-54);
  *                               s must be a multiple of 32.  L2-normalise `out` afterwards (nrf_render_clip_embedding's last step).
  *                               Evaluated as W . sum_s (weights / ||W a||) a with ||W a||^2 = a^T (W^T W) a (the output layer is bias-free, hence linear): the
- *                               256 -> 768 layer runs once per ray.  Takes n * 256 floats of stream-ordered scratch (hipMallocAsync / hipFreeAsync). */
+ *                               256 -> 768 layer runs once per ray.  Takes n * 256 floats of stream-ordered scratch (hipMallocAsync / hipFreeAsync).
+ *                               The weight image holds W^T W and W each times a power of two chosen from max|W^T W| (fp16 range; mlp_lerf_mfma.hip), so `out` does not
+ *                               depend on a power-of-two scale of W (pinned for W x 2^-8 .. 2^+8); the 1e-8 floor applies to ||W a|| with W at the image's scale, its
+ *                               largest column norm in (sqrt 2, sqrt 8] -- the reference initialisation's own. */
 NRF_API int nrf_lerf_mfma_available(const nrf_mlp *m);
 /* Arithmetic of the four fused entries below, per handle: NRF_PREC_F16_MFMA (default: fp16 operands, fp32 accumulate) or NRF_PREC_F16_SPLIT (hi + lo fp16
  * operand pairs, three products: fp32-grade, as LeRFImpl::forward computes -- mlp_lerf_split_mfma.hip).  Call between, not during, passes. */

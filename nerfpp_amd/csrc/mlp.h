@@ -67,6 +67,7 @@ struct nrf_mlp {
     float *d_lerf_gram = nullptr;            // LeRF device pack: the Gram matrix [256][256] in its packed form (scaled, block triangle), W^T W itself, the bits of its largest entry
     bool lerf_gram_current = false;          // d_lerf_gram's W^T W belongs to the parameters now in d_params (set by the device packer, cleared by a host re-pack)
     bool lerf_device_pack = false;           // the device packers reproduce the host packers' images byte for byte (checked at creation): nrf_mlp_set_params stays on the device
+    int lerf_le1_exp = 0;                    // LeRF: kernel C's image of the embedding layer is LE1 * 2^-lerf_le1_exp; the kernel-B launchers compensate (mlp_lerf_mfma.hip: lerf_le1_exponent)
     float lerf_gram_scale = 1.0f;            // LeRF: the Gram matrix of the embedding layer is stored divided by this power of two (fp16 range), see mlp_lerf_mfma.hip
     void *d_packed_bwd = nullptr;            // W^T fragments of the matrix-core backward (mlp_small_bwd_mfma.hip)
     size_t packed_bwd_bytes = 0;

@@ -1282,6 +1282,7 @@ static int lerf_device_pack_verify(nrf_mlp *m, hipStream_t st)
     NRF_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < 3; i++) { host[i].resize(bytes[i]); NRF_HIP(hipMemcpy(host[i].data(), dev[i], bytes[i], hipMemcpyDeviceToHost)); }
     const float scale = m->lerf_gram_scale;
+    const int le1_exp = m->lerf_le1_exp;
     bool same = mlp_lerf_pack_f16_device(m, st) == NRF_OK && mlp_lerf_pack_sigma_f32_device(m, st) == NRF_OK;
     if (same) {
         NRF_HIP(hipStreamSynchronize(st));
@@ -1290,11 +1291,12 @@ static int lerf_device_pack_verify(nrf_mlp *m, hipStream_t st)
             NRF_HIP(hipMemcpy(mine[i].data(), dev[i], bytes[i], hipMemcpyDeviceToHost));
             same = memcmp(mine[i].data(), host[i].data(), bytes[i]) == 0;
         }
-        same = same && m->lerf_gram_scale == scale;
+        same = same && m->lerf_gram_scale == scale && m->lerf_le1_exp == le1_exp;
     }
     if (!same) {
         for (int i = 0; i < 3; i++) NRF_HIP(hipMemcpy(dev[i], host[i].data(), bytes[i], hipMemcpyHostToDevice));
         m->lerf_gram_scale = scale;
+        m->lerf_le1_exp = le1_exp;
     }
     m->lerf_device_pack = same;
     return NRF_OK;

@@ -261,7 +261,8 @@ k_lerf_embed(int64_t nrays, const float *__restrict__ asum, const half8 *__restr
 }
 
 // value of the weight that multiplies operand element (kstep, h, j) for output row `row` of kernel layer L (host packer and device packer: one statement of the layout)
-__host__ __device__ inline float lerf_wval(const float *hp, const float *gram, int L, int row, int kstep, int h, int j)
+// le1_exp: the image holds LE1 * 2^-le1_exp (lerf_le1_exponent)
+__host__ __device__ inline float lerf_wval(const float *hp, const float *gram, int L, int row, int kstep, int h, int j, int le1_exp)
 {
     const size_t off0 = 0, off1 = off0 + (size_t)HID * IN, off2 = off1 + (size_t)(1 + GEO) * HID, off3 = off2 + (size_t)HID * (GEO + IN);
     const int chained = 32 * (kstep >> 1) + perm_row(kstep & 1, h, j);
@@ -275,7 +276,7 @@ __host__ __device__ inline float lerf_wval(const float *hp, const float *gram, i
         return hp[off2 + (size_t)row * (GEO + IN) + GEO + (16 * (kstep - 4) + 8 * h + j)];
     }
     if (L == 3) return gram[(size_t)row * HID + chained];
-    return hp[off3 + (size_t)row * HID + natural];          // LE1 for kernel C: its operand comes from memory, natural order
+    return ldexpf(hp[off3 + (size_t)row * HID + natural], -le1_exp);          // LE1 for kernel C: its operand comes from memory, natural order
 }
 
 // fragment f of the image -> (layer, tile, k-step): layers in order, tiles of a layer in order, k-steps of a tile in order
@@ -324,12 +325,12 @@ __global__ void k_lerf_gram_finish(float *__restrict__ gram, int e)
 }
 
 // one workgroup per fragment, one thread per element: the fp16 image and the split image's (hi, lo) fragment pair
-__global__ void __launch_bounds__(512) k_lerf_fill(const float *__restrict__ hp, const float *__restrict__ gram, _Float16 *__restrict__ img, _Float16 *__restrict__ img2)
+__global__ void __launch_bounds__(512) k_lerf_fill(const float *__restrict__ hp, const float *__restrict__ gram, _Float16 *__restrict__ img, _Float16 *__restrict__ img2, int le1_exp)
 {
     const int f = blockIdx.x, e = threadIdx.x, lane = e >> 3, j = e & 7;
     int L, tile, k;
     lerf_frag_id(f, L, tile, k);
-    const float v = lerf_wval(hp, gram, L, tile * 32 + (lane & 31), k, lane >> 5, j);
+    const float v = lerf_wval(hp, gram, L, tile * 32 + (lane & 31), k, lane >> 5, j, le1_exp);
     const _Float16 hv = (_Float16)v;
     img[(size_t)f * 512 + e] = hv;
     img2[(size_t)(2 * f) * 512 + e] = hv;
@@ -344,6 +345,27 @@ static bool lerf_mfma_supported(const nrf_mlp_small_desc &d)
 {
     return d.input_ch == IN && d.num_layers == 2 && d.hidden_dim == HID && d.geo_feat_dim == GEO && d.hidden_dim_color == EMB;
 }
+
+// The Gram matrix's power-of-two exponent e (host and device packer): the image holds G 2^-e with max|G| 2^-e in (512, 1024] -- scaled DOWN into fp16's range for
+// large weights (entries of G are sums of 768 products and pass 65504 for weights of moderate size) and UP for small ones: at max|G| ~ 1e-4 (LE1 of the default
+// initialisation x 2^-8) the off-diagonal entries, a hundredth of the diagonal, are fp16 subnormals, and the per-sample norm was off by 1e-3 (2^-10: 3e-2).
+// Exact scaling either way; the kernels multiply a^T G a back by 2^e (lerf_gram_scale).
+static int lerf_gram_exponent(float gmax)
+{
+    if (!(gmax > 0.0f) || !std::isfinite(gmax)) return 0;
+    int e = 0;
+    const float mant = frexpf(gmax / 1024.0f, &e);          // gmax / 1024 = mant 2^e, mant in [0.5, 1)
+    if (mant == 0.5f) e -= 1;                               // an exact power of two sits at the upper end
+    return e < -100 ? -100 : e;                             // 2^e stays a normal float
+}
+
+// Kernel C multiplies two fp16 (hi, lo) operands, LE1 and the ray's sum asum = sum_s (w_s / ||W a_s||) a_s, whose product does not depend on the scale of LE1 while each
+// factor does: with LE1 x 2^-8 the lo parts of the weights (and the hi parts of the small ones) are fp16 subnormals and the direction of a ray sum was off by 1e-5, with
+// LE1 x 2^+8 asum shrinks the same way.  The image therefore holds LE1 2^-c and kernel B is handed 2^(e - 2c) for 2^e (launch_lerf, launch_lerf_split), which makes
+// its shares, hence asum, 2^c larger: c follows the Gram exponent e (max|G| = LE1's largest squared column norm), c = floor((e + 8) / 2), so that e - 2c is -8 or -7 -- the
+// largest column norm of the image's LE1 lies in (sqrt 2, sqrt 8] whatever the parameters' scale, and a network scaled by a power of two computes the same bits.
+// c = 0 for the reference's initialisation (column norms^2 of 2 .. 8); the 1e-8 floor of the normalisation applies to ||W a|| 2^-c.
+static int lerf_le1_exponent(int e) { return (e + 8) >> 1; }
 
 int mlp_lerf_pack_f16(nrf_mlp *m, const std::vector<float> &hp)
 {
@@ -389,14 +411,14 @@ int mlp_lerf_pack_f16(nrf_mlp *m, const std::vector<float> &hp)
             for (auto &x : th) x.join();
         }
     }
-    // fp16 range: entries of G are sums of 768 products and pass 65504 for weights of moderate size; G is stored divided by a power of two that brings
-    // max|G| to <= 1024 (exact scaling; the kernels multiply a^T G a back), so neither the entries nor the fp16 rounding of large ones can overflow
+    // fp16 range: G is stored divided by the power of two that brings max|G| into (512, 1024] (lerf_gram_exponent), so neither the entries nor the fp16 rounding of
+    // large ones can overflow and those of a small matrix stay normal numbers
     {
         float gmax = 0.0f;
         for (float g : gram) gmax = fmaxf(gmax, fabsf(g));
-        int e = 0;
-        if (gmax > 1024.0f) (void)frexpf(gmax / 1024.0f, &e);
+        const int e = lerf_gram_exponent(gmax);
         m->lerf_gram_scale = ldexpf(1.0f, e);
+        m->lerf_le1_exp = lerf_le1_exponent(e);
         if (e != 0) for (float &g : gram) g = ldexpf(g, -e);
     }
     // ... and as its upper BLOCK triangle: a^T G a = sum_T a_T^T G_TT a_T + 2 sum_{T < U} a_T^T G_TU a_U over 32-neuron blocks (G is symmetric), so the image
@@ -425,7 +447,7 @@ int mlp_lerf_pack_f16(nrf_mlp *m, const std::vector<float> &hp)
             const FragId id = frags[(size_t)f];
             for (int lane = 0; lane < 64; lane++)
                 for (int j = 0; j < 8; j++) {
-                    const float v = lerf_wval(hp.data(), gram.data(), id.L, id.tile * 32 + (lane & 31), id.k, lane >> 5, j);
+                    const float v = lerf_wval(hp.data(), gram.data(), id.L, id.tile * 32 + (lane & 31), id.k, lane >> 5, j, m->lerf_le1_exp);
                     const _Float16 hv = (_Float16)v;
                     const size_t e = (size_t)lane * 8 + j;
                     img[(size_t)f * 512 + e] = hv;
@@ -466,13 +488,13 @@ int mlp_lerf_pack_f16_device(nrf_mlp *m, hipStream_t st)
     NRF_HIP(hipMemcpyAsync(&bits, gmax, sizeof(bits), hipMemcpyDeviceToHost, st));
     NRF_HIP(hipStreamSynchronize(st));
     float gm; memcpy(&gm, &bits, 4);
-    int e = 0;
-    if (gm > 1024.0f) (void)frexpf(gm / 1024.0f, &e);
+    const int e = lerf_gram_exponent(gm);
     m->lerf_gram_scale = ldexpf(1.0f, e);
+    m->lerf_le1_exp = lerf_le1_exponent(e);
     hipLaunchKernelGGL(k_lerf_gram_finish, dim3(HID * HID / 256), dim3(256), 0, st, m->d_lerf_gram, e);
     NRF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_lerf_fill, dim3(IMAGE_FRAGS), dim3(512), 0, st, (const float *)m->d_params, (const float *)m->d_lerf_gram, reinterpret_cast<_Float16 *>(m->d_packed_f16),
-                       reinterpret_cast<_Float16 *>(m->d_packed_split));
+                       reinterpret_cast<_Float16 *>(m->d_packed_split), m->lerf_le1_exp);
     NRF_LAUNCH_CHECK();
     m->lerf_gram_current = true;
     return NRF_OK;
@@ -482,7 +504,7 @@ template <int NL>
 static int launch_lerf(const nrf_mlp *m, const Args &a_in, int64_t p, hipStream_t st)
 {
     Args a = a_in;
-    a.gram_scale = m->lerf_gram_scale;
+    a.gram_scale = NL == 2 ? m->lerf_gram_scale : ldexpf(m->lerf_gram_scale, -2 * m->lerf_le1_exp);          // kernel B: shares 2^c larger, for kernel C's LE1 2^-c (lerf_le1_exponent)
     const size_t lds = (size_t)3 * MAXF * 1024;
     const int64_t nblocks = ceil_div(p, NBLK);
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);       // persistent: one 8-wave workgroup per CU (216 VGPRs: two waves per SIMD)

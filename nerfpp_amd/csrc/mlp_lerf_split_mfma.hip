@@ -676,7 +676,7 @@ template <int NL>
 static int launch_lerf_split(const nrf_mlp *m, const Args &a_in, int64_t p, hipStream_t st)
 {
     Args a = a_in;
-    a.gram_scale = m->lerf_gram_scale;
+    a.gram_scale = NL == 2 ? m->lerf_gram_scale : ldexpf(m->lerf_gram_scale, -2 * m->lerf_le1_exp);          // kernel B: shares 2^c larger, for kernel C's LE1 2^-c (mlp_lerf_mfma.hip: lerf_le1_exponent)
     const size_t lds = (size_t)3 * SMAXF * 1024;
     const size_t lds_geo = lds + (size_t)SNW * (GEO_OPER_FRAGS + 1) * 1024;          // + the waves' operand slots (k_lerf_split_geo)
     const int64_t nblocks = NL == 2 ? ceil_div(p, SNBLK) : ceil_div(p / a.s, (int64_t)SNW);       // kernel B: one ray per wave

@@ -1017,6 +1017,9 @@ NRF_API int nrf_lerf_backward_points_src(const nrf_lerf_renderer *r, const void 
  * from call to call -- not from hipMallocAsync, whose pool proved unsafe inside a LibTorch host (scratch.hip).  nrf_scratch_trim gives the idle blocks back to the driver
  * (after a hipDeviceSynchronize of their devices) and returns the bytes freed; optional. */
 NRF_API size_t nrf_scratch_trim(void);
+/* Bytes of device memory the library holds right now: everything its handles own plus its scratch blocks, idle ones included.  Pinned host memory is not counted.
+ * One counter for the process (all devices); every device allocation of the library goes through it. */
+NRF_API int64_t nrf_device_bytes_in_use(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Instrumentation (bench / tests)

@@ -275,6 +275,7 @@ _ABI = """
     nrf_lerf_renderer_last_features(pppppppp)
     nrf_lerf_backward_points_src(pplpppppilipfppppzp)
     nrf_scratch_trim()->z
+    nrf_device_bytes_in_use()->l
     nrf_set_render_lanes(i)
     nrf_get_render_lanes()
     nrf_set_live_colour(i)

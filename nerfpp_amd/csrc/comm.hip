@@ -26,7 +26,8 @@ struct nrf_comm {
     int world = 1, rank = 0;
     bool owned = false;
     // nrf_allreduce_grads: the overflow word the ranks agree on before any gradient is exchanged (device float + pinned mirror; created on first use)
-    mutable float *d_word = nullptr, *h_word = nullptr;
+    mutable nrf::DevBuf d_word;
+    mutable nrf::PinnedBuf h_word;
 };
 
 namespace nrf {
@@ -190,9 +191,9 @@ int nrf_comm_create_timeout(const void *id, int world, int rank, double timeout_
     } else {
         NRF_NCCL(R, R->CommInitRank(&c, world, uid, rank));     // on the calling thread's current HIP device; blocks until all ranks arrive
     }
-    nrf_comm *cm = new nrf_comm();
+    std::unique_ptr<nrf_comm> cm(new nrf_comm());
     cm->comm = c; cm->world = world; cm->rank = rank; cm->owned = true;
-    *out = cm;
+    *out = cm.release();
     return NRF_OK;
 }
 
@@ -215,19 +216,17 @@ int nrf_comm_wrap(void *nccl_comm, nrf_comm **out)
     NRF_CHECK_ARG(nccl_comm && out, "nrf_comm_wrap: null pointer");
     const Rccl *R = rccl();
     if (!R) return NRF_ERR_UNSUPPORTED;
-    nrf_comm *cm = new nrf_comm();
+    std::unique_ptr<nrf_comm> cm(new nrf_comm());
     cm->comm = static_cast<ncclComm_t>(nccl_comm);
     ncclResult_t e1 = R->CommCount(cm->comm, &cm->world), e2 = R->CommUserRank(cm->comm, &cm->rank);
-    if (e1 != ncclSuccess || e2 != ncclSuccess) { delete cm; set_error("nrf_comm_wrap: not a live ncclComm_t of the RCCL mapped into this process"); return NRF_ERR_INVALID_ARG; }
-    *out = cm;
+    if (e1 != ncclSuccess || e2 != ncclSuccess) { set_error("nrf_comm_wrap: not a live ncclComm_t of the RCCL mapped into this process"); return NRF_ERR_INVALID_ARG; }
+    *out = cm.release();
     return NRF_OK;
 }
 
 void nrf_comm_destroy(nrf_comm *c)
 {
     if (!c) return;
-    if (c->d_word) (void)hipFree(c->d_word);
-    if (c->h_word) (void)hipHostFree(c->h_word);
     if (c->owned && c->comm && g_rccl.handle) (void)g_rccl.CommDestroy(c->comm);
     delete c;
 }
@@ -295,19 +294,18 @@ int nrf_allreduce_grads(const nrf_comm *c, float *const *d_grads, const int64_t 
     if (!R) return NRF_ERR_UNSUPPORTED;
     hipStream_t st = as_stream(stream);
     if (overflow >= 0) {
-        if (!c->d_word) {
-            NRF_HIP(hipMalloc(reinterpret_cast<void **>(&c->d_word), sizeof(float)));
-            NRF_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_word), sizeof(float), hipHostMallocDefault));
-        }
-        *c->h_word = overflow ? 1.0f : 0.0f;
-        NRF_HIP(hipMemcpyAsync(c->d_word, c->h_word, sizeof(float), hipMemcpyHostToDevice, st));
+        NRF_TRY(c->d_word.resize(sizeof(float)));          // (both: created on first use, kept afterwards)
+        NRF_TRY(c->h_word.resize(sizeof(float)));
+        float *const d_word = c->d_word.as<float>(), *const h_word = c->h_word.as<float>();
+        *h_word = overflow ? 1.0f : 0.0f;
+        NRF_HIP(hipMemcpyAsync(d_word, h_word, sizeof(float), hipMemcpyHostToDevice, st));
         NRF_NCCL(R, R->GroupStart());
-        const ncclResult_t e1 = R->AllReduce(c->d_word, c->d_word, 1, ncclFloat, ncclMax, c->comm, st);
+        const ncclResult_t e1 = R->AllReduce(d_word, d_word, 1, ncclFloat, ncclMax, c->comm, st);
         const ncclResult_t e2 = settle_group_end(R, c, R->GroupEnd());
         if (e1 != ncclSuccess || e2 != ncclSuccess) { set_error("nrf_allreduce_grads: the overflow agreement failed: %s", R->GetErrorString(e1 != ncclSuccess ? e1 : e2)); return NRF_ERR_HIP; }
-        NRF_HIP(hipMemcpyAsync(c->h_word, c->d_word, sizeof(float), hipMemcpyDeviceToHost, st));
+        NRF_HIP(hipMemcpyAsync(h_word, d_word, sizeof(float), hipMemcpyDeviceToHost, st));
         NRF_HIP(hipStreamSynchronize(st));
-        if (*c->h_word > 0.0f) { *skip_out = 1; return NRF_OK; }
+        if (*h_word > 0.0f) { *skip_out = 1; return NRF_OK; }
     }
     const int64_t bucket = bucket_bytes > 0 ? (bucket_bytes / 4 > 0 ? bucket_bytes / 4 : 1) : ((int64_t)32 << 20) / 4;          // elements; default 32 MiB
     NRF_NCCL(R, R->GroupStart());

@@ -12,14 +12,10 @@
 
 #include "nerfpp_hip.h"
 #include "nrf_math.h"
+#include "owned.h"          // set_error, the NRF_* early-return macros, DevBuf / PinnedBuf / Scratch
 
 namespace nrf {
 
-void set_error(const char *fmt, ...);
-// the library's own stream-ordered scratch (scratch.hip): a buffer for work enqueued on `st`; given back, it serves the next taker ON THAT STREAM.  Drop-in replacements of
-// hipMallocAsync / hipFreeAsync (same return type), which proved unsafe inside the LibTorch host
-hipError_t scratch_take(void **out, size_t bytes, hipStream_t st);
-hipError_t scratch_give(void *p, hipStream_t st);
 // render.hip, for mesh.hip: sigma = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at p explicit points [p, 3], bit for bit, on the exact-fp32 density kernels where the
 // renderer has them (1 <= p <= 2^30)
 size_t renderer_density_ws_bytes(const nrf_renderer *r, int64_t p);
@@ -31,38 +27,6 @@ const char *density_grad_unsupported(const nrf_hash *h, const nrf_mlp *m);
 int density_grad_launch(const nrf_hash *h, const nrf_mlp *m, const PointSource &ps, int64_t p, const float *wsel, float *sigma, float *grad, hipStream_t st);
 //   out[ray] = sum_j w[ray][j] * sign * safe_normalize(v[row][v_col .. v_col + 2]), row = src ? src[ray * s + j] : ray * s + j, ascending j, w == 0 skipped
 int normals_composite(int64_t n, int s, const float *v, int v_stride, int v_col, const int32_t *src, float sign, const float *weights, float *out, hipStream_t st);
-
-#define NRF_CHECK_ARG(cond, ...)                                   \
-    do {                                                           \
-        if (!(cond)) {                                             \
-            ::nrf::set_error(__VA_ARGS__);                         \
-            return NRF_ERR_INVALID_ARG;                            \
-        }                                                          \
-    } while (0)
-
-#define NRF_HIP(call)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            ::nrf::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return NRF_ERR_HIP;                                                                   \
-        }                                                                                         \
-    } while (0)
-
-#define NRF_LAUNCH_CHECK()                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = hipGetLastError();                                                        \
-        if (e_ != hipSuccess) {                                                                   \
-            ::nrf::set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
-            return NRF_ERR_HIP;                                                                   \
-        }                                                                                         \
-    } while (0)
-
-#define NRF_TRY(expr)                  \
-    do {                               \
-        int s_ = (expr);               \
-        if (s_ != NRF_OK) return s_;   \
-    } while (0)
 
 // One-time kernel attribute setup (the dynamic-LDS window of a kernel) is per DEVICE, not per process: a process that drives several GPUs (the nrf_comm_* C ABI
 // allows one communicator per device) must set it on each.  needed() is true until done() has been called for the calling thread's current device; the setup

@@ -30,19 +30,18 @@ struct HashParams {
 struct nrf_hash {
     nrf_hash_desc desc;
     nrf::HashParams params;
-    void *d_table = nullptr;
+    nrf::DevBuf d_table;
     bool table_set = false;
     bool primes_set = false;
     // fast-path image of the table (hash_fast.hip), rebuilt lazily after the table or primes change
-    void *d_fast = nullptr;
-    size_t fast_bytes = 0;
+    nrf::DevBuf d_fast;
     bool fast_valid = false;
     int dense_levels = 0;
     // RMS of the table's entries (device float; a deterministic two-stage sum: the same table always gives the same bits), re-derived on demand
     // (hash_table_rms_update) when the table was uploaded since, and a counter of the uploads: what a renderer's split-precision network scales its first layer by
     // (mlp.h, k_small_scales)
-    float *d_table_rms = nullptr;
-    float *d_rms_part = nullptr;
+    nrf::DevBuf d_table_rms;          // one float
+    nrf::DevBuf d_rms_part;           // float [RMS_BLOCKS]
     uint64_t table_version = 0, rms_version = ~(uint64_t)0;
     size_t dense_budget = (size_t)24 << 30;   // bytes of dense image to bake (levels 0.. while they fit): 4.4 GB at 16..512; at 16..1024 the finest level (35 GB) stays hashed -- HBM is 288 GB
 };

@@ -221,10 +221,10 @@ int hash_table_rms_update(nrf_hash *h, hipStream_t st)
     if (!h || !h->table_set || !h->d_table_rms) return NRF_OK;
     if (h->rms_version == h->table_version) return NRF_OK;
     const int64_t elems = nrf_hash_table_elems(h);
-    if (h->desc.mode == NRF_HASH_NGP) hipLaunchKernelGGL(k_sumsq_partial<float>, dim3(RMS_BLOCKS), dim3(256), 0, st, elems, reinterpret_cast<const float *>(h->d_table), h->d_rms_part);
-    else hipLaunchKernelGGL(k_sumsq_partial<__half>, dim3(RMS_BLOCKS), dim3(256), 0, st, elems, reinterpret_cast<const __half *>(h->d_table), h->d_rms_part);
+    if (h->desc.mode == NRF_HASH_NGP) hipLaunchKernelGGL(k_sumsq_partial<float>, dim3(RMS_BLOCKS), dim3(256), 0, st, elems, h->d_table.as<const float>(), h->d_rms_part.as<float>());
+    else hipLaunchKernelGGL(k_sumsq_partial<__half>, dim3(RMS_BLOCKS), dim3(256), 0, st, elems, h->d_table.as<const __half>(), h->d_rms_part.as<float>());
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_rms_final, dim3(1), dim3(1), 0, st, elems, h->d_rms_part, h->d_table_rms);
+    hipLaunchKernelGGL(k_rms_final, dim3(1), dim3(1), 0, st, elems, h->d_rms_part.as<float>(), h->d_table_rms.as<float>());
     NRF_LAUNCH_CHECK();
     h->rms_version = h->table_version;
     return NRF_OK;
@@ -310,7 +310,8 @@ int nrf_hash_create(const nrf_hash_desc *desc, nrf_hash **out)
     NRF_CHECK_ARG(desc->n_features == 1 || desc->n_features == 2 || desc->n_features == 4 || desc->n_features == 8, "nrf_hash_create: n_features %d not in {1,2,4,8}", desc->n_features);
     NRF_CHECK_ARG(desc->base_resolution >= 1 && desc->finest_resolution >= desc->base_resolution, "nrf_hash_create: bad resolutions");
     for (int a = 0; a < 3; a++) NRF_CHECK_ARG(desc->bbox[3 + a] > desc->bbox[a], "nrf_hash_create: empty bounding box on axis %d", a);
-    nrf_hash *h = new nrf_hash();
+    std::unique_ptr<nrf_hash> owner(new nrf_hash());
+    nrf_hash *h = owner.get();
     h->desc = *desc;
     const int L = desc->n_levels;
     HashParams &hp = h->params;
@@ -336,28 +337,19 @@ int nrf_hash_create(const nrf_hash_desc *desc, nrf_hash **out)
     }
     const int64_t elems = (int64_t)L * ((int64_t)1 << desc->log2_hashmap_size) * desc->n_features;
     const size_t bytes = (size_t)elems * (desc->mode == NRF_HASH_NGP ? 4 : 2);
-    hipError_t e = hipMalloc(&h->d_table, bytes);
-    if (e != hipSuccess) { set_error("nrf_hash_create: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); delete h; return NRF_ERR_HIP; }
-    hp.table = h->d_table;
-    *out = h;
+    NRF_TRY(h->d_table.resize(bytes));
+    hp.table = h->d_table.as<void>();
+    *out = owner.release();
     return NRF_OK;
 }
 
-void nrf_hash_destroy(nrf_hash *h)
-{
-    if (!h) return;
-    if (h->d_table) (void)hipFree(h->d_table);
-    if (h->d_fast) (void)hipFree(h->d_fast);
-    if (h->d_table_rms) (void)hipFree(h->d_table_rms);
-    if (h->d_rms_part) (void)hipFree(h->d_rms_part);
-    delete h;
-}
+void nrf_hash_destroy(nrf_hash *h) { delete h; }
 
 int nrf_hash_memory_bytes(const nrf_hash *h, int64_t *table_bytes, int64_t *baked_bytes)
 {
     NRF_CHECK_ARG(h, "nrf_hash_memory_bytes: null pointer");
     if (table_bytes) *table_bytes = nrf_hash_table_elems(h) * (h->desc.mode == NRF_HASH_CU ? 2 : 4);
-    if (baked_bytes) *baked_bytes = (int64_t)h->fast_bytes;
+    if (baked_bytes) *baked_bytes = (int64_t)h->d_fast.bytes();
     return NRF_OK;
 }
 
@@ -370,23 +362,23 @@ int nrf_hash_set_table(nrf_hash *h, const float *src, int src_on_device, void *s
     const int64_t elems = nrf_hash_table_elems(h);
     hipStream_t st = as_stream(stream);
     if (!h->d_table_rms) {
-        NRF_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_table_rms), sizeof(float)));
-        NRF_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_rms_part), RMS_BLOCKS * sizeof(float)));
+        NRF_TRY(h->d_table_rms.resize(sizeof(float)));
+        NRF_TRY(h->d_rms_part.resize(RMS_BLOCKS * sizeof(float)));
     }
     if (h->desc.mode == NRF_HASH_NGP) {
-        NRF_HIP(hipMemcpyAsync(h->d_table, src, (size_t)elems * 4, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        NRF_HIP(hipMemcpyAsync(h->d_table.as<void>(), src, (size_t)elems * 4, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     } else {
         // fp32 master -> fp16 once (the reference re-casts on every forward, CuHashEmbedder.cu:257)
         const float *d_src = src;
-        float *tmp = nullptr;
+        DevBuf tmp;
         if (!src_on_device) {
-            NRF_HIP(hipMalloc(reinterpret_cast<void **>(&tmp), (size_t)elems * 4));
-            NRF_HIP(hipMemcpyAsync(tmp, src, (size_t)elems * 4, hipMemcpyHostToDevice, st));
-            d_src = tmp;
+            NRF_TRY(tmp.resize((size_t)elems * 4));
+            NRF_HIP(hipMemcpyAsync(tmp.as<void>(), src, (size_t)elems * 4, hipMemcpyHostToDevice, st));
+            d_src = tmp.as<float>();
         }
-        hipLaunchKernelGGL(k_f32_to_f16, dim3((unsigned)ceil_div(elems, 256)), dim3(256), 0, st, elems, d_src, reinterpret_cast<__half *>(h->d_table));
+        hipLaunchKernelGGL(k_f32_to_f16, dim3((unsigned)ceil_div(elems, 256)), dim3(256), 0, st, elems, d_src, h->d_table.as<__half>());
         NRF_LAUNCH_CHECK();
-        if (tmp) { NRF_HIP(hipStreamSynchronize(st)); NRF_HIP(hipFree(tmp)); }
+        if (tmp) NRF_HIP(hipStreamSynchronize(st));          // (the conversion has read tmp before it is freed at the end of this scope)
     }
     h->table_set = true;
     h->fast_valid = false;

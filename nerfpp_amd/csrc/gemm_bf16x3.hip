@@ -944,11 +944,9 @@ int gemm_tn_bf16x3_2(int64_t P, Seg g, Seg x, int col0, Seg x1, int col1, int sk
     if (slices < 1) slices = 1;
     a.slice_pts = ((P32 / 32 + slices - 1) / slices) * 32;
     slices = (P32 + a.slice_pts - 1) / a.slice_pts;
-    float *part = nullptr;
-    if (scratch_take(reinterpret_cast<void **>(&part), ((size_t)slices * out * nn + (db ? (size_t)slices * out : 0)) * sizeof(float), st) != hipSuccess) {
-        set_error("gemm_tn_bf16x3: scratch allocation failed");
-        return NRF_ERR_HIP;
-    }
+    Scratch buf;
+    NRF_TRY(buf.take(((size_t)slices * out * nn + (db ? (size_t)slices * out : 0)) * sizeof(float), st));
+    float *part = buf.as<float>();
     gb_poison(part, ((size_t)slices * out * nn + (db ? (size_t)slices * out : 0)) * sizeof(float), st);
     a.part = part;
     a.bpart = db ? part + (size_t)slices * out * nn : nullptr;
@@ -962,9 +960,7 @@ int gemm_tn_bf16x3_2(int64_t P, Seg g, Seg x, int col0, Seg x1, int col1, int sk
     else hipLaunchKernelGGL(k_gemm_tn<false>, dim3((unsigned)(slices * tiles)), dim3(256), 2 * TN_STAGE, st, a);
     hipLaunchKernelGGL(k_tn_sum, dim3((unsigned)ceil_div((int64_t)out * nn, (int64_t)256)), dim3(256), 0, st, (int)slices, out, a.n, a.n1, in, col0, col1, two ? skip1 : 0, two ? keep1 : 0, (const float *)part, dw);
     if (db) hipLaunchKernelGGL(k_tn_bias_sum, dim3((unsigned)out), dim3(64), 0, st, (int)slices, out, (const float *)a.bpart, db);
-    const hipError_t le = hipGetLastError();
-    (void)scratch_give(part, st);
-    if (le != hipSuccess) { set_error("gemm_tn_bf16x3: launch failed: %s", hipGetErrorString(le)); return NRF_ERR_HIP; }
+    NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
 
@@ -1000,8 +996,9 @@ int gemm_tn_thin(int64_t P, Seg g, Seg x, int out, int in, int col0, float *dw, 
     int64_t slices = P / 1024; if (slices > 512) slices = 512; if (slices < 1) slices = 1;
     const int64_t slice_pts = (P + slices - 1) / slices;
     slices = (P + slice_pts - 1) / slice_pts;
-    float *part = nullptr;
-    if (scratch_take(reinterpret_cast<void **>(&part), (size_t)slices * 4 * x.n * sizeof(float), st) != hipSuccess) { set_error("gemm_tn_thin: scratch allocation failed"); return NRF_ERR_HIP; }
+    Scratch buf;
+    NRF_TRY(buf.take((size_t)slices * 4 * x.n * sizeof(float), st));
+    float *part = buf.as<float>();
     gb_poison(part, (size_t)slices * 4 * x.n * sizeof(float), st);
     const dim3 grid((unsigned)ceil_div((int64_t)x.n, (int64_t)256), (unsigned)slices);
     for (int o0 = 0; o0 < out; o0 += 4) {
@@ -1014,9 +1011,7 @@ int gemm_tn_thin(int64_t P, Seg g, Seg x, int out, int in, int col0, float *dw, 
         hipLaunchKernelGGL(k_tn_sum, dim3((unsigned)ceil_div((int64_t)oc * x.n, (int64_t)256)), dim3(256), 0, st, (int)slices, oc, x.n, 0, in, col0, 0, 0, 0, (const float *)part,
                            dw + (size_t)o0 * in);
     }
-    const hipError_t le = hipGetLastError();
-    (void)scratch_give(part, st);
-    if (le != hipSuccess) { set_error("gemm_tn_thin: launch failed: %s", hipGetErrorString(le)); return NRF_ERR_HIP; }
+    NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
 
@@ -1092,8 +1087,9 @@ static int gemm_nt_launch(GemmNT &g, const float *B, int ldb, hipStream_t st)
     const int T = (g.k0 + GB_BK - 1) / GB_BK + (g.k1 + GB_BK - 1) / GB_BK;
     g.npad = (int)ceil_div((int64_t)g.N, (int64_t)bn) * bn;
     g.bimg_half = (int64_t)T * 2 * g.npad * 32;
-    unsigned char *ws = nullptr;
-    if (scratch_take(reinterpret_cast<void **>(&ws), (size_t)(2 * g.bimg_half + 16), st) != hipSuccess) { set_error("gemm_nt_split: scratch allocation failed"); return NRF_ERR_HIP; }
+    Scratch buf;
+    NRF_TRY(buf.take((size_t)(2 * g.bimg_half + 16), st));
+    unsigned char *ws = buf.as<unsigned char>();
     gb_poison(ws, (size_t)(2 * g.bimg_half + 16), st);
     uint32_t *bmax = reinterpret_cast<uint32_t *>(ws + 2 * g.bimg_half);
     if (F16) {
@@ -1116,9 +1112,7 @@ static int gemm_nt_launch(GemmNT &g, const float *B, int ldb, hipStream_t st)
         else hipLaunchKernelGGL((k_gemm_nt_rows<8, F16>), dim3(pgrid), dim3(512), GB_ROWS_LDS, st, g);
     } else if (wide) hipLaunchKernelGGL((k_gemm_nt<4, F16>), dim3((unsigned)blocks), dim3(512), LDS4, st, g);
     else hipLaunchKernelGGL((k_gemm_nt<2, F16>), dim3((unsigned)blocks), dim3(256), LDS2, st, g);
-    const hipError_t le = hipGetLastError();
-    (void)scratch_give(ws, st);
-    if (le != hipSuccess) { set_error("gemm_nt_split: launch failed: %s", hipGetErrorString(le)); return NRF_ERR_HIP; }
+    NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
 

@@ -99,18 +99,18 @@ int run_linear_fast(int64_t npts, Seg a, Seg b, const nrf_mlp *m, const LinearLa
                     int relu_bits_ld)
 {
     if (const int arith = npts >= 256 ? train_gemm_for(m) : 0)          // split-precision matrix-core product, bias + ReLU in its epilogue (gemm_bf16x3.hip)
-        return gemm_nt_split(arith, npts, L.out, a, b, m->d_params + L.w_off, L.in, y + y_off, y_stride, L.d_bias, relu, nullptr, 0, st, nullptr, 0, nullptr, 0, nullptr,
+        return gemm_nt_split(arith, npts, L.out, a, b, m->params() + L.w_off, L.in, y + y_off, y_stride, L.bias(), relu, nullptr, 0, st, nullptr, 0, nullptr, 0, nullptr,
                              relu ? relu_bits : nullptr, relu_bits_ld);
     if (relu_bits) { set_error("internal: run_linear_fast: mask bits exist in the split-precision modes only"); return NRF_ERR_INVALID_ARG; }
     rocblas_handle h = (npts >= 256) ? rb_handle(st) : nullptr;
     if (!h || npts > 0x7fffffff) return run_linear(npts, a, b, L, relu, y, y_stride, y_off, st);
-    const float *wb = m->d_params + L.w_off;
+    const float *wb = m->params() + L.w_off;
     if (!gemm_fwd_seg(h, npts, a, wb, L.in, 0, L.out, 0.0f, y, y_stride, y_off) || !gemm_fwd_seg(h, npts, b, wb, L.in, a.n, L.out, 1.0f, y, y_stride, y_off)) {
         set_error("rocblas_sgemm failed (forward layer %d -> %d over %lld points)", L.in, L.out, (long long)npts);
         return NRF_ERR_HIP;
     }
-    if (L.d_bias || relu) {
-        hipLaunchKernelGGL(k_bias_relu, dim3((unsigned)ceil_div(npts * L.out, 256)), dim3(256), 0, st, npts * L.out, L.out, y, y_stride, y_off, (const float *)L.d_bias, relu);
+    if (L.bias() || relu) {
+        hipLaunchKernelGGL(k_bias_relu, dim3((unsigned)ceil_div(npts * L.out, 256)), dim3(256), 0, st, npts * L.out, L.out, y, y_stride, y_off, (const float *)L.bias(), relu);
         NRF_LAUNCH_CHECK();
     }
     return NRF_OK;
@@ -147,11 +147,9 @@ int run_grad_w_fast(int64_t npts, Seg g, Seg a, Seg b, int out, int in, float *d
     const float one = 1.0f, zero = 0.0f;
     constexpr int SLICES = 32;
     const bool split = g_rb.sgemm_sb && npts >= 16384 && (int64_t)out * in <= 1024 * 1024;
-    float *part = nullptr;
-    if (split) {
-        const int nmax = a.n > b.n ? a.n : b.n;
-        if (scratch_take(reinterpret_cast<void **>(&part), (size_t)SLICES * out * nmax * sizeof(float), st) != hipSuccess) { set_error("run_grad_w_fast: scratch allocation failed"); return NRF_ERR_HIP; }
-    }
+    Scratch buf;
+    if (split) NRF_TRY(buf.take((size_t)SLICES * out * (a.n > b.n ? a.n : b.n) * sizeof(float), st));
+    float *part = buf.as<float>();
     auto seg = [&](Seg x, int col0) {
         if (x.n == 0) return true;
         if (split) {
@@ -168,9 +166,7 @@ int run_grad_w_fast(int64_t npts, Seg g, Seg a, Seg b, int out, int in, float *d
         return g_rb.sgemm(h, rocblas_operation_none, rocblas_operation_transpose, x.n, out, (rocblas_int)npts, &one, x.p + x.off, x.stride, g.p + g.off, g.stride, &one, dw + col0,
                           in) == rocblas_status_success;
     };
-    const bool ok = seg(a, 0) && seg(b, a.n);
-    if (part) (void)scratch_give(part, st);
-    if (!ok) { set_error("rocblas_sgemm failed (weight gradient %d x %d over %lld points)", out, in, (long long)npts); return NRF_ERR_HIP; }
+    if (!(seg(a, 0) && seg(b, a.n))) { set_error("rocblas_sgemm failed (weight gradient %d x %d over %lld points)", out, in, (long long)npts); return NRF_ERR_HIP; }
     return NRF_OK;
 }
 
@@ -244,19 +240,19 @@ int run_backprop_fast(int64_t npts, Seg g, const nrf_mlp *m, const LinearLayer &
     if (arith && !add && thin_on && L.out <= 48 && (L.in & 3) == 0 && thin_lds <= 64 * 1024 && rows16(y, y_stride) && (!mask_act || rows16(mask_act, mask_stride))) {
         const int64_t tiles = ceil_div(npts, (int64_t)64);
         hipLaunchKernelGGL(k_backprop_thin, dim3((unsigned)(tiles < 768 ? tiles : 768)), dim3(256), thin_lds, st, npts, L.out, L.in, g.p + g.off, g.stride,
-                           (const float *)(m->d_params + L.w_off), y, y_stride, mask_act, mask_stride);
+                           (const float *)(m->params() + L.w_off), y, y_stride, mask_act, mask_stride);
         NRF_LAUNCH_CHECK();
         return NRF_OK;
     }
-    if (arith)          // G . W with W^T [in][out] as the K-contiguous second operand (L.d_wt, refreshed by every nrf_mlp_set_params)
-        return gemm_nt_split(arith, npts, L.in, g, Seg{nullptr, 0, 0, 0}, L.d_wt, L.out, y, y_stride, nullptr, 0, mask_act, mask_stride, st, add, add_stride, nullptr, 0, nullptr,
+    if (arith)          // G . W with W^T [in][out] as the K-contiguous second operand (L.wt(), refreshed by every nrf_mlp_set_params)
+        return gemm_nt_split(arith, npts, L.in, g, Seg{nullptr, 0, 0, 0}, L.wt(), L.out, y, y_stride, nullptr, 0, mask_act, mask_stride, st, add, add_stride, nullptr, 0, nullptr,
                              nullptr, 0, mask_bits, mask_bits_ld);
     if (mask_act || add) { set_error("internal: run_backprop_fast: the fused ReLU mask exists in bf16x3 mode only"); return NRF_ERR_INVALID_ARG; }
     rocblas_handle h = (npts >= 256) ? rb_handle(st) : nullptr;
     if (!h || npts > 0x7fffffff) return run_backprop(npts, g, m, L, y, y_stride, st);
     const float one = 1.0f, zero = 0.0f;
     // Y_cm (in x pts, ld y_stride) = W_cm (in x out, ld in) . G_cm (out x pts, ld g.stride)
-    if (g_rb.sgemm(h, rocblas_operation_none, rocblas_operation_none, L.in, (rocblas_int)npts, L.out, &one, m->d_params + L.w_off, L.in, g.p + g.off, g.stride, &zero, y, y_stride) !=
+    if (g_rb.sgemm(h, rocblas_operation_none, rocblas_operation_none, L.in, (rocblas_int)npts, L.out, &one, m->params() + L.w_off, L.in, g.p + g.off, g.stride, &zero, y, y_stride) !=
         rocblas_status_success) {
         set_error("rocblas_sgemm failed (backprop %d <- %d over %lld points)", L.in, L.out, (long long)npts);
         return NRF_ERR_HIP;
@@ -290,15 +286,17 @@ int gemm_rm(hipStream_t st, bool transA, bool transB, int64_t M, int64_t N, int6
     constexpr int SLICES = 32;
     if (g_rb.sgemm_sb && K >= 16384 && M * N <= 1024 * 1024 && transA && !transB && (K % SLICES) == 0) {
         // A: [K x M], B: [K x N]: slice b takes rows [b K / 32, (b + 1) K / 32) of both
-        float *part = nullptr;
-        if (scratch_take(reinterpret_cast<void **>(&part), (size_t)SLICES * M * N * sizeof(float), st) != hipSuccess) { set_error("gemm_rm: scratch allocation failed"); return NRF_ERR_HIP; }
+        Scratch buf;
+        NRF_TRY(buf.take((size_t)SLICES * M * N * sizeof(float), st));
+        float *part = buf.as<float>();
         const float zero = 0.0f;
         const int64_t per = K / SLICES;
-        const bool ok = g_rb.sgemm_sb(h, o1, o2, (rocblas_int)N, (rocblas_int)M, (rocblas_int)per, &alpha, B, ldb, (rocblas_stride)(per * ldb), A, lda, (rocblas_stride)(per * lda), &zero, part,
-                                      (rocblas_int)N, (rocblas_stride)(M * N), SLICES) == rocblas_status_success;
-        if (ok) hipLaunchKernelGGL(k_sum_partials_rm, dim3((unsigned)ceil_div(M * N, 256)), dim3(256), 0, st, SLICES, (int)M, (int)N, (const float *)part, beta, C, ldc);
-        (void)scratch_give(part, st);
-        if (!ok) { set_error("rocblas_sgemm_strided_batched failed (%lld x %lld over %lld)", (long long)M, (long long)N, (long long)K); return NRF_ERR_HIP; }
+        if (g_rb.sgemm_sb(h, o1, o2, (rocblas_int)N, (rocblas_int)M, (rocblas_int)per, &alpha, B, ldb, (rocblas_stride)(per * ldb), A, lda, (rocblas_stride)(per * lda), &zero, part,
+                          (rocblas_int)N, (rocblas_stride)(M * N), SLICES) != rocblas_status_success) {
+            set_error("rocblas_sgemm_strided_batched failed (%lld x %lld over %lld)", (long long)M, (long long)N, (long long)K);
+            return NRF_ERR_HIP;
+        }
+        hipLaunchKernelGGL(k_sum_partials_rm, dim3((unsigned)ceil_div(M * N, 256)), dim3(256), 0, st, SLICES, (int)M, (int)N, (const float *)part, beta, C, ldc);
         return NRF_OK;
     }
     if (g_rb.sgemm(h, o1, o2, (rocblas_int)N, (rocblas_int)M, (rocblas_int)K, &alpha, B, ldb, A, lda, &beta, C, ldc) != rocblas_status_success) {

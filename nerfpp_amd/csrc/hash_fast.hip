@@ -208,28 +208,26 @@ int hash_fast_prepare(nrf_hash *h, size_t budget_bytes, hipStream_t st)
     }
     if (nb == 0 && h->d_fast) {          // budget 0 (a training loop): give the image back
         NRF_HIP(hipStreamSynchronize(st));
-        NRF_HIP(hipFree(h->d_fast));
-        h->d_fast = nullptr; h->fast_bytes = 0;
+        h->d_fast.reset();
     }
     bool fresh_image = false;
     if (nb > 0) {
         const size_t need = (size_t)total * entry_bytes;
         // (re)allocate when the image grew -- or shrank to less than half (a training loop lowers the budget to a few coarse levels: the gigabytes go back)
-        if (h->fast_bytes < need || h->fast_bytes / 2 > need) {
-            if (h->d_fast) { NRF_HIP(hipStreamSynchronize(st)); NRF_HIP(hipFree(h->d_fast)); }
-            h->d_fast = nullptr; h->fast_bytes = 0;
-            NRF_HIP(hipMalloc(&h->d_fast, need));
-            h->fast_bytes = need;
+        if (h->d_fast.bytes() < need || h->d_fast.bytes() / 2 > need) {
+            if (h->d_fast) NRF_HIP(hipStreamSynchronize(st));
+            h->d_fast.reset();
+            NRF_TRY(h->d_fast.resize(need));
             fresh_image = true;
         }
-        hp.dense = h->d_fast;
+        hp.dense = h->d_fast.as<void>();
         for (int l = 0; l < nb; l++) {
             const int64_t dim = (int64_t)floorf(hp.level_scale[l]) + 2;
             const int64_t entries = (l + 1 < nb ? hp.dense_off[l + 1] : total) - hp.dense_off[l];
             if (ngp) hipLaunchKernelGGL(k_bake_dense_ngp, dim3((unsigned)ceil_div(entries, 256)), dim3(256), 0, st, hp, l, (uint32_t)dim, entries,
-                                        reinterpret_cast<uint4 *>(h->d_fast) + hp.dense_off[l] * 2);
+                                        h->d_fast.as<uint4>() + hp.dense_off[l] * 2);
             else hipLaunchKernelGGL(k_bake_dense, dim3((unsigned)ceil_div(entries, 256)), dim3(256), 0, st, hp, l, (uint32_t)dim, entries,
-                                    reinterpret_cast<uint4 *>(h->d_fast) + hp.dense_off[l]);
+                                    h->d_fast.as<uint4>() + hp.dense_off[l]);
             NRF_LAUNCH_CHECK();
         }
     }

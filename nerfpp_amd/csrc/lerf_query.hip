@@ -100,8 +100,8 @@ QueryImage take_image(Bump &b)
 
 int build_image(const nrf_mlp *m, const QueryImage &q, const float *pos, const float *neg, int n_neg, hipStream_t st)
 {
-    const float *w3 = m->d_params + (size_t)HID * IN + (size_t)(1 + GEO) * HID + (size_t)HID * (GEO + IN);
-    NRF_HIP(hipMemcpyAsync(q.img, static_cast<const char *>(m->d_packed_split) + SPLIT_LE0_OFF, SPLIT_COPY, hipMemcpyDeviceToDevice, st));
+    const float *w3 = m->params() + (size_t)HID * IN + (size_t)(1 + GEO) * HID + (size_t)HID * (GEO + IN);
+    NRF_HIP(hipMemcpyAsync(q.img, m->d_packed_split.as<const char>() + SPLIT_LE0_OFF, SPLIT_COPY, hipMemcpyDeviceToDevice, st));
     NRF_HIP(hipMemsetAsync(q.umax, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_query_proj_f64, dim3(HID), dim3(QSLOTS), 0, st, w3, pos, neg, n_neg, q.u, q.umax);
     NRF_LAUNCH_CHECK();

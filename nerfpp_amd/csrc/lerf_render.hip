@@ -34,7 +34,7 @@ struct nrf_lerf_renderer {
     nrf_lerf_renderer_desc desc;
     int embed_dim = 0;
     // prompt embeddings on the device (SetLeRFPrompts, LeRFRenderer.h:86): [P, E] positives, [Q, E] negatives
-    float *d_pos = nullptr, *d_neg = nullptr;
+    nrf::DevBuf d_pos, d_neg;
     int n_pos = 0, n_neg = 0;
     // lanes of this renderer's Chunk loop.  ONE by default: the LeRF kernels gain nothing from sharing the CUs (800x800 frame, same call: 1 lane 140-143 ms, 2 lanes
     // 146-147 ms at Chunk 32768; docs/history/profiles/round4/r4g_lerf_lane_chunk_sweep.log) -- their sum is matrix-bound and the F = 8 encode is at the HBM roofline by itself
@@ -42,21 +42,20 @@ struct nrf_lerf_renderer {
     mutable nrf::Lanes chunk_lanes;   // lanes of the Chunk loop, created on first use (chunk_loop.h)
     // the pass's non-finite word (nrf_render_params.overflow_policy): ONE per call -- the pass has no fp32 single-call twin to render a flagged chunk again with, so a
     // flagged call is an error under every detecting policy; a pinned mirror and the event of a deferred copy
-    mutable uint32_t *d_flag = nullptr, *h_flag = nullptr;
+    mutable nrf::DevBuf d_flag;          // one uint32_t
+    mutable nrf::PinnedBuf h_flag;       // two
     mutable hipEvent_t flag_ev = nullptr;
     mutable bool flag_pending = false;
     mutable int64_t flagged_calls = 0;
     // where the last chunk left the language features of its fine depths (nrf_lerf_renderer_last_features; chunk_loop.h): the level-major fp16 table
     // [16][cols][8], the keep mask by column, the merge map [n, sf] -- in the caller's workspace; valid after a call that rendered exactly ONE chunk
     mutable nrf::FeatureView view;
+    // Destruction order is spelled out in this body, not left to the order of the members: the lanes are drained before what their kernels write is freed, and a pending
+    // deferred copy has landed before the pinned words it lands in are released.  The buffers above free themselves after the body has run.
     ~nrf_lerf_renderer()
     {
-        chunk_lanes.drop();          // first: the lanes are drained before what their kernels write is freed
+        chunk_lanes.drop();
         if (flag_ev) { (void)hipEventSynchronize(flag_ev); (void)hipEventDestroy(flag_ev); }
-        if (d_flag) (void)hipFree(d_flag);
-        if (h_flag) (void)hipHostFree(h_flag);
-        if (d_pos) (void)hipFree(d_pos);
-        if (d_neg) (void)hipFree(d_neg);
     }
 };
 
@@ -129,22 +128,21 @@ static void jet_lut_host(uint8_t *lut)
 }
 
 static std::mutex g_lut_mu;
-static uint8_t *g_lut_dev[64] = {};          // per device
+static DevBuf *const g_lut_dev = new DevBuf[64];          // per device; kept for the life of the process (never destroyed: nothing is freed behind the runtime's own teardown)
 
 static int jet_lut_device(const uint8_t **out, hipStream_t st)
 {
     int dev = 0;
     NRF_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_lut_mu);
-    uint8_t *&p = g_lut_dev[dev & 63];
-    if (!p) {
+    DevBuf &lut = g_lut_dev[dev & 63];
+    if (!lut) {
         uint8_t host[256 * 3];
         jet_lut_host(host);
-        NRF_HIP(hipMalloc(reinterpret_cast<void **>(&p), sizeof(host)));
-        NRF_HIP(hipMemcpy(p, host, sizeof(host), hipMemcpyHostToDevice));          // 768 bytes, once per device
+        NRF_TRY(lut.upload(host, sizeof(host)));          // 768 bytes, once per device
     }
     (void)st;
-    *out = p;
+    *out = lut.as<uint8_t>();
     return NRF_OK;
 }
 
@@ -152,7 +150,7 @@ static int jet_lut_device(const uint8_t **out, hipStream_t st)
 void lerf_renderer_query_parts(const nrf_lerf_renderer *r, const nrf_hash **h, const nrf_mlp **m, const float **pos, int *n_pos, const float **neg, int *n_neg, int *embed_dim)
 {
     *h = r->desc.lang_embed; *m = r->desc.lerf;
-    *pos = r->d_pos; *n_pos = r->n_pos; *neg = r->d_neg; *n_neg = r->n_neg; *embed_dim = r->embed_dim;
+    *pos = r->d_pos.as<float>(); *n_pos = r->n_pos; *neg = r->d_neg.as<float>(); *n_neg = r->n_neg; *embed_dim = r->embed_dim;
 }
 
 static int lerf_lanes(const nrf_lerf_renderer *r) { return r->lanes < 1 ? 1 : (r->lanes > Lanes::MAX ? Lanes::MAX : r->lanes); }
@@ -309,10 +307,10 @@ int nrf_lerf_renderer_create(const nrf_lerf_renderer_desc *desc, nrf_lerf_render
     NRF_CHECK_ARG(desc->lerf->family == MLP_LERF, "nrf_lerf_renderer_create: the head must be a LeRF handle (nrf_mlp_lerf_create)");
     NRF_CHECK_ARG(nrf_hash_output_dims(desc->lang_embed) == desc->lerf->in_dims, "nrf_lerf_renderer_create: the embedder emits %d features, the LeRF head takes %d",
                   nrf_hash_output_dims(desc->lang_embed), desc->lerf->in_dims);
-    nrf_lerf_renderer *r = new nrf_lerf_renderer();
+    std::unique_ptr<nrf_lerf_renderer> r(new nrf_lerf_renderer());
     r->desc = *desc;
     r->embed_dim = desc->lerf->out_dims - 1;
-    *out = r;
+    *out = r.release();
     return NRF_OK;
 }
 
@@ -331,17 +329,17 @@ int nrf_lerf_set_prompts(nrf_lerf_renderer *r, const float *positives, int n_pos
     NRF_CHECK_ARG(n_pos >= 0 && n_neg >= 0 && (n_pos == 0) == (n_neg == 0), "nrf_lerf_set_prompts: positives and negatives come together (got %d and %d); 0 and 0 clears them", n_pos, n_neg);
     hipStream_t st = as_stream(stream);
     NRF_HIP(hipStreamSynchronize(st));                      // a render in flight may still read the old prompts
-    if (r->d_pos) { NRF_HIP(hipFree(r->d_pos)); r->d_pos = nullptr; }
-    if (r->d_neg) { NRF_HIP(hipFree(r->d_neg)); r->d_neg = nullptr; }
+    r->d_pos.reset();
+    r->d_neg.reset();
     r->n_pos = r->n_neg = 0;
     if (n_pos == 0) return NRF_OK;
     NRF_CHECK_ARG(positives && negatives, "nrf_lerf_set_prompts: null pointer");
     const size_t row = (size_t)r->embed_dim * sizeof(float);
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&r->d_pos), n_pos * row));
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&r->d_neg), n_neg * row));
+    NRF_TRY(r->d_pos.resize(n_pos * row));
+    NRF_TRY(r->d_neg.resize(n_neg * row));
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    NRF_HIP(hipMemcpyAsync(r->d_pos, positives, n_pos * row, kind, st));
-    NRF_HIP(hipMemcpyAsync(r->d_neg, negatives, n_neg * row, kind, st));
+    NRF_HIP(hipMemcpyAsync(r->d_pos.as<float>(), positives, n_pos * row, kind, st));
+    NRF_HIP(hipMemcpyAsync(r->d_neg.as<float>(), negatives, n_neg * row, kind, st));
     NRF_HIP(hipStreamSynchronize(st));
     r->n_pos = n_pos; r->n_neg = n_neg;
     return NRF_OK;
@@ -363,8 +361,8 @@ static inline bool lerf_detects(const nrf_render_params *p) { return p->overflow
 static int lerf_flag_buffers(const nrf_lerf_renderer *r)
 {
     if (r->d_flag) return NRF_OK;
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&r->d_flag), sizeof(uint32_t)));
-    NRF_HIP(hipHostMalloc(reinterpret_cast<void **>(&r->h_flag), 2 * sizeof(uint32_t), hipHostMallocDefault));          // [0] synchronous read-back, [1] deferred copy
+    NRF_TRY(r->d_flag.resize(sizeof(uint32_t)));
+    NRF_TRY(r->h_flag.resize(2 * sizeof(uint32_t)));          // [0] synchronous read-back, [1] deferred copy
     NRF_HIP(hipEventCreateWithFlags(&r->flag_ev, hipEventDisableTiming));
     return NRF_OK;
 }
@@ -375,7 +373,7 @@ static int lerf_take_deferred(const nrf_lerf_renderer *r, bool wait, const char 
     if (wait) NRF_HIP(hipEventSynchronize(r->flag_ev));
     else if (hipEventQuery(r->flag_ev) != hipSuccess) return NRF_OK;
     r->flag_pending = false;
-    if (!r->h_flag[1]) return NRF_OK;
+    if (!r->h_flag.as<uint32_t>()[1]) return NRF_OK;
     r->flagged_calls++;
     set_error("%s: an EARLIER LeRF render call (NRF_OVERFLOW_DEFERRED) produced non-finite language densities / embeddings: an fp16 operand of the fused passes left its range", who);
     return NRF_ERR_NONFINITE;
@@ -388,7 +386,7 @@ static int lerf_flag_begin(const nrf_lerf_renderer *r, const nrf_render_params *
     if (!lerf_detects(p)) return NRF_OK;
     NRF_TRY(lerf_flag_buffers(r));
     NRF_TRY(lerf_take_deferred(r, p->overflow_policy == NRF_OVERFLOW_DEFERRED, who));
-    NRF_HIP(hipMemsetAsync(r->d_flag, 0, sizeof(uint32_t), st));
+    NRF_HIP(hipMemsetAsync(r->d_flag.as<uint32_t>(), 0, sizeof(uint32_t), st));
     return NRF_OK;
 }
 
@@ -396,14 +394,14 @@ static int lerf_flag_end(const nrf_lerf_renderer *r, const nrf_render_params *p,
 {
     if (!lerf_detects(p)) return NRF_OK;
     if (p->overflow_policy == NRF_OVERFLOW_DEFERRED) {
-        NRF_HIP(hipMemcpyAsync(r->h_flag + 1, r->d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        NRF_HIP(hipMemcpyAsync(r->h_flag.as<uint32_t>() + 1, r->d_flag.as<uint32_t>(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         NRF_HIP(hipEventRecord(r->flag_ev, st));
         r->flag_pending = true;
         return NRF_OK;
     }
-    NRF_HIP(hipMemcpyAsync(r->h_flag, r->d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    NRF_HIP(hipMemcpyAsync(r->h_flag.as<uint32_t>(), r->d_flag.as<uint32_t>(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     NRF_HIP(hipStreamSynchronize(st));
-    if (!r->h_flag[0]) return NRF_OK;
+    if (!r->h_flag.as<uint32_t>()[0]) return NRF_OK;
     r->flagged_calls++;
     set_error("%s: non-finite language densities / embeddings: an fp16 operand of the fused LeRF passes left its range (weights / features of unusual magnitude).  The pass has "
               "no fp32 single-call twin: render through the stage calls (nrf_mlp_forward NRF_PREC_F32 + nrf_raw2weights + nrf_render_clip_embedding)", who);
@@ -424,7 +422,7 @@ int nrf_lerf_render_rays(const nrf_lerf_renderer *r, const float *d_rays, int ra
     NRF_CHECK_ARG(r && p && out, "nrf_lerf_render_rays: null pointer");
     if (n == 0) return lerf_render_rays_impl(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, stream, nullptr);
     NRF_TRY(lerf_flag_begin(r, p, as_stream(stream), "nrf_lerf_render_rays"));
-    NRF_TRY(lerf_render_rays_impl(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, stream, lerf_detects(p) ? r->d_flag : nullptr));
+    NRF_TRY(lerf_render_rays_impl(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, stream, lerf_detects(p) ? r->d_flag.as<uint32_t>() : nullptr));
     return lerf_flag_end(r, p, as_stream(stream), "nrf_lerf_render_rays");
 }
 
@@ -481,7 +479,7 @@ static int lerf_render_rays_impl(const nrf_lerf_renderer *r, const float *d_rays
         float *emb = out->d_embedding ? out->d_embedding : ws.emb;
         NRF_TRY(nrf::launch_clip_embedding(acc, E, E, ones, n, 1, emb, as_stream(stream), d_flag));
         if (out->d_relevancy)
-            NRF_TRY(nrf_lerf_relevancy(emb, n, E, r->d_pos, r->n_pos, r->d_neg, r->n_neg, 0, out->d_relevancy, stream));     // LeRFRenderer.cpp:79 (one positive phrase)
+            NRF_TRY(nrf_lerf_relevancy(emb, n, E, r->d_pos.as<float>(), r->n_pos, r->d_neg.as<float>(), r->n_neg, 0, out->d_relevancy, stream));     // LeRFRenderer.cpp:79 (one positive phrase)
     }
     r->view.set(x, cols, keep, src, n, sf);
     return NRF_OK;
@@ -539,7 +537,7 @@ static int lerf_batchify_run(const nrf_lerf_renderer *r, const float *d_rays, in
                              const float *d_u, const nrf_lerf_outputs *out, const LerfBatchWs &bw, void *stream)
 {
     if (n > 0) NRF_TRY(lerf_flag_begin(r, p, as_stream(stream), "nrf_lerf_batchify_rays"));
-    uint32_t *const d_flag = (n > 0 && lerf_detects(p)) ? r->d_flag : nullptr;
+    uint32_t *const d_flag = (n > 0 && lerf_detects(p)) ? r->d_flag.as<uint32_t>() : nullptr;
     const int L = bw.L;
     const int64_t lc = bw.lc;
     if (L > 0) {

@@ -416,7 +416,7 @@ static bool lerf_train_gram(const nrf_mlp *m, int s)
     const bool on = st != 0;
     const int hd = m->small.hidden_dim, E = m->small.hidden_dim_color;
     (void)E;
-    return on && fp32_gemm_available() && m->small.num_layers >= 2 && hd <= 256 && (size_t)(9 * s + 9 * hd + 2) * sizeof(float) <= 60 * 1024 && !m->layers.back().d_bias;
+    return on && fp32_gemm_available() && m->small.num_layers >= 2 && hd <= 256 && (size_t)(9 * s + 9 * hd + 2) * sizeof(float) <= 60 * 1024 && !m->layers.back().bias();
 }
 
 // dw [E][hd] -= W [E][hd] . M [hd][hd]   (the Gram form's last term: a product of two small matrices, one thread per entry, k ascending)
@@ -520,7 +520,7 @@ static int head_backward_chunk(const nrf_mlp *m, const float *emb, const uint8_t
         // ---- last layer, normalize, RenderCLIPEmbedding and their backward in the layer's INPUT space (see k_ltg_ray_u) ----
         const LinearLayer &L1 = m->layers[NL - 1];
         const int hd = L1.in;
-        const float *wle = m->d_params + L1.w_off;                         // W [E][hd]
+        const float *wle = m->params() + L1.w_off;                         // W [E][hd]
         const float *a = H[NL - 2];                                        // [c, hd] (stride W): post-ReLU input of the last layer
         float *sga = hle;                                                  // S = A G, then g_a in place: columns [0, hd) of the buffer h would have taken
         float *ba = G[1];                                                  // beta_j a_j
@@ -537,7 +537,7 @@ static int head_backward_chunk(const nrf_mlp *m, const float *emb, const uint8_t
         else NRF_TRY(gemm_rm(st, false, true, rays, E, hd, 1.0f, u, hd, wle, hd, 0.0f, v, E));                             // V = U W^T
         hipLaunchKernelGGL(k_ltg_ray_v, dim3((unsigned)rays), dim3(256), 0, st, E, (const float *)v, g_rendered, gv, rendered);
         NRF_LAUNCH_CHECK();
-        if (arith_r) NRF_TRY(gemm_nt_split(arith_r, rays, hd, Seg{gv, E, 0, E}, none, L1.d_wt, E, q, hd, nullptr, 0, nullptr, 0, st));     // Q = G_V W = G_V (W^T)^T: W^T [hd][E] is the layer's d_wt
+        if (arith_r) NRF_TRY(gemm_nt_split(arith_r, rays, hd, Seg{gv, E, 0, E}, none, L1.wt(), E, q, hd, nullptr, 0, nullptr, 0, st));     // Q = G_V W = G_V (W^T)^T: W^T [hd][E] is the layer's d_wt
         else NRF_TRY(gemm_rm(st, false, false, rays, hd, E, 1.0f, gv, E, wle, hd, 0.0f, q, hd));                           // Q = G_V W
         hipLaunchKernelGGL(k_ltg_ray_g, dim3((unsigned)rays), dim3(256), (size_t)(s + hd + 1) * sizeof(float) + (size_t)s * sizeof(double), st, s, hd, (const float *)q, a, W, sga, W, ba, W, (const float *)pp, keep, z,
                            dirs, d_stride, g33, W, arith ? 1 : 0);
@@ -631,15 +631,14 @@ int nrf_huber_rows_nanmean(const float *d_pred, const float *d_target, int64_t n
 {
     NRF_CHECK_ARG(d_pred && d_target && d_loss && n > 0 && e > 0 && delta > 0.0f, "nrf_huber_rows_nanmean: bad argument");
     hipStream_t st = as_stream(stream);
-    float *tmp = nullptr;
-    NRF_HIP(scratch_take(reinterpret_cast<void **>(&tmp), (size_t)(n + 1) * sizeof(float), st));
-    int rc = NRF_OK;
+    Scratch buf;
+    NRF_TRY(buf.take((size_t)(n + 1) * sizeof(float), st));
+    float *tmp = buf.as<float>();
     hipLaunchKernelGGL(k_huber_rows, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, n, e, delta, d_pred, d_target, tmp);
     hipLaunchKernelGGL(k_nanmean, dim3(1), dim3(256), 0, st, n, (const float *)tmp, d_loss, tmp + n);
     if (d_grad) hipLaunchKernelGGL(k_huber_rows_grad, dim3((unsigned)ceil_div(n * e, 256)), dim3(256), 0, st, n, e, delta, d_pred, d_target, (const float *)tmp, (const float *)(tmp + n), d_grad);
-    if (hipGetLastError() != hipSuccess) { set_error("nrf_huber_rows_nanmean: launch failed"); rc = NRF_ERR_HIP; }
-    (void)scratch_give(tmp, st);
-    return rc;
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
 }
 
 size_t nrf_lerf_head_backward_workspace_bytes(const nrf_mlp *lerf, int64_t n, int s)
@@ -663,29 +662,27 @@ int nrf_lerf_head_backward(const nrf_mlp *lerf, const float *d_emb, const uint8_
     const int64_t rays_per = lt_rays_per_pass(lerf, n, s);
     const int in = lerf->small.input_ch;
     // Gram form of the last layer: G = W^T W once per call (the weights change every step), stream-ordered scratch
+    Scratch gram_buf;
     float *gram = nullptr;
     if (lerf_train_gram(lerf, s)) {
         const LinearLayer &L1 = lerf->layers.back();
         const int64_t rmax = n < rays_per ? n : rays_per;          // G, M, then the per-ray rows u, v, g_v, q of one chunk
-        NRF_HIP(scratch_take(reinterpret_cast<void **>(&gram), ((size_t)2 * L1.in * L1.in + (size_t)rmax * (2 * L1.in + 2 * L1.out)) * sizeof(float), st));
-        const float *wle = lerf->d_params + L1.w_off;
-        int rcg;
+        NRF_TRY(gram_buf.take(((size_t)2 * L1.in * L1.in + (size_t)rmax * (2 * L1.in + 2 * L1.out)) * sizeof(float), st));
+        gram = gram_buf.as<float>();
+        const float *wle = lerf->params() + L1.w_off;
         if (lerf->lerf_gram_current && lerf->d_lerf_gram && L1.in == 256)
             // the Gram matrix the device packer formed at the last parameter upload (double accumulation, unscaled copy behind the packed one): nothing to compute
-            rcg = hipMemcpyAsync(gram, lerf->d_lerf_gram + (size_t)L1.in * L1.in, (size_t)L1.in * L1.in * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess ? NRF_OK : NRF_ERR_HIP;
-        else rcg = gemm_rm(st, true, false, L1.in, L1.in, L1.out, 1.0f, wle, L1.in, wle, L1.in, 0.0f, gram, L1.in);
-        if (rcg != NRF_OK) { (void)scratch_give(gram, st); return rcg; }
+            NRF_HIP(hipMemcpyAsync(gram, lerf->d_lerf_gram.as<float>() + (size_t)L1.in * L1.in, (size_t)L1.in * L1.in * sizeof(float), hipMemcpyDeviceToDevice, st));
+        else NRF_TRY(gemm_rm(st, true, false, L1.in, L1.in, L1.out, 1.0f, wle, L1.in, wle, L1.in, 0.0f, gram, L1.in));
     }
-    int rc = NRF_OK;
-    for (int64_t r0 = 0; r0 < n && rc == NRF_OK; r0 += rays_per) {
+    for (int64_t r0 = 0; r0 < n; r0 += rays_per) {
         const int64_t rays = (n - r0) < rays_per ? (n - r0) : rays_per;
         const int64_t p0 = r0 * s;
-        rc = head_backward_chunk(lerf, d_emb + p0 * in, d_keep ? d_keep + p0 : nullptr, d_z + p0, d_dirs + r0 * d_stride, d_stride, d_noise ? d_noise + p0 : nullptr, noise_std,
+        NRF_TRY(head_backward_chunk(lerf, d_emb + p0 * in, d_keep ? d_keep + p0 : nullptr, d_z + p0, d_dirs + r0 * d_stride, d_stride, d_noise ? d_noise + p0 : nullptr, noise_std,
                                  rays, s, d_g_rendered + r0 * E, d_g_params, d_g_emb ? d_g_emb + p0 * in : nullptr, d_rendered ? d_rendered + r0 * E : nullptr,
-                                 d_weights ? d_weights + p0 : nullptr, w.base, w.buf, w.nrm, gram, st);
+                                 d_weights ? d_weights + p0 : nullptr, w.base, w.buf, w.nrm, gram, st));
     }
-    if (gram) (void)scratch_give(gram, st);
-    return rc;
+    return NRF_OK;
 }
 
 // ... with the language grid in front: pts [n, s, 3] -> nrf_hash_encode (fp32 rows) -> the head's backward -> nrf_hash_backward_rays, chunk by chunk of whole rays

@@ -14,11 +14,11 @@ enum { MLP_SMALL = 0, MLP_NERF = 1, MLP_LERF = 2 };
 // device, asynchronously -- an optimisation step no longer takes a host round trip.
 enum : uint8_t { WM_ZERO = 0, WM_F16_HI = 1, WM_F16_LO = 2, WM_F32 = 3 };
 struct WeightMap {
-    int32_t *d_src = nullptr;
-    uint8_t *d_kind = nullptr;
+    DevBuf d_src;              // int32_t [n]
+    DevBuf d_kind;             // uint8_t [n]
     int64_t n = 0;
     int elem = 2;              // bytes per element of the image: 2 (fp16, kinds HI / LO) or 4 (fp32)
-    void *d_out = nullptr;     // the image (owned by the handle's d_packed_* / layer fields)
+    void *d_out = nullptr;     // BORROWED: the image, or a place inside it (owned by the handle's d_packed_* / layer fields, which outlive the map)
     bool scaled = false;       // gathers from the handle's SCALED blob (d_params_scaled): the split-precision operand images
 };
 
@@ -30,8 +30,10 @@ enum { SMALL_MAX_GROUPS = 12, SMALL_SCALE_INV_SIGMA = 0, SMALL_SCALE_INV_RGB = 1
 
 struct LinearLayer {
     int in = 0, out = 0;
-    float *d_wt = nullptr;      // W^T [in][out] fp32 (lane = output neuron reads coalesced)
-    float *d_bias = nullptr;    // [out] or nullptr
+    DevBuf d_wt;                // W^T [in][out] fp32 (lane = output neuron reads coalesced)
+    DevBuf d_bias;              // [out] fp32, or empty
+    float *wt() const { return d_wt.as<float>(); }
+    float *bias() const { return d_bias.as<float>(); }
     size_t w_off = 0;           // offset of W [out][in] in the parameter blob (floats)
 };
 
@@ -54,32 +56,30 @@ struct nrf_mlp {
     // classic network, host re-pack: views_linears_0 o feature_linear as computed by mlp_nerf_pack_f16, handed to mlp_nerf_pack_sigma_f32 of the same upload (then cleared)
     std::vector<float> host_merged, host_merged_b;
     std::vector<nrf::LinearLayer> layers;    // in forward order (see mlp.hip for the per-family order)
-    float *d_params = nullptr;               // the fp32 blob, checkpoint order, on device
+    nrf::DevBuf d_params;                    // the fp32 blob, checkpoint order, on device
     int64_t n_params = 0;
     // packed operands of the matrix-core paths (built at create time)
-    void *d_packed_f16 = nullptr;
-    size_t packed_f16_bytes = 0;
-    void *d_packed_split = nullptr;          // NRF_PREC_F16_SPLIT: (hi, lo) fragment pairs
-    size_t packed_split_bytes = 0;
-    void *d_packed_sigma_f32 = nullptr;      // fp32 MFMA fragments of the sigma net (sigma_small_f32.hip)
-    size_t packed_sigma_f32_bytes = 0;
+    nrf::DevBuf d_packed_f16;
+    nrf::DevBuf d_packed_split;              // NRF_PREC_F16_SPLIT: (hi, lo) fragment pairs
+    nrf::DevBuf d_packed_sigma_f32;          // fp32 MFMA fragments of the sigma net (sigma_small_f32.hip)
     int lerf_precision = NRF_PREC_F16_MFMA;  // arithmetic of the fused LeRF passes (nrf_lerf_set_precision)
-    float *d_lerf_gram = nullptr;            // LeRF device pack: the Gram matrix [256][256] in its packed form (scaled, block triangle), W^T W itself, the bits of its largest entry
+    nrf::DevBuf d_lerf_gram;                 // LeRF device pack: the Gram matrix [256][256] in its packed form (scaled, block triangle), W^T W itself, the bits of its largest entry
     bool lerf_gram_current = false;          // d_lerf_gram's W^T W belongs to the parameters now in d_params (set by the device packer, cleared by a host re-pack)
     bool lerf_device_pack = false;           // the device packers reproduce the host packers' images byte for byte (checked at creation): nrf_mlp_set_params stays on the device
     int lerf_le1_exp = 0;                    // LeRF: kernel C's image of the embedding layer is LE1 * 2^-lerf_le1_exp; the kernel-B launchers compensate (mlp_lerf_mfma.hip: lerf_le1_exponent)
     float lerf_gram_scale = 1.0f;            // LeRF: the Gram matrix of the embedding layer is stored divided by this power of two (fp16 range), see mlp_lerf_mfma.hip
-    void *d_packed_bwd = nullptr;            // W^T fragments of the matrix-core backward (mlp_small_bwd_mfma.hip)
-    size_t packed_bwd_bytes = 0;
+    nrf::DevBuf d_packed_bwd;                // W^T fragments of the matrix-core backward (mlp_small_bwd_mfma.hip)
     std::vector<nrf::WeightMap> maps;        // NeRFSmall: every derived image as a gather from d_params (empty: nrf_mlp_set_params repacks on the host)
     // range-safe split precision (see SMALL_MAX_GROUPS above): chosen ON THE DEVICE from the blob at every nrf_mlp_set_params (k_small_scales), in stream order
-    float *d_params_scaled = nullptr;        // blob[i] * gscale[group[i]]: what the split images (d_packed_split, the GEO tail of d_packed_sigma_f32) gather from
-    uint8_t *d_group = nullptr;              // scale group of blob element i
-    float *d_gscale = nullptr;               // [SMALL_MAX_GROUPS] powers of two
-    float *d_scales = nullptr;               // [SMALL_SCALE_COUNT] what the kernels read: 2^-S_sigma, 2^-S_colour, 2^S_hidden (all 1 while no scaling is in force)
+    nrf::DevBuf d_params_scaled;             // fp32 blob[i] * gscale[group[i]]: what the split images (d_packed_split, the GEO tail of d_packed_sigma_f32) gather from
+    nrf::DevBuf d_group;                     // uint8_t: scale group of blob element i
+    nrf::DevBuf d_gscale;                    // fp32 [SMALL_MAX_GROUPS] powers of two
+    nrf::DevBuf d_scales;                    // fp32 [SMALL_SCALE_COUNT] what the kernels read: 2^-S_sigma, 2^-S_colour, 2^S_hidden (all 1 while no scaling is in force)
     float in_rms_hint = 0.25f;               // expected RMS of the position features; nrf_mlp_set_input_rms_hint
-    const float *d_in_rms_src = nullptr;     // ... or where to read it on the device: the RMS of the hash table a renderer pairs this network with (render.hip, ensure_scales)
+    const float *d_in_rms_src = nullptr;     // BORROWED ... or where to read it on the device: the RMS of the hash table a renderer pairs this network with (render.hip, ensure_scales)
     uint64_t in_rms_seen = 0;                // table upload counter of that hash grid at the last rescale
+    float *params() const { return d_params.as<float>(); }
+    float *scales() const { return d_scales.as<float>(); }
     bool split_scaling = true;               // false: the split images from the blob as it is (nrf_mlp_set_split_scaling; NRF_SPLIT_UNSCALED=1 makes that the default)
 };
 

@@ -95,7 +95,7 @@ int run_linear(int64_t npts, Seg a, Seg b, const LinearLayer &L, int relu, float
     if (in != L.in) { set_error("internal: linear layer expects %d inputs, got %d", L.in, in); return NRF_ERR_INVALID_ARG; }
     const int threads = L.out >= 256 ? 256 : (int)ceil_div(L.out, 64) * 64;
     const size_t lds = (size_t)in * LIN_TP * sizeof(float);
-    hipLaunchKernelGGL(k_linear, dim3((unsigned)ceil_div(npts, LIN_TP)), dim3(threads), lds, st, npts, a, b, L.d_wt, L.d_bias, L.out, relu, y, y_stride, y_off);
+    hipLaunchKernelGGL(k_linear, dim3((unsigned)ceil_div(npts, LIN_TP)), dim3(threads), lds, st, npts, a, b, L.wt(), L.bias(), L.out, relu, y, y_stride, y_off);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
@@ -326,7 +326,7 @@ int run_backprop(int64_t npts, Seg g, const nrf_mlp *m, const LinearLayer &L, fl
     const Seg none{nullptr, 0, 0, 0};
     const int threads = L.in >= 256 ? 256 : (int)ceil_div(L.in, 64) * 64;
     const size_t lds = (size_t)L.out * LIN_TP * sizeof(float);
-    hipLaunchKernelGGL(k_linear, dim3((unsigned)ceil_div(npts, LIN_TP)), dim3(threads), lds, st, npts, g, none, m->d_params + L.w_off, (const float *)nullptr, L.in, 0, y,
+    hipLaunchKernelGGL(k_linear, dim3((unsigned)ceil_div(npts, LIN_TP)), dim3(threads), lds, st, npts, g, none, m->params() + L.w_off, (const float *)nullptr, L.in, 0, y,
                        y_stride, 0);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
@@ -625,12 +625,12 @@ int mlp_nerf_backward(const nrf_mlp *m, const float *x, int xs, const float *g_o
             // d / d h through alpha_linear is the rank-1 product g_alpha (x) w_alpha: formed inside the sum (no [c, 256] array of its own), with h_{D-1}'s ReLU mask --
             // the first pts_linears stage below finds it applied.  Split-precision modes: both in the write-out of the back-propagation product through feature_linear
             if (const int arith = run_backprop_fuses_mask(m, c) ? train_gemm_for(m) : 0)
-                NRF_TRY(gemm_nt_split(arith, c, feat.in, g_feat, none, feat.d_wt, feat.out, gh, W, nullptr, 0, H[D - 1], W, st, nullptr, 0, g_alpha.p + g_alpha.off, g_alpha.stride,
-                                      m->d_params + alpha.w_off, nullptr, 0, bits_of(H[D - 1]), bits_ld));
+                NRF_TRY(gemm_nt_split(arith, c, feat.in, g_feat, none, feat.wt(), feat.out, gh, W, nullptr, 0, H[D - 1], W, st, nullptr, 0, g_alpha.p + g_alpha.off, g_alpha.stride,
+                                      m->params() + alpha.w_off, nullptr, 0, bits_of(H[D - 1]), bits_ld));
             else {
             NRF_TRY(run_backprop_fast(c, g_feat, m, feat, G[1], W, st));
             hipLaunchKernelGGL(k_sum_rank1, dim3((unsigned)ceil_div(c * Wd, 256)), dim3(256), 0, st, c, Wd, (const float *)G[1], W, g_alpha.p + g_alpha.off, g_alpha.stride,
-                               (const float *)(m->d_params + alpha.w_off), gh, W, (const float *)H[D - 1], W);
+                               (const float *)(m->params() + alpha.w_off), gh, W, (const float *)H[D - 1], W);
             NRF_LAUNCH_CHECK();
             }
             gh_masked = true;
@@ -660,7 +660,7 @@ int mlp_nerf_backward(const nrf_mlp *m, const float *x, int xs, const float *g_o
             if (cat && fuse && !g_x) {
                 // the skip layer's input is cat[input_pts, h]: nobody asks for d / d input_pts, so only the h columns are formed -- rows [in, in + Wd) of W^T as a product of
                 // their own, which lands at column 0 with h_{l-1}'s ReLU mask applied by its write-out (the whole product + a masked copy of 256 of its 319 columns before)
-                NRF_TRY(gemm_nt_split(train_gemm_for(m), c, Wd, g, none, L.d_wt + (size_t)in * L.out, L.out, dst, W, nullptr, 0, H[l - 1], W, st, nullptr, 0, nullptr, 0, nullptr,
+                NRF_TRY(gemm_nt_split(train_gemm_for(m), c, Wd, g, none, L.wt() + (size_t)in * L.out, L.out, dst, W, nullptr, 0, H[l - 1], W, st, nullptr, 0, nullptr, 0, nullptr,
                                       nullptr, 0, bits_of(H[l - 1]), bits_ld));
                 premasked = true;
                 gcur = dst;
@@ -700,14 +700,12 @@ static int add_layer(nrf_mlp *m, const std::vector<float> &hp, size_t &off, int 
     for (int o = 0; o < out; o++)
         for (int k = 0; k < in; k++) wt[(size_t)k * out + o] = hp[off + (size_t)o * in + k];
     off += (size_t)in * out;
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&L.d_wt), wt.size() * sizeof(float)));
-    NRF_HIP(hipMemcpy(L.d_wt, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
+    NRF_TRY(L.d_wt.upload(wt.data(), wt.size() * sizeof(float)));
     if (bias) {
-        NRF_HIP(hipMalloc(reinterpret_cast<void **>(&L.d_bias), (size_t)out * sizeof(float)));
-        NRF_HIP(hipMemcpy(L.d_bias, hp.data() + off, (size_t)out * sizeof(float), hipMemcpyHostToDevice));
+        NRF_TRY(L.d_bias.upload(hp.data() + off, (size_t)out * sizeof(float)));
         off += out;
     }
-    m->layers.push_back(L);
+    m->layers.push_back(std::move(L));
     if (in > m->max_width) m->max_width = in;
     if (out > m->max_width) m->max_width = out;
     return NRF_OK;
@@ -730,8 +728,7 @@ static int fetch_params(const float *params, int on_device, int64_t n, hipStream
         NRF_HIP(hipMemcpyAsync(host.data(), params, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         NRF_HIP(hipStreamSynchronize(st));
     } else memcpy(host.data(), params, (size_t)n * 4);
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_params), (size_t)n * 4));
-    NRF_HIP(hipMemcpy(m->d_params, host.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    NRF_TRY(m->d_params.upload(host.data(), (size_t)n * 4));
     m->n_params = n;
     return NRF_OK;
 }
@@ -811,25 +808,17 @@ static int upload_weight_map(nrf_mlp *m, const HostMap &hm, void *d_out)
     WeightMap wm;
     wm.n = (int64_t)hm.src.size(); wm.elem = hm.elem; wm.d_out = d_out;
     if (wm.n == 0) return NRF_OK;
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&wm.d_src), (size_t)wm.n * 4));
-    NRF_HIP(hipMemcpy(wm.d_src, hm.src.data(), (size_t)wm.n * 4, hipMemcpyHostToDevice));
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&wm.d_kind), (size_t)wm.n));
-    NRF_HIP(hipMemcpy(wm.d_kind, hm.kind.data(), (size_t)wm.n, hipMemcpyHostToDevice));
-    m->maps.push_back(wm);
+    NRF_TRY(wm.d_src.upload(hm.src.data(), (size_t)wm.n * 4));
+    NRF_TRY(wm.d_kind.upload(hm.kind.data(), (size_t)wm.n));
+    m->maps.push_back(std::move(wm));
     return NRF_OK;
-}
-
-static void drop_weight_maps(nrf_mlp *m)
-{
-    for (auto &w : m->maps) { if (w.d_src) (void)hipFree(w.d_src); if (w.d_kind) (void)hipFree(w.d_kind); }
-    m->maps.clear();
 }
 
 // NeRFSmall, after the images exist: NRF_OK with m->maps filled, or with m->maps empty when a layout does not decode (the host repack then stays in charge)
 static int build_weight_maps(nrf_mlp *m, const std::vector<float> &hp)
 {
     if (m->family != MLP_SMALL || m->n_params >= (int64_t)WM_RADIX_LO * WM_RADIX_LO) return NRF_OK;
-    for (auto &L : m->layers) if (L.d_bias) return NRF_OK;
+    for (auto &L : m->layers) if (L.bias()) return NRF_OK;
     if (const char *e = getenv("NRF_MLP_HOST_REPACK")) if (atoi(e) != 0) return NRF_OK;
     const auto &d = m->small;
     enum { I_F16, I_SPLIT, I_BWD, I_SIG_HEAD, I_SIG_TAIL, N_IMG };
@@ -845,15 +834,15 @@ static int build_weight_maps(nrf_mlp *m, const std::vector<float> &hp)
     images(hp, real);
     for (int q = 0; q < 4; q++) images(weight_map_probe(m->n_params, q), probe[q]);
     const int elem[N_IMG] = { 2, 2, 2, 4, 2 };
-    void *dst[N_IMG] = { m->d_packed_f16, m->d_packed_split, m->d_packed_bwd, m->d_packed_sigma_f32,
-                         m->d_packed_sigma_f32 ? static_cast<char *>(m->d_packed_sigma_f32) + real[I_SIG_HEAD].size() : nullptr };
-    const size_t have[N_IMG] = { m->packed_f16_bytes, m->packed_split_bytes, m->packed_bwd_bytes, m->packed_sigma_f32_bytes, m->packed_sigma_f32_bytes };
+    void *dst[N_IMG] = { m->d_packed_f16.as<void>(), m->d_packed_split.as<void>(), m->d_packed_bwd.as<void>(), m->d_packed_sigma_f32.as<void>(),
+                         m->d_packed_sigma_f32 ? m->d_packed_sigma_f32.as<char>() + real[I_SIG_HEAD].size() : nullptr };
+    const size_t have[N_IMG] = { m->d_packed_f16.bytes(), m->d_packed_split.bytes(), m->d_packed_bwd.bytes(), m->d_packed_sigma_f32.bytes(), m->d_packed_sigma_f32.bytes() };
     for (int im = 0; im < N_IMG; im++) {
-        if (real[im].empty()) { if (dst[im] && im != I_SIG_TAIL && have[im]) { drop_weight_maps(m); return NRF_OK; } continue; }
+        if (real[im].empty()) { if (dst[im] && im != I_SIG_TAIL && have[im]) { m->maps.clear(); return NRF_OK; } continue; }
         const size_t want = (im == I_SIG_HEAD || im == I_SIG_TAIL) ? real[I_SIG_HEAD].size() + real[I_SIG_TAIL].size() : real[im].size();
         const std::vector<uint8_t> four[4] = { probe[0][im], probe[1][im], probe[2][im], probe[3][im] };
         HostMap hm;
-        if (!dst[im] || have[im] != want || !decode_weight_map(four, elem[im], m->n_params, hm) || !weight_map_reproduces(hm, hp, real[im])) { drop_weight_maps(m); return NRF_OK; }
+        if (!dst[im] || have[im] != want || !decode_weight_map(four, elem[im], m->n_params, hm) || !weight_map_reproduces(hm, hp, real[im])) { m->maps.clear(); return NRF_OK; }
         NRF_TRY(upload_weight_map(m, hm, dst[im]));
         m->maps.back().scaled = im == I_SPLIT || im == I_SIG_TAIL;      // the split-precision operands: gathered from the range-scaled blob (mlp_small_rescale)
     }
@@ -862,7 +851,7 @@ static int build_weight_maps(nrf_mlp *m, const std::vector<float> &hp)
         hm.src.resize((size_t)L.in * L.out); hm.kind.assign(hm.src.size(), WM_F32);
         for (int o = 0; o < L.out; o++)
             for (int k = 0; k < L.in; k++) hm.src[(size_t)k * L.out + o] = (int32_t)(L.w_off + (size_t)o * L.in + k);
-        NRF_TRY(upload_weight_map(m, hm, L.d_wt));
+        NRF_TRY(upload_weight_map(m, hm, L.wt()));
     }
     return NRF_OK;
 }
@@ -890,8 +879,8 @@ __global__ void __launch_bounds__(256) k_nerf_merged_f64(const float *__restrict
 static int nerf_derive_on_device(const nrf_mlp *m, hipStream_t st)
 {
     const auto &Lv = m->layers[8], &Lf = m->layers[9];          // views_linears_0, feature_linear (nrf_mlp_nerf_create's order)
-    const float *wv = m->d_params + Lv.w_off, *bv = wv + (size_t)Lv.in * Lv.out, *wf = m->d_params + Lf.w_off, *bf = wf + (size_t)Lf.in * Lf.out;
-    float *merged = m->d_params + m->n_params;
+    const float *wv = m->params() + Lv.w_off, *bv = wv + (size_t)Lv.in * Lv.out, *wf = m->params() + Lf.w_off, *bf = wf + (size_t)Lf.in * Lf.out;
+    float *merged = m->params() + m->n_params;
     k_nerf_merged_f64<<<dim3(NERF_MERGED_ROWS), dim3(NERF_MERGED_W), 0, st>>>(wv, Lv.in, wf, bf, bv, merged, merged + (size_t)NERF_MERGED_ROWS * NERF_MERGED_W);
     NRF_HIP(hipGetLastError());
     return NRF_OK;
@@ -935,9 +924,9 @@ static int build_weight_maps_nerf(nrf_mlp *m, const std::vector<float> &hp)
         for (int q = 0; q < 4; q++) r.p[q] = bytes_of(probe[q]);
         regs.push_back(std::move(r));
     };
-    char *f16 = static_cast<char *>(m->d_packed_f16), *spl = static_cast<char *>(m->d_packed_split), *sig = static_cast<char *>(m->d_packed_sigma_f32);
+    char *f16 = m->d_packed_f16.as<char>(), *spl = m->d_packed_split.as<char>(), *sig = m->d_packed_sigma_f32.as<char>();
     const size_t img_b = real.img.size() * 2, img2_b = real.img2.size() * 2, bias_b = real.bias.size() * 4;
-    if (m->packed_f16_bytes != img_b + bias_b || m->packed_split_bytes != img2_b + bias_b || m->packed_sigma_f32_bytes != real.sig.size() * 4) return NRF_OK;
+    if (m->d_packed_f16.bytes() != img_b + bias_b || m->d_packed_split.bytes() != img2_b + bias_b || m->d_packed_sigma_f32.bytes() != real.sig.size() * 4) return NRF_OK;
     add([](const Images &o) { return wm_bytes(o.img.data(), o.img.size() * 2); }, 2, f16);
     add([](const Images &o) { return wm_bytes(o.bias.data(), o.bias.size() * 4); }, 4, f16 + img_b);
     add([](const Images &o) { return wm_bytes(o.img2.data(), o.img2.size() * 2); }, 2, spl);
@@ -953,14 +942,13 @@ static int build_weight_maps_nerf(nrf_mlp *m, const std::vector<float> &hp)
         if (!decode_weight_map(four, regs[i].elem, next, hms[i]) || !weight_map_reproduces(hms[i], ext, regs[i].real)) return NRF_OK;
     }
     // re-home the blob with room for the derived block, derive it on the device and check it against the host's bits
-    float *big = nullptr;
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&big), (size_t)next * 4));
-    NRF_HIP(hipMemcpy(big, m->d_params, (size_t)n * 4, hipMemcpyDeviceToDevice));
-    (void)hipFree(m->d_params);
-    m->d_params = big;
+    DevBuf big;
+    NRF_TRY(big.resize((size_t)next * 4));
+    NRF_HIP(hipMemcpy(big.as<float>(), m->params(), (size_t)n * 4, hipMemcpyDeviceToDevice));
+    m->d_params = std::move(big);
     NRF_TRY(nerf_derive_on_device(m, nullptr));
     std::vector<float> dev_derived((size_t)NERF_DERIVED);
-    NRF_HIP(hipMemcpy(dev_derived.data(), m->d_params + n, dev_derived.size() * 4, hipMemcpyDeviceToHost));
+    NRF_HIP(hipMemcpy(dev_derived.data(), m->params() + n, dev_derived.size() * 4, hipMemcpyDeviceToHost));
     if (memcmp(dev_derived.data(), ext.data() + n, dev_derived.size() * 4) != 0) return NRF_OK;          // (maps stay empty: host repack)
     for (size_t i = 0; i < regs.size(); i++) NRF_TRY(upload_weight_map(m, hms[i], regs[i].dst));
     return NRF_OK;
@@ -973,6 +961,19 @@ __global__ void k_transpose_wt(int in, int out, const float *__restrict__ w, flo
     if (e >= (int64_t)in * out) return;
     const int k = (int)(e / out), o = (int)(e - (int64_t)k * out);
     wt[e] = w[(size_t)o * in + k];
+}
+
+// W^T [in][out] and the bias of every layer (the generic fp32 kernels' operands) from the blob in d_params, on the device in `st`'s order: a training loop comes here
+// every step, and the host transposes + two small uploads per layer were most of what was left of nrf_mlp_set_params (classic 8x256: 12 layers)
+static int refresh_layers_on_device(const nrf_mlp *m, hipStream_t st)
+{
+    for (auto &L : m->layers) {
+        const int64_t ne = (int64_t)L.in * L.out;
+        k_transpose_wt<<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(L.in, L.out, m->params() + L.w_off, L.wt());
+        NRF_LAUNCH_CHECK();
+        if (L.bias()) NRF_HIP(hipMemcpyAsync(L.bias(), m->params() + L.w_off + (size_t)L.in * L.out, (size_t)L.out * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return NRF_OK;
 }
 
 __global__ void k_apply_weight_map(int64_t n, const int32_t *__restrict__ src, const uint8_t *__restrict__ kind, const float *__restrict__ params, void *__restrict__ out, int elem)
@@ -1127,21 +1128,22 @@ __global__ void k_scale_blob(int64_t n, const float *__restrict__ w, const uint8
 int mlp_small_rescale(nrf_mlp *m, hipStream_t st)
 {
     if (!m || m->family != MLP_SMALL || m->maps.empty() || !m->d_group) return NRF_OK;
+    float *scaled = m->d_params_scaled.as<float>(), *gscale = m->d_gscale.as<float>();
     if (!m->split_scaling) {
         const float ones[SMALL_MAX_GROUPS > SMALL_SCALE_COUNT ? SMALL_MAX_GROUPS : SMALL_SCALE_COUNT] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-        NRF_HIP(hipMemcpyAsync(m->d_params_scaled, m->d_params, (size_t)m->n_params * 4, hipMemcpyDeviceToDevice, st));
-        NRF_HIP(hipMemcpyAsync(m->d_gscale, ones, SMALL_MAX_GROUPS * sizeof(float), hipMemcpyHostToDevice, st));
-        NRF_HIP(hipMemcpyAsync(m->d_scales, ones, SMALL_SCALE_COUNT * sizeof(float), hipMemcpyHostToDevice, st));
+        NRF_HIP(hipMemcpyAsync(scaled, m->params(), (size_t)m->n_params * 4, hipMemcpyDeviceToDevice, st));
+        NRF_HIP(hipMemcpyAsync(gscale, ones, SMALL_MAX_GROUPS * sizeof(float), hipMemcpyHostToDevice, st));
+        NRF_HIP(hipMemcpyAsync(m->scales(), ones, SMALL_SCALE_COUNT * sizeof(float), hipMemcpyHostToDevice, st));
         NRF_HIP(hipStreamSynchronize(st));            // (`ones` is a stack array)
     } else {
-        k_small_scales<<<dim3(1), dim3(256), 0, st>>>(m->small, m->d_params, m->in_rms_hint, m->d_in_rms_src, m->d_gscale, m->d_scales);
+        k_small_scales<<<dim3(1), dim3(256), 0, st>>>(m->small, m->params(), m->in_rms_hint, m->d_in_rms_src, gscale, m->scales());
         NRF_HIP(hipGetLastError());
-        k_scale_blob<<<dim3((unsigned)((m->n_params + 255) / 256)), dim3(256), 0, st>>>(m->n_params, m->d_params, m->d_group, m->d_gscale, m->d_params_scaled);
+        k_scale_blob<<<dim3((unsigned)((m->n_params + 255) / 256)), dim3(256), 0, st>>>(m->n_params, m->params(), m->d_group.as<uint8_t>(), gscale, scaled);
         NRF_HIP(hipGetLastError());
     }
     for (auto &w : m->maps) {
         if (!w.scaled) continue;
-        k_apply_weight_map<<<dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, st>>>(w.n, w.d_src, w.d_kind, m->d_params_scaled, w.d_out, w.elem);
+        k_apply_weight_map<<<dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, st>>>(w.n, w.d_src.as<int32_t>(), w.d_kind.as<uint8_t>(), scaled, w.d_out, w.elem);
         NRF_HIP(hipGetLastError());
     }
     return NRF_OK;
@@ -1152,8 +1154,7 @@ static int small_scale_setup(nrf_mlp *m)
 {
     const auto &d = m->small;
     std::vector<float> ones(SMALL_MAX_GROUPS > SMALL_SCALE_COUNT ? SMALL_MAX_GROUPS : SMALL_SCALE_COUNT, 1.0f);
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_scales), SMALL_SCALE_COUNT * sizeof(float)));
-    NRF_HIP(hipMemcpy(m->d_scales, ones.data(), SMALL_SCALE_COUNT * sizeof(float), hipMemcpyHostToDevice));
+    NRF_TRY(m->d_scales.upload(ones.data(), SMALL_SCALE_COUNT * sizeof(float)));
     if (m->maps.empty() || d.use_pred_normal || d.num_layers + d.num_layers_color + 1 > SMALL_MAX_GROUPS) return NRF_OK;
     std::vector<uint8_t> group((size_t)m->n_params, 0);
     size_t off = 0;
@@ -1168,11 +1169,9 @@ static int small_scale_setup(nrf_mlp *m)
             group[off + i] = (uint8_t)(l == 0 ? ((int)(i % in) >= d.input_ch_views ? d.num_layers + 1 : d.num_layers) : d.num_layers + 1 + l);
         off += (size_t)in * out;
     }
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_group), group.size()));
-    NRF_HIP(hipMemcpy(m->d_group, group.data(), group.size(), hipMemcpyHostToDevice));
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_gscale), SMALL_MAX_GROUPS * sizeof(float)));
-    NRF_HIP(hipMemcpy(m->d_gscale, ones.data(), SMALL_MAX_GROUPS * sizeof(float), hipMemcpyHostToDevice));
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_params_scaled), (size_t)m->n_params * 4));
+    NRF_TRY(m->d_group.upload(group.data(), group.size()));
+    NRF_TRY(m->d_gscale.upload(ones.data(), SMALL_MAX_GROUPS * sizeof(float)));
+    NRF_TRY(m->d_params_scaled.resize((size_t)m->n_params * 4));
     if (const char *e = getenv("NRF_SPLIT_UNSCALED")) m->split_scaling = atoi(e) == 0;          // A/B switch of the default
     return NRF_OK;
 }
@@ -1212,8 +1211,9 @@ int nrf_mlp_small_create(const nrf_mlp_small_desc *d, const float *params, int p
     NRF_CHECK_ARG(d && params && out, "nrf_mlp_small_create: null pointer");
     NRF_CHECK_ARG(d->input_ch > 0 && d->input_ch_views >= 0 && d->num_layers >= 1 && d->hidden_dim > 0 && d->geo_feat_dim >= 0 &&
                   d->num_layers_color >= 1 && d->hidden_dim_color > 0, "nrf_mlp_small_create: bad dimensions");
-    nrf_mlp *m = new nrf_mlp();
     NRF_CHECK_ARG(!d->use_pred_normal || (d->num_layers_normals >= 1 && d->hidden_dim_normals > 0), "nrf_mlp_small_create: use_pred_normal needs num_layers_normals >= 1 and hidden_dim_normals > 0");
+    std::unique_ptr<nrf_mlp> owner(new nrf_mlp());
+    nrf_mlp *m = owner.get();
     m->family = MLP_SMALL; m->small = *d;
     m->in_dims = d->input_ch + d->input_ch_views; m->out_dims = d->use_pred_normal ? 7 : 4;
     std::vector<float> hp;
@@ -1232,8 +1232,8 @@ int nrf_mlp_small_create(const nrf_mlp_small_desc *d, const float *params, int p
     if (s == NRF_OK) s = small_scale_setup(m);
     if (s == NRF_OK) s = mlp_small_rescale(m, as_stream(stream));
     if (s == NRF_OK) s = hipStreamSynchronize(as_stream(stream)) == hipSuccess ? NRF_OK : NRF_ERR_HIP;
-    if (s != NRF_OK) { nrf_mlp_destroy(m); return s; }
-    *out = m;
+    if (s != NRF_OK) return s;
+    *out = owner.release();
     return NRF_OK;
 }
 
@@ -1242,7 +1242,8 @@ int nrf_mlp_nerf_create(const nrf_mlp_nerf_desc *d, const float *params, int par
     NRF_CHECK_ARG(d && params && out, "nrf_mlp_nerf_create: null pointer");
     NRF_CHECK_ARG(d->depth >= 2 && d->width >= 2 && d->input_ch > 0 && d->skip >= -1 && d->skip < d->depth - 1, "nrf_mlp_nerf_create: bad dimensions");
     NRF_CHECK_ARG(d->use_viewdirs ? d->input_ch_views > 0 : d->output_ch > 0, "nrf_mlp_nerf_create: bad head dimensions");
-    nrf_mlp *m = new nrf_mlp();
+    std::unique_ptr<nrf_mlp> owner(new nrf_mlp());
+    nrf_mlp *m = owner.get();
     m->family = MLP_NERF; m->nerf = *d;
     m->in_dims = d->input_ch + (d->use_viewdirs ? d->input_ch_views : 0);
     m->out_dims = d->use_viewdirs ? 4 : d->output_ch;
@@ -1263,21 +1264,21 @@ int nrf_mlp_nerf_create(const nrf_mlp_nerf_desc *d, const float *params, int par
     if (s == NRF_OK) s = mlp_nerf_pack_f16(m, hp);
     if (s == NRF_OK) s = mlp_nerf_pack_sigma_f32(m, hp);
     if (s == NRF_OK) s = build_weight_maps_nerf(m, hp);
-    if (s != NRF_OK) { nrf_mlp_destroy(m); return s; }
-    *out = m;
+    if (s != NRF_OK) return s;
+    *out = owner.release();
     return NRF_OK;
 }
 
 // The LeRF head's device packers (mlp_lerf_pack_f16_device, mlp_lerf_pack_sigma_f32_device) against the host packers' images, which the handle holds at this point:
-// the three images are read back, rebuilt on the device from m->d_params and read back again; equal byte for byte (and the same Gram scale) -> nrf_mlp_set_params keeps
+// the three images are read back, rebuilt on the device from m->params() and read back again; equal byte for byte (and the same Gram scale) -> nrf_mlp_set_params keeps
 // this handle's parameter uploads on the device.  Anything else -> the host images are restored and the host packers stay in charge.  NRF_MLP_HOST_REPACK=1 skips it.
 static int lerf_device_pack_verify(nrf_mlp *m, hipStream_t st)
 {
     m->lerf_device_pack = false;
     if (const char *e = getenv("NRF_MLP_HOST_REPACK")) if (atoi(e) != 0) return NRF_OK;
     if (!m->d_packed_f16 || !m->d_packed_split || !m->d_packed_sigma_f32) return NRF_OK;
-    void *dev[3] = { m->d_packed_f16, m->d_packed_split, m->d_packed_sigma_f32 };
-    const size_t bytes[3] = { m->packed_f16_bytes, m->packed_split_bytes, m->packed_sigma_f32_bytes };
+    void *dev[3] = { m->d_packed_f16.as<void>(), m->d_packed_split.as<void>(), m->d_packed_sigma_f32.as<void>() };
+    const size_t bytes[3] = { m->d_packed_f16.bytes(), m->d_packed_split.bytes(), m->d_packed_sigma_f32.bytes() };
     std::vector<uint8_t> host[3], mine[3];
     NRF_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < 3; i++) { host[i].resize(bytes[i]); NRF_HIP(hipMemcpy(host[i].data(), dev[i], bytes[i], hipMemcpyDeviceToHost)); }
@@ -1317,7 +1318,8 @@ NRF_API int nrf_mlp_lerf_create(const nrf_mlp_small_desc *d, const float *params
 {
     NRF_CHECK_ARG(d && params && out, "nrf_mlp_lerf_create: null pointer");
     NRF_CHECK_ARG(d->input_ch > 0 && d->num_layers >= 1 && d->hidden_dim > 0 && d->geo_feat_dim >= 0 && d->hidden_dim_color > 0, "nrf_mlp_lerf_create: bad dimensions");
-    nrf_mlp *m = new nrf_mlp();
+    std::unique_ptr<nrf_mlp> owner(new nrf_mlp());
+    nrf_mlp *m = owner.get();
     m->family = MLP_LERF; m->small = *d;
     m->in_dims = d->input_ch; m->out_dims = d->hidden_dim_color + 1;
     std::vector<float> hp;
@@ -1330,8 +1332,8 @@ NRF_API int nrf_mlp_lerf_create(const nrf_mlp_small_desc *d, const float *params
     if (s == NRF_OK) s = mlp_lerf_pack_f16(m, hp);
     if (s == NRF_OK) s = mlp_lerf_pack_sigma_f32(m, hp);
     if (s == NRF_OK) s = lerf_device_pack_verify(m, as_stream(stream));
-    if (s != NRF_OK) { nrf_mlp_destroy(m); return s; }
-    *out = m;
+    if (s != NRF_OK) return s;
+    *out = owner.release();
     return NRF_OK;
 }
 
@@ -1344,32 +1346,23 @@ int nrf_mlp_set_params(nrf_mlp *m, const float *params, int params_on_device, vo
         // NeRFSmall: blob and every derived image refreshed on the device, in stream order, nothing waits.  Work issued earlier on `stream` (and on the library's
         // lanes, which are joined to it before a render call returns) still reads the old images and finishes first; another stream of the caller's must be ordered
         // by the caller, as for any in-place update.
-        NRF_HIP(hipMemcpyAsync(m->d_params, params, (size_t)m->n_params * 4, params_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        NRF_HIP(hipMemcpyAsync(m->params(), params, (size_t)m->n_params * 4, params_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         if (m->family == MLP_NERF) {
             // classic network: W^T and bias of every layer (the fp32 kernels' operands), then the merged views layer behind the blob: the maps below gather from both
-            for (auto &L : m->layers) {
-                const int64_t ne = (int64_t)L.in * L.out;
-                k_transpose_wt<<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(L.in, L.out, m->d_params + L.w_off, L.d_wt);
-                NRF_HIP(hipGetLastError());
-                if (L.d_bias) NRF_HIP(hipMemcpyAsync(L.d_bias, m->d_params + L.w_off + (size_t)L.in * L.out, (size_t)L.out * 4, hipMemcpyDeviceToDevice, st));
-            }
+            NRF_TRY(refresh_layers_on_device(m, st));
             NRF_TRY(nerf_derive_on_device(m, st));
         }
         for (auto &w : m->maps) {
             if (w.scaled && m->d_group) continue;          // the split-precision operands: below, from the range-scaled blob
-            k_apply_weight_map<<<dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, st>>>(w.n, w.d_src, w.d_kind, m->d_params, w.d_out, w.elem);
+            k_apply_weight_map<<<dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, st>>>(w.n, w.d_src.as<int32_t>(), w.d_kind.as<uint8_t>(), m->params(), w.d_out, w.elem);
             NRF_HIP(hipGetLastError());
         }
         return mlp_small_rescale(m, st);
     }
     if (m->family == MLP_LERF && m->lerf_device_pack && params_on_device) {
         // the LeRF head: blob, transposed layers and the matrix-core images all on the device, in stream order (one 4-byte read-back inside: the Gram matrix's scale)
-        NRF_HIP(hipMemcpyAsync(m->d_params, params, (size_t)m->n_params * 4, hipMemcpyDeviceToDevice, st));
-        for (auto &L : m->layers) {
-            const int64_t ne = (int64_t)L.in * L.out;
-            k_transpose_wt<<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(L.in, L.out, m->d_params + L.w_off, L.d_wt);
-            NRF_HIP(hipGetLastError());
-        }
+        NRF_HIP(hipMemcpyAsync(m->params(), params, (size_t)m->n_params * 4, hipMemcpyDeviceToDevice, st));
+        NRF_TRY(refresh_layers_on_device(m, st));          // (the head has no biases)
         NRF_TRY(mlp_lerf_pack_f16_device(m, st));
         return mlp_lerf_pack_sigma_f32_device(m, st);
     }
@@ -1381,15 +1374,8 @@ int nrf_mlp_set_params(nrf_mlp *m, const float *params, int params_on_device, vo
         memcpy(hp.data(), params, hp.size() * 4);
         NRF_HIP(hipStreamSynchronize(st));             // the derived images are overwritten in place: nothing may still be reading them
     }
-    NRF_HIP(hipMemcpyAsync(m->d_params, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st));
-    // W^T [in][out] and the bias of every layer (the generic fp32 kernels' operands) from the uploaded blob, on the device: a training loop comes here every step, and the
-    // host transposes + two small uploads per layer were most of what was left of this call (classic 8x256: 12 layers)
-    for (auto &L : m->layers) {
-        const int64_t ne = (int64_t)L.in * L.out;
-        k_transpose_wt<<<dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st>>>(L.in, L.out, m->d_params + L.w_off, L.d_wt);
-        NRF_HIP(hipGetLastError());
-        if (L.d_bias) NRF_HIP(hipMemcpyAsync(L.d_bias, m->d_params + L.w_off + (size_t)L.in * L.out, (size_t)L.out * 4, hipMemcpyDeviceToDevice, st));
-    }
+    NRF_HIP(hipMemcpyAsync(m->params(), hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st));
+    NRF_TRY(refresh_layers_on_device(m, st));
     NRF_HIP(hipStreamSynchronize(st));
     if (m->family == MLP_SMALL) { if (m->small.use_pred_normal) return NRF_OK; NRF_TRY(mlp_small_pack_f16(m, hp)); return mlp_small_pack_sigma_f32(m, hp); }
     if (m->family == MLP_NERF) { NRF_TRY(mlp_nerf_pack_f16(m, hp)); return mlp_nerf_pack_sigma_f32(m, hp); }
@@ -1418,10 +1404,10 @@ int nrf_mlp_get_split_scales(const nrf_mlp *m, float *group_scales_out, float *k
     NRF_CHECK_ARG(m && group_scales_out && kernel_scales_out, "nrf_mlp_get_split_scales: null pointer");
     for (int i = 0; i < SMALL_MAX_GROUPS; i++) group_scales_out[i] = 1.0f;
     for (int i = 0; i < SMALL_SCALE_COUNT; i++) kernel_scales_out[i] = 1.0f;
-    if (m->family != MLP_SMALL || !m->d_scales) return NRF_OK;
+    if (m->family != MLP_SMALL || !m->scales()) return NRF_OK;
     hipStream_t st = as_stream(stream);
-    if (m->d_gscale) NRF_HIP(hipMemcpyAsync(group_scales_out, m->d_gscale, SMALL_MAX_GROUPS * sizeof(float), hipMemcpyDeviceToHost, st));
-    NRF_HIP(hipMemcpyAsync(kernel_scales_out, m->d_scales, SMALL_SCALE_COUNT * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (m->d_gscale) NRF_HIP(hipMemcpyAsync(group_scales_out, m->d_gscale.as<float>(), SMALL_MAX_GROUPS * sizeof(float), hipMemcpyDeviceToHost, st));
+    NRF_HIP(hipMemcpyAsync(kernel_scales_out, m->scales(), SMALL_SCALE_COUNT * sizeof(float), hipMemcpyDeviceToHost, st));
     NRF_HIP(hipStreamSynchronize(st));
     return NRF_OK;
 }
@@ -1474,26 +1460,7 @@ int nrf_mlp_backward_f16_lm_src(const nrf_mlp *m, const void *d_feats_lm, int64_
                                       m->small.input_ch, d_workspace, workspace_bytes, as_stream(stream), pstride, d_src);
 }
 
-void nrf_mlp_destroy(nrf_mlp *m)
-{
-    if (!m) return;
-    for (auto &L : m->layers) {
-        if (L.d_wt) (void)hipFree(L.d_wt);
-        if (L.d_bias) (void)hipFree(L.d_bias);
-    }
-    drop_weight_maps(m);
-    if (m->d_params) (void)hipFree(m->d_params);
-    if (m->d_packed_f16) (void)hipFree(m->d_packed_f16);
-    if (m->d_packed_split) (void)hipFree(m->d_packed_split);
-    if (m->d_packed_bwd) (void)hipFree(m->d_packed_bwd);
-    if (m->d_packed_sigma_f32) (void)hipFree(m->d_packed_sigma_f32);
-    if (m->d_lerf_gram) (void)hipFree(m->d_lerf_gram);
-    if (m->d_params_scaled) (void)hipFree(m->d_params_scaled);
-    if (m->d_group) (void)hipFree(m->d_group);
-    if (m->d_gscale) (void)hipFree(m->d_gscale);
-    if (m->d_scales) (void)hipFree(m->d_scales);
-    delete m;
-}
+void nrf_mlp_destroy(nrf_mlp *m) { delete m; }
 
 int nrf_mlp_output_dims(const nrf_mlp *m) { return m ? m->out_dims : 0; }
 
@@ -1503,11 +1470,9 @@ int nrf_mlp_forward(const nrf_mlp *m, const float *d_x, int64_t p, int precision
     if (p == 0) return NRF_OK;
     hipStream_t st = as_stream(stream);
     const size_t wsb = mlp_workspace_bytes(m, p, precision);
-    void *ws = nullptr;
-    NRF_HIP(scratch_take(&ws, wsb, st));          // stream-ordered scratch for the standalone entry point
-    const int s = mlp_forward(m, d_x, m->in_dims, p, precision, d_out, m->out_dims, ws, wsb, st);
-    NRF_HIP(scratch_give(ws, st));
-    return s;
+    Scratch ws;                                    // stream-ordered scratch for the standalone entry point
+    NRF_TRY(ws.take(wsb, st));
+    return mlp_forward(m, d_x, m->in_dims, p, precision, d_out, m->out_dims, ws.as<void>(), wsb, st);
 }
 
 // ... without waiting: the two words are copied into h_flags2 (two uint32, best pinned) in `stream`'s order; the caller reads them once the stream (or an event recorded

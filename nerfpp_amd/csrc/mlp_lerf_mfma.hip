@@ -462,27 +462,21 @@ int mlp_lerf_pack_f16(nrf_mlp *m, const std::vector<float> &hp)
         for (int t = 0; t < nt; t++) th.emplace_back(fill, IMAGE_FRAGS * t / nt, IMAGE_FRAGS * (t + 1) / nt);
         for (auto &x : th) x.join();
     }
-    if (m->d_packed_f16 && m->packed_f16_bytes != img.size() * sizeof(_Float16)) { (void)hipFree(m->d_packed_f16); m->d_packed_f16 = nullptr; }
-    m->packed_f16_bytes = img.size() * sizeof(_Float16);
-    if (!m->d_packed_f16) NRF_HIP(hipMalloc(&m->d_packed_f16, m->packed_f16_bytes));          // a re-pack of the same shape writes in place (the caller has synchronised: mlp.hip)
-    NRF_HIP(hipMemcpy(m->d_packed_f16, img.data(), m->packed_f16_bytes, hipMemcpyHostToDevice));
-    if (m->d_packed_split && m->packed_split_bytes != img2.size() * sizeof(_Float16)) { (void)hipFree(m->d_packed_split); m->d_packed_split = nullptr; }
-    m->packed_split_bytes = img2.size() * sizeof(_Float16);
-    if (!m->d_packed_split) NRF_HIP(hipMalloc(&m->d_packed_split, m->packed_split_bytes));
-    NRF_HIP(hipMemcpy(m->d_packed_split, img2.data(), m->packed_split_bytes, hipMemcpyHostToDevice));
-    return NRF_OK;
+    NRF_TRY(m->d_packed_f16.upload(img.data(), img.size() * sizeof(_Float16)));          // a re-pack of the same shape writes in place (the caller has synchronised: mlp.hip)
+    return m->d_packed_split.upload(img2.data(), img2.size() * sizeof(_Float16));
 }
 
-// The images from m->d_params on the device, in `st`'s order; one 4-byte read-back (the Gram matrix's largest entry decides its power-of-two scale, which the
+// The images from m->params() on the device, in `st`'s order; one 4-byte read-back (the Gram matrix's largest entry decides its power-of-two scale, which the
 // launchers pass by value).  Needs the image buffers of a first host pack.
 int mlp_lerf_pack_f16_device(nrf_mlp *m, hipStream_t st)
 {
-    if (!lerf_mfma_supported(m->small) || !m->d_packed_f16 || !m->d_packed_split || m->packed_f16_bytes != (size_t)IMAGE_FRAGS * 512 * sizeof(_Float16)) return NRF_ERR_UNSUPPORTED;
-    if (!m->d_lerf_gram) NRF_HIP(hipMalloc(reinterpret_cast<void **>(&m->d_lerf_gram), (size_t)2 * HID * HID * sizeof(float) + 16));          // [packed form | W^T W itself | max bits]
-    uint32_t *gmax = reinterpret_cast<uint32_t *>(m->d_lerf_gram + (size_t)2 * HID * HID);
-    const float *w3 = m->d_params + (size_t)HID * IN + (size_t)(1 + GEO) * HID + (size_t)HID * (GEO + IN);
+    if (!lerf_mfma_supported(m->small) || !m->d_packed_f16 || !m->d_packed_split || m->d_packed_f16.bytes() != (size_t)IMAGE_FRAGS * 512 * sizeof(_Float16)) return NRF_ERR_UNSUPPORTED;
+    NRF_TRY(m->d_lerf_gram.resize((size_t)2 * HID * HID * sizeof(float) + 16));          // [packed form | W^T W itself | max bits]
+    float *gram = m->d_lerf_gram.as<float>();
+    uint32_t *gmax = reinterpret_cast<uint32_t *>(gram + (size_t)2 * HID * HID);
+    const float *w3 = m->params() + (size_t)HID * IN + (size_t)(1 + GEO) * HID + (size_t)HID * (GEO + IN);
     NRF_HIP(hipMemsetAsync(gmax, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_lerf_gram_f64, dim3(HID), dim3(HID), 0, st, w3, m->d_lerf_gram, gmax);
+    hipLaunchKernelGGL(k_lerf_gram_f64, dim3(HID), dim3(HID), 0, st, w3, gram, gmax);
     NRF_LAUNCH_CHECK();
     uint32_t bits = 0;
     NRF_HIP(hipMemcpyAsync(&bits, gmax, sizeof(bits), hipMemcpyDeviceToHost, st));
@@ -491,10 +485,10 @@ int mlp_lerf_pack_f16_device(nrf_mlp *m, hipStream_t st)
     const int e = lerf_gram_exponent(gm);
     m->lerf_gram_scale = ldexpf(1.0f, e);
     m->lerf_le1_exp = lerf_le1_exponent(e);
-    hipLaunchKernelGGL(k_lerf_gram_finish, dim3(HID * HID / 256), dim3(256), 0, st, m->d_lerf_gram, e);
+    hipLaunchKernelGGL(k_lerf_gram_finish, dim3(HID * HID / 256), dim3(256), 0, st, gram, e);
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_lerf_fill, dim3(IMAGE_FRAGS), dim3(512), 0, st, (const float *)m->d_params, (const float *)m->d_lerf_gram, reinterpret_cast<_Float16 *>(m->d_packed_f16),
-                       reinterpret_cast<_Float16 *>(m->d_packed_split), m->lerf_le1_exp);
+    hipLaunchKernelGGL(k_lerf_fill, dim3(IMAGE_FRAGS), dim3(512), 0, st, (const float *)m->params(), (const float *)gram, m->d_packed_f16.as<_Float16>(),
+                       m->d_packed_split.as<_Float16>(), m->lerf_le1_exp);
     NRF_LAUNCH_CHECK();
     m->lerf_gram_current = true;
     return NRF_OK;
@@ -508,7 +502,7 @@ static int launch_lerf(const nrf_mlp *m, const Args &a_in, int64_t p, hipStream_
     const size_t lds = (size_t)3 * MAXF * 1024;
     const int64_t nblocks = ceil_div(p, NBLK);
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);       // persistent: one 8-wave workgroup per CU (216 VGPRs: two waves per SIMD)
-    hipLaunchKernelGGL((k_lerf_mfma<NL>), dim3(grid), dim3(64 * NW), lds, st, p, a, reinterpret_cast<const half8 *>(m->d_packed_f16));
+    hipLaunchKernelGGL((k_lerf_mfma<NL>), dim3(grid), dim3(64 * NW), lds, st, p, a, m->d_packed_f16.as<const half8>());
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
@@ -516,23 +510,18 @@ static int launch_lerf(const nrf_mlp *m, const Args &a_in, int64_t p, hipStream_
 // kernel B into a stream-ordered scratch asum [n][256] (zeroed), then kernel C
 static int lerf_embedding_passes(const nrf_mlp *m, lerf::Args a, int64_t n, int s, float *d_out, hipStream_t st)
 {
-    float *asum = nullptr;
     const size_t bytes = (size_t)n * lerf::HID * sizeof(float);
-    NRF_HIP(scratch_take(reinterpret_cast<void **>(&asum), bytes, st));
-    int rc = hipMemsetAsync(asum, 0, bytes, st) == hipSuccess ? NRF_OK : NRF_ERR_HIP;
-    if (rc != NRF_OK) set_error("hipMemsetAsync failed");
-    else {
-        ProfScope prof(NRF_PROF_MLP, st);
-        a.out = asum;
-        rc = launch_lerf<4>(m, a, n * (int64_t)s, st);
-        if (rc == NRF_OK) {
-            hipLaunchKernelGGL(lerf::k_lerf_embed, dim3((unsigned)ceil_div(ceil_div(n, (int64_t)32), (int64_t)4)), dim3(256), 0, st, n, (const float *)asum,
-                               reinterpret_cast<const half8 *>(m->d_packed_f16), d_out);
-            if (hipGetLastError() != hipSuccess) { set_error("k_lerf_embed launch failed"); rc = NRF_ERR_HIP; }
-        }
-    }
-    (void)scratch_give(asum, st);
-    return rc;
+    Scratch buf;
+    NRF_TRY(buf.take(bytes, st));
+    float *asum = buf.as<float>();
+    NRF_HIP(hipMemsetAsync(asum, 0, bytes, st));
+    ProfScope prof(NRF_PROF_MLP, st);
+    a.out = asum;
+    NRF_TRY(launch_lerf<4>(m, a, n * (int64_t)s, st));
+    hipLaunchKernelGGL(lerf::k_lerf_embed, dim3((unsigned)ceil_div(ceil_div(n, (int64_t)32), (int64_t)4)), dim3(256), 0, st, n, (const float *)asum,
+                       m->d_packed_f16.as<const half8>(), d_out);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
 }
 
 }  // namespace nrf
@@ -541,7 +530,7 @@ using namespace nrf;
 
 extern "C" {
 
-int nrf_lerf_mfma_available(const nrf_mlp *m) { return m && m->family == MLP_LERF && m->d_packed_f16 != nullptr; }
+int nrf_lerf_mfma_available(const nrf_mlp *m) { return m && m->family == MLP_LERF && bool(m->d_packed_f16); }
 
 int nrf_lerf_set_precision(nrf_mlp *m, int precision)
 {

@@ -681,7 +681,7 @@ static int launch_lerf_split(const nrf_mlp *m, const Args &a_in, int64_t p, hipS
     const size_t lds_geo = lds + (size_t)SNW * (GEO_OPER_FRAGS + 1) * 1024;          // + the waves' operand slots (k_lerf_split_geo)
     const int64_t nblocks = NL == 2 ? ceil_div(p, SNBLK) : ceil_div(p / a.s, (int64_t)SNW);       // kernel B: one ray per wave
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);       // persistent: one 4-wave workgroup per CU
-    const half8 *img = reinterpret_cast<const half8 *>(m->d_packed_split);
+    const half8 *img = m->d_packed_split.as<const half8>();
     static PerDeviceOnce attr_set;          // idempotent one-time setup per device (common.h)
     if (attr_set.needed()) {
         NRF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_lerf_split<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -883,7 +883,7 @@ int lerf_split_query(const nrf_mlp *m, const lerf::QueryArgs &a_in, int64_t p, c
     return NRF_OK;
 }
 
-int lerf_split_available(const nrf_mlp *m) { return m && m->family == MLP_LERF && m->d_packed_split != nullptr && m->packed_split_bytes == (size_t)2 * lerf::IMAGE_FRAGS * 1024; }
+int lerf_split_available(const nrf_mlp *m) { return m && m->family == MLP_LERF && bool(m->d_packed_split) && m->d_packed_split.bytes() == (size_t)2 * lerf::IMAGE_FRAGS * 1024; }
 
 int lerf_split_sigma(const nrf_mlp *m, const lerf::Args &a, int64_t p, hipStream_t st)
 {
@@ -894,22 +894,16 @@ int lerf_split_sigma(const nrf_mlp *m, const lerf::Args &a, int64_t p, hipStream
 // kernel B into a stream-ordered scratch asum [n][256] (zeroed), then kernel C
 int lerf_split_embedding_passes(const nrf_mlp *m, lerf::Args a, int64_t n, int s, float *d_out, hipStream_t st)
 {
-    float *asum = nullptr;
-    const size_t bytes = (size_t)n * lerf::HID * sizeof(float);
-    NRF_HIP(scratch_take(reinterpret_cast<void **>(&asum), bytes, st));
-    int rc = NRF_OK;              // every row of asum is stored by the wave that owns its ray: no zero fill
-    if (rc == NRF_OK) {
-        ProfScope prof(NRF_PROF_MLP, st);
-        a.out = asum;
-        rc = lerf::launch_lerf_split<4>(m, a, n * (int64_t)s, st);
-        if (rc == NRF_OK) {
-            hipLaunchKernelGGL(lerf::k_lerf_embed_split, dim3((unsigned)ceil_div(ceil_div(n, (int64_t)32), (int64_t)4)), dim3(256), 0, st, n, (const float *)asum,
-                               reinterpret_cast<const half8 *>(m->d_packed_split), d_out);
-            if (hipGetLastError() != hipSuccess) { set_error("k_lerf_embed_split launch failed"); rc = NRF_ERR_HIP; }
-        }
-    }
-    (void)scratch_give(asum, st);          // stream-ordered: also on the error paths
-    return rc;
+    Scratch buf;
+    NRF_TRY(buf.take((size_t)n * lerf::HID * sizeof(float), st));
+    float *asum = buf.as<float>();              // every row of asum is stored by the wave that owns its ray: no zero fill
+    ProfScope prof(NRF_PROF_MLP, st);
+    a.out = asum;
+    NRF_TRY(lerf::launch_lerf_split<4>(m, a, n * (int64_t)s, st));
+    hipLaunchKernelGGL(lerf::k_lerf_embed_split, dim3((unsigned)ceil_div(ceil_div(n, (int64_t)32), (int64_t)4)), dim3(256), 0, st, n, (const float *)asum,
+                       m->d_packed_split.as<const half8>(), d_out);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
 }
 
 }  // namespace nrf

@@ -374,16 +374,12 @@ int mlp_nerf_pack_f16(nrf_mlp *m, const std::vector<float> &hp)
     if (!nerf_f16_images_host(d, hp.data(), merged.data(), merged_b.data(), img, img2, bias)) return NRF_ERR_INVALID_ARG;
     m->host_merged = merged; m->host_merged_b = merged_b;          // for mlp_nerf_pack_sigma_f32 of the same upload
     const size_t b1 = img.size() * sizeof(_Float16) + bias.size() * sizeof(float), b2 = img2.size() * sizeof(_Float16) + bias.size() * sizeof(float);
-    if (m->d_packed_f16 && m->packed_f16_bytes != b1) { (void)hipFree(m->d_packed_f16); m->d_packed_f16 = nullptr; }        // a re-pack of the same shape writes in place (the caller has synchronised)
-    m->packed_f16_bytes = b1;
-    if (!m->d_packed_f16) NRF_HIP(hipMalloc(&m->d_packed_f16, b1));
-    NRF_HIP(hipMemcpy(m->d_packed_f16, img.data(), img.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    NRF_HIP(hipMemcpy(static_cast<char *>(m->d_packed_f16) + img.size() * sizeof(_Float16), bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (m->d_packed_split && m->packed_split_bytes != b2) { (void)hipFree(m->d_packed_split); m->d_packed_split = nullptr; }
-    m->packed_split_bytes = b2;
-    if (!m->d_packed_split) NRF_HIP(hipMalloc(&m->d_packed_split, b2));
-    NRF_HIP(hipMemcpy(m->d_packed_split, img2.data(), img2.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    NRF_HIP(hipMemcpy(static_cast<char *>(m->d_packed_split) + img2.size() * sizeof(_Float16), bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
+    NRF_TRY(m->d_packed_f16.resize(b1));        // a re-pack of the same shape writes in place (the caller has synchronised)
+    NRF_HIP(hipMemcpy(m->d_packed_f16.as<char>(), img.data(), img.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    NRF_HIP(hipMemcpy(m->d_packed_f16.as<char>() + img.size() * sizeof(_Float16), bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
+    NRF_TRY(m->d_packed_split.resize(b2));
+    NRF_HIP(hipMemcpy(m->d_packed_split.as<char>(), img2.data(), img2.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    NRF_HIP(hipMemcpy(m->d_packed_split.as<char>() + img2.size() * sizeof(_Float16), bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
     return NRF_OK;
 }
 
@@ -402,8 +398,8 @@ static int launch_nerf(const nrf_mlp *m, const NerfInput &in, bool fused, int64_
         NRF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mlp_nerf_mfma<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set.done();
     }
-    const half8 *packed = reinterpret_cast<const half8 *>(m->d_packed_f16);
-    const float *biases = reinterpret_cast<const float *>(static_cast<const char *>(m->d_packed_f16) + (size_t)NerfNet::total_frags() * 1024);
+    const half8 *packed = m->d_packed_f16.as<const half8>();
+    const float *biases = reinterpret_cast<const float *>(m->d_packed_f16.as<const char>() + (size_t)NerfNet::total_frags() * 1024);
     if (fused) hipLaunchKernelGGL(k_mlp_nerf_mfma<true>, dim3(grid), dim3(64 * NW), lds, st, p, in, packed, biases, out, os);
     else hipLaunchKernelGGL(k_mlp_nerf_mfma<false>, dim3(grid), dim3(64 * NW), lds, st, p, in, packed, biases, out, os);
     NRF_LAUNCH_CHECK();
@@ -416,7 +412,7 @@ int mlp_nerf_forward_mfma(const nrf_mlp *m, const float *x, int xs, int64_t p, f
     return launch_nerf(m, in, false, p, out, os, st);
 }
 
-int mlp_nerf_mfma_available(const nrf_mlp *m) { return m && m->family == MLP_NERF && m->d_packed_f16 != nullptr; }
+int mlp_nerf_mfma_available(const nrf_mlp *m) { return m && m->family == MLP_NERF && bool(m->d_packed_f16); }
 
 // renderer fast path: points from (rays, z) -- or explicit `pts` [p,3] when not NULL --, PE in registers, per-ray fp16 direction encodings -> raw [p,4]
 int mlp_nerf_forward_mfma_fused(const nrf_mlp *m, const float *pts, const float *rays, int ray_stride, const float *z, int s, const __half *dirs, int64_t p, float *out, hipStream_t st)

@@ -366,7 +366,7 @@ int launch_dirs_pe_split(const float *rays, int stride, int64_t n, __half *out_h
     return NRF_OK;
 }
 
-int mlp_nerf_split_available(const nrf_mlp *m) { return m && m->family == MLP_NERF && m->d_packed_split != nullptr; }
+int mlp_nerf_split_available(const nrf_mlp *m) { return m && m->family == MLP_NERF && bool(m->d_packed_split); }
 
 int mlp_nerf_forward_split(const nrf_mlp *m, const NerfInput &in, bool fused, int64_t p, float *out, int os, hipStream_t st)
 {
@@ -375,7 +375,7 @@ int mlp_nerf_forward_split(const nrf_mlp *m, const NerfInput &in, bool fused, in
         return NRF_ERR_UNSUPPORTED;
     }
     const size_t img_bytes = (size_t)NerfNetS::total_frags() * 1024;
-    if (m->packed_split_bytes != img_bytes + NBIAS * sizeof(float)) { set_error("internal: classic NeRF split image is %zu bytes, kernel expects %zu", m->packed_split_bytes, img_bytes + NBIAS * sizeof(float)); return NRF_ERR_INVALID_ARG; }
+    if (m->d_packed_split.bytes() != img_bytes + NBIAS * sizeof(float)) { set_error("internal: classic NeRF split image is %zu bytes, kernel expects %zu", m->d_packed_split.bytes(), img_bytes + NBIAS * sizeof(float)); return NRF_ERR_INVALID_ARG; }
     const size_t lds = (size_t)3 * SMAXF * 1024;          // + the static bias array
     const int64_t nblocks = ceil_div(p, SNBLK);
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);       // one persistent workgroup per CU
@@ -385,8 +385,8 @@ int mlp_nerf_forward_split(const nrf_mlp *m, const NerfInput &in, bool fused, in
         NRF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mlp_nerf_split<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set.done();
     }
-    const half8 *packed = reinterpret_cast<const half8 *>(m->d_packed_split);
-    const float *biases = reinterpret_cast<const float *>(static_cast<const char *>(m->d_packed_split) + img_bytes);
+    const half8 *packed = m->d_packed_split.as<const half8>();
+    const float *biases = reinterpret_cast<const float *>(m->d_packed_split.as<const char>() + img_bytes);
     if (fused) hipLaunchKernelGGL(k_mlp_nerf_split<true>, dim3(grid), dim3(64 * SNW), lds, st, p, in, packed, biases, out, os);
     else hipLaunchKernelGGL(k_mlp_nerf_split<false>, dim3(grid), dim3(64 * SNW), lds, st, p, in, packed, biases, out, os);
     NRF_LAUNCH_CHECK();

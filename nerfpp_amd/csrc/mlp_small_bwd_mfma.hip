@@ -571,7 +571,7 @@ bool mlp_small_bwd_image_host(const nrf_mlp *m, const std::vector<float> &hp, st
 {
     const auto &d = m->small;
     bool ok = bwd_supported(d);
-    for (auto &L : m->layers) if (L.d_bias) ok = false;
+    for (auto &L : m->layers) if (L.bias()) ok = false;
     if (!ok) return false;
     const int G = d.geo_feat_dim;
     auto natural = [](int ks, int h, int j) { return 16 * ks + 8 * h + j; };
@@ -607,16 +607,8 @@ bool mlp_small_bwd_image_host(const nrf_mlp *m, const std::vector<float> &hp, st
 int mlp_small_pack_bwd(nrf_mlp *m, const std::vector<float> &hp)
 {
     std::vector<uint8_t> img;
-    if (!mlp_small_bwd_image_host(m, hp, img)) {
-        if (m->d_packed_bwd) { (void)hipFree(m->d_packed_bwd); m->d_packed_bwd = nullptr; m->packed_bwd_bytes = 0; }
-        return NRF_OK;
-    }
-    const size_t bytes = img.size();
-    if (m->d_packed_bwd && m->packed_bwd_bytes != bytes) { (void)hipFree(m->d_packed_bwd); m->d_packed_bwd = nullptr; }
-    if (!m->d_packed_bwd) NRF_HIP(hipMalloc(&m->d_packed_bwd, bytes));        // host path of nrf_mlp_set_params: overwritten in place
-    m->packed_bwd_bytes = bytes;
-    NRF_HIP(hipMemcpy(m->d_packed_bwd, img.data(), bytes, hipMemcpyHostToDevice));
-    return NRF_OK;
+    if (!mlp_small_bwd_image_host(m, hp, img)) { m->d_packed_bwd.reset(); return NRF_OK; }
+    return m->d_packed_bwd.upload(img.data(), img.size());        // host path of nrf_mlp_set_params: overwritten in place
 }
 
 static const int64_t BWD_MFMA_CHUNK = 1 << 22;       // points per launch; every launch ends with one float atomic per parameter and workgroup
@@ -690,13 +682,13 @@ static int backward_mfma_impl(const nrf_mlp *m, const float *x, int xs, const __
             using P = BwdPlan<NL_, NLC_>;                                                                                                                 \
             auto kfn = k_small_bwd<NL_, NLC_>;                                                                                                            \
             const size_t lds = (size_t)(P::fwd_frags() + P::bwd_frags()) * 1024 + (size_t)m->n_params * 4;                                                \
-            if (m->packed_f16_bytes != (size_t)P::fwd_frags() * 1024 || m->packed_bwd_bytes != (size_t)P::bwd_frags() * 1024 || lds > 160 * 1024) {        \
+            if (m->d_packed_f16.bytes() != (size_t)P::fwd_frags() * 1024 || m->d_packed_bwd.bytes() != (size_t)P::bwd_frags() * 1024 || lds > 160 * 1024) {        \
                 set_error("internal: NeRFSmall backward image sizes do not match the kernel plan"); return NRF_ERR_UNSUPPORTED;                            \
             }                                                                                                                                             \
             NRF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
             const LmInput lmi{feats_lm ? (lm_src ? feats_lm : feats_lm + p0) : nullptr, lm_src ? lm_pstride : p, dirs, s_per_ray, p0, lm_src};                  \
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * BW), lds, st, c, x ? x + p0 * xs : nullptr, xs, g_out + p0 * gos, gos, reinterpret_cast<const half8 *>(m->d_packed_f16), \
-                               reinterpret_cast<const half8 *>(m->d_packed_bwd), scratch, g_params, g_x ? g_x + p0 * gxs : nullptr, gxs, absmax, (int)m->n_params, lo, lmi); \
+            hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * BW), lds, st, c, x ? x + p0 * xs : nullptr, xs, g_out + p0 * gos, gos, m->d_packed_f16.as<const half8>(), \
+                               m->d_packed_bwd.as<const half8>(), scratch, g_params, g_x ? g_x + p0 * gxs : nullptr, gxs, absmax, (int)m->n_params, lo, lmi); \
                                                                                                      \
         }
         NRF_BW(3, 4) NRF_BW(3, 3) NRF_BW(2, 4) NRF_BW(2, 3)

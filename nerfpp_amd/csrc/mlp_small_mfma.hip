@@ -772,16 +772,8 @@ int mlp_small_pack_f16(nrf_mlp *m, const std::vector<float> &hp)
     std::vector<uint8_t> a, b;
     if (!mlp_small_images_host(d, hp, a, b)) return NRF_OK;      // the matrix-core precisions then report NRF_ERR_UNSUPPORTED at forward time
     // re-pack after nrf_mlp_set_params (host path): same sizes, so the device images are overwritten in place
-    auto upload = [](void *&dst, size_t &have, const std::vector<uint8_t> &img) -> int {
-        const size_t bytes = img.size();
-        if (dst && have != bytes) { (void)hipFree(dst); dst = nullptr; }
-        if (!dst) NRF_HIP(hipMalloc(&dst, bytes));
-        have = bytes;
-        NRF_HIP(hipMemcpy(dst, img.data(), bytes, hipMemcpyHostToDevice));
-        return NRF_OK;
-    };
-    NRF_TRY(upload(m->d_packed_f16, m->packed_f16_bytes, a));
-    NRF_TRY(upload(m->d_packed_split, m->packed_split_bytes, b));
+    NRF_TRY(m->d_packed_f16.upload(a.data(), a.size()));
+    NRF_TRY(m->d_packed_split.upload(b.data(), b.size()));
     return mlp_small_pack_bwd(m, hp);
 }
 
@@ -790,13 +782,13 @@ static int launch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool sp
 {
     using Plan = SmallPlan<2, V_KS, NL, NLC>;
     const size_t lds = (size_t)Plan::total() * 1024 * (split ? 2 : 1);
-    const size_t have = split ? m->packed_split_bytes : m->packed_f16_bytes;
+    const size_t have = split ? m->d_packed_split.bytes() : m->d_packed_f16.bytes();
     if (lds != have) { set_error("internal: packed weight image is %zu bytes, kernel expects %zu", have, lds); return NRF_ERR_INVALID_ARG; }
     const int64_t nblocks = ceil_div(p, block_pts_of(split));
     // persistent: 256 CUs x 3 resident 4-wave workgroups (146 VGPRs, 40-46 KB LDS), or x 1 resident 8-wave workgroup with the 80-92 KB split image
     const int64_t cap = split ? 256 : 768;
     const unsigned grid = (unsigned)(nblocks < cap ? nblocks : cap);
-    const half8 *img = reinterpret_cast<const half8 *>(split ? m->d_packed_split : m->d_packed_f16);
+    const half8 *img = (split ? m->d_packed_split : m->d_packed_f16).as<const half8>();
 #define NRF_GO(LM_, SP_, LO_, ...)                                                                                                            \
     do {                                                                                                                                      \
         auto kfn = k_mlp_small_mfma<2, V_KS, NL, NLC, LM_, SP_, LO_, ##__VA_ARGS__>;                                                          \
@@ -827,7 +819,7 @@ static int launch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool sp
 
 static int dispatch_small(const nrf_mlp *m, const SmallInput &in, bool lm, bool split, int64_t p, float *out, int os, hipStream_t st, bool listed = false);
 
-int mlp_small_mfma_available(const nrf_mlp *m) { return m && m->family == MLP_SMALL && m->d_packed_f16 != nullptr && m->d_packed_split != nullptr; }
+int mlp_small_mfma_available(const nrf_mlp *m) { return m && m->family == MLP_SMALL && bool(m->d_packed_f16) && bool(m->d_packed_split); }
 
 // renderer fast path: level-major fp16 features + per-ray fp16 direction features + keep mask -> raw [p,4] (sigma masked).
 // dirs_lo != NULL selects the split-precision kernel (NRF_PREC_F16_SPLIT).
@@ -889,7 +881,7 @@ static int dispatch_small(const nrf_mlp *m, const SmallInput &in_, bool lm, bool
     const auto &d = m->small;
     SmallInput in = in_;
     in.ray_mul = 0; in.ray_shift = 0;
-    in.scales = m->d_scales;
+    in.scales = m->scales();
     if (lm && in.s >= 1) {
         // ray = floor(p / s) for p < 2^31 as (p * M) >> (31 + L), L = ceil(log2 s), M = ceil(2^(31 + L) / s) < 2^32 (Granlund-Montgomery round-up); the kernel takes the
         // high word of the product and shifts by L - 1 (s = 1: ray = p, flagged by a negative shift)

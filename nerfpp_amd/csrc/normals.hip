@@ -190,9 +190,9 @@ template <int F, bool CU>
 int launch_grad_f(const nrf_hash *h, const nrf_mlp *m, const PointSource &ps, int64_t p, const float *wsel, float *sigma, float *grad, hipStream_t st)
 {
     const int nl = m->small.num_layers;
-    const float *w0 = m->d_params + m->layers[0].w_off;
-    const float *w1 = nl == 3 ? m->d_params + m->layers[1].w_off : nullptr;
-    const float *wl = m->d_params + m->layers[nl - 1].w_off;
+    const float *w0 = m->params() + m->layers[0].w_off;
+    const float *w1 = nl == 3 ? m->params() + m->layers[1].w_off : nullptr;
+    const float *wl = m->params() + m->layers[nl - 1].w_off;
     const int mask_keep = m->out_dims == 4 ? 1 : 0;
     // bounded launches: a grid of at most 2^24 blocks per launch
     const int64_t slab = (int64_t)NG_THREADS << 24;

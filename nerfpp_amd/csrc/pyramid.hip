@@ -193,7 +193,7 @@ struct nrf_pyramid {
     std::vector<uint8_t> have;                 // per grid cell of every block
     std::vector<int64_t> cell0;                // first cell of each block in `have`
     int64_t elems = 0;
-    float *d_emb = nullptr;
+    nrf::DevBuf d_emb;                         // float [elems]
 };
 
 int nrf_pyramid_level_geometry(int img_w, int img_h, int clip, float overlap, int zoom, int *out)
@@ -231,7 +231,7 @@ int nrf_pyramid_create(int d, int clip_size, float overlap, int max_zoom_out, in
                   "nrf_pyramid_create: bad argument (D %d, clip %d, overlap %g, max_zoom_out %d, images %d)", d, clip_size, (double)overlap, max_zoom_out, n_images);
     for (int i = 0; i < n_images; i++)
         NRF_CHECK_ARG(wh[2 * i] >= 1 && wh[2 * i + 1] >= 1, "nrf_pyramid_create: view %d has size %d x %d", i, wh[2 * i], wh[2 * i + 1]);
-    nrf_pyramid *p = new nrf_pyramid();
+    std::unique_ptr<nrf_pyramid> p(new nrf_pyramid());
     p->d = d; p->clip = clip_size; p->overlap = overlap; p->max_zoom = max_zoom_out; p->n_images = n_images; p->n_levels = max_zoom_out + 2;
     p->wh.assign(wh, wh + 2 * n_images);
     const int nb = n_images * p->n_levels;
@@ -254,23 +254,15 @@ int nrf_pyramid_create(int d, int clip_size, float overlap, int max_zoom_out, in
     p->have.assign((size_t)cells, 0);
     p->elems = cells * d;
     if (p->elems > 0) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->d_emb), (size_t)p->elems * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(p->d_emb, 0, (size_t)p->elems * sizeof(float));
-        if (e != hipSuccess) {
-            if (p->d_emb) (void)hipFree(p->d_emb);
-            delete p;
-            set_error("nrf_pyramid_create: %s", hipGetErrorString(e));
-            return NRF_ERR_HIP;
-        }
+        NRF_TRY(p->d_emb.resize((size_t)p->elems * sizeof(float)));
+        NRF_HIP(hipMemset(p->d_emb.as<float>(), 0, (size_t)p->elems * sizeof(float)));
     }
-    *out = p;
+    *out = p.release();
     return NRF_OK;
 }
 
 int nrf_pyramid_destroy(nrf_pyramid *p)
 {
-    if (!p) return NRF_OK;
-    if (p->d_emb) NRF_HIP(hipFree(p->d_emb));
     delete p;
     return NRF_OK;
 }
@@ -308,21 +300,16 @@ int nrf_pyramid_set_entries(nrf_pyramid *p, int64_t n, const int32_t *keys, cons
     const int64_t m = (int64_t)mv.size() / 2;
     hipStream_t st = as_stream(stream);
     const size_t src_bytes = align_up((size_t)n * d * sizeof(float), 256), mv_bytes = mv.size() * sizeof(int64_t);
-    char *tmp = nullptr;
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&tmp), src_bytes + mv_bytes));
-    hipError_t e = hipMemcpyAsync(tmp, emb, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp + src_bytes, mv.data(), mv_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_pyramid_scatter, dim3((unsigned)m), dim3(256), 0, st, reinterpret_cast<const float *>(tmp), reinterpret_cast<const int64_t *>(tmp + src_bytes), d,
-                           p->d_emb);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);         // the host arrays and the staging buffer are released before returning
-    (void)hipFree(tmp);
-    if (e != hipSuccess) {
-        set_error("nrf_pyramid_set_entries: %s", hipGetErrorString(e));
-        return NRF_ERR_HIP;
-    }
+    DevBuf staging;
+    NRF_TRY(staging.resize(src_bytes + mv_bytes));
+    char *tmp = staging.as<char>();
+    NRF_HIP(hipMemcpyAsync(tmp, emb, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, st));
+    NRF_HIP(hipMemcpyAsync(tmp + src_bytes, mv.data(), mv_bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pyramid_scatter, dim3((unsigned)m), dim3(256), 0, st, reinterpret_cast<const float *>(tmp), reinterpret_cast<const int64_t *>(tmp + src_bytes), d,
+                       p->d_emb.as<float>());
+    NRF_LAUNCH_CHECK();
+    NRF_HIP(hipStreamSynchronize(st));         // the host arrays and the staging buffer are released before returning
+    staging.reset();
     for (int64_t k = 0; k < n; k++) {
         if (!p->have[(size_t)cell[k]]) {
             p->have[(size_t)cell[k]] = 1;
@@ -354,7 +341,7 @@ int pyr_plan(const nrf_pyramid *p, int img_id, float scale, const char *who, Pyr
         NRF_CHECK_ARG(p->off[b] >= 0 && p->filled[b] == (int64_t)p->nw[b] * p->nh[b],
                       "%s: scale %g needs level %d of image %d, which has %lld of its %d x %d entries", who, (double)scale, zs[k], img_id, (long long)p->filled[b], p->nw[b],
                       p->nh[b]);
-        c->lv[k].emb = p->d_emb + p->off[b];
+        c->lv[k].emb = p->d_emb.as<float>() + p->off[b];
         c->lv[k].nw = p->nw[b]; c->lv[k].nh = p->nh[b]; c->lv[k].win = p->win[b];
     }
     const float zo1 = (float)z1, zo2 = (float)z2;

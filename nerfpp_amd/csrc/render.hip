@@ -25,7 +25,8 @@ struct nrf_renderer {
     int lanes = 0;                // this renderer's lane count; 0: the process-wide default (nrf_set_render_lanes / NRF_RENDER_LANES)
     // non-finite words of the matrix-core precisions (nrf_render_params.overflow_policy): one per chunk of the current call on the device, a pinned host mirror for the
     // synchronous policies and one for the deferred copy, and the event that says the deferred copy has landed
-    mutable uint32_t *d_flags = nullptr, *h_flags = nullptr, *h_deferred = nullptr;      // h_deferred: NRF_DEFERRED_RING x NRF_FLAG_SLOTS words
+    mutable nrf::DevBuf d_flags;                       // uint32_t words
+    mutable nrf::PinnedBuf h_flags, h_deferred;        // h_deferred: NRF_DEFERRED_RING x NRF_FLAG_SLOTS words
     mutable hipEvent_t deferred_ev[32] = {};
     mutable int deferred_slots[32] = {};               // > 0: a deferred copy of that many words is pending in ring entry i
     mutable int deferred_head = 0;                     // ring entry the next deferred copy goes to (entries are filled and looked at in order)
@@ -33,13 +34,12 @@ struct nrf_renderer {
     // where the most recent SINGLE-chunk render of the feature-reusing fast path (CuHashEmbedder mode) left its hash features in the caller's workspace
     // (nrf_renderer_last_features; chunk_loop.h)
     mutable nrf::FeatureView view;
+    // Destruction order is spelled out in this body, not left to the order of the members: the lanes are drained before what their kernels write is freed, and every
+    // pending deferred copy has landed before the pinned words it lands in are released.  The buffers above free themselves after the body has run.
     ~nrf_renderer()
     {
-        chunk_lanes.drop();          // first: the lanes are drained before what their kernels write is freed
+        chunk_lanes.drop();
         for (auto &e : deferred_ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
-        if (d_flags) (void)hipFree(d_flags);
-        if (h_flags) (void)hipHostFree(h_flags);
-        if (h_deferred) (void)hipHostFree(h_deferred);
     }
 };
 constexpr int NRF_FLAG_SLOTS = 4096;        // chunks of one call that have a word of their own (further chunks share them modulo this)
@@ -164,9 +164,9 @@ static int ensure_scales(const nrf_renderer *r, hipStream_t st)
     const nrf_hash *h = r->desc.hash;
     nrf_mlp *m = const_cast<nrf_mlp *>(r->desc.mlp);
     if (!h || !m || m->family != MLP_SMALL || !m->d_group || !h->d_table_rms) return NRF_OK;
-    if (m->d_in_rms_src == h->d_table_rms && m->in_rms_seen == h->table_version) return NRF_OK;
+    if (m->d_in_rms_src == h->d_table_rms.as<float>() && m->in_rms_seen == h->table_version) return NRF_OK;
     NRF_TRY(hash_table_rms_update(const_cast<nrf_hash *>(h), st));
-    m->d_in_rms_src = h->d_table_rms; m->in_rms_seen = h->table_version;
+    m->d_in_rms_src = h->d_table_rms.as<float>(); m->in_rms_seen = h->table_version;
     return mlp_small_rescale(m, st);
 }
 
@@ -362,7 +362,7 @@ int nrf_profile_read(double *ms, int64_t *launches, int reset)
 int nrf_renderer_create(const nrf_renderer_desc *desc, nrf_renderer **out)
 {
     NRF_CHECK_ARG(desc && out && desc->mlp, "nrf_renderer_create: null pointer");
-    nrf_renderer *r = new nrf_renderer();
+    std::unique_ptr<nrf_renderer> r(new nrf_renderer());
     r->desc = *desc;
     r->in_ch = desc->hash ? nrf_hash_output_dims(desc->hash) : 3 + 6 * desc->pe_freqs;
     switch (desc->dirs_encoder) {
@@ -370,20 +370,19 @@ int nrf_renderer_create(const nrf_renderer_desc *desc, nrf_renderer **out)
         case NRF_DIRS_PE: r->in_views = 3 + 6 * desc->dirs_param; break;
         case NRF_DIRS_SH_LIBTORCH:
         case NRF_DIRS_SH_CUDA: r->in_views = desc->dirs_param * desc->dirs_param; break;
-        default: delete r; set_error("nrf_renderer_create: unknown direction encoder %d", desc->dirs_encoder); return NRF_ERR_INVALID_ARG;
+        default: set_error("nrf_renderer_create: unknown direction encoder %d", desc->dirs_encoder); return NRF_ERR_INVALID_ARG;
     }
     const int max_deg = desc->dirs_encoder == NRF_DIRS_SH_LIBTORCH ? 5 : 8;
     if ((desc->dirs_encoder == NRF_DIRS_SH_LIBTORCH || desc->dirs_encoder == NRF_DIRS_SH_CUDA) && (desc->dirs_param < 1 || desc->dirs_param > max_deg)) {
-        delete r; set_error("nrf_renderer_create: SH degree %d outside [1,%d]", desc->dirs_param, max_deg); return NRF_ERR_INVALID_ARG;
+        set_error("nrf_renderer_create: SH degree %d outside [1,%d]", desc->dirs_param, max_deg); return NRF_ERR_INVALID_ARG;
     }
-    if (!desc->hash && (desc->pe_freqs < 1 || desc->pe_freqs > 32)) { delete r; set_error("nrf_renderer_create: pe_freqs %d outside [1,32]", desc->pe_freqs); return NRF_ERR_INVALID_ARG; }
+    if (!desc->hash && (desc->pe_freqs < 1 || desc->pe_freqs > 32)) { set_error("nrf_renderer_create: pe_freqs %d outside [1,32]", desc->pe_freqs); return NRF_ERR_INVALID_ARG; }
     if (r->in_ch + r->in_views != desc->mlp->in_dims) {
         set_error("nrf_renderer_create: encoders produce %d + %d features but the MLP expects %d", r->in_ch, r->in_views, desc->mlp->in_dims);
-        delete r;
         return NRF_ERR_INVALID_ARG;
     }
-    if (desc->mlp->out_dims < 4) { delete r; set_error("nrf_renderer_create: the MLP must output at least rgb + sigma"); return NRF_ERR_INVALID_ARG; }
-    *out = r;
+    if (desc->mlp->out_dims < 4) { set_error("nrf_renderer_create: the MLP must output at least rgb + sigma"); return NRF_ERR_INVALID_ARG; }
+    *out = r.release();
     return NRF_OK;
 }
 
@@ -564,9 +563,9 @@ static int normals_check(const nrf_renderer *r, const RenderParamsX *p, const Re
 static int flag_buffers(const nrf_renderer *r)
 {
     if (r->d_flags) return NRF_OK;
-    NRF_HIP(hipMalloc(reinterpret_cast<void **>(&r->d_flags), NRF_FLAG_SLOTS * sizeof(uint32_t)));
-    NRF_HIP(hipHostMalloc(reinterpret_cast<void **>(&r->h_flags), NRF_FLAG_SLOTS * sizeof(uint32_t), hipHostMallocDefault));
-    NRF_HIP(hipHostMalloc(reinterpret_cast<void **>(&r->h_deferred), (size_t)NRF_DEFERRED_RING * NRF_FLAG_SLOTS * sizeof(uint32_t), hipHostMallocDefault));
+    NRF_TRY(r->d_flags.resize(NRF_FLAG_SLOTS * sizeof(uint32_t)));
+    NRF_TRY(r->h_flags.resize(NRF_FLAG_SLOTS * sizeof(uint32_t)));
+    NRF_TRY(r->h_deferred.resize((size_t)NRF_DEFERRED_RING * NRF_FLAG_SLOTS * sizeof(uint32_t)));
     for (auto &e : r->deferred_ev) NRF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return NRF_OK;
 }
@@ -581,7 +580,7 @@ static int take_deferred(const nrf_renderer *r, bool wait, const char *who, int 
         if (r->deferred_slots[e] > 0) {
             if (wait) NRF_HIP(hipEventSynchronize(r->deferred_ev[e]));
             else if (hipEventQuery(r->deferred_ev[e]) != hipSuccess) break;                            // later entries were recorded later
-            for (int i = 0; i < r->deferred_slots[e]; i++) bad += r->h_deferred[(size_t)e * NRF_FLAG_SLOTS + i] != 0;
+            for (int i = 0; i < r->deferred_slots[e]; i++) bad += r->h_deferred.as<uint32_t>()[(size_t)e * NRF_FLAG_SLOTS + i] != 0;
             r->deferred_slots[e] = 0;
         }
         if (only_entry >= 0) break;
@@ -607,16 +606,16 @@ static int settle_flags(const nrf_renderer *r, const nrf_render_params *p, int s
     if (pol == NRF_OVERFLOW_DEFERRED) {
         const int e = r->deferred_head;
         if (r->deferred_slots[e]) NRF_TRY(take_deferred(r, true, who, e));      // the ring is full: the copy of NRF_DEFERRED_RING calls ago (the host waits only when it runs that far ahead)
-        NRF_HIP(hipMemcpyAsync(r->h_deferred + (size_t)e * NRF_FLAG_SLOTS, r->d_flags, (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        NRF_HIP(hipMemcpyAsync(r->h_deferred.as<uint32_t>() + (size_t)e * NRF_FLAG_SLOTS, r->d_flags.as<uint32_t>(), (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         NRF_HIP(hipEventRecord(r->deferred_ev[e], st));
         r->deferred_slots[e] = slots;
         r->deferred_head = (e + 1) % NRF_DEFERRED_RING;
         return NRF_OK;
     }
-    NRF_HIP(hipMemcpyAsync(r->h_flags, r->d_flags, (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    NRF_HIP(hipMemcpyAsync(r->h_flags.as<uint32_t>(), r->d_flags.as<uint32_t>(), (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     NRF_HIP(hipStreamSynchronize(st));
     int bad = 0;
-    for (int i = 0; i < slots; i++) bad += r->h_flags[i] != 0;
+    for (int i = 0; i < slots; i++) bad += r->h_flags.as<uint32_t>()[i] != 0;
     if (!bad) return NRF_OK;
     r->flagged_chunks += bad;
     if (pol == NRF_OVERFLOW_ERROR) {
@@ -625,7 +624,7 @@ static int settle_flags(const nrf_renderer *r, const nrf_render_params *p, int s
         return NRF_ERR_NONFINITE;
     }
     (void)chunk_of;
-    for (int i = 0; i < slots; i++) if (r->h_flags[i]) { NRF_TRY(rerender(i)); }
+    for (int i = 0; i < slots; i++) if (r->h_flags.as<uint32_t>()[i]) { NRF_TRY(rerender(i)); }
     return NRF_OK;
 }
 
@@ -636,12 +635,11 @@ static int rerender_f32(const nrf_renderer *r, const float *d_rays, int ray_stri
     RenderParamsX q = *p;
     q.precision = NRF_PREC_F32;
     const size_t need = rays_ws_bytes(r, n, &q, q.normals);
-    void *ws = d_workspace; size_t wsb = workspace_bytes; void *tmp = nullptr;
-    if (need > workspace_bytes) { NRF_HIP(scratch_take(&tmp, need, st)); ws = tmp; wsb = need; }
-    const int rc = render_rays_impl(r, d_rays, ray_stride, n, &q, d_t, d_u, out, ws, wsb, st, nullptr);
-    if (tmp) (void)scratch_give(tmp, st);
-    if (rc == NRF_OK) r->rerendered_chunks++;
-    return rc;
+    void *ws = d_workspace; size_t wsb = workspace_bytes; Scratch tmp;
+    if (need > workspace_bytes) { NRF_TRY(tmp.take(need, st)); ws = tmp.as<void>(); wsb = need; }
+    NRF_TRY(render_rays_impl(r, d_rays, ray_stride, n, &q, d_t, d_u, out, ws, wsb, st, nullptr));
+    r->rerendered_chunks++;
+    return NRF_OK;
 }
 
 }  // namespace nrf
@@ -668,8 +666,8 @@ static int render_rays_entry(const nrf_renderer *r, const float *d_rays, int ray
     hipStream_t st = as_stream(stream);
     NRF_TRY(flag_buffers(r));
     NRF_TRY(take_deferred(r, false, "nrf_render_rays"));
-    NRF_HIP(hipMemsetAsync(r->d_flags, 0, sizeof(uint32_t), st));
-    NRF_TRY(render_rays_impl(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, stream, r->d_flags));
+    NRF_HIP(hipMemsetAsync(r->d_flags.as<uint32_t>(), 0, sizeof(uint32_t), st));
+    NRF_TRY(render_rays_impl(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, stream, r->d_flags.as<uint32_t>()));
     return settle_flags(r, p, 1, st, "nrf_render_rays", [](int) {}, [&](int) { return rerender_f32(r, d_rays, ray_stride, n, p, d_t, d_u, out, d_workspace, workspace_bytes, st); });
 }
 
@@ -978,11 +976,11 @@ static int batchify_run(const nrf_renderer *r, const float *d_rays, int ray_stri
     if (det) {
         NRF_TRY(flag_buffers(r));
         NRF_TRY(take_deferred(r, false, "nrf_batchify_rays"));
-        NRF_HIP(hipMemsetAsync(r->d_flags, 0, NRF_FLAG_SLOTS * sizeof(uint32_t), as_stream(stream)));
+        NRF_HIP(hipMemsetAsync(r->d_flags.as<uint32_t>(), 0, NRF_FLAG_SLOTS * sizeof(uint32_t), as_stream(stream)));
     }
     struct ChunkRec { int64_t first, count; };
     std::vector<ChunkRec> done_chunks;
-    auto flag_of = [&](size_t idx) -> uint32_t * { return det ? r->d_flags + (idx % NRF_FLAG_SLOTS) : nullptr; };
+    auto flag_of = [&](size_t idx) -> uint32_t * { return det ? r->d_flags.as<uint32_t>() + (idx % NRF_FLAG_SLOTS) : nullptr; };
     // the policy, once every chunk has been issued and the lanes have joined `stream` (nrf_render_params.overflow_policy)
     auto settle = [&]() -> int {
         if (!det || done_chunks.empty()) return NRF_OK;

@@ -18,7 +18,12 @@ namespace {
 struct Block { void *p; size_t size; int device; hipStream_t st; bool busy; };
 std::mutex g_mu;
 std::vector<Block> g_blocks;
+std::atomic<int64_t> g_device_bytes{0};
+hipError_t block_alloc(void **p, size_t size) { const hipError_t e = hipMalloc(p, size); if (e == hipSuccess) device_bytes_add((int64_t)size); return e; }
+void block_free(const Block &b) { (void)hipFree(b.p); device_bytes_add(-(int64_t)b.size); }
 }  // namespace
+
+void device_bytes_add(int64_t delta) { g_device_bytes.fetch_add(delta, std::memory_order_relaxed); }
 
 hipError_t scratch_take(void **out, size_t bytes, hipStream_t st)
 {
@@ -35,17 +40,17 @@ hipError_t scratch_take(void **out, size_t bytes, hipStream_t st)
     if (best && best->size <= 4 * bytes + ((size_t)1 << 20)) { best->busy = true; *out = best->p; return hipSuccess; }          // (not a 1 GB block for 16 bytes)
     const size_t size = (bytes + ((size_t)1 << 16) - 1) & ~(((size_t)1 << 16) - 1);
     void *p = nullptr;
-    e = hipMalloc(&p, size);
+    e = block_alloc(&p, size);
     if (e != hipSuccess) {
         // out of memory: give the idle blocks of this device back and try once more.  (The device is drained as a whole: a block's stream may have been destroyed since
         // -- its handle must not be touched again)
         (void)hipDeviceSynchronize();
         for (size_t i = 0; i < g_blocks.size();) {
-            if (!g_blocks[i].busy && g_blocks[i].device == dev) { (void)hipFree(g_blocks[i].p); g_blocks.erase(g_blocks.begin() + (long)i); }
+            if (!g_blocks[i].busy && g_blocks[i].device == dev) { block_free(g_blocks[i]); g_blocks.erase(g_blocks.begin() + (long)i); }
             else i++;
         }
         (void)hipGetLastError();
-        e = hipMalloc(&p, size);
+        e = block_alloc(&p, size);
         if (e != hipSuccess) return e;
     }
     g_blocks.push_back(Block{p, size, dev, st, true});
@@ -72,7 +77,7 @@ size_t scratch_trim()
         if (!g_blocks[i].busy) {
             (void)hipSetDevice(g_blocks[i].device);
             if (synced != g_blocks[i].device) { (void)hipDeviceSynchronize(); synced = g_blocks[i].device; }          // (never the block's stream handle: it may be gone)
-            (void)hipFree(g_blocks[i].p);
+            block_free(g_blocks[i]);
             freed += g_blocks[i].size;
             g_blocks.erase(g_blocks.begin() + (long)i);
         } else i++;
@@ -86,3 +91,6 @@ size_t scratch_trim()
 /* Gives the library's idle scratch blocks back to the driver (drains the device first); returns the bytes freed.  Optional: the blocks are reused
  * from call to call and amount to the peak of one stream's short-lived buffers. */
 extern "C" NRF_API size_t nrf_scratch_trim(void) { return nrf::scratch_trim(); }
+
+/* Bytes of device memory the library holds right now: what its handles own plus its scratch blocks, idle ones included (pinned host memory is not counted). */
+extern "C" NRF_API int64_t nrf_device_bytes_in_use(void) { return nrf::g_device_bytes.load(std::memory_order_relaxed); }

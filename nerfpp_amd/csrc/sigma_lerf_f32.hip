@@ -178,12 +178,7 @@ int mlp_lerf_pack_sigma_f32(nrf_mlp *m, const std::vector<float> &hp)
                 const int i = lane & 31, row = i == 0 ? 32 : i, k = 2 * (4 * g + j) + (lane >> 5);       // output row of cat[sigma, geo0..31]: tile row 0 <- geo31
                 img.push_back(w1[(size_t)row * lerf::HID + k]);
             }
-    const size_t bytes = img.size() * sizeof(float);
-    if (m->d_packed_sigma_f32 && m->packed_sigma_f32_bytes != bytes) { (void)hipFree(m->d_packed_sigma_f32); m->d_packed_sigma_f32 = nullptr; }
-    if (!m->d_packed_sigma_f32) NRF_HIP(hipMalloc(&m->d_packed_sigma_f32, bytes));
-    m->packed_sigma_f32_bytes = bytes;
-    NRF_HIP(hipMemcpy(m->d_packed_sigma_f32, img.data(), bytes, hipMemcpyHostToDevice));
-    return NRF_OK;
+    return m->d_packed_sigma_f32.upload(img.data(), img.size() * sizeof(float));
 }
 
 // the same image from the parameter blob on the device (one thread per element; the index arithmetic of the host loops above)
@@ -212,8 +207,8 @@ static_assert(lsig::W0_F4 * 4 == 8 * 16 * 64 * 4 && lsig::W1G_F4 * 4 == 64 * 64 
 int mlp_lerf_pack_sigma_f32_device(nrf_mlp *m, hipStream_t st)
 {
     const size_t n = (size_t)lsig::W0_F4 * 4 + 256 + (size_t)lsig::W1G_F4 * 4;
-    if (!lerf_sigma_f32_supported(m->small) || !m->d_packed_sigma_f32 || m->packed_sigma_f32_bytes != n * sizeof(float)) return NRF_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_lsig_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)m->d_params, reinterpret_cast<float *>(m->d_packed_sigma_f32));
+    if (!lerf_sigma_f32_supported(m->small) || !m->d_packed_sigma_f32 || m->d_packed_sigma_f32.bytes() != n * sizeof(float)) return NRF_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_lsig_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->params(), m->d_packed_sigma_f32.as<float>());
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
@@ -224,7 +219,7 @@ using namespace nrf;
 
 extern "C" {
 
-int nrf_lerf_sigma_exact_available(const nrf_mlp *m) { return m && m->family == MLP_LERF && m->d_packed_sigma_f32 != nullptr; }
+int nrf_lerf_sigma_exact_available(const nrf_mlp *m) { return m && m->family == MLP_LERF && bool(m->d_packed_sigma_f32); }
 
 int nrf_lerf_sigma_exact_lm_strided(const nrf_mlp *m, const void *d_feats_lm, int64_t pstride, const uint8_t *d_keep, int64_t p, float *d_sigma, void *d_geo,
                                     int64_t geo_stride, void *stream)
@@ -243,7 +238,7 @@ int nrf_lerf_sigma_exact_lm_strided(const nrf_mlp *m, const void *d_feats_lm, in
     NRF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(lsig::k_lerf_sigma_f32<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lsig::LDS_BYTES));
     const int64_t nblocks = ceil_div(p, lsig::BLOCK_PTS);
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);          // persistent: one 8-wave workgroup per CU
-    const float *img = reinterpret_cast<const float *>(m->d_packed_sigma_f32);
+    const float *img = m->d_packed_sigma_f32.as<const float>();
     const _Float16 *x = reinterpret_cast<const _Float16 *>(d_feats_lm);
     if (d_geo) hipLaunchKernelGGL((lsig::k_lerf_sigma_f32<true>), dim3(grid), dim3(64 * lsig::WAVES), lsig::LDS_BYTES, st, p, x, pstride, d_keep, img, d_sigma,
                                   reinterpret_cast<half8 *>(d_geo), geo_stride);

@@ -474,15 +474,10 @@ int mlp_nerf_pack_sigma_f32(nrf_mlp *m, const std::vector<float> &hp)
     std::vector<float> img;
     size_t f16_at = 0, f16_floats = 0;
     if (!nerf_sigma_image_host(d, hp.data(), merged.data(), merged_b.data(), img, f16_at, f16_floats)) return NRF_ERR_INVALID_ARG;
-    const size_t bytes = img.size() * sizeof(float);
-    if (m->d_packed_sigma_f32 && m->packed_sigma_f32_bytes != bytes) { (void)hipFree(m->d_packed_sigma_f32); m->d_packed_sigma_f32 = nullptr; }
-    if (!m->d_packed_sigma_f32) NRF_HIP(hipMalloc(&m->d_packed_sigma_f32, bytes));
-    m->packed_sigma_f32_bytes = bytes;
-    NRF_HIP(hipMemcpy(m->d_packed_sigma_f32, img.data(), bytes, hipMemcpyHostToDevice));
-    return NRF_OK;
+    return m->d_packed_sigma_f32.upload(img.data(), img.size() * sizeof(float));
 }
 
-int mlp_nerf_sigma_f32_available(const nrf_mlp *m) { return m && m->family == MLP_NERF && m->d_packed_sigma_f32 != nullptr; }
+int mlp_nerf_sigma_f32_available(const nrf_mlp *m) { return m && m->family == MLP_NERF && bool(m->d_packed_sigma_f32); }
 
 // The classic network's coarse pass: raw [p, 4] = (rgb, sigma) with sigma bit-identical to NRF_PREC_F32 (exact fp32 on the matrix cores) and rgb from the exact h8 in
 // split precision.  Points explicit (pts [p, 3]) or formed from (rays, z) as o + d z; dirs / dirs_lo: PE(4) of the view direction as fp16 (hi, lo) rows [n, 32]
@@ -497,7 +492,7 @@ int mlp_nerf_exact_coarse(const nrf_mlp *m, const float *pts, const float *rays,
     const int64_t nblocks = ceil_div(p, nsig::BLK);
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);          // persistent: one 4-wave workgroup per CU
     hipLaunchKernelGGL(nsig::k_sigma_nerf_f32, dim3(grid), dim3(64 * nsig::NW), nsig::LDS_BYTES, st, p, pts, rays, ray_stride, z, s,
-                       reinterpret_cast<const _Float16 *>(dirs), reinterpret_cast<const _Float16 *>(dirs_lo), reinterpret_cast<const float *>(m->d_packed_sigma_f32), raw);
+                       reinterpret_cast<const _Float16 *>(dirs), reinterpret_cast<const _Float16 *>(dirs_lo), m->d_packed_sigma_f32.as<const float>(), raw);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

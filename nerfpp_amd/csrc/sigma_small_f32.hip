@@ -262,15 +262,13 @@ int mlp_small_pack_sigma_f32(nrf_mlp *m, const std::vector<float> &hp)
     std::vector<uint8_t> head, tail;
     if (!mlp_small_sigma_image_host(m->small, hp, head, tail)) return NRF_OK;
     const size_t bytes = head.size() + tail.size();
-    if (m->d_packed_sigma_f32 && m->packed_sigma_f32_bytes != bytes) { (void)hipFree(m->d_packed_sigma_f32); m->d_packed_sigma_f32 = nullptr; }
-    if (!m->d_packed_sigma_f32) NRF_HIP(hipMalloc(&m->d_packed_sigma_f32, bytes));
-    m->packed_sigma_f32_bytes = bytes;
-    NRF_HIP(hipMemcpy(m->d_packed_sigma_f32, head.data(), head.size(), hipMemcpyHostToDevice));
-    NRF_HIP(hipMemcpy(static_cast<char *>(m->d_packed_sigma_f32) + head.size(), tail.data(), tail.size(), hipMemcpyHostToDevice));
+    NRF_TRY(m->d_packed_sigma_f32.resize(bytes));
+    NRF_HIP(hipMemcpy(m->d_packed_sigma_f32.as<char>(), head.data(), head.size(), hipMemcpyHostToDevice));
+    NRF_HIP(hipMemcpy(m->d_packed_sigma_f32.as<char>() + head.size(), tail.data(), tail.size(), hipMemcpyHostToDevice));
     return NRF_OK;
 }
 
-int mlp_small_sigma_f32_available(const nrf_mlp *m) { return m && m->family == MLP_SMALL && m->d_packed_sigma_f32 != nullptr; }
+int mlp_small_sigma_f32_available(const nrf_mlp *m) { return m && m->family == MLP_SMALL && bool(m->d_packed_sigma_f32); }
 
 // sigma [p] = keep ? NeRFSmall sigma-net output 0 : 0, bit-identical to NRF_PREC_F32.  feats: level-major [16][pstride] half2, or float2 when f32_in.
 // geo != NULL: also the (sigma, geo_feat) operand fragments of the colour net, planes [hi | lo][geo_stride columns][2 lane halves] of 16 bytes, column = point index
@@ -282,7 +280,7 @@ int mlp_small_sigma_f32_lm(const nrf_mlp *m, const void *feats, int f32_in, int6
     ProfScope prof(NRF_PROF_SIGMA, st);
     const int64_t nblocks = ceil_div(p, SIG_BLOCK_PTS);
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);          // persistent: one 8-wave workgroup per CU
-    const float *img = reinterpret_cast<const float *>(m->d_packed_sigma_f32);
+    const float *img = m->d_packed_sigma_f32.as<const float>();
     const int nl = m->small.num_layers;
     if (geo && (m->small.geo_feat_dim > 15 || m->small.hidden_dim != 64)) { set_error("internal: geo hand-over outside the built NeRFSmall family"); return NRF_ERR_UNSUPPORTED; }
     half8 *g = static_cast<half8 *>(geo);
@@ -291,10 +289,10 @@ int mlp_small_sigma_f32_lm(const nrf_mlp *m, const void *feats, int f32_in, int6
     do {                                                                                                                                                             \
         constexpr bool A_ = !F_;                                                                                                                                     \
         if (A_ && a32) {                                                                                                                                             \
-            if (g) hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, true, A_>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->d_scales); \
-            else hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, false, A_>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->d_scales); \
-        } else if (g) hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, true, false>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->d_scales); \
-        else hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, false, false>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->d_scales);   \
+            if (g) hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, true, A_>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->scales()); \
+            else hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, false, A_>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->scales()); \
+        } else if (g) hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, true, false>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->scales()); \
+        else hipLaunchKernelGGL((k_sigma_small_f32<NL_, F_, false, false>), dim3(grid), dim3(64 * SIG_WAVES), 0, st, p, feats, pstride, keep, img, sigma, g, geo_stride, m->scales());   \
     } while (0)
     if (nl == 3) { if (f32_in) NRF_GO(3, true); else NRF_GO(3, false); }
     else { if (f32_in) NRF_GO(2, true); else NRF_GO(2, false); }

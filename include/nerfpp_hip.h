@@ -595,6 +595,46 @@ NRF_API int nrf_lattice_components(const uint8_t *d_mask, int nx, int ny, int nz
                                    size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depth fusion (tsdf.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* A truncated signed distance volume (TSDF) on the lattice of nrf_density_grid (P = bmin + (float)i * step, step = (bmax - bmin) / (float)(n - 1) per axis, x fastest,
+ * nx, ny, nz >= 2; bbox[6] on the host), fused from rendered depth: d_tsdf [nz][ny][nx] fp32 (initial value 1), d_weight [nz][ny][nx] fp32 (initial value 0) and an
+ * optional d_color [4][nz][ny][nx] (planes r, g, b and the colour weight cw; initial value 0).  Its level 0 is the surface (outside positive): -tsdf is a lattice for
+ * nrf_isosurface_*.  None of the three entries takes a workspace, synchronises the stream or uses atomics; two runs give the same bits.
+ * One observation: d_depth [h,w] (the ray parameter of nrf_get_rays' directions, camera-space z = -1: the depth map of a non-NDC render), d_acc [h,w] or NULL, d_rgb
+ * [h,w,3] or NULL, the K and c2w the view was rendered with. */
+typedef struct {
+    const float *d_depth;
+    const float *d_acc;
+    const float *d_rgb;
+    int h, w;
+    float K[9];
+    float c2w[12];
+} nrf_tsdf_view;
+/* nrf_tsdf_integrate: every lattice point takes the n_views views (a HOST array) in array order; each source-level fp32 operation below is rounded once.
+ *   1. q = P - t (t = column 3 of c2w); xc = (R00*qx + R10*qy) + R20*qz, yc and zc the same with columns 1 and 2 of R; zd = -zc; the view is skipped unless zd > 0.
+ *   2. u = fx*(xc/zd) + cx, v = cy - fy*(yc/zd) (the inverse of nrf_get_rays); fu = floorf(u + 0.5f), fv = floorf(v + 0.5f); skipped unless 0 <= fu < w and
+ *      0 <= fv < h, compared as floats (NaN and huge values skip); the pixel is ((int)fu, (int)fv).
+ *   3. d = depth[pixel].  With d_acc, a = acc[pixel]: a >= acc_min: d = d / a (the expected depth of what the ray hit); else a < acc_min and carve: a background
+ *      observation, s = 1, no colour, on at step 5; otherwise (NaN a; a < acc_min without carve) skipped.  Skipped unless d is finite and d > 0.
+ *   4. sdf = d - zd; skipped if sdf < -trunc; s = fminf(1, sdf / trunc).
+ *   5. Wn = W + 1; D = (D*W + s) / Wn; W = fminf(Wn, max_weight).
+ *   6. With d_color and d_rgb, after step 4 and where fabsf(sdf) <= trunc: cn = cw + 1; c = (c*cw + rgb) / cn per channel; cw = fminf(cn, max_weight).
+ * Any n_views (0: NRF_OK, nothing done); up to 16 views per launch, their cameras in the kernel arguments: no device allocation, no copy, and one call over V views gives
+ * the bits of V calls of one view each.  Per launch the volume moves 8 B per lattice point (40 B with d_color).  NRF_ERR_INVALID_ARG, nothing launched: a null
+ * d_tsdf / d_weight / bbox / d_depth, n < 2 on an axis, h or w < 1, trunc or acc_min not finite or <= 0, max_weight < 1 (or NaN), a box with max <= min.
+ * nrf_tsdf_observed: d_ok[i] = 1 iff weight > 0 at all 27 lattice points r + {-1,0,1}^3 (indices clamped into the lattice), r = (int)floorf(g + 0.5f),
+ *   g = (pt - bmin) / step per axis, of d_pts [p,3]; a non-finite coordinate gives 0.  (floorf(g + 0.5f) is clamped to [-1, n] before the conversion, which changes
+ *   no result.)  The band a surface was seen in: the zero level between the observed band behind a surface and the never-observed interior is no surface.
+ * nrf_tsdf_sample_color: d_rgb [p,3] = the colour volume at d_pts, trilinear over the corners that hold a colour: i0 = clamp((int)floorf(g), 0, n-2) (clamped as a
+ *   float, NaN as 0), f = fminf(fmaxf(g - (float)i0, 0), 1) per axis; corner weight (wx*wy)*wz, each factor f or 1 - f, corners in the order bit 0 = x, bit 1 = y,
+ *   bit 2 = z; den = sum of the weights, num = sum of weight * c, both over the corners with cw > 0 and added in that order from 0; num / den, or 0 where den == 0. */
+NRF_API int nrf_tsdf_integrate(float *d_tsdf, float *d_weight, float *d_color, int nx, int ny, int nz, const float *bbox, const nrf_tsdf_view *views, int n_views,
+                               float trunc, float acc_min, float max_weight, int carve, void *stream);
+NRF_API int nrf_tsdf_observed(const float *d_weight, int nx, int ny, int nz, const float *bbox, const float *d_pts, int64_t p, uint8_t *d_ok, void *stream);
+NRF_API int nrf_tsdf_sample_color(const float *d_color, int nx, int ny, int nz, const float *bbox, const float *d_pts, int64_t p, float *d_rgb, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Image metrics (image_metrics.hip; the reference has only the training loop's PSNR, NeRFExecutor.h:893)
  * ------------------------------------------------------------------------------------------- */
 /* How good a frame is, on the device and in fp64 (in fp32 the variances E[x^2] - mu^2 cancel against c2: a flat pair 0.25 / 0.75 is off by 1.19e-4).  Images are

@@ -179,6 +179,9 @@ _ABI = """
     nrf_mesh_components(pllpppzp)
     nrf_lattice_components_workspace_bytes(iii)->z
     nrf_lattice_components(piiiipppzp)
+    nrf_tsdf_integrate(pppiiippifffip)
+    nrf_tsdf_observed(piiipplpp)
+    nrf_tsdf_sample_color(piiipplpp)
     nrf_ssim_window(p)
     nrf_ssim_workspace_bytes(iiii)->z
     nrf_ssim(ppiiiidpppzp)

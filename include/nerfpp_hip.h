@@ -635,6 +635,46 @@ NRF_API int nrf_tsdf_observed(const float *d_weight, int nx, int ny, int nz, con
 NRF_API int nrf_tsdf_sample_color(const float *d_color, int nx, int ny, int nz, const float *bbox, const float *d_pts, int64_t p, float *d_rgb, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mesh rasteriser (raster.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* A deterministic z-buffer of a triangle list seen through the camera of nrf_get_rays (K [9] and c2w [12] on the HOST, as there): d_verts [V,3] fp32, d_faces [F,3]
+ * int32 (counter-clockwise seen from outside), d_attr [V,n_attr] fp32 or NULL -> d_depth [h,w] (required), d_face [h,w] int32 or NULL, d_bary [h,w,3] or NULL,
+ * d_out_attr [h,w,n_attr], d_stats [4] uint32 or NULL (ADDED to; the caller zeroes it).  0 <= F <= 2^31 - 2, 0 <= V < 2^31, 1 <= h, w <= NRF_RASTER_GUARD.
+ * The call synchronises nothing and allocates nothing; two runs give the same bits, and any permutation of the face list gives the same depth bits.
+ * Each source-level fp32 operation below is rounded once; the edge functions are int64 and exact.
+ *   1. Per vertex: q = P - t (t = column 3 of c2w); xc = (R00*qx + R10*qy) + R20*qz, yc and zc the same with columns 1 and 2 of R; zd = -zc; u = fx*(xc/zd) + cx,
+ *      v = cy - fy*(yc/zd) (steps 1-2 of nrf_tsdf_integrate without the pixel rounding).  Pixel centres sit at integer (u, v); zd is the ray parameter of
+ *      nrf_get_rays' directions, the unit of DepthMap / AccMap.
+ *   2. A face is CLIPPED (skipped whole; no polygon clipping) unless all three vertices have zd > near_z, fabsf(u) <= GUARD and fabsf(v) <= GUARD, compared as floats
+ *      (NaN and +-inf clip).  A face with an index outside [0, V) is BAD: skipped before anything of it is dereferenced.
+ *   3. X = (int)rintf(u * 256.0f), Y = (int)rintf(v * 256.0f) (round half to even).
+ *   4. In int64, E_ab(p) = (bx-ax)*(py-ay) - (by-ay)*(px-ax); e0 = E_12(p), e1 = E_20(p), e2 = E_01(p) at the pixel centre p = (256 i, 256 j); A = E_01(v2).
+ *      A == 0 is DEGENERATE: skipped.  cull == 1 draws front faces only: v grows downward, so a face that is counter-clockwise seen from outside has A < 0, and a
+ *      face with A > 0 is CULLED.  cull == 0 draws both.
+ *   5. s = sign(A).  Pixel (i, j) is inside iff for each edge k: s*e_k > 0, or s*e_k == 0 and the edge is top-left.  Edge k runs v1->v2, v2->v0, v0->v1 for
+ *      k = 0, 1, 2; with (dx, dy) = s*(b - a) it is top-left iff dy < 0 || (dy == 0 && dx > 0).  Pixels visited: columns ceil(minX/256) .. floor(maxX/256) clamped
+ *      to [0, w-1], rows likewise with Y and h.
+ *   6. b_k = (float)((double)(s*e_k) / (double)(s*A)); r_k = 1.0f / zd_k; p_k = b_k * r_k; S = (p0 + p1) + p2; depth = 1.0f / S (perspective-correct).
+ *   7. key = ((uint64)float_bits(depth) << 32) | face index; the pixel keeps the minimum key: the nearest face, and at an exact depth tie the lowest index.
+ *   8. Resolve, a pass of its own: a hit pixel takes depth and face from the key, b_k recomputed by the same expressions, and
+ *      attr_c = ((p0*a0c + p1*a1c) + p2*a2c) / S; a pixel no face covers gets depth 0, face -1, bary 0, attributes 0.
+ *   9. d_stats += {drawn, clipped, degenerate or culled, bad index}: the four counts of one call sum to F.
+ * A face whose clamped bounding box holds more than NRF_RASTER_WIDE_PIXELS pixels is rasterised by a whole workgroup (same arithmetic, same bits).
+ * NRF_ERR_INVALID_ARG, message starting "nrf_raster_mesh", nothing launched or written: a null d_depth; a null d_verts, d_faces, K or c2w with F > 0; h or w < 1 or
+ * > GUARD; n_attr < 0 or > NRF_RASTER_MAX_ATTR; n_attr > 0 with a null d_attr or d_out_attr; near_z not finite or <= 0; cull not 0 or 1; F or V out of range; a
+ * workspace that is null or smaller than nrf_raster_workspace_bytes (0 for a shape the call refuses).  F == 0 is valid and writes the background. */
+#define NRF_RASTER_SUBPIXEL 256          /* fixed-point steps per pixel */
+#define NRF_RASTER_GUARD 16384           /* |u|, |v| beyond this clip the face; also the largest h or w */
+#define NRF_RASTER_MAX_ATTR 8
+#ifndef NRF_RASTER_WIDE_PIXELS           /* tuning builds set another (make EXTRA=-DNRF_RASTER_WIDE_PIXELS=n); no result depends on it */
+#define NRF_RASTER_WIDE_PIXELS 256       /* bounding-box pixel count above which a face goes to the wide kernel */
+#endif
+NRF_API size_t nrf_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int h, int w);
+NRF_API int nrf_raster_mesh(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *d_attr, int n_attr, int h, int w,
+                            const float *K, const float *c2w, float near_z, int cull, float *d_depth, int32_t *d_face, float *d_bary, float *d_out_attr,
+                            uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Image metrics (image_metrics.hip; the reference has only the training loop's PSNR, NeRFExecutor.h:893)
  * ------------------------------------------------------------------------------------------- */
 /* How good a frame is, on the device and in fp64 (in fp32 the variances E[x^2] - mu^2 cancel against c2: a flat pair 0.25 / 0.75 is off by 1.19e-4).  Images are

@@ -182,6 +182,8 @@ _ABI = """
     nrf_tsdf_integrate(pppiiippifffip)
     nrf_tsdf_observed(piiipplpp)
     nrf_tsdf_sample_color(piiipplpp)
+    nrf_raster_workspace_bytes(llii)->z
+    nrf_raster_mesh(plplpiiippfippppppzp)
     nrf_ssim_window(p)
     nrf_ssim_workspace_bytes(iiii)->z
     nrf_ssim(ppiiiidpppzp)

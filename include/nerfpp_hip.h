@@ -675,6 +675,81 @@ NRF_API int nrf_raster_mesh(const float *d_verts, int64_t n_verts, const int32_t
                             uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Geometry in space (geometry.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* Comparing two surfaces in 3D: points drawn on a triangle list in proportion to area, the nearest point of one set for every point of another, and the sums that
+ * Chamfer distance, Hausdorff distance and precision / recall at a distance are made of.  Each source-level fp32 operation below is rounded once; sqrtf and / are
+ * correctly rounded.  Every entry takes a caller-owned workspace sized by its *_workspace_bytes twin (0 for a shape the entry refuses) and allocates nothing.  Only
+ * nrf_mesh_sample_count synchronises the stream.  Refusals -- NRF_ERR_INVALID_ARG, or NRF_ERR_WORKSPACE for a workspace below the twin's size, the message starting
+ * with the entry's name -- come before any launch or write.  Two runs of any entry give the same bits.
+ *
+ * Surface sampling: d_verts [V,3] fp32, d_faces [F,3] int32, 0 <= V, F < 2^31; density (points per unit area) finite and >= 0; a count call, then an emit call over
+ * the same mesh, seed and workspace.
+ *   1. Per face f: e1 = v1 - v0, e2 = v2 - v0 per component; c = e1 x e2 with every component fl(fl(a*b) - fl(c*d)): cx = e1y*e2z - e1z*e2y, cy = e1z*e2x - e1x*e2z,
+ *      cz = e1x*e2y - e1y*e2x; s = (cx*cx + cy*cy) + cz*cz; area = 0.5f * sqrtf(s).
+ *   2. a = area * density; n_f = (int)floorf(a) + (nrf_rng_uniform(seed, NRF_RNG_SURFACE_COUNT, f) < a - floorf(a)): the expectation of n_f is a.
+ *   3. A face with an index outside [0, V) is BAD: n_f = 0, nothing of it is dereferenced.  A face with a non-finite vertex coordinate or a non-finite area is
+ *      NON-FINITE: n_f = 0.  Neither enters the area.  n_f > NRF_SAMPLE_MAX_PER_FACE is CLAMPED to that constant.  d_stats [3] uint32 or NULL (ADDED to; the caller
+ *      zeroes it) += {bad, non-finite, clamped}.
+ *   4. The first point of face f is the exclusive integer prefix sum of n_f over the faces in order; *n_points is the total.  *total_area is the fp64 sum of
+ *      (double)area over the faces that are neither bad nor non-finite, added in this order: blocks of 256 consecutive faces; within a block the 64 values of each of
+ *      the 4 waves by the butterfly v += v[lane ^ o], o = 32, 16, 8, 4, 2, 1, then ((w0 + w1) + w2) + w3; the block sums b_k: thread t of 256 adds k = t, t + 256, ...
+ *      in ascending order from 0.0, then s[t] += s[t + o] for t < o, o = 128, 64, ..., 1.  No atomics.
+ *   5. nrf_mesh_sample_count returns both values to the host (the one synchronisation).  A total of 2^31 or more: NRF_ERR_INVALID_ARG, the message says so (the
+ *      area is still returned).  density == 0 is valid: the area and zero points.  F == 0: zero points, area 0.
+ *   6. nrf_mesh_sample_emit, for point p (global index) of face f: u = nrf_rng_uniform(seed, NRF_RNG_SURFACE_UV, 2p), v = nrf_rng_uniform(seed, NRF_RNG_SURFACE_UV,
+ *      2p + 1); if u + v > 1.0f then u = 1.0f - u, v = 1.0f - v; P = (v0 + u*e1) + v*e2 per component.  d_points [n,3]; d_face [n] int32 or NULL gets f; d_uv [n,2] or
+ *      NULL gets (u, v) after the reflection: P is the barycentric combination (1-u-v, u, v) of the face's corners.  n_points is the count call's; the kernel writes no
+ *      point beyond it nor beyond the count call's own total (kept in the workspace), so a wrong n_points cannot overrun a buffer.
+ *
+ * Nearest points: d_query [nq,3], d_target [nt,3] fp32, 0 <= nq, nt < 2^31 -> d_dist2 [nq] fp32, d_index [nq] int32.
+ *   CONTRACT.  d2(q, j) = (dx*dx + dy*dy) + dz*dz with dx = qx - tx and likewise y, z.  For a finite query the result is the minimum of the key
+ *   ((uint64)float_bits(d2) << 32) | j over all finite targets j with d2 <= fl(max_dist * max_dist); max_dist >= 0, +inf for no limit.  So: the nearest target, on an
+ *   exact tie the lowest index, the same bits whatever the grid, the order of the targets or the scheduling.  No such target: d2 = +inf, index = -1; a non-finite query
+ *   gets the same.  A d2 that overflows to +inf with a valid index is a valid answer.  d_stats [3] uint32 or NULL (ADDED to) += {non-finite queries, non-finite targets,
+ *   queries served by the fallback below}.  nt == 0 is valid; nq == 0 is valid and launches nothing.
+ *   MECHANISM.  A uniform grid of nx * ny * nz cells over bbox[6] (HOST values: min xyz, max xyz; max > min, finite), x fastest; 1 <= nx, ny, nz <= NRF_NN_MAX_DIM and
+ *   nx * ny * nz <= NRF_NN_MAX_CELLS.  Per axis inv_h = (float)n / (bmax - bmin), h = 1.0f / inv_h, and the cell coordinate of x is
+ *   clamp((int)floorf((x - bmin) * inv_h), 0, n - 1): a point outside the box lives in a border cell, which therefore extends outward without bound.  Finite targets
+ *   are counted per cell (integer atomics), the counts scanned, and the targets scattered into cell order as 16-byte records {x, y, z, index}; the order inside a
+ *   cell may vary from run to run, the key minimum does not depend on it.  One lane per query scans ring r = 0, 1, ... of cells (Chebyshev distance r from the
+ *   query's cell, clamped to the grid) and after ring r stops iff every cell has been scanned, or min(best_d2, fl(max_dist * max_dist)) < fl(B * B), strictly, with
+ *   B = fl(fl((float)r * h_min) * 0.999f), h_min the smallest of the three h.
+ *   WHY THE STOP IS EXACT.  Let tau(x) = (x - bmin) * inv_h in real arithmetic.  The computed value is fl(fl(x - bmin) * inv_h): two roundings, so for a coordinate
+ *   whose computed cell is k (unclamped, or clamped at a border) tau >= k - e resp. tau < k + 1 + e with e <= 1024 * 2^-23 < 1.3e-4 (dims <= 1024).  A target not yet
+ *   scanned after ring r sits in a cell at least r + 1 cells from the query's cell along some axis, so on that axis the real separation is at least
+ *   (r - 2e) / inv_h >= r * (1 - 2.6e-4) / inv_h, for points in the outward-extending border cells too (they only lie farther out).  B is at most
+ *   r * h_min * 0.999 * (1 + 2^-23), and h_min <= (1 / inv_h) * (1 + 2^-24) on every axis: B is a float no larger than that separation.  Rounding of -, * and + is
+ *   monotone: |fl(qx - tx)| >= B, its square is >= fl(B * B), and adding the other two non-negative squares keeps that.  Every unscanned target therefore has
+ *   d2 >= fl(B * B): it can neither beat nor tie a strictly smaller best, and once fl(B * B) exceeds fl(max_dist * max_dist) none of them counts.
+ *   FALLBACK.  A query with no stop after ring NRF_NN_MAX_RINGS (an outlier, a sparse set, a query far outside the box) is appended to a list in the workspace; a second
+ *   kernel, a fixed grid of workgroups striding the list by the count read on the device, brute-forces ALL records for each such query with a block-wide minimum of the
+ *   key.  Both kernels form d2 through one inline function.  Every loop is bounded by a clamped range or a count; nothing waits on another workgroup.
+ *
+ * Distance statistics: d_dist2 [n] fp32 (0 <= n < 2^40), taus [n_tau] on the HOST (0 <= n_tau <= NRF_STATS_MAX_TAU, each finite and >= 0) -> d_out [4 + n_tau]
+ * doubles on the device: over the FINITE entries, with d = sqrtf(d2) in fp32, {count, sum of (double)d, sum of (double)d2, max of d (0 where none), count(d <= tau_k)
+ * ...}.  A +inf entry ("none within max_dist") is left out of the sums and is a miss for every tau; divide by n, not by count, for a recall.  Order: blocks of 4096
+ * entries, lane t of 256 takes entries t, t + 256, ... in ascending order from 0.0; then the wave butterfly, the four wave sums and the ordered pass of step 4 above.
+ * n == 0 gives zeros.  No synchronisation. */
+#define NRF_SAMPLE_MAX_PER_FACE 65536    /* the most points one face receives */
+#define NRF_NN_MAX_DIM 1024              /* the largest grid dimension: the stop rule's slack (0.999f) is proved for dims up to this */
+#define NRF_NN_MAX_CELLS (1 << 26)       /* the largest nx * ny * nz: 4 B per cell twice over in the workspace */
+#ifndef NRF_NN_MAX_RINGS                 /* tuning builds set another (make EXTRA=-DNRF_NN_MAX_RINGS=n); no result depends on it */
+#define NRF_NN_MAX_RINGS 16              /* the last ring a query scans before it goes to the brute-force list */
+#endif
+#define NRF_STATS_MAX_TAU 4
+NRF_API size_t nrf_mesh_sample_workspace_bytes(int64_t n_verts, int64_t n_faces);
+NRF_API int nrf_mesh_sample_count(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, float density, uint64_t seed, int64_t *n_points,
+                                  double *total_area, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_mesh_sample_emit(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, uint64_t seed, int64_t n_points, float *d_points,
+                                 int32_t *d_face, float *d_uv, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_nearest_points_workspace_bytes(int64_t nq, int64_t nt, int nx, int ny, int nz);
+NRF_API int nrf_nearest_points(const float *d_query, int64_t nq, const float *d_target, int64_t nt, const float *bbox, int nx, int ny, int nz, float max_dist,
+                               float *d_dist2, int32_t *d_index, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_distance_stats_workspace_bytes(int64_t n);
+NRF_API int nrf_distance_stats(const float *d_dist2, int64_t n, const float *taus, int n_tau, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Image metrics (image_metrics.hip; the reference has only the training loop's PSNR, NeRFExecutor.h:893)
  * ------------------------------------------------------------------------------------------- */
 /* How good a frame is, on the device and in fp64 (in fp32 the variances E[x^2] - mu^2 cancel against c2: a flat pair 0.25 / 0.75 is off by 1.19e-4).  Images are

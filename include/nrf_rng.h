@@ -24,7 +24,9 @@ enum {
     NRF_RNG_PRECOND = 6,       /* stochastic preconditioning   [n, S+Ni, 3]    */
     NRF_RNG_R_FINE = 7,
     NRF_RNG_THETA_FINE = 8,
-    NRF_RNG_NOISE_FINE = 9
+    NRF_RNG_NOISE_FINE = 9,
+    NRF_RNG_SURFACE_COUNT = 10, /* nrf_mesh_sample_*: the Bernoulli draw of a face's fractional point   [F]  */
+    NRF_RNG_SURFACE_UV = 11     /* nrf_mesh_sample_*: the (u, v) of a surface point                     [n, 2] */
 };
 
 NRF_HD uint32_t nrf_rng_u32(uint64_t seed, uint32_t stream, uint64_t idx)

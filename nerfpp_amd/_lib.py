@@ -17,6 +17,7 @@ NRF_PREC_F32, NRF_PREC_F16_MFMA, NRF_PREC_F16_SPLIT = 0, 1, 2
 NRF_DIRS_NONE, NRF_DIRS_PE, NRF_DIRS_SH_LIBTORCH, NRF_DIRS_SH_CUDA = 0, 1, 2, 3
 (NRF_RNG_T_RAND, NRF_RNG_R_COARSE, NRF_RNG_THETA_COARSE, NRF_RNG_NOISE_COARSE, NRF_RNG_U_PDF, NRF_RNG_PRECOND, NRF_RNG_R_FINE, NRF_RNG_THETA_FINE,
  NRF_RNG_NOISE_FINE) = range(1, 10)       # include/nrf_rng.h
+NRF_RNG_SURFACE_COUNT, NRF_RNG_SURFACE_UV = 10, 11
 NRF_PROF_NAMES = ("hash", "mlp", "composite", "sample", "other", "sigma", "mlp_colour")
 NRF_COARSE_AUTO, NRF_COARSE_FULL, NRF_COARSE_SIGMA_F32 = 0, 1, 2
 NRF_OVERFLOW_AUTO, NRF_OVERFLOW_RERENDER, NRF_OVERFLOW_ERROR, NRF_OVERFLOW_DEFERRED, NRF_OVERFLOW_IGNORE = 0, 1, 2, 3, 4
@@ -184,6 +185,13 @@ _ABI = """
     nrf_tsdf_sample_color(piiipplpp)
     nrf_raster_workspace_bytes(llii)->z
     nrf_raster_mesh(plplpiiippfippppppzp)
+    nrf_mesh_sample_workspace_bytes(ll)->z
+    nrf_mesh_sample_count(plplfqppppzp)
+    nrf_mesh_sample_emit(plplqlppppzp)
+    nrf_nearest_points_workspace_bytes(lliii)->z
+    nrf_nearest_points(plplpiiifppppzp)
+    nrf_distance_stats_workspace_bytes(l)->z
+    nrf_distance_stats(plpippzp)
     nrf_ssim_window(p)
     nrf_ssim_workspace_bytes(iiii)->z
     nrf_ssim(ppiiiidpppzp)

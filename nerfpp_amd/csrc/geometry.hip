@@ -1,0 +1,687 @@
+// geometry.hip -- comparing surfaces in space: an area-weighted sampling of a triangle list (nrf_mesh_sample_count / _emit), the nearest neighbour of every point of
+// one set in another (nrf_nearest_points) and the sums a Chamfer distance or an F-score is made of (nrf_distance_stats).  The reference has none of it; the contract is
+// stated in include/nerfpp_hip.h and restated in numpy by tests/geometry_ref.py, which the GPU tests compare with bit for bit.
+//
+// Sampling.  k_sample_faces: one lane per face -- indices checked before anything is read, the fp32 area, the face's point count n_f (floor of area * density plus
+//   one Bernoulli draw of the fraction), the block's total of n_f and its ordered fp64 sum of the areas.  k_geo_scan (one workgroup) turns the block totals into block
+//   offsets, k_geo_finish adds the area partials in image_metrics.hip's order, k_sample_offsets writes every face's first point.  The emit kernel runs one lane per
+//   POINT and finds its face by a binary search in the offsets: a face clamped to NRF_SAMPLE_MAX_PER_FACE points costs its lanes nothing extra.  Every position comes
+//   from an integer prefix sum and every draw is a pure function of (seed, stream, index): two runs give the same arrays.
+// Nearest points.  A uniform grid over the caller's box: k_nn_bin<0> (one non-returning atomic add per finite target), the scan of the cell counts (k_nn_cell_sums,
+//   k_geo_scan, k_nn_cell_starts), k_nn_bin<1> (16-byte records {x, y, z, index} in cell order; the order INSIDE a cell is whatever the atomics gave).  k_nn_query:
+//   one lane per query scans rings of cells outward, every ring as contiguous runs of records (the x-neighbours of a row are one range of the start array), keeps the
+//   minimum of ((uint64)float_bits(d2) << 32) | index and stops by the rule the header proves.  A query still open after NRF_NN_MAX_RINGS rings is appended to a list
+//   (ballot, popcount, one returning atomic per wave); k_nn_far, a fixed grid of workgroups, brute-forces all records for each listed query with a block-wide minimum.
+//   Both form d2 in nn_d2: one copy of the arithmetic.  The minimum of a set does not depend on the order it arrives in, so the result depends on neither the grid,
+//   the scheduling nor the order of the targets (beyond the tie-break by index the key states).
+// Statistics.  k_dist_stats: 4096 entries per block, lane t takes t, t + 256, ... in ascending order; wave shuffle tree, four wave sums in order, one row of eight fp64
+//   partials per block; k_geo_finish adds the rows in image_metrics.hip's k_finish order.  No atomics.
+// Every loop is bounded by a clamped range or a count; no kernel waits on another workgroup.
+#include "common.h"
+#include "scan.h"
+#include "workspace.h"
+#include "nrf_rng.h"
+
+#include <climits>
+#include <cmath>
+
+namespace nrf {
+
+namespace {
+
+constexpr int GEO_BLOCK = 256;
+constexpr int SCAN_BLOCK = 1024;
+constexpr int FAR_GRID = 1024;           // workgroups of k_nn_far: 4 per CU
+constexpr int STATS_TILE = 4096;         // entries per block of k_dist_stats
+constexpr int STATS_VALUES = 8;          // count, sum d, sum d2, max d, four tau counts
+constexpr unsigned long long NN_NONE = ((unsigned long long)0x7f800000u << 32) | 0xffffffffu;          // d2 = +inf, index = -1: above every key with a valid index
+
+// ---------------------------------------------------------------------------------------------- shared: scan of block totals, ordered fp64 sums
+// one workgroup: exclusive scan of bsum[0 .. nb) in place; *total = the sum
+__global__ void __launch_bounds__(SCAN_BLOCK) k_geo_scan(int64_t nb, int64_t *__restrict__ bsum, int64_t *__restrict__ total)
+{
+    __shared__ int64_t sh[SCAN_BLOCK];
+    int64_t carry = 0;
+    for (int64_t b0 = 0; b0 < nb; b0 += SCAN_BLOCK) {
+        const int64_t b = b0 + threadIdx.x;
+        const int64_t v = b < nb ? bsum[b] : 0;
+        int64_t t;
+        const int64_t e = block_exclusive_scan<int64_t, SCAN_BLOCK>(v, sh, t);
+        if (b < nb) bsum[b] = carry + e;
+        carry += t;
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// the block's sum of one double per lane: wave shuffle tree, then the four wave sums in wave order (valid in thread 0)
+__device__ __forceinline__ double block_sum_ordered(double v, double *s_wave)
+{
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double a = s_wave[0];
+#pragma unroll
+    for (int k = 1; k < GEO_BLOCK / 64; k++) a += s_wave[k];
+    __syncthreads();
+    return a;
+}
+
+__device__ __forceinline__ double wave_max(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+
+// out[v] = the sum over k of partials[k * nv + v] (v == max_at: the maximum): one block; thread t takes k = t, t + 256, ... in ascending order, then a fixed tree
+__global__ void __launch_bounds__(GEO_BLOCK) k_geo_finish(int64_t count, int nv, int max_at, const double *__restrict__ partials, double *__restrict__ out, int n_out)
+{
+    __shared__ double s_a[GEO_BLOCK];
+    const int t = threadIdx.x;
+    for (int v = 0; v < n_out; v++) {
+        const bool is_max = v == max_at;
+        double a = 0.0;
+        for (int64_t k = t; k < count; k += GEO_BLOCK) a = is_max ? fmax(a, partials[k * nv + v]) : a + partials[k * nv + v];
+        s_a[t] = a;
+        __syncthreads();
+        for (int off = GEO_BLOCK / 2; off > 0; off >>= 1) {
+            if (t < off) s_a[t] = is_max ? fmax(s_a[t], s_a[t + off]) : s_a[t] + s_a[t + off];
+            __syncthreads();
+        }
+        if (t == 0) out[v] = s_a[0];
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- 1. surface sampling
+struct SampleWs {
+    int64_t *header;         // [0] the number of points; [1] the bits of the fp64 total area
+    int32_t *count;          // [F] n_f
+    int32_t *offset;         // [F] the face's first point
+    int64_t *bsum;           // [blocks] n_f per block of 256 faces, scanned in place
+    double *area;            // [blocks] the area partials
+};
+
+SampleWs sample_layout(Bump &b, int64_t n_faces)
+{
+    SampleWs s;
+    const size_t nb = (size_t)ceil_div(n_faces > 0 ? n_faces : 1, GEO_BLOCK);
+    s.header = b.take<int64_t>(4);
+    s.count = b.take<int32_t>((size_t)n_faces);
+    s.offset = b.take<int32_t>((size_t)n_faces);
+    s.bsum = b.take<int64_t>(nb);
+    s.area = b.take<double>(nb);
+    return s;
+}
+
+bool sample_shape_ok(int64_t n_verts, int64_t n_faces) { return n_verts >= 0 && n_verts <= INT32_MAX && n_faces >= 0 && n_faces <= INT32_MAX; }
+
+__device__ __forceinline__ bool finite3(const float p[3]) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
+
+// the corners of face f; false (nothing dereferenced) where an index lies outside [0, V)
+__device__ __forceinline__ bool face_corners(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t f, float v0[3], float e1[3], float e2[3],
+                                             bool &finite)
+{
+    const int32_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+    if (i0 < 0 || i0 >= n_verts || i1 < 0 || i1 >= n_verts || i2 < 0 || i2 >= n_verts) return false;
+    float v1[3], v2[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        v0[a] = verts[(int64_t)i0 * 3 + a];
+        v1[a] = verts[(int64_t)i1 * 3 + a];
+        v2[a] = verts[(int64_t)i2 * 3 + a];
+        e1[a] = v1[a] - v0[a];
+        e2[a] = v2[a] - v0[a];
+    }
+    finite = finite3(v0) && finite3(v1) && finite3(v2);
+    return true;
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_sample_faces(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, float density,
+                                                            uint64_t seed, int32_t *__restrict__ count, int64_t *__restrict__ bsum, double *__restrict__ area_part,
+                                                            uint32_t *__restrict__ stats)
+{
+    __shared__ int sh[GEO_BLOCK];
+    __shared__ double s_wave[GEO_BLOCK / 64];
+    const int64_t f = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    int n = 0, cls = -1;          // class 0 bad index, 1 non-finite, 2 clamped
+    double area64 = 0.0;
+    if (f < n_faces) {
+        float v0[3], e1[3], e2[3];
+        bool finite = false;
+        if (!face_corners(verts, n_verts, faces, f, v0, e1, e2, finite)) {
+            cls = 0;
+        } else {
+            const float cx = e1[1] * e2[2] - e1[2] * e2[1];
+            const float cy = e1[2] * e2[0] - e1[0] * e2[2];
+            const float cz = e1[0] * e2[1] - e1[1] * e2[0];
+            const float s = (cx * cx + cy * cy) + cz * cz;
+            const float area = 0.5f * sqrtf(s);
+            if (!finite || !isfinite(area)) {
+                cls = 1;
+            } else {
+                area64 = (double)area;
+                const float a = area * density;
+                const float fa = floorf(a);
+                if (fa > (float)NRF_SAMPLE_MAX_PER_FACE) {          // also a == +inf; the conversion below is defined
+                    n = NRF_SAMPLE_MAX_PER_FACE;
+                    cls = 2;
+                } else {
+                    n = (int)fa + (nrf_rng_uniform(seed, NRF_RNG_SURFACE_COUNT, (uint64_t)f) < a - fa ? 1 : 0);
+                    if (n > NRF_SAMPLE_MAX_PER_FACE) { n = NRF_SAMPLE_MAX_PER_FACE; cls = 2; }
+                }
+            }
+        }
+        count[f] = n;
+    }
+    int total, t0, t1, t2;
+    (void)block_exclusive_scan<int, GEO_BLOCK>(n, sh, total);
+    const double part = block_sum_ordered(area64, s_wave);
+    if (threadIdx.x == 0) {
+        bsum[blockIdx.x] = total;
+        area_part[blockIdx.x] = part;
+    }
+    if (!stats) return;          // uniform
+    (void)block_exclusive_scan<int, GEO_BLOCK>(cls == 0, sh, t0);
+    (void)block_exclusive_scan<int, GEO_BLOCK>(cls == 1, sh, t1);
+    (void)block_exclusive_scan<int, GEO_BLOCK>(cls == 2, sh, t2);
+    if (threadIdx.x == 0) {          // counts: their values do not depend on the order of the additions
+        if (t0) atomicAdd(stats + 0, (uint32_t)t0);
+        if (t1) atomicAdd(stats + 1, (uint32_t)t1);
+        if (t2) atomicAdd(stats + 2, (uint32_t)t2);
+    }
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_sample_offsets(int64_t n_faces, const int32_t *__restrict__ count, const int64_t *__restrict__ bsum,
+                                                              int32_t *__restrict__ offset)
+{
+    __shared__ int sh[GEO_BLOCK];
+    const int64_t f = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    int total;
+    const int e = block_exclusive_scan<int, GEO_BLOCK>(f < n_faces ? count[f] : 0, sh, total);
+    const int64_t at = bsum[blockIdx.x] + e;
+    if (f < n_faces) offset[f] = at > INT32_MAX ? INT32_MAX : (int32_t)at;          // a total beyond int32 is refused by the count call: nothing is emitted from it
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_sample_points(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, uint64_t seed,
+                                                             int64_t n_points, const int64_t *__restrict__ header, const int32_t *__restrict__ offset,
+                                                             float *__restrict__ points, int32_t *__restrict__ out_face, float *__restrict__ out_uv)
+{
+    const int64_t p = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    if (p >= n_points || p >= header[0]) return;          // never beyond the caller's buffers, never beyond what the count call laid out
+    // the last face whose first point is <= p: faces without points share their successor's offset, so this is the face that owns p
+    int64_t lo = 0, hi = n_faces;                         // offset[lo] <= p < offset[hi] (offset[n_faces] = the total)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)offset[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    const int64_t f = lo;
+    float u = nrf_rng_uniform(seed, NRF_RNG_SURFACE_UV, 2 * (uint64_t)p);
+    float v = nrf_rng_uniform(seed, NRF_RNG_SURFACE_UV, 2 * (uint64_t)p + 1);
+    if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }
+    float v0[3] = {0.0f, 0.0f, 0.0f}, e1[3] = {0.0f, 0.0f, 0.0f}, e2[3] = {0.0f, 0.0f, 0.0f};
+    bool finite;
+    (void)face_corners(verts, n_verts, faces, f, v0, e1, e2, finite);          // true: the count call gave points to valid faces only
+#pragma unroll
+    for (int a = 0; a < 3; a++) points[p * 3 + a] = (v0[a] + u * e1[a]) + v * e2[a];
+    if (out_face) out_face[p] = (int32_t)f;
+    if (out_uv) { out_uv[p * 2 + 0] = u; out_uv[p * 2 + 1] = v; }
+}
+
+#ifdef NRF_SAMPLE_EMIT_BY_FACE
+// the alternative the header leaves open, for tuning builds (make EXTRA=-DNRF_SAMPLE_EMIT_BY_FACE): one lane per FACE writes its n_f points; same bits
+__global__ void __launch_bounds__(GEO_BLOCK) k_sample_points_by_face(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces,
+                                                                     uint64_t seed, int64_t n_points, const int64_t *__restrict__ header, const int32_t *__restrict__ count,
+                                                                     const int32_t *__restrict__ offset, float *__restrict__ points, int32_t *__restrict__ out_face,
+                                                                     float *__restrict__ out_uv)
+{
+    const int64_t f = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    if (f >= n_faces) return;
+    const int n = count[f];
+    if (n <= 0) return;
+    const int64_t first = offset[f], limit = n_points < header[0] ? n_points : header[0];
+    if (first < 0) return;          // not a workspace of the count call
+    float v0[3], e1[3], e2[3];
+    bool finite;
+    if (!face_corners(verts, n_verts, faces, f, v0, e1, e2, finite)) return;
+    for (int64_t p = first; p < first + n && p < limit; p++) {
+        float u = nrf_rng_uniform(seed, NRF_RNG_SURFACE_UV, 2 * (uint64_t)p);
+        float v = nrf_rng_uniform(seed, NRF_RNG_SURFACE_UV, 2 * (uint64_t)p + 1);
+        if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }
+#pragma unroll
+        for (int a = 0; a < 3; a++) points[p * 3 + a] = (v0[a] + u * e1[a]) + v * e2[a];
+        if (out_face) out_face[p] = (int32_t)f;
+        if (out_uv) { out_uv[p * 2 + 0] = u; out_uv[p * 2 + 1] = v; }
+    }
+}
+#endif
+
+// ---------------------------------------------------------------------------------------------- 2. nearest points
+struct NnGrid {
+    int n[3];
+    int64_t cells;
+    float bmin[3], inv_h[3];
+    float h_min;             // the smallest cell edge, fl(1 / inv_h)
+};
+
+struct NnWs {
+    uint32_t *start;         // [cells + 1] counts, then the exclusive scan: the records of cell c are start[c] .. start[c + 1]
+    uint32_t *cursor;        // [cells] where the next record of a cell goes
+    int64_t *bsum;           // [cell blocks]
+    int64_t *total;          // [1]
+    float4 *rec;             // [nt] {x, y, z, index bits} in cell order
+    int32_t *far;            // [nq] the queries of the brute-force kernel
+    uint32_t *n_far;         // [1]
+};
+
+NnWs nn_layout(Bump &b, int64_t nq, int64_t nt, int64_t cells)
+{
+    NnWs s;
+    s.start = b.take<uint32_t>((size_t)cells + 1);
+    s.cursor = b.take<uint32_t>((size_t)cells);
+    s.bsum = b.take<int64_t>((size_t)ceil_div(cells, GEO_BLOCK));
+    s.total = b.take<int64_t>(1);
+    s.rec = b.take<float4>((size_t)nt);
+    s.far = b.take<int32_t>((size_t)nq);
+    s.n_far = b.take<uint32_t>(1);
+    return s;
+}
+
+bool nn_shape_ok(int64_t nq, int64_t nt, int nx, int ny, int nz)
+{
+    return nq >= 0 && nq <= INT32_MAX && nt >= 0 && nt <= INT32_MAX && nx >= 1 && nx <= NRF_NN_MAX_DIM && ny >= 1 && ny <= NRF_NN_MAX_DIM && nz >= 1 &&
+           nz <= NRF_NN_MAX_DIM && (int64_t)nx * ny * nz <= NRF_NN_MAX_CELLS;
+}
+
+// the header's cell coordinate: clamp((int)floorf((x - bmin) * inv_h), 0, n - 1), clamped as a float so that the conversion is defined for every finite x
+__device__ __forceinline__ int nn_cell(float x, float bmin, float inv_h, int n)
+{
+    const float t = floorf((x - bmin) * inv_h);
+    return (int)fminf(fmaxf(t, 0.0f), (float)(n - 1));
+}
+
+__device__ __forceinline__ int64_t nn_cell_of(const NnGrid &g, float x, float y, float z)
+{
+    const int cx = nn_cell(x, g.bmin[0], g.inv_h[0], g.n[0]), cy = nn_cell(y, g.bmin[1], g.inv_h[1], g.n[1]), cz = nn_cell(z, g.bmin[2], g.inv_h[2], g.n[2]);
+    return ((int64_t)cz * g.n[1] + cy) * g.n[0] + cx;
+}
+
+// the one place d2 is formed
+__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, const float4 &t)
+{
+    const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+__device__ __forceinline__ void nn_take(float qx, float qy, float qz, const float4 &t, float md2, unsigned long long &best)
+{
+    const float d2 = nn_d2(qx, qy, qz, t);
+    const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | __float_as_uint(t.w);
+    if (d2 <= md2 && k < best) best = k;
+}
+
+// pass 0: count[cell]++ per finite target; pass 1: the record goes to cursor[cell]++
+template <int PASS>
+__global__ void __launch_bounds__(GEO_BLOCK) k_nn_bin(const float *__restrict__ target, int64_t nt, NnGrid g, uint32_t *__restrict__ cell_word, float4 *__restrict__ rec,
+                                                      uint32_t *__restrict__ stats)
+{
+    __shared__ int sh[GEO_BLOCK];
+    const int64_t j = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    int bad = 0;
+    if (j < nt) {
+        const float x = target[j * 3 + 0], y = target[j * 3 + 1], z = target[j * 3 + 2];
+        if (isfinite(x) && isfinite(y) && isfinite(z)) {
+            const int64_t c = nn_cell_of(g, x, y, z);
+            if (PASS == 0) {
+                (void)__hip_atomic_fetch_add(cell_word + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // the result is unused: no return trip
+            } else {
+                const uint32_t at = atomicAdd(cell_word + c, 1u);          // < the finite targets <= nt: every target is counted once and placed once
+                rec[at] = make_float4(x, y, z, __uint_as_float((uint32_t)j));
+            }
+        } else {
+            bad = 1;
+        }
+    }
+    if (PASS != 0 || !stats) return;          // uniform
+    int total;
+    (void)block_exclusive_scan<int, GEO_BLOCK>(bad, sh, total);
+    if (threadIdx.x == 0 && total) atomicAdd(stats + 1, (uint32_t)total);
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_nn_cell_sums(int64_t cells, const uint32_t *__restrict__ count, int64_t *__restrict__ bsum)
+{
+    __shared__ int sh[GEO_BLOCK];
+    const int64_t c = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    int total;
+    (void)block_exclusive_scan<int, GEO_BLOCK>(c < cells ? (int)count[c] : 0, sh, total);          // a block holds at most nt < 2^31 targets
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// counts -> starts in place (start[cells] = the number of records), and the scatter's cursors
+__global__ void __launch_bounds__(GEO_BLOCK) k_nn_cell_starts(int64_t cells, uint32_t *__restrict__ start, const int64_t *__restrict__ bsum, uint32_t *__restrict__ cursor)
+{
+    __shared__ int sh[GEO_BLOCK];
+    const int64_t c = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    const int n = c < cells ? (int)start[c] : 0;
+    int total;
+    const int e = block_exclusive_scan<int, GEO_BLOCK>(n, sh, total);
+    if (c >= cells) return;
+    const uint32_t at = (uint32_t)(bsum[blockIdx.x] + e);
+    start[c] = at;
+    cursor[c] = at;
+    if (c == cells - 1) start[cells] = at + (uint32_t)n;
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_nn_query(const float *__restrict__ query, int64_t nq, NnGrid g, float md2, const uint32_t *__restrict__ start,
+                                                        const float4 *__restrict__ rec, float *__restrict__ dist2, int32_t *__restrict__ index, int32_t *__restrict__ far,
+                                                        uint32_t *__restrict__ n_far, uint32_t *__restrict__ stats)
+{
+    __shared__ int sh[GEO_BLOCK];
+    const int64_t q = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool live = q < nq;
+    float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+    if (live) { qx = query[q * 3 + 0]; qy = query[q * 3 + 1]; qz = query[q * 3 + 2]; }
+    const bool finite = live && isfinite(qx) && isfinite(qy) && isfinite(qz);
+    unsigned long long best = NN_NONE;
+    bool open = false;          // rings exhausted without a stop: the brute-force kernel's
+    if (finite && start[g.cells] != 0) {
+        const int cx = nn_cell(qx, g.bmin[0], g.inv_h[0], g.n[0]), cy = nn_cell(qy, g.bmin[1], g.inv_h[1], g.n[1]), cz = nn_cell(qz, g.bmin[2], g.inv_h[2], g.n[2]);
+        // the ring that completes the grid as seen from this cell
+        const int r_all = max(max(max(cx, g.n[0] - 1 - cx), max(cy, g.n[1] - 1 - cy)), max(cz, g.n[2] - 1 - cz));
+        open = true;
+        for (int r = 0; r <= NRF_NN_MAX_RINGS; r++) {
+            const int z0 = max(cz - r, 0), z1 = min(cz + r, g.n[2] - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.n[1] - 1);
+            const int x0 = max(cx - r, 0), x1 = min(cx + r, g.n[0] - 1);
+            for (int z = z0; z <= z1; z++) {
+                for (int y = y0; y <= y1; y++) {
+                    const int64_t row = ((int64_t)z * g.n[1] + y) * g.n[0];
+                    const bool shell = z == cz - r || z == cz + r || y == cy - r || y == cy + r;          // the whole row belongs to ring r
+                    if (shell) {
+                        const uint32_t a = start[row + x0], b = start[row + x1 + 1];
+                        for (uint32_t i = a; i < b; i++) nn_take(qx, qy, qz, rec[i], md2, best);
+                    } else {                                                                                 // r >= 1: the two end cells, where the grid has them
+                        if (cx - r >= 0) {
+                            const uint32_t a = start[row + cx - r], b = start[row + cx - r + 1];
+                            for (uint32_t i = a; i < b; i++) nn_take(qx, qy, qz, rec[i], md2, best);
+                        }
+                        if (cx + r <= g.n[0] - 1) {
+                            const uint32_t a = start[row + cx + r], b = start[row + cx + r + 1];
+                            for (uint32_t i = a; i < b; i++) nn_take(qx, qy, qz, rec[i], md2, best);
+                        }
+                    }
+                }
+            }
+            if (r >= r_all) { open = false; break; }          // every cell has been scanned
+            const float B = ((float)r * g.h_min) * 0.999f;
+            const float B2 = B * B;
+            // every unscanned target has d2 >= B2 (header): a strictly smaller best cannot be beaten or tied, and beyond max_dist nothing counts
+            if (fminf(__uint_as_float((uint32_t)(best >> 32)), md2) < B2) { open = false; break; }
+        }
+    }
+    // every lane of the wave arrives here, so the ballot sees the whole wave
+    const unsigned long long wm = __ballot(open);
+    if (wm) {
+        uint32_t at = 0;
+        if (lane == 0) at = atomicAdd(n_far, (uint32_t)__popcll(wm));
+        at = __shfl(at, 0, 64);
+        if (open) far[at + __popcll(wm & ((1ull << lane) - 1))] = (int32_t)q;          // at + rank < nq: every query is appended at most once
+    }
+    if (live && !open) {
+        dist2[q] = __uint_as_float((uint32_t)(best >> 32));
+        index[q] = (int32_t)(uint32_t)best;
+    }
+    if (!stats) return;          // uniform
+    int total;
+    (void)block_exclusive_scan<int, GEO_BLOCK>(live && !finite, sh, total);
+    if (threadIdx.x == 0 && total) atomicAdd(stats + 0, (uint32_t)total);
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_nn_far(const float *__restrict__ query, float md2, const uint32_t *__restrict__ start, int64_t cells,
+                                                      const float4 *__restrict__ rec, float *__restrict__ dist2, int32_t *__restrict__ index, const int32_t *__restrict__ far,
+                                                      const uint32_t *__restrict__ n_far, uint32_t *__restrict__ stats)
+{
+    __shared__ unsigned long long s_best[GEO_BLOCK / 64];
+    const uint32_t n = *n_far, n_rec = start[cells];
+    if (stats && blockIdx.x == 0 && threadIdx.x == 0 && n) atomicAdd(stats + 2, n);
+    for (uint32_t i = blockIdx.x; i < n; i += FAR_GRID) {          // uniform over the workgroup
+        const int64_t q = far[i];
+        const float qx = query[q * 3 + 0], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
+        unsigned long long best = NN_NONE;
+        for (uint32_t t = threadIdx.x; t < n_rec; t += GEO_BLOCK) nn_take(qx, qy, qz, rec[t], md2, best);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off, 64), lo = __shfl_xor((uint32_t)best, off, 64);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            best = o < best ? o : best;
+        }
+        if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 1; k < GEO_BLOCK / 64; k++) best = s_best[k] < best ? s_best[k] : best;
+            dist2[q] = __uint_as_float((uint32_t)(best >> 32));
+            index[q] = (int32_t)(uint32_t)best;
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- 3. distance statistics
+struct Taus {
+    float t[NRF_STATS_MAX_TAU];
+    int n;
+};
+
+struct StatsWs {
+    double *partials;          // [blocks][8]
+};
+
+int64_t stats_blocks(int64_t n) { return n > 0 ? ceil_div(n, STATS_TILE) : 1; }
+
+void stats_layout(Bump &b, int64_t n, StatsWs &ws) { ws.partials = b.take<double>((size_t)stats_blocks(n) * STATS_VALUES); }
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_dist_stats(const float *__restrict__ d2, int64_t n, Taus taus, double *__restrict__ partials)
+{
+    __shared__ double s_wave[GEO_BLOCK / 64];
+    const int t = threadIdx.x;
+    const int64_t first = (int64_t)blockIdx.x * STATS_TILE;
+    const int64_t left = n - first;
+    const int cnt = left < STATS_TILE ? (int)(left > 0 ? left : 0) : STATS_TILE;
+    double acc[STATS_VALUES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int e = t; e < cnt; e += GEO_BLOCK) {
+        const float v = d2[first + e];
+        if (!isfinite(v)) continue;
+        const float d = sqrtf(v);
+        acc[0] += 1.0;
+        acc[1] += (double)d;
+        acc[2] += (double)v;
+        acc[3] = fmax(acc[3], (double)d);
+#pragma unroll
+        for (int k = 0; k < NRF_STATS_MAX_TAU; k++)
+            if (k < taus.n && d <= taus.t[k]) acc[4 + k] += 1.0;
+    }
+#pragma unroll
+    for (int v = 0; v < STATS_VALUES; v++) {
+        double a;
+        if (v == 3) {
+            a = wave_max(acc[3]);
+            if ((t & 63) == 0) s_wave[t >> 6] = a;
+            __syncthreads();
+            a = fmax(fmax(s_wave[0], s_wave[1]), fmax(s_wave[2], s_wave[3]));
+            __syncthreads();
+        } else {
+            a = block_sum_ordered(acc[v], s_wave);
+        }
+        if (t == 0) partials[(int64_t)blockIdx.x * STATS_VALUES + v] = a;
+    }
+}
+
+}  // namespace
+
+}  // namespace nrf
+
+using namespace nrf;
+
+extern "C" {
+
+size_t nrf_mesh_sample_workspace_bytes(int64_t n_verts, int64_t n_faces)
+{
+    if (!sample_shape_ok(n_verts, n_faces)) return 0;
+    return measure([&](Bump &b) { sample_layout(b, n_faces); });
+}
+
+int nrf_mesh_sample_count(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, float density, uint64_t seed, int64_t *n_points,
+                          double *total_area, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(sample_shape_ok(n_verts, n_faces), "nrf_mesh_sample_count: %lld vertices, %lld faces (both 0 .. 2^31 - 1)", (long long)n_verts, (long long)n_faces);
+    NRF_CHECK_ARG(n_points && total_area, "nrf_mesh_sample_count: null n_points or total_area");
+    NRF_CHECK_ARG(n_faces == 0 || d_faces, "nrf_mesh_sample_count: null d_faces");
+    NRF_CHECK_ARG(d_verts || n_verts == 0 || n_faces == 0, "nrf_mesh_sample_count: null d_verts");
+    NRF_CHECK_ARG(std::isfinite(density) && density >= 0.0f, "nrf_mesh_sample_count: the density must be finite and >= 0 (got %g)", (double)density);
+    NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_mesh_sample_count: the workspace must be non-null and 8-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    const SampleWs ws = sample_layout(bump, n_faces);
+    NRF_TRY(ws_check(bump, nrf_mesh_sample_workspace_bytes(n_verts, n_faces), "nrf_mesh_sample_count"));
+    hipStream_t st = as_stream(stream);
+    const int64_t nb = ceil_div(n_faces, GEO_BLOCK);
+    NRF_HIP(hipMemsetAsync(ws.header, 0, 4 * sizeof(int64_t), st));
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_sample_faces, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, density, seed, ws.count, ws.bsum, ws.area,
+                           d_stats);
+        NRF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_geo_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, nb, ws.bsum, ws.header);
+        NRF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_geo_finish, dim3(1), dim3(GEO_BLOCK), 0, st, nb, 1, -1, (const double *)ws.area, reinterpret_cast<double *>(ws.header + 1), 1);
+        NRF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_sample_offsets, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, n_faces, (const int32_t *)ws.count, (const int64_t *)ws.bsum, ws.offset);
+        NRF_LAUNCH_CHECK();
+    }
+    int64_t h[2] = {0, 0};
+    NRF_HIP(hipMemcpyAsync(h, ws.header, sizeof(h), hipMemcpyDeviceToHost, st));
+    NRF_HIP(hipStreamSynchronize(st));
+    *n_points = h[0];
+    std::memcpy(total_area, &h[1], sizeof(double));
+    NRF_CHECK_ARG(h[0] <= INT32_MAX, "nrf_mesh_sample_count: %lld points exceed the int32 range of the offsets (lower the density)", (long long)h[0]);
+    return NRF_OK;
+}
+
+int nrf_mesh_sample_emit(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, uint64_t seed, int64_t n_points, float *d_points,
+                         int32_t *d_face, float *d_uv, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(sample_shape_ok(n_verts, n_faces), "nrf_mesh_sample_emit: %lld vertices, %lld faces (both 0 .. 2^31 - 1)", (long long)n_verts, (long long)n_faces);
+    NRF_CHECK_ARG(n_points >= 0 && n_points <= INT32_MAX, "nrf_mesh_sample_emit: %lld points (0 .. 2^31 - 1)", (long long)n_points);
+    NRF_CHECK_ARG(n_points == 0 || (d_points && d_faces && d_verts && n_faces > 0 && n_verts > 0), "nrf_mesh_sample_emit: %lld points with a null d_points, d_faces or d_verts, or of an empty mesh",
+                  (long long)n_points);
+    NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_mesh_sample_emit: the workspace must be non-null and 8-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    const SampleWs ws = sample_layout(bump, n_faces);
+    NRF_TRY(ws_check(bump, nrf_mesh_sample_workspace_bytes(n_verts, n_faces), "nrf_mesh_sample_emit"));
+    if (n_points == 0) return NRF_OK;
+#ifdef NRF_SAMPLE_EMIT_BY_FACE
+    hipLaunchKernelGGL(k_sample_points_by_face, dim3((unsigned)ceil_div(n_faces, GEO_BLOCK)), dim3(GEO_BLOCK), 0, as_stream(stream), d_verts, (int32_t)n_verts, d_faces, n_faces,
+                       seed, n_points, (const int64_t *)ws.header, (const int32_t *)ws.count, (const int32_t *)ws.offset, d_points, d_face, d_uv);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+#endif
+    hipLaunchKernelGGL(k_sample_points, dim3((unsigned)ceil_div(n_points, GEO_BLOCK)), dim3(GEO_BLOCK), 0, as_stream(stream), d_verts, (int32_t)n_verts, d_faces, n_faces, seed,
+                       n_points, (const int64_t *)ws.header, (const int32_t *)ws.offset, d_points, d_face, d_uv);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
+size_t nrf_nearest_points_workspace_bytes(int64_t nq, int64_t nt, int nx, int ny, int nz)
+{
+    if (!nn_shape_ok(nq, nt, nx, ny, nz)) return 0;
+    return measure([&](Bump &b) { nn_layout(b, nq, nt, (int64_t)nx * ny * nz); });
+}
+
+int nrf_nearest_points(const float *d_query, int64_t nq, const float *d_target, int64_t nt, const float *bbox, int nx, int ny, int nz, float max_dist, float *d_dist2,
+                       int32_t *d_index, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(nn_shape_ok(nq, nt, nx, ny, nz), "nrf_nearest_points: %lld queries, %lld targets (0 .. 2^31 - 1), grid %d x %d x %d (each 1 .. %d, product <= %d)",
+                  (long long)nq, (long long)nt, nx, ny, nz, NRF_NN_MAX_DIM, NRF_NN_MAX_CELLS);
+    NRF_CHECK_ARG(nq == 0 || (d_query && d_dist2 && d_index), "nrf_nearest_points: null d_query, d_dist2 or d_index");
+    NRF_CHECK_ARG(nt == 0 || d_target, "nrf_nearest_points: null d_target");
+    NRF_CHECK_ARG(bbox, "nrf_nearest_points: null bbox");
+    NRF_CHECK_ARG(max_dist >= 0.0f, "nrf_nearest_points: max_dist must be >= 0 or +inf (got %g)", (double)max_dist);          // NaN fails
+    NnGrid g;
+    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
+    g.cells = (int64_t)nx * ny * nz;
+    g.h_min = INFINITY;
+    for (int a = 0; a < 3; a++) {
+        const float extent = bbox[3 + a] - bbox[a];
+        const float inv_h = (float)g.n[a] / extent;
+        const float h = 1.0f / inv_h;
+        NRF_CHECK_ARG(std::isfinite(bbox[a]) && std::isfinite(bbox[3 + a]) && extent > 0.0f && std::isfinite(extent) && std::isfinite(inv_h) && inv_h > 0.0f &&
+                          std::isfinite(h) && h > 0.0f,
+                      "nrf_nearest_points: empty, inverted or non-finite box on axis %d ([%g, %g])", a, (double)bbox[a], (double)bbox[3 + a]);
+        g.bmin[a] = bbox[a];
+        g.inv_h[a] = inv_h;
+        g.h_min = h < g.h_min ? h : g.h_min;
+    }
+    NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 15) == 0, "nrf_nearest_points: the workspace must be non-null and 16-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    const NnWs ws = nn_layout(bump, nq, nt, g.cells);
+    NRF_TRY(ws_check(bump, nrf_nearest_points_workspace_bytes(nq, nt, nx, ny, nz), "nrf_nearest_points"));
+    if (nq == 0) return NRF_OK;
+    hipStream_t st = as_stream(stream);
+    const float md2 = max_dist * max_dist;
+    const int64_t cb = ceil_div(g.cells, GEO_BLOCK);
+    NRF_HIP(hipMemsetAsync(ws.start, 0, ((size_t)g.cells + 1) * sizeof(uint32_t), st));
+    NRF_HIP(hipMemsetAsync(ws.n_far, 0, sizeof(uint32_t), st));
+    if (nt > 0) {
+        const unsigned tb = (unsigned)ceil_div(nt, GEO_BLOCK);
+        hipLaunchKernelGGL(k_nn_bin<0>, dim3(tb), dim3(GEO_BLOCK), 0, st, d_target, nt, g, ws.start, ws.rec, d_stats);
+        NRF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_nn_cell_sums, dim3((unsigned)cb), dim3(GEO_BLOCK), 0, st, g.cells, (const uint32_t *)ws.start, ws.bsum);
+        NRF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_geo_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, cb, ws.bsum, ws.total);
+        NRF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_nn_cell_starts, dim3((unsigned)cb), dim3(GEO_BLOCK), 0, st, g.cells, ws.start, (const int64_t *)ws.bsum, ws.cursor);
+        NRF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_nn_bin<1>, dim3(tb), dim3(GEO_BLOCK), 0, st, d_target, nt, g, ws.cursor, ws.rec, d_stats);
+        NRF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_nn_query, dim3((unsigned)ceil_div(nq, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_query, nq, g, md2, (const uint32_t *)ws.start, (const float4 *)ws.rec,
+                       d_dist2, d_index, ws.far, ws.n_far, d_stats);
+    NRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_nn_far, dim3(FAR_GRID), dim3(GEO_BLOCK), 0, st, d_query, md2, (const uint32_t *)ws.start, g.cells, (const float4 *)ws.rec, d_dist2, d_index,
+                       (const int32_t *)ws.far, (const uint32_t *)ws.n_far, d_stats);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
+size_t nrf_distance_stats_workspace_bytes(int64_t n)
+{
+    if (n < 0 || n >= ((int64_t)1 << 40)) return 0;
+    return measure([&](Bump &b) { StatsWs ws; stats_layout(b, n, ws); });
+}
+
+int nrf_distance_stats(const float *d_dist2, int64_t n, const float *taus, int n_tau, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 40), "nrf_distance_stats: %lld entries (0 .. 2^40 - 1)", (long long)n);
+    NRF_CHECK_ARG(n_tau >= 0 && n_tau <= NRF_STATS_MAX_TAU, "nrf_distance_stats: %d thresholds (0 .. %d)", n_tau, NRF_STATS_MAX_TAU);
+    NRF_CHECK_ARG(d_out && (d_dist2 || n == 0) && (taus || n_tau == 0), "nrf_distance_stats: null d_out, d_dist2 or taus");
+    Taus t{};
+    t.n = n_tau;
+    for (int k = 0; k < n_tau; k++) {
+        NRF_CHECK_ARG(std::isfinite(taus[k]) && taus[k] >= 0.0f, "nrf_distance_stats: threshold %d must be finite and >= 0 (got %g)", k, (double)taus[k]);
+        t.t[k] = taus[k];
+    }
+    NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_distance_stats: the workspace must be non-null and 8-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    StatsWs ws;
+    stats_layout(bump, n, ws);
+    NRF_TRY(ws_check(bump, nrf_distance_stats_workspace_bytes(n), "nrf_distance_stats"));
+    hipStream_t st = as_stream(stream);
+    const int64_t nb = stats_blocks(n);
+    hipLaunchKernelGGL(k_dist_stats, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, d_dist2, n, t, ws.partials);
+    NRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_geo_finish, dim3(1), dim3(GEO_BLOCK), 0, st, nb, STATS_VALUES, 3, (const double *)ws.partials, d_out, 4 + n_tau);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
+}  // extern "C"

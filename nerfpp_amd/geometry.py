@@ -1,0 +1,194 @@
+"""Comparing surfaces in space: SampleSurface, InterpolateAttributes, NearestPoints, TransferAttributes and SurfaceDistance over the C ABI (include/nerfpp_hip.h,
+geometry.hip).
+
+The reference has no geometry metrics; the names follow the mirror's style.  A Mesh is sampled in proportion to area (every draw a pure function of seed and index),
+two point sets are compared through a uniform-grid nearest-neighbour search whose result is the minimum of a packed (distance bits, index) key -- so it depends on
+neither the grid nor the order of the points -- and the sums behind Chamfer distance, Hausdorff distance and precision / recall / F-score at a distance are ordered
+fp64 reductions.  tests/geometry_ref.py equals every output bit for bit and two runs agree.  This is the sampled point-to-point distance of the DTU / Tanks and Temples
+benchmarks, not an exact point-to-triangle distance.
+"""
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import mesh as M
+from .modules import _ptr, _stream, _dev_f32
+
+# NRF_SAMPLE_* / NRF_NN_* / NRF_STATS_* of the header (tests/test_geometry_host.py holds them to it)
+SAMPLE_MAX_PER_FACE, NN_MAX_DIM, NN_MAX_CELLS, NN_MAX_RINGS, STATS_MAX_TAU = 65536, 1024, 1 << 26, 16, 4
+OCCUPANCY = 128.0        # what GridDims aims at by default: about 20-30 targets per occupied cell as measured; coarse enough that 16 rings reach far
+_ATTRS = ("Colors", "Normals", "Relevancy")
+
+
+@dataclass
+class SurfaceSamples:
+    Points: torch.Tensor          # [n, 3] f32
+    Faces: torch.Tensor           # [n] int32: the face each point lies on
+    UV: torch.Tensor              # [n, 2] f32: the point is (1 - u - v) v0 + u v1 + v v2 of that face
+    Area: float                   # the mesh's area (fp64 sum of the fp32 face areas)
+    Stats: Optional[torch.Tensor] = None          # [3] int32 on the device: faces with a bad index, with a non-finite vertex or area, clamped to SAMPLE_MAX_PER_FACE
+
+
+@dataclass
+class SurfaceDistanceResult:          # float64 device tensors, as EvaluateViews returns them; a is the prediction, b the truth
+    Accuracy: torch.Tensor            # mean distance from a's points to their nearest point of b
+    Completeness: torch.Tensor        # mean distance from b's points to their nearest point of a
+    Chamfer: torch.Tensor             # the mean of the two
+    ChamferSq: torch.Tensor           # mean squared distance a -> b plus mean squared distance b -> a
+    Hausdorff: torch.Tensor           # the largest of all those distances
+    Precision: torch.Tensor           # [n_tau] the share of a's points within tau of b
+    Recall: torch.Tensor              # [n_tau] the share of b's points within tau of a
+    FScore: torch.Tensor              # [n_tau] 2 P R / (P + R), 0 where P + R = 0
+    Taus: tuple = ()
+
+
+def _mesh_arrays(mesh):
+    verts = _dev_f32(mesh.Vertices).reshape(-1, 3)
+    faces = mesh.Faces.to(device=verts.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+    return verts, faces
+
+
+def _workspace(nbytes, dev):
+    return torch.empty((max(1, int(nbytes)),), device=dev, dtype=torch.uint8)
+
+
+def _count(verts, faces, density, seed, stats, ws):
+    n, area = C.c_int64(0), C.c_double(0.0)
+    L.check(L.lib().nrf_mesh_sample_count(_ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0], float(density), int(seed), C.addressof(n), C.addressof(area),
+                                          _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    return int(n.value), float(area.value)
+
+
+def SampleSurface(mesh, n_points=None, density=None, seed=0):
+    """Points on `mesh` drawn in proportion to area (nrf_mesh_sample_count / _emit): face f receives floor(area_f * density) points plus one more with the probability
+    of the fraction, so the total is ABOUT area * density, not exactly (its standard deviation is below sqrt(area * density)).  Give density (points per unit area) or
+    n_points; with n_points one extra count call at density 0 measures the area and density = n_points / area.  Each count call synchronises the stream once."""
+    if (n_points is None) == (density is None):
+        raise L.NrfError("SampleSurface: give exactly one of n_points and density")
+    verts, faces = _mesh_arrays(mesh)
+    dev = verts.device
+    ws = _workspace(L.lib().nrf_mesh_sample_workspace_bytes(verts.shape[0], faces.shape[0]), dev)
+    if density is None:
+        _, area = _count(verts, faces, 0.0, seed, None, ws)
+        density = float(n_points) / area if area > 0.0 else 0.0
+    stats = torch.zeros((3,), device=dev, dtype=torch.int32)
+    n, area = _count(verts, faces, density, seed, stats, ws)
+    pts = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    face = torch.empty((n,), device=dev, dtype=torch.int32)
+    uv = torch.empty((n, 2), device=dev, dtype=torch.float32)
+    L.check(L.lib().nrf_mesh_sample_emit(_ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0], int(seed), n, _ptr(pts), _ptr(face), _ptr(uv), _ptr(ws), ws.numel(),
+                                         _stream()))
+    return SurfaceSamples(pts, face, uv, area, stats)
+
+
+def InterpolateAttributes(mesh, samples, name):
+    """[n, C] the attribute `name` of `mesh` (Colors, Normals, Relevancy) at `samples`: (1 - u - v) a0 + u a1 + v a2 of each sample's face."""
+    if name not in _ATTRS or getattr(mesh, name) is None:
+        raise L.NrfError(f"InterpolateAttributes: the mesh has no {name!r}")
+    attr = _dev_f32(getattr(mesh, name))
+    a = attr.reshape(attr.shape[0], -1)
+    f = mesh.Faces.to(device=a.device, dtype=torch.int64)[samples.Faces.to(torch.int64)]
+    u, v = samples.UV[:, :1], samples.UV[:, 1:]
+    out = (1.0 - u - v) * a[f[:, 0]] + u * a[f[:, 1]] + v * a[f[:, 2]]
+    return out[:, 0] if attr.dim() == 1 else out
+
+
+def _as_points(x, n_points, seed):
+    if isinstance(x, M.Mesh):
+        return SampleSurface(x, n_points=n_points, seed=seed).Points
+    return _dev_f32(x).reshape(-1, 3)
+
+
+def GridDims(bbox, n_targets, occupancy=OCCUPANCY):
+    """(nx, ny, nz) of the default search grid: cells as cubic as the dims allow whose edge puts about `occupancy` targets into an occupied cell when the targets
+    lie on a surface that spans the box (the cells a surface of extent L crosses number about 3 (L / h)^2), never more than 64 cells per target."""
+    b = np.asarray(bbox, np.float64).reshape(6)
+    ext = np.maximum(b[3:] - b[:3], 1e-30)
+    n_long = min(max(math.ceil(math.sqrt(max(n_targets, 1) / (3.0 * occupancy))), 1), NN_MAX_DIM)
+    cap = min(NN_MAX_CELLS, max(64 * n_targets, 1))
+    while True:
+        h = ext.max() / n_long
+        dims = [int(min(max(math.ceil(e / h - 1e-9), 1), NN_MAX_DIM)) for e in ext]
+        if dims[0] * dims[1] * dims[2] <= cap or n_long == 1:
+            return tuple(dims)
+        n_long = max(1, int(n_long * 0.8))
+
+
+def _bbox_of(points):
+    """The box of the finite points, widened to a positive extent on every axis: one host synchronisation"""
+    p = points[torch.isfinite(points).all(dim=1)]
+    if p.shape[0] == 0:
+        return np.array([0, 0, 0, 1, 1, 1], np.float32)
+    lo, hi = p.min(dim=0).values.cpu().numpy().astype(np.float64), p.max(dim=0).values.cpu().numpy().astype(np.float64)
+    pad = np.maximum((hi - lo) * 1e-3, np.maximum(np.abs(hi), np.abs(lo)) * 1e-6 + 1e-30)
+    return np.concatenate([lo - pad, hi + pad]).astype(np.float32)
+
+
+def NearestPoints(query, target, max_dist=None, bbox=None, cells=None, stats=None):
+    """For every point of query [nq, 3] its nearest point of target [nt, 3] -> (Dist2 [nq] f32 squared distance, Index [nq] int32 into target): nrf_nearest_points.
+    On an exact tie the lowest index; +inf and -1 where the target has no finite point (within max_dist, where given) or the query point is not finite.
+    bbox [6] (min xyz, max xyz) is where the search grid lies; points outside it are still found.  bbox=None takes the box of the target, which costs ONE host
+    synchronisation; pass the renderer's box (or any box around the target) to avoid it.  cells = (nx, ny, nz) overrides GridDims.  The result depends on neither.
+    stats: an int32 [3] device tensor to add {non-finite queries, non-finite targets, queries served by the brute-force fallback} to."""
+    q, t = _dev_f32(query).reshape(-1, 3), _dev_f32(target).reshape(-1, 3)
+    dev = q.device
+    nq, nt = int(q.shape[0]), int(t.shape[0])
+    box = _bbox_of(t) if bbox is None else np.ascontiguousarray(torch.as_tensor(bbox).detach().cpu().numpy() if torch.is_tensor(bbox) else bbox, np.float32).reshape(6)
+    nx, ny, nz = GridDims(box, nt) if cells is None else (int(c) for c in cells)
+    d2 = torch.empty((nq,), device=dev, dtype=torch.float32)
+    idx = torch.empty((nq,), device=dev, dtype=torch.int32)
+    lib = L.lib()
+    ws = _workspace(lib.nrf_nearest_points_workspace_bytes(nq, nt, nx, ny, nz), dev)
+    L.check(lib.nrf_nearest_points(_ptr(q), nq, _ptr(t), nt, box.ctypes.data_as(C.c_void_p), nx, ny, nz, float("inf") if max_dist is None else float(max_dist),
+                                   _ptr(d2), _ptr(idx), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    return d2, idx
+
+
+def DistanceStats(dist2, taus=()):
+    """[4 + len(taus)] float64 on the device: count, sum of d, sum of d^2, max d and count(d <= tau) over the finite entries of dist2 (nrf_distance_stats)."""
+    d2 = _dev_f32(dist2).reshape(-1)
+    t = np.ascontiguousarray(taus, np.float32).reshape(-1)
+    out = torch.empty((4 + len(t),), device=d2.device, dtype=torch.float64)
+    lib = L.lib()
+    ws = _workspace(lib.nrf_distance_stats_workspace_bytes(d2.numel()), d2.device)
+    L.check(lib.nrf_distance_stats(_ptr(d2), d2.numel(), t.ctypes.data_as(C.c_void_p), len(t), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_dist=None, bbox=None):
+    """A copy of dst_mesh whose attributes `names` are those of the nearest vertex of src_mesh (the ones src_mesh carries): TSDF colours onto an isosurface, relevancy
+    onto another mesh.  A vertex without a neighbour (within max_dist) gets zeros."""
+    import dataclasses
+    _, idx = NearestPoints(dst_mesh.Vertices, src_mesh.Vertices, max_dist=max_dist, bbox=bbox)
+    found = idx >= 0
+    at = idx.clamp(min=0).to(torch.int64)
+    new = {}
+    for name in names:
+        a = getattr(src_mesh, name)
+        if a is None:
+            continue
+        g = a.to(idx.device)[at]
+        new[name] = torch.where(found.reshape((-1,) + (1,) * (g.dim() - 1)), g, torch.zeros_like(g))
+    return dataclasses.replace(dst_mesh, **new)
+
+
+def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_dist=None, bbox=None):
+    """How far apart two surfaces are, a the prediction and b the truth, each a Mesh (sampled: SampleSurface(n_points=n_points, seed=seed)) or a [N, 3] tensor of
+    points (used as they are).  Returns a SurfaceDistanceResult of float64 device tensors.  With max_dist, points without a neighbour that near are left out of the
+    means and count as misses in Precision / Recall.  bbox as in NearestPoints (None: two synchronisations, one per direction)."""
+    if len(taus) > STATS_MAX_TAU:
+        raise L.NrfError(f"SurfaceDistance: {len(taus)} thresholds, at most {STATS_MAX_TAU}")
+    pa, pb = _as_points(a, n_points, seed), _as_points(b, n_points, seed)
+    sa = DistanceStats(NearestPoints(pa, pb, max_dist=max_dist, bbox=bbox)[0], taus)
+    sb = DistanceStats(NearestPoints(pb, pa, max_dist=max_dist, bbox=bbox)[0], taus)
+    acc, comp = sa[1] / sa[0], sb[1] / sb[0]
+    # tensor / tensor: a division by a Python scalar is carried out as a multiplication by its reciprocal, which is not the correctly rounded quotient
+    na, nb = (torch.full((), float(x.shape[0]), device=sa.device, dtype=torch.float64) for x in (pa, pb))
+    p, r = sa[4:] / na, sb[4:] / nb
+    f = torch.where(p + r > 0, 2.0 * p * r / (p + r), torch.zeros_like(p))
+    return SurfaceDistanceResult(acc, comp, 0.5 * (acc + comp), sa[2] / sa[0] + sb[2] / sb[0], torch.maximum(sa[3], sb[3]), p, r, f, tuple(float(t) for t in taus))

@@ -750,6 +750,54 @@ NRF_API size_t nrf_distance_stats_workspace_bytes(int64_t n);
 NRF_API int nrf_distance_stats(const float *d_dist2, int64_t n, const float *taus, int n_tau, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mesh simplification (simplify.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* Vertex clustering on a uniform grid: the vertices of a cell become one vertex, faces that lose a corner to a neighbour disappear, and of several faces that land on
+ * the same three cells at most one survives, chosen by their net orientation.  d_verts [V,3] fp32, d_faces [F,3] int32; bbox[6] HOST values (min xyz, max xyz); a count
+ * call, then an emit call over the same mesh, box, dims and workspace.  Each source-level fp32 operation below is rounded once; / is correctly rounded.  The
+ * workspace is caller-owned, 8-byte aligned and sized by nrf_mesh_simplify_workspace_bytes (0 for a shape the entries refuse); nothing is allocated.  Refusals --
+ * NRF_ERR_INVALID_ARG, or NRF_ERR_WORKSPACE for a workspace below the twin's size, the message starting with the entry's name -- come before any launch or write.
+ * Two runs give the same bits, whatever the workspace held before.
+ *   1. GRID.  0 <= V, F < 2^31; 1 <= nx, ny, nz <= NRF_SIMPLIFY_MAX_DIM; nx * ny * nz <= NRF_SIMPLIFY_MAX_CELLS; the box finite with max > min.  Per axis
+ *      inv_h = (float)n / (bmax - bmin) and h = 1.0f / inv_h (as nrf_nearest_points forms them).  For a finite vertex t = (x - bmin) * inv_h and
+ *      c = clamp((int)floorf(t), 0, n - 1); its cell is cx + nx * (cy + ny * cz).  A vertex with a non-finite coordinate has no cell.
+ *   2. FACES.  Each face falls into the first class that applies: an index outside [0, V): BAD, nothing of it is dereferenced; a corner without a cell: NON-FINITE;
+ *      two corners in one cell: COLLAPSED; the rest are candidates, each with a triple of three distinct cells (c0, c1, c2) in corner order.  A vertex is USED if it
+ *      is a corner of a face that is neither BAD nor NON-FINITE.
+ *   3. COINCIDENT FACES.  Sort a candidate's triple to (a < b < c); the face is EVEN if (c0, c1, c2) is a rotation of (a, b, c) and ODD otherwise.  For each distinct
+ *      sorted triple net = #even - #odd over all candidates with it.  net == 0: none is kept; net > 0: the even candidate of lowest face index; net < 0: the odd
+ *      candidate of lowest face index.  Every candidate not kept is REMOVED.  (Two sheets pressed onto the same three cells with opposite windings cancel, and a
+ *      pocket folded onto itself leaves no fin.)  d_stats [4] uint32 or NULL (ADDED to; the caller zeroes it) += {bad, non-finite, collapsed, removed}.
+ *   4. OUTPUT ORDER.  Kept faces are emitted in ascending input face index; d_face_src [n_out_faces] or NULL gets that index.  An output vertex exists for every cell
+ *      that is a corner of a kept face; output vertices are numbered in ascending cell index.  Neither order depends on scheduling, on the hash table or on the order
+ *      of the input vertices.  d_out_faces [n_out_faces,3] holds the output ids of (c0, c1, c2) in the face's own corner order: winding is preserved.  d_cluster [V]
+ *      or NULL: the output id of v's cell, -1 if the cell has no output vertex or v has no cell.
+ *   5. POSITION.  The members of an output vertex are the USED vertices of its cell.  Per member and axis o = clamp(t - (float)c, 0.0f, 1.0f) and
+ *      q = (int64)(o * 1048576.0f); S is the int64 sum of q and m the member count (integer atomics: the order does not matter).
+ *      tm = (float)((double)c + ((double)S / (double)m) * 2^-20) and P = bmin + tm * h.
+ *   6. REPRESENTATIVE.  Per member d2 = (dx*dx + dy*dy) + dz*dz with dx = x - Px and likewise y, z; d_rep [n_out_verts] or NULL gets the low word of the minimum of
+ *      the key ((uint64)float_bits(d2) << 32) | v: the member nearest the mean, on a tie the lowest index.  position == NRF_SIMPLIFY_POS_MEAN writes P to
+ *      d_out_verts [n_out_verts,3], NRF_SIMPLIFY_POS_MEMBER the representative's own coordinates; any other value is refused.
+ * nrf_mesh_simplify_count runs steps 1-4 and returns the two totals (its one synchronisation); they stay in the workspace.  nrf_mesh_simplify_emit takes them as the
+ * sizes of the caller's buffers: it reads the workspace's pair back (it waits for the stream once, as nrf_isosurface_emit does) and refuses any other pair before
+ * anything is written, so a wrong total can neither overrun a buffer nor leave one half filled.  V == 0 or F == 0 is valid and gives 0 / 0.
+ * MECHANISM.  An open-addressing table of a power-of-two number of slots >= 2F, slot = {owner face, net, lowest even face, lowest odd face}.  The owner is set once by
+ * a compare-and-swap from EMPTY and never changes; the slot's key is the sorted triple of its owner, read from per-face triples an EARLIER launch wrote, so no
+ * multi-word key is ever published.  A face that meets a slot whose owner has its key adds +-1 to net and lowers its parity's minimum, otherwise it probes the next
+ * slot; the walk is bounded by the slot count.  A second launch reads the finished slots.  Positions come from integer prefix sums over faces and over cells.  No
+ * output depends on the hash function, the table size or the arrival order, and nothing waits on another workgroup. */
+#define NRF_SIMPLIFY_MAX_DIM 1024
+#define NRF_SIMPLIFY_MAX_CELLS (1 << 27)
+#define NRF_SIMPLIFY_POS_MEAN 0
+#define NRF_SIMPLIFY_POS_MEMBER 1
+NRF_API size_t nrf_mesh_simplify_workspace_bytes(int64_t n_verts, int64_t n_faces, int nx, int ny, int nz);
+NRF_API int nrf_mesh_simplify_count(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz,
+                                    int64_t *n_out_verts, int64_t *n_out_faces, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_mesh_simplify_emit(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz, int position,
+                                   int64_t n_out_verts, int64_t n_out_faces, float *d_out_verts, int32_t *d_out_faces, int32_t *d_rep, int32_t *d_face_src,
+                                   int32_t *d_cluster, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Image metrics (image_metrics.hip; the reference has only the training loop's PSNR, NeRFExecutor.h:893)
  * ------------------------------------------------------------------------------------------- */
 /* How good a frame is, on the device and in fp64 (in fp32 the variances E[x^2] - mu^2 cancel against c2: a flat pair 0.25 / 0.75 is off by 1.19e-4).  Images are

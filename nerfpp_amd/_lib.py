@@ -192,6 +192,9 @@ _ABI = """
     nrf_nearest_points(plplpiiifppppzp)
     nrf_distance_stats_workspace_bytes(l)->z
     nrf_distance_stats(plpippzp)
+    nrf_mesh_simplify_workspace_bytes(lliii)->z
+    nrf_mesh_simplify_count(plplpiiippppzp)
+    nrf_mesh_simplify_emit(plplpiiiillppppppzp)
     nrf_ssim_window(p)
     nrf_ssim_workspace_bytes(iiii)->z
     nrf_ssim(ppiiiidpppzp)

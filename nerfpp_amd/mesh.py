@@ -1,11 +1,13 @@
-"""Mesh export: DensityGrid, Isosurface, ExtractMesh, MeshComponents, FilterComponents and SavePLY over the C ABI (include/nerfpp_hip.h, mesh.hip,
-components.hip).
+"""Mesh export: DensityGrid, Isosurface, ExtractMesh, MeshComponents, FilterComponents, SimplifyMesh, SimplifyToFaces and SavePLY over the C ABI
+(include/nerfpp_hip.h, mesh.hip, components.hip, simplify.hip).
 
 The reference has no mesh export; the names follow the mirror's style.  The density lattice is the exact-fp32 sigma of the renderer's network
 (== RunNetwork(..., NRF_PREC_F32)[..., 3] bit for bit); the isosurface is marching tetrahedra on the Kuhn split of each cell, in an order fixed by integer
-prefix scans (two extractions give the same arrays).
+prefix scans (two extractions give the same arrays).  Simplification is vertex clustering on a uniform grid with coincident faces settled by their net orientation;
+every output is fixed by integers and single-rounding steps (tests/simplify_ref.py restates them).
 """
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -16,6 +18,9 @@ from . import _lib as L
 from .modules import _HashBase, _ptr, _stream, _dev_f32
 
 COLOR_CHUNK = 1 << 18        # vertices per RunNetwork call of ExtractMesh
+# NRF_SIMPLIFY_* of the header (tests/test_simplify_host.py holds them to it)
+SIMPLIFY_MAX_DIM, SIMPLIFY_MAX_CELLS, SIMPLIFY_POS_MEAN, SIMPLIFY_POS_MEMBER = 1024, 1 << 27, 0, 1
+_POSITIONS = {"mean": SIMPLIFY_POS_MEAN, "member": SIMPLIFY_POS_MEMBER}
 
 
 @dataclass
@@ -114,11 +119,12 @@ def _safe_normalize(v, eps=1e-8):
 
 
 def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, precision=L.NRF_PREC_F32, normals="lattice", keep_largest=None,
-                min_component_faces=0):
+                min_component_faces=0, simplify_cell=None):
     """DensityGrid -> Isosurface -> per-vertex colour: sigmoid of RunNetwork's rgb at the vertex seen along -normal (a ray hitting the surface head-on), in chunks.
     normals="lattice": the isosurface's central-difference normals; "field": -safe_normalize(DensityGradient(vertices)), the field's own analytic normal
     (also the colour's view direction).  keep_largest / min_component_faces: FilterComponents on the bare isosurface, before the field normals and the colours,
-    so a dropped floater costs no network evaluation."""
+    so a dropped floater costs no network evaluation.  simplify_cell: SimplifyMesh(cell_size=simplify_cell) after that filter and before the field normals and the
+    colours, for the same reason; the lattice normals of the result are those of each cluster's representative."""
     if normals not in ("lattice", "field"):
         raise L.NrfError(f"ExtractMesh: normals must be 'lattice' or 'field', got {normals!r}")
     bb = _bbox(renderer, bbox)
@@ -128,6 +134,9 @@ def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, pre
     if keep_largest is not None or min_component_faces > 0:
         kept = FilterComponents(Mesh(verts, faces, lattice_normals), keep_largest, min_component_faces)
         verts, faces, lattice_normals = kept.Vertices, kept.Faces, kept.Normals
+    if simplify_cell is not None:
+        small = SimplifyMesh(Mesh(verts, faces, lattice_normals), cell_size=simplify_cell)
+        verts, faces, lattice_normals = small.Vertices, small.Faces, small.Normals
     normals = lattice_normals if normals == "lattice" else -_safe_normalize(DensityGradient(renderer, verts)[1])
     rgb = None
     if colors:
@@ -190,6 +199,139 @@ def FilterComponents(mesh, keep_largest=None, min_faces=0, labels=None):
         largest[top] = True
         keep &= largest
     return _submesh(mesh, keep[face_label], mesh.Relevancy)
+
+
+def _finite_box(verts):
+    """(lo [3], hi [3]) float32 numpy: the box of the finite vertices ((0, 0) where there is none): one host synchronisation"""
+    v = verts[torch.isfinite(verts).all(dim=1)]
+    if v.shape[0] == 0:
+        return np.zeros(3, np.float32), np.zeros(3, np.float32)
+    return v.min(dim=0).values.cpu().numpy().astype(np.float32), v.max(dim=0).values.cpu().numpy().astype(np.float32)
+
+
+def _cube_dims(extent, n_long):
+    """Per axis the number of cells of edge max(extent) / n_long that cover it, 1 .. SIMPLIFY_MAX_DIM: as cubic as whole numbers of cells allow"""
+    ext = np.asarray(extent, np.float64)
+    cell = float(ext.max()) / n_long if ext.max() > 0 else 1.0
+    return tuple(int(min(max(math.ceil(e / cell - 1e-9), 1), SIMPLIFY_MAX_DIM)) for e in ext)
+
+
+def _simplify_grid(verts, cell_size, resolution, bbox):
+    """(box [6] float32 numpy, (nx, ny, nz)) of SimplifyMesh"""
+    if (cell_size is None) == (resolution is None):
+        raise L.NrfError("SimplifyMesh: give exactly one of cell_size and resolution")
+    if bbox is None:
+        lo, hi = _finite_box(verts)
+    else:
+        b = np.asarray(torch.as_tensor(bbox).detach().cpu().numpy() if torch.is_tensor(bbox) else bbox, np.float32).reshape(6)
+        lo, hi = b[:3].copy(), b[3:].copy()
+    if cell_size is not None:
+        cell = float(cell_size)
+        if not (math.isfinite(cell) and cell > 0.0):
+            raise L.NrfError(f"SimplifyMesh: cell_size must be finite and > 0, got {cell_size!r}")
+        ext = hi.astype(np.float64) - lo.astype(np.float64)
+        dims = tuple(int(min(max(math.ceil(e / cell), 1), SIMPLIFY_MAX_DIM)) for e in ext)
+        hi = (lo.astype(np.float64) + np.asarray(dims, np.float64) * cell).astype(np.float32)          # cube cells; an axis of zero extent is one cell thick
+    else:
+        dims = _resolution(resolution)
+        ext = hi.astype(np.float64) - lo.astype(np.float64)
+        if (ext <= 0).any():          # an axis of zero extent is widened by one cell: the largest cell edge of the other axes, 1 where there is none
+            edge = max([e / n for e, n in zip(ext, dims) if e > 0], default=1.0)
+            hi = np.where(ext > 0, hi, (lo.astype(np.float64) + edge).astype(np.float32)).astype(np.float32)
+    return np.ascontiguousarray(np.concatenate([lo, hi]), np.float32), dims
+
+
+class _Simplifier:
+    """One mesh, one workspace, any number of count calls and the emit call after the last of them"""
+    def __init__(self, mesh):
+        self.verts = _dev_f32(mesh.Vertices).reshape(-1, 3)
+        self.faces = mesh.Faces.to(device=self.verts.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+        self.nv, self.nf = int(self.verts.shape[0]), int(self.faces.shape[0])
+        self.ws = None
+
+    def count(self, box, dims):
+        lib = L.lib()
+        need = int(lib.nrf_mesh_simplify_workspace_bytes(self.nv, self.nf, *dims))
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = None          # the old one goes first
+            self.ws = torch.empty((max(1, need),), device=self.verts.device, dtype=torch.uint8)
+        self.stats = torch.zeros((4,), device=self.verts.device, dtype=torch.int32)
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        L.check(lib.nrf_mesh_simplify_count(_ptr(self.verts), self.nv, _ptr(self.faces), self.nf, box.ctypes.data_as(C.c_void_p), *dims, C.addressof(nv), C.addressof(nf),
+                                            _ptr(self.stats), _ptr(self.ws), self.ws.numel(), _stream()))
+        self.box, self.dims, self.out = box, dims, (int(nv.value), int(nf.value))
+        return self.out
+
+    def emit(self, position):
+        dev = self.verts.device
+        nv, nf = self.out
+        verts = torch.empty((nv, 3), device=dev, dtype=torch.float32)
+        faces = torch.empty((nf, 3), device=dev, dtype=torch.int32)
+        rep = torch.empty((nv,), device=dev, dtype=torch.int32)
+        face_src = torch.empty((nf,), device=dev, dtype=torch.int32)
+        cluster = torch.empty((self.nv,), device=dev, dtype=torch.int32)
+        L.check(L.lib().nrf_mesh_simplify_emit(_ptr(self.verts), self.nv, _ptr(self.faces), self.nf, self.box.ctypes.data_as(C.c_void_p), *self.dims, position, nv, nf,
+                                               _ptr(verts), _ptr(faces), _ptr(rep), _ptr(face_src), _ptr(cluster), _ptr(self.ws), self.ws.numel(), _stream()))
+        return verts, faces, rep, face_src, cluster
+
+
+def _position(position):
+    if position not in _POSITIONS:
+        raise L.NrfError(f"position must be 'mean' or 'member', got {position!r}")
+    return _POSITIONS[position]
+
+
+def _simplified(mesh, s, position, return_maps):
+    verts, faces, rep, face_src, cluster = s.emit(position)
+    at = rep.to(torch.int64)
+
+    def gather(t):
+        return None if t is None else t.to(verts.device)[at]
+    out = Mesh(verts, faces, gather(mesh.Normals), gather(mesh.Colors), gather(mesh.Relevancy))
+    return (out, (cluster, face_src, rep, s.stats)) if return_maps else out
+
+
+def SimplifyMesh(mesh, cell_size=None, resolution=None, bbox=None, position="mean", return_maps=False):
+    """Vertex clustering (nrf_mesh_simplify_count / _emit): the vertices of every cell of a uniform grid become one vertex, faces with two corners in one cell
+    disappear, and of the faces that land on the same three cells the one their net orientation names survives (none where the orientations cancel, so a pocket
+    folded onto itself leaves no fin).  Give exactly one of cell_size (cube cells: n = clamp(ceil(extent / cell_size), 1, 1024) per axis, bmax = bmin + n * cell_size)
+    and resolution (an int or (nx, ny, nz) over the box).  bbox [6] defaults to the box of the mesh's finite vertices (one host synchronisation); an axis of zero
+    extent is widened by one cell.  position="mean": the mean of the vertices a cell's surviving or collapsed faces use, on a 2^-20 fixed-point lattice inside the
+    cell, so it does not depend on their order; "member": the coordinates of the representative, the input vertex nearest that mean (lowest index on a tie).
+    Normals, Colors and Relevancy are the representative's.  Kept faces stay in input order with their winding, output vertices ascend in cell index, and two runs
+    give the same bits.  An empty result is a valid empty Mesh.  return_maps: also (cluster [V] int32: the output vertex of every input vertex or -1, face_src [F']
+    int32: the input face of every output face, rep [V'] int32: the representative, stats [4] int32: faces with a bad index, with a non-finite vertex, collapsed,
+    removed as coincident).  Vertex clustering does not preserve topology in general."""
+    pos = _position(position)
+    s = _Simplifier(mesh)
+    box, dims = _simplify_grid(s.verts, cell_size, resolution, bbox)
+    s.count(box, dims)
+    return _simplified(mesh, s, pos, return_maps)
+
+
+def SimplifyToFaces(mesh, target_faces, position="mean"):
+    """(mesh, n): SimplifyMesh(mesh, resolution=dims) on the grid of n cells along the longest axis of the box of the finite vertices -- and as many cells of that
+    edge as cover each other axis, so the cells are as cubic as whole numbers allow; (n, n, n) for a cubic box -- for the largest n tried whose face count is
+    <= target_faces.  n is bisected in [1, 1024] with count calls only (at most 10, one more before the emit); grids beyond the library's cell limit are not tried.
+    The face count is NOT strictly monotone in n (a finer grid can cancel a pocket a coarser one kept), so a larger n that also qualifies may exist; n = 1 always
+    qualifies, with 0 faces."""
+    pos = _position(position)
+    s = _Simplifier(mesh)
+    lo_v, hi_v = _finite_box(s.verts)
+    ext = hi_v.astype(np.float64) - lo_v.astype(np.float64)
+
+    def grid(n):
+        return _simplify_grid(s.verts, None, _cube_dims(ext, n), np.concatenate([lo_v, hi_v]))
+    lo, hi = 1, SIMPLIFY_MAX_DIM + 1          # lo qualifies, hi does not (or is out of range)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        box, dims = grid(mid)
+        if dims[0] * dims[1] * dims[2] <= SIMPLIFY_MAX_CELLS and s.count(box, dims)[1] <= int(target_faces):
+            lo = mid
+        else:
+            hi = mid
+    s.count(*grid(lo))
+    return _simplified(mesh, s, pos, False), lo
 
 
 def SavePLY(path, mesh):

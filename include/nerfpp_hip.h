@@ -1188,7 +1188,7 @@ NRF_API int nrf_lerf_relevancy_grid(const nrf_lerf_renderer *r, const float *bbo
  * ------------------------------------------------------------------------------------------- */
 /* lang_loss = huber_loss(pred, target, reduction none, delta).sum(-1).nanmean() (NeRFExecutor.h:970-974; delta 1.25 there): d_loss [1]; d_grad [n, e] = d loss / d pred
  * (NULL: not wanted).  A row holding a NaN leaves the mean (count = the other rows); its gradient row is 0 except NaN at the NaN elements -- what LibTorch's backward
- * leaves there (golden train_lerf_nan). */
+ * leaves there (golden train_lerf_nan).  With EVERY row NaN the loss is NaN and so is the whole gradient (1 / 0 rows times 0), as LibTorch's. */
 NRF_API int nrf_huber_rows_nanmean(const float *d_pred, const float *d_target, int64_t n, int e, float delta, float *d_loss, float *d_grad, void *stream);
 /* Backward of the FINE pass of LeRFRenderer::RenderRays (LeRFRenderer.cpp:141-172; the coarse pass carries none: z_samples are detached, :150) downstream of the language
  * grid: d_emb [n*s, in] = lang_embed_fn->forward(pts) -> LeRFImpl::forward (LeRF.cpp:86-108) -> sigma_le[~keep] = 0 (LeRFRenderer.cpp:37-38) -> RawToLEOutputs' weights

@@ -105,7 +105,7 @@ int run_linear_fast(int64_t npts, Seg a, Seg b, const nrf_mlp *m, const LinearLa
     rocblas_handle h = (npts >= 256) ? rb_handle(st) : nullptr;
     if (!h || npts > 0x7fffffff) return run_linear(npts, a, b, L, relu, y, y_stride, y_off, st);
     const float *wb = m->params() + L.w_off;
-    if (!gemm_fwd_seg(h, npts, a, wb, L.in, 0, L.out, 0.0f, y, y_stride, y_off) || !gemm_fwd_seg(h, npts, b, wb, L.in, a.n, L.out, 1.0f, y, y_stride, y_off)) {
+    if (!gemm_fwd_seg(h, npts, a, wb, L.in, 0, L.out, 0.0f, y, y_stride, y_off) || !gemm_fwd_seg(h, npts, b, wb, L.in, a.n, L.out, a.n > 0 ? 1.0f : 0.0f, y, y_stride, y_off)) {          // (an empty first segment has written nothing to add to)
         set_error("rocblas_sgemm failed (forward layer %d -> %d over %lld points)", L.in, L.out, (long long)npts);
         return NRF_ERR_HIP;
     }

@@ -95,7 +95,8 @@ __global__ void k_nanmean(int64_t n, const float *__restrict__ row_loss, float *
     if (threadIdx.x == 0) { *loss = (float)(acc / cnt); *inv_count = 1.0f / (float)cnt; }
 }
 
-// d loss / d pred: nansum hands a NaN row 0 instead of 1 / count; huber's own derivative multiplies it (NaN * 0 = NaN at a NaN element: what LibTorch leaves there)
+// d loss / d pred: nansum hands a NaN row (1 / count) * 0 instead of 1 / count; huber's own derivative multiplies it (NaN * 0 = NaN at a NaN element: what LibTorch
+// leaves there).  With EVERY row NaN the count is 0 and that factor is inf * 0 = NaN: LibTorch's gradient is NaN throughout, not only at the NaN elements
 __global__ void k_huber_rows_grad(int64_t n, int e, float delta, const float *__restrict__ pred, const float *__restrict__ target, const float *__restrict__ row_loss,
                                   const float *__restrict__ inv_count, float *__restrict__ grad)
 {
@@ -103,7 +104,7 @@ __global__ void k_huber_rows_grad(int64_t n, int e, float delta, const float *__
     if (idx >= n * e) return;
     const int64_t i = idx / e;
     const float rl = row_loss[i];
-    const float go = (rl == rl) ? inv_count[0] : 0.0f;
+    const float go = (rl == rl) ? inv_count[0] : inv_count[0] * 0.0f;
     const float d = pred[idx] - target[idx];
     grad[idx] = (d < -delta) ? -delta * go : (d > delta ? delta * go : d * go);
 }
@@ -589,8 +590,10 @@ static int head_backward_chunk(const nrf_mlp *m, const float *emb, const uint8_t
     }
     // g = d / d cat[geo, in]: the sigma net's output gradient = (g_sigma [already in g33 column 0], g_geo)
     const float *g_x0 = g.p;
-    hipLaunchKernelGGL(k_lt_copy_cols, dim3((unsigned)ceil_div(c * geo, 256)), dim3(256), 0, st, c, geo, g_x0, W, 0, (const float *)nullptr, 0, 0, g33, W, 1);
-    NRF_LAUNCH_CHECK();
+    if (geo > 0) {          // (geo_feat_dim = 0: no geo columns, and an empty grid is a launch error)
+        hipLaunchKernelGGL(k_lt_copy_cols, dim3((unsigned)ceil_div(c * geo, 256)), dim3(256), 0, st, c, geo, g_x0, W, 0, (const float *)nullptr, 0, 0, g33, W, 1);
+        NRF_LAUNCH_CHECK();
+    }
     g = Seg{g33, W, 0, 1 + geo};
     // the gradient buffers still free: not g33 (G[0]), not the one holding g_x0
     float *freeb[2]; int nf = 0;

@@ -1567,7 +1567,7 @@ ORC_API void orc_huber_rows_nanmean(const float *pred, const float *target, int6
     if (grad) {
         const float norm = 1.0f / (float)cnt;
         for (int64_t i = 0; i < n; i++) {
-            const float go = isnan_row[i] ? 0.0f : norm;
+            const float go = isnan_row[i] ? norm * 0.0f : norm;      /* nansum's backward: grad * mask; inf * 0 = NaN when every row is NaN (count 0), as LibTorch */
             for (int k = 0; k < e; k++) {
                 const float d = pred[i * e + k] - target[i * e + k];
                 grad[i * e + k] = (d < -delta) ? -delta * go : (d > delta ? delta * go : d * go);        /* NaN d: the last branch, NaN * 0 = NaN */

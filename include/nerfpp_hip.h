@@ -843,6 +843,80 @@ NRF_API int nrf_ssim_loss(const float *d_x, const float *d_y, int b, int h, int 
                           double *d_grad64, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Texture atlases (texture.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* A per-face texture atlas: every face of a triangle list owns a right triangle of T x T / 2 texels of one image, so the resolution of the colour does not depend on
+ * the face count.  Meant for meshes whose faces are of nearly one size (nrf_mesh_simplify_*).  The layout is integer arithmetic on (F, T) alone; no entry takes a
+ * workspace, allocates, synchronises or uses atomics; each source-level fp32 operation below is rounded once, sqrtf and / are correctly rounded; two runs give the
+ * same bits.  Refusals -- NRF_ERR_INVALID_ARG, the message starting with the entry's name -- come before any launch or write.
+ *
+ * LAYOUT of (F, T), F faces and a tile of T texels, NRF_ATLAS_MIN_TILE <= T <= NRF_ATLAS_MAX_TILE, 0 <= F <= 2^31 - 2:
+ *   cells = (F + 1) / 2 (integer division); cols = the smallest integer with cols * cols >= cells; rows = (cells + cols - 1) / cols (0 where cells == 0);
+ *   width = cols * T, height = rows * T.  The atlas is [height, width, C], row-major, texel (X, Y) in column X of row Y.
+ *   Texel (X, Y) lies in cell (X / T) + cols * (Y / T) at the local indices i = X % T, j = Y % T.  Face f lives in cell f >> 1.  The texels of a cell with
+ *   i + j <= T - 2 belong to its LOWER face 2 * cell, and (i, j) are that face's indices; the others belong to its UPPER face 2 * cell + 1, whose indices are the
+ *   mirrored (T - 1 - i, T - 1 - j), so i + j <= T - 1 there.  A texel whose face is >= F (the upper half of the last cell of an odd F, the cells past the last face)
+ *   has no owner.  Every texel has at most one owner.
+ *   With n = T - 3 the corners 0, 1, 2 of a face sit at the centres of its texels (0, 0), (n, 0), (0, n): the texel with the face's indices (i, j) has the
+ *   barycentrics b1 = (float)i / (float)n, b2 = (float)j / (float)n, b0 = (1.0f - b1) - b2.  Owned texels with i + j > n extrapolate in the plane of the face: they
+ *   are the padding, and there is no dilation pass.  A bilinear footprint at a point of the face reads only texels with i + j <= n + 1 = T - 2, all of them the
+ *   face's own in either half of a cell (tests/test_texture_host.py).
+ * nrf_atlas_dims (host only): *width, *height of (n_faces, tile).  Refused: a tile outside [MIN, MAX], n_faces < 0 or > 2^31 - 2, a null pointer, a side above
+ *   NRF_ATLAS_MAX_SIZE -- the message names 2 * (NRF_ATLAS_MAX_SIZE / tile)^2, the number of faces that fit.  F == 0 gives 0 x 0.
+ *
+ * nrf_atlas_texels: what to bake.  d_verts [V,3] fp32, d_faces [F,3] int32, d_normals [V,3] or NULL, 0 <= V < 2^31; one lane per texel of the atlas rows
+ *   [row0, row0 + rows) (0 <= row0, 0 <= rows, row0 + rows <= height; rows == 0 does nothing) -> d_face [rows,width] int32 (required), d_bary [rows,width,3],
+ *   d_pos [rows,width,3], d_rays [rows,width,11], each of the three or NULL.  A slab holds the bits of the same rows of a whole run.
+ *   1. The owner f and the face's indices (i, j) by the layout; no owner: face -1.
+ *   2. (v0, v1, v2) = d_faces[f]; an index outside [0, V): face -1, before anything of the face is dereferenced.
+ *   3. e1 = v1 - v0, e2 = v2 - v0 per component; c = e1 x e2 with every component fl(fl(a*b) - fl(c*d)) as in nrf_mesh_sample_count step 1;
+ *      s = (cx*cx + cy*cy) + cz*cz; len = sqrtf(s); unless len > 0 (as floats: zero and NaN fail) the face is degenerate: face -1.
+ *   4. b1, b2, b0 as above; P = v0 + (b1*e1 + b2*e2) per component.
+ *   5. N = c / len per component.  With d_normals: m = (b0*n0 + b1*n1) + b2*n2 per component, l = sqrtf((mx*mx + my*my) + mz*mz), and where l > 0, N = m / l.
+ *   6. The ray, in the [n,11] form of nrf_pack_rays: origin P + offset*N, direction -N, near 0, far 2.0f*offset, view direction -N: a camera `offset` above the
+ *      surface looking down the normal, through the surface to `offset` below it.
+ *   7. A texel with face -1 gets zeros in d_bary, d_pos and d_rays.
+ *   Refused: what nrf_atlas_dims refuses; V out of range; a null d_face with rows > 0; a null d_verts (with V > 0) or d_faces with F > 0; offset not finite or < 0;
+ *   a row window outside the atlas.
+ *
+ * nrf_texture_sample: d_tex [height,width,C] of (n_faces, tile), 1 <= C <= NRF_TEXTURE_MAX_CHANNELS, at p >= 0 pairs of d_face [p] int32 and d_bary [p,3] (b0, b1,
+ *   b2: what nrf_mesh_sample_emit's d_uv and nrf_raster_mesh's d_bary hold; b0 is not read) -> d_out [p,C].
+ *   1. f < 0 or f >= n_faces: zeros.
+ *   2. nf = (float)n; x = b1 * nf; x = 0 unless x > 0 (NaN gives 0); x = nf if x > nf.  y from b2 likewise.
+ *   3. The face's indices (i, j) name the texel (X0 + i, Y0 + j) of an even f and (X0 + T - 1 - i, Y0 + T - 1 - j) of an odd f, with cell = f >> 1,
+ *      X0 = (cell % cols) * T, Y0 = (cell / cols) * T.
+ *   4. NRF_TEXTURE_NEAREST: i = (int)rintf(x), j = (int)rintf(y) (round half to even); if i + j > n + 1 then j = n + 1 - i (i <= n, so j >= 1: the owned texel of
+ *      column i nearest in j); out_c = tex[texel (i, j)][c].
+ *   5. NRF_TEXTURE_BILINEAR: ix = floorf(x), fx = x - ix, iy = floorf(y), fy = y - iy; gx = 1.0f - fx, gy = 1.0f - fy.  The corners (ix, iy), (ix + 1, iy),
+ *      (ix, iy + 1), (ix + 1, iy + 1) carry the weights gx*gy, fx*gy, gx*fy, fx*fy; out_c starts at 0.0f and takes out_c = out_c + w * tex[corner][c] in that
+ *      order.  A corner whose indices have i + j > n + 1 is NOT READ and its term is left out: at a point of the face its weight is 0 in exact arithmetic, and the
+ *      texel belongs to a neighbour or to nobody, so whatever it holds (a NaN, too) never reaches the result.
+ *   Refused: what nrf_atlas_dims refuses; C out of range; a filter that is neither constant; p < 0; with p > 0 a null d_face, d_bary or d_out, or a null d_tex
+ *   where the atlas is not empty.  With n_faces == 0 every output is 0.
+ *
+ * nrf_texture_shade: deferred texturing of a nrf_raster_mesh result: d_face_map [h,w] int32 and d_bary_map [h,w,3] of the same d_verts, d_faces, K and c2w (HOST
+ *   values, as there), the atlas of (F, tile) -> d_out [h,w,C].  Per pixel:
+ *   1. f = face_map; f < 0 or f >= F, or a corner index outside [0, V): zeros.
+ *   2. zd_k of the three corners by step 1 of nrf_raster_mesh, the same expressions.
+ *   3. r_k = 1.0f / zd_k; p_k = b_k * r_k; S = (p0 + p1) + p2; beta_k = p_k / S: the barycentrics on the face, perspective-correct.
+ *   4. nrf_texture_sample's steps 2-5 at (f, beta), by the same device function.
+ *   Refused: what nrf_texture_sample refuses of (F, tile, C, filter); h or w < 1 or > NRF_RASTER_GUARD; V out of range; a null d_face_map, d_bary_map or d_out;
+ *   with F > 0 a null d_verts (V > 0), d_faces, K, c2w or d_tex. */
+#define NRF_ATLAS_MIN_TILE 4
+#define NRF_ATLAS_MAX_TILE 64
+#define NRF_ATLAS_MAX_SIZE 16384         /* the largest width or height */
+#define NRF_TEXTURE_MAX_CHANNELS 8
+#define NRF_TEXTURE_NEAREST 0
+#define NRF_TEXTURE_BILINEAR 1
+NRF_API int nrf_atlas_dims(int64_t n_faces, int tile, int *width, int *height);
+NRF_API int nrf_atlas_texels(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *d_normals, int tile, float offset, int row0,
+                             int rows, int32_t *d_face, float *d_bary, float *d_pos, float *d_rays, void *stream);
+NRF_API int nrf_texture_sample(const float *d_tex, int64_t n_faces, int tile, int channels, const int32_t *d_face, const float *d_bary, int64_t p, int filter,
+                               float *d_out, void *stream);
+NRF_API int nrf_texture_shade(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const int32_t *d_face_map, const float *d_bary_map, int h,
+                              int w, const float *K, const float *c2w, const float *d_tex, int tile, int channels, int filter, float *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Density gradient (normals.hip; the reference's calculate_normals, never finished there)
  * ------------------------------------------------------------------------------------------- */
 /* d_sigma [p] (may be NULL) = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at d_pts [p,3], bit for bit (keep mask of NeRFRenderer.h:187-188 included: it writes

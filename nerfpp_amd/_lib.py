@@ -204,6 +204,10 @@ _ABI = """
     nrf_ms_ssim(ppiiiidippzp)
     nrf_ssim_loss_workspace_bytes(iiii)->z
     nrf_ssim_loss(ppiiiiddppppzp)
+    nrf_atlas_dims(lipp)
+    nrf_atlas_texels(plplpifiippppp)
+    nrf_texture_sample(pliipplipp)
+    nrf_texture_shade(plplppiipppiiipp)
     nrf_density_grad_workspace_bytes(pl)->z
     nrf_density_grad(pplpppzp)
     nrf_render_rays_workspace_bytes(plp)->z

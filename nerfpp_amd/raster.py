@@ -101,21 +101,24 @@ def FilterVisible(mesh, views, **kw):
     return M._submesh(mesh, VisibleFaces(mesh, views, **kw), mesh.Relevancy)
 
 
-def EvaluateMesh(mesh, renderer, views, rparams, background=None, acc_min=0.5, **kw):
+def EvaluateMesh(mesh, renderer, views, rparams, background=None, acc_min=0.5, texture=None, **kw):
     """Score a mesh against the field it came from: every dataset.View is rendered twice, the field by RenderView and the mesh by RenderMeshView (same dims and K, so
     RenderFactor is honoured).  Returns float64 device tensors as EvaluateViews does, {name: [n_views], "mean_" + name: its mean} for
       psnr, ssim   metrics.PSNR / SSIM of the mesh's RGBMap over `background` (3 values; None: white if rparams.WhiteBkgr, else black) against the render's RGBMap;
       depth_error  the mean |depth_mesh - DepthMap / AccMap| over the pixels both hit (the render where AccMap >= acc_min); NaN where none is;
       iou          intersection over union of the two hit masks.
-    The mesh needs Colors.  NDC and LeRF renderers are refused as FuseViews refuses them."""
+    The mesh needs Colors -- or, with texture (a texture.TextureAtlas of three channels baked for this mesh), its RGBMap comes from the atlas through
+    texture.RenderMeshViewTextured and Colors is not read.  NDC and LeRF renderers are refused as FuseViews refuses them."""
     from . import metrics
     from .renderer import LeRFRenderer, RenderView
     if isinstance(renderer, LeRFRenderer):
         raise L.NrfError("EvaluateMesh: a LeRF renderer renders no colour; score against its NeRFRenderer")
     if rparams.Ndc:
         raise L.NrfError("EvaluateMesh: the depth of an NDC render is not metric (rparams.Ndc must be False)")
-    if mesh.Colors is None:
+    if texture is None and mesh.Colors is None:
         raise L.NrfError("EvaluateMesh: the mesh has no Colors to compare with the render")
+    if texture is not None and int(texture.Image.shape[-1]) != 3:
+        raise L.NrfError(f"EvaluateMesh: the texture must hold 3 channels to compare with the render, got {int(texture.Image.shape[-1])}")
     bg = (1.0, 1.0, 1.0) if background is None and rparams.WhiteBkgr else (0.0, 0.0, 0.0) if background is None else tuple(float(b) for b in background)
     kw["attrs"] = ("Colors",)
     names = ("psnr", "ssim", "depth_error", "iou")
@@ -123,7 +126,11 @@ def EvaluateMesh(mesh, renderer, views, rparams, background=None, acc_min=0.5, *
     dev = torch.device("cuda", torch.cuda.current_device())
     for v in views:
         o = RenderView(renderer, v.Pose, v.W, v.H, v.K, rparams).Outputs
-        m = RenderMeshView(mesh, v, rparams, **kw)
+        if texture is None:
+            m = RenderMeshView(mesh, v, rparams, **kw)
+        else:
+            from .texture import RenderMeshViewTextured
+            m = RenderMeshViewTextured(mesh, texture, v, rparams, **kw)
         h, w = m.DepthMap.shape
         acc_m = m.AccMap
         rgb_m = m.RGBMap + (1.0 - acc_m)[..., None] * torch.tensor(bg, device=acc_m.device, dtype=torch.float32)

@@ -917,6 +917,78 @@ NRF_API int nrf_texture_shade(const float *d_verts, int64_t n_verts, const int32
                               int w, const float *K, const float *c2w, const float *d_tex, int tile, int channels, int filter, float *d_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mesh adjacency, smoothing and vertex normals (smooth.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* The inverted index of a triangle list -- per vertex its faces and its neighbours -- and the two gathers that read it.  The workspace is the caller's, 8-byte
+ * aligned and sized by nrf_mesh_adjacency_workspace_bytes (0 for a refused shape); nothing is allocated; refusals -- NRF_ERR_INVALID_ARG or NRF_ERR_WORKSPACE, the
+ * message starting with the entry's name -- come before any launch or write; two runs give the same bits whatever the workspace and the outputs held; each
+ * source-level fp32 operation below is rounded once (no FMA contraction), / and sqrtf are correctly rounded.  V == 0 or F == 0 is valid everywhere.
+ *
+ * ADJACENCY of d_faces [F,3] int32 over n_verts = V vertices, 0 <= V, F < 2^31.  A face is skipped whole if it has a corner outside [0, V) (counted in stats[0];
+ * nothing of it is dereferenced) or, failing that, two equal corners (stats[1]); the others are the VALID faces.  Two valid faces with the same corners are two faces.
+ *   d_face_start [V+1] int64, d_face_list [n_incident] int32: row v = [d_face_start[v], d_face_start[v+1]) lists the valid faces with v as a corner in ascending face
+ *     index; n_incident = 3 * (valid faces) = d_face_start[V].
+ *   d_nbr_start [V+1] int64, d_nbr [n_neighbours] int32: row v lists the distinct vertices that share a valid face with v in ascending vertex index;
+ *     d_nbr_faces [n_neighbours] int32, beside d_nbr: the number of valid faces that contain that edge -- 1 a boundary edge, 2 an interior edge, more a non-manifold
+ *     one.  n_neighbours = d_nbr_start[V] = twice the number of undirected edges.
+ *   d_flags [V] uint8: NRF_ADJ_BOUNDARY where some edge of the vertex has exactly one face, NRF_ADJ_NONMANIFOLD where some edge has more than two; 0 for a vertex
+ *     no valid face uses.
+ *   d_stats [8] int64, WRITTEN: {faces skipped for a bad index, faces skipped for a repeated corner, used vertices, undirected edges, boundary edges, non-manifold
+ *     edges, the longest face row, the longest neighbour row}.
+ *   Every output but d_face_list is the same for any order of the faces and any rotation or reflection of their corners; d_face_list is ascending in the face
+ *   indices it is given.  Nothing depends on scheduling.
+ * nrf_mesh_adjacency_count builds the rows in the workspace and returns the two totals (its one synchronisation).  nrf_mesh_adjacency_emit takes them as the sizes
+ * of the caller's buffers: it reads the workspace's pair back (it waits for the stream once) and refuses any other pair before anything is written, as
+ * nrf_mesh_simplify_emit does.  Refused besides: V or F out of range, a null d_faces with F > 0, a null or misaligned workspace, a null out-parameter; in emit
+ * n_incident outside [0, 3F], n_neighbours outside [0, 6F], a null output that has elements (d_face_start, d_nbr_start and d_stats always have).
+ * MECHANISM.  Degrees by integer atomics, row starts by integer prefix sums, rows filled through an integer cursor in arrival order and then sorted by rank (the
+ * rank of an entry is the number of smaller ones, ties by position) -- first the faces of a row, then the 2 * len far ends of its half-edges, whose runs of equal
+ * values are the neighbours and their face counts.  A row of at most NRF_ADJ_SHORT_ROW faces is sorted by one lane, a longer one by one workgroup of 256 lanes
+ * (len^2 / 256 comparisons per lane: a hub of 4 096 faces is well under a millisecond's worth); the two paths run the same steps and give the same rows.
+ *
+ * nrf_mesh_smooth: Taubin's lambda|mu filter, or with mu == 0 the umbrella Laplacian, of d_x [V,C] fp32, 1 <= C <= NRF_SMOOTH_MAX_CHANNELS, over the neighbour rows
+ *   above (d_nbr_start, d_nbr, d_nbr_faces, d_flags of the same V; n_neighbours = the length of d_nbr).  d_out [V,C] gets the result, d_tmp [V,C] is scratch (its
+ *   final content is unspecified); d_x is not written.  iterations >= 0; 0 copies d_x to d_out.  One iteration is a step with factor lambda and then, if mu != 0, a
+ *   step with factor mu.  One step, per vertex i and channel, from x (the previous step's values; every vertex reads the same x):
+ *     1. J = the row of i in its stored order.  Under NRF_SMOOTH_CURVE a vertex with NRF_ADJ_BOUNDARY keeps only the neighbours with d_nbr_faces == 1: the boundary
+ *        smooths as a curve and does not slide into the interior.  Under NRF_SMOOTH_FIXED a vertex with NRF_ADJ_BOUNDARY is copied.  An empty J copies the vertex.
+ *     2. s = (..((x[j0] + x[j1]) + x[j2]) + ..), sequentially, at EVERY row length; m = s / (float)|J|; d = m - x[i]; out = x[i] + fl(f * d).
+ *   Non-finite values propagate by IEEE rules (the payload of a NaN is unspecified).  One launch per step, one lane per vertex, a gather with no atomics.  An entry of
+ *   d_nbr outside [0, V) and the part of a row outside [0, n_neighbours) are never dereferenced (rows of nrf_mesh_adjacency_emit have neither).  Under
+ *   NRF_SMOOTH_FREE d_nbr_faces and d_flags are not read and may be NULL; NRF_SMOOTH_FIXED reads d_flags alone.
+ *   Refused: V out of range, n_neighbours < 0, C, iterations < 0 or > 2^30 - 1 (the step count is an int), a lambda or mu that is not finite, a boundary mode
+ *   that is none of the three; with V > 0 a null d_x, d_out, d_tmp, d_nbr_start or an array the mode reads, two of d_x, d_out, d_tmp equal, or one of them not
+ *   aligned to a whole vertex (4, 8, 4, 16 bytes for C = 1 .. 4).
+ *
+ * nrf_mesh_vertex_normals: d_out [V,3] from d_verts [V,3], d_faces [F,3] and the face rows above (n_incident = the length of d_face_list).  Per face with corners
+ *   (a, b, c) in the face's own order: e1 = b - a, e2 = c - a, n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), each product rounded, then the
+ *   difference: outward for counter-clockwise faces.  NRF_NORMALS_AREA contributes n; NRF_NORMALS_UNIT contributes n / l per component with
+ *   l = sqrtf((nx*nx + ny*ny) + nz*nz), and zeros where l == 0.  Per vertex S = the contributions of its row added sequentially in ascending face index (the first
+ *   one starts the sum); len = sqrtf((Sx*Sx + Sy*Sy) + Sz*Sz); out = S / len per component, zeros where len == 0 or the row is empty.
+ *   The sum follows the order of the faces: the result is deterministic, NOT invariant under a permutation of the faces.
+ *   An entry of the row outside [0, F) or a face with a corner outside [0, V) is skipped, never dereferenced.  Refused: V or F out of range, n_incident outside
+ *   [0, 3F], a weighting that is neither constant; with V > 0 a null d_verts, d_face_start, d_out, d_faces (F > 0) or d_face_list (n_incident > 0), d_out == d_verts. */
+#define NRF_ADJ_BOUNDARY 1
+#define NRF_ADJ_NONMANIFOLD 2
+#define NRF_ADJ_SHORT_ROW 32             /* face rows up to this length are sorted by one lane, longer ones by one workgroup */
+#define NRF_SMOOTH_MAX_CHANNELS 4
+#define NRF_SMOOTH_FREE 0
+#define NRF_SMOOTH_FIXED 1
+#define NRF_SMOOTH_CURVE 2
+#define NRF_NORMALS_AREA 0
+#define NRF_NORMALS_UNIT 1
+NRF_API size_t nrf_mesh_adjacency_workspace_bytes(int64_t n_verts, int64_t n_faces);
+NRF_API int nrf_mesh_adjacency_count(const int32_t *d_faces, int64_t n_verts, int64_t n_faces, int64_t *n_incident, int64_t *n_neighbours, void *d_workspace,
+                                     size_t workspace_bytes, void *stream);
+NRF_API int nrf_mesh_adjacency_emit(const int32_t *d_faces, int64_t n_verts, int64_t n_faces, int64_t n_incident, int64_t n_neighbours, int64_t *d_face_start,
+                                    int32_t *d_face_list, int64_t *d_nbr_start, int32_t *d_nbr, int32_t *d_nbr_faces, uint8_t *d_flags, int64_t *d_stats,
+                                    void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_mesh_smooth(const float *d_x, float *d_out, float *d_tmp, int64_t n_verts, int channels, int iterations, float lambda, float mu, int boundary,
+                            const int64_t *d_nbr_start, const int32_t *d_nbr, const int32_t *d_nbr_faces, const uint8_t *d_flags, int64_t n_neighbours, void *stream);
+NRF_API int nrf_mesh_vertex_normals(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const int64_t *d_face_start,
+                                    const int32_t *d_face_list, int64_t n_incident, int weighting, float *d_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Density gradient (normals.hip; the reference's calculate_normals, never finished there)
  * ------------------------------------------------------------------------------------------- */
 /* d_sigma [p] (may be NULL) = raw[..., 3] of nrf_run_network(NRF_PREC_F32) at d_pts [p,3], bit for bit (keep mask of NeRFRenderer.h:187-188 included: it writes

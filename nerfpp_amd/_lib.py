@@ -208,6 +208,11 @@ _ABI = """
     nrf_atlas_texels(plplpifiippppp)
     nrf_texture_sample(pliipplipp)
     nrf_texture_shade(plplppiipppiiipp)
+    nrf_mesh_adjacency_workspace_bytes(ll)->z
+    nrf_mesh_adjacency_count(pllpppzp)
+    nrf_mesh_adjacency_emit(pllllppppppppzp)
+    nrf_mesh_smooth(pppliiffipppplp)
+    nrf_mesh_vertex_normals(plplpplipp)
     nrf_density_grad_workspace_bytes(pl)->z
     nrf_density_grad(pplpppzp)
     nrf_render_rays_workspace_bytes(plp)->z

@@ -296,30 +296,11 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_sp_stats(int64_t nb, const uint4
     if (threadIdx.x < 4 && sh[threadIdx.x]) atomicAdd(stats + threadIdx.x, sh[threadIdx.x]);
 }
 
-// one workgroup: exclusive scan of bsum[0 .. nb) in place; *total = the sum.  Every thread takes SCAN_ITEMS consecutive entries, so a mesh of 11 M faces (44 k block
-// totals) is six rounds of the block scan, not forty-four
+// one workgroup: exclusive scan of bsum[0 .. nb) in place; *total = the sum (scan.h)
 __global__ void __launch_bounds__(SCAN_BLOCK) k_sp_scan(int64_t nb, int64_t *__restrict__ bsum, int64_t *__restrict__ total)
 {
     __shared__ int64_t sh[SCAN_BLOCK];
-    int64_t carry = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += (int64_t)SCAN_BLOCK * SCAN_ITEMS) {
-        const int64_t first = b0 + (int64_t)threadIdx.x * SCAN_ITEMS;
-        int64_t v[SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; k++) {
-            v[k] = first + k < nb ? bsum[first + k] : 0;
-            sum += v[k];
-        }
-        int64_t t;
-        int64_t run = carry + block_exclusive_scan<int64_t, SCAN_BLOCK>(sum, sh, t);
-#pragma unroll
-        for (int k = 0; k < SCAN_ITEMS; k++) {
-            if (first + k < nb) bsum[first + k] = run;
-            run += v[k];
-        }
-        carry += t;
-    }
-    if (threadIdx.x == 0) *total = carry;
+    block_totals_scan<int64_t, SCAN_BLOCK, SCAN_ITEMS>(nb, bsum, total, sh);
 }
 
 __global__ void __launch_bounds__(SP_BLOCK) k_sp_cell_sums(int64_t cells, const int32_t *__restrict__ cellid, int64_t *__restrict__ cbsum)

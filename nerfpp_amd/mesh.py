@@ -1,5 +1,5 @@
-"""Mesh export: DensityGrid, Isosurface, ExtractMesh, MeshComponents, FilterComponents, SimplifyMesh, SimplifyToFaces and SavePLY over the C ABI
-(include/nerfpp_hip.h, mesh.hip, components.hip, simplify.hip).
+"""Mesh export: DensityGrid, Isosurface, ExtractMesh, MeshComponents, FilterComponents, SimplifyMesh, SimplifyToFaces, BuildAdjacency, MeshTopology,
+VertexNormals, SmoothMesh, SmoothAttributes and SavePLY over the C ABI (include/nerfpp_hip.h, mesh.hip, components.hip, simplify.hip, smooth.hip).
 
 The reference has no mesh export; the names follow the mirror's style.  The density lattice is the exact-fp32 sigma of the renderer's network
 (== RunNetwork(..., NRF_PREC_F32)[..., 3] bit for bit); the isosurface is marching tetrahedra on the Kuhn split of each cell, in an order fixed by integer
@@ -21,6 +21,13 @@ COLOR_CHUNK = 1 << 18        # vertices per RunNetwork call of ExtractMesh
 # NRF_SIMPLIFY_* of the header (tests/test_simplify_host.py holds them to it)
 SIMPLIFY_MAX_DIM, SIMPLIFY_MAX_CELLS, SIMPLIFY_POS_MEAN, SIMPLIFY_POS_MEMBER = 1024, 1 << 27, 0, 1
 _POSITIONS = {"mean": SIMPLIFY_POS_MEAN, "member": SIMPLIFY_POS_MEMBER}
+# NRF_ADJ_* / NRF_SMOOTH_* / NRF_NORMALS_* of the header (tests/test_smooth_host.py holds them to it)
+ADJ_BOUNDARY, ADJ_NONMANIFOLD, ADJ_SHORT_ROW, SMOOTH_MAX_CHANNELS = 1, 2, 32, 4
+SMOOTH_FREE, SMOOTH_FIXED, SMOOTH_CURVE = 0, 1, 2
+NORMALS_AREA, NORMALS_UNIT = 0, 1
+_BOUNDARIES = {"free": SMOOTH_FREE, "fixed": SMOOTH_FIXED, "curve": SMOOTH_CURVE}
+_WEIGHTINGS = {"area": NORMALS_AREA, "unit": NORMALS_UNIT}
+_ATTRIBUTES = ("Colors", "Relevancy")
 
 
 @dataclass
@@ -119,14 +126,19 @@ def _safe_normalize(v, eps=1e-8):
 
 
 def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, precision=L.NRF_PREC_F32, normals="lattice", keep_largest=None,
-                min_component_faces=0, simplify_cell=None):
+                min_component_faces=0, simplify_cell=None, smooth_iterations=0):
     """DensityGrid -> Isosurface -> per-vertex colour: sigmoid of RunNetwork's rgb at the vertex seen along -normal (a ray hitting the surface head-on), in chunks.
     normals="lattice": the isosurface's central-difference normals; "field": -safe_normalize(DensityGradient(vertices)), the field's own analytic normal
     (also the colour's view direction).  keep_largest / min_component_faces: FilterComponents on the bare isosurface, before the field normals and the colours,
     so a dropped floater costs no network evaluation.  simplify_cell: SimplifyMesh(cell_size=simplify_cell) after that filter and before the field normals and the
-    colours, for the same reason; the lattice normals of the result are those of each cluster's representative."""
+    colours, for the same reason; the lattice normals of the result are those of each cluster's representative.  smooth_iterations > 0: SmoothMesh(iterations=
+    smooth_iterations) with its defaults after both and before the colours; the normals are then VertexNormals of the smoothed faces whatever `normals` says (neither
+    the lattice's nor the field's belong to the moved geometry).  0 (the default) issues no call."""
     if normals not in ("lattice", "field"):
         raise L.NrfError(f"ExtractMesh: normals must be 'lattice' or 'field', got {normals!r}")
+    smooth_iterations = int(smooth_iterations)
+    if smooth_iterations < 0:
+        raise L.NrfError(f"ExtractMesh: smooth_iterations must be >= 0, got {smooth_iterations}")
     bb = _bbox(renderer, bbox)
     sigma = DensityGrid(renderer, bb, resolution)
     verts, faces, lattice_normals = Isosurface(sigma, bb, threshold)
@@ -137,7 +149,11 @@ def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, pre
     if simplify_cell is not None:
         small = SimplifyMesh(Mesh(verts, faces, lattice_normals), cell_size=simplify_cell)
         verts, faces, lattice_normals = small.Vertices, small.Faces, small.Normals
-    normals = lattice_normals if normals == "lattice" else -_safe_normalize(DensityGradient(renderer, verts)[1])
+    if smooth_iterations > 0:
+        smooth = SmoothMesh(Mesh(verts, faces, lattice_normals), iterations=smooth_iterations)
+        verts, normals = smooth.Vertices, smooth.Normals
+    else:
+        normals = lattice_normals if normals == "lattice" else -_safe_normalize(DensityGradient(renderer, verts)[1])
     rgb = None
     if colors:
         rgb = torch.empty_like(verts)
@@ -332,6 +348,150 @@ def SimplifyToFaces(mesh, target_faces, position="mean"):
             hi = mid
     s.count(*grid(lo))
     return _simplified(mesh, s, pos, False), lo
+
+
+@dataclass
+class MeshAdjacency:
+    """nrf_mesh_adjacency_*: the rows of the header's ADJACENCY, device tensors"""
+    FaceStart: torch.Tensor      # [V + 1] int64
+    FaceList: torch.Tensor       # [3 * valid faces] int32: per vertex its valid faces, ascending
+    NbrStart: torch.Tensor       # [V + 1] int64
+    Nbr: torch.Tensor            # [2 * edges] int32: per vertex its distinct neighbours, ascending
+    NbrFaces: torch.Tensor       # [2 * edges] int32: the faces on that edge (1 boundary, 2 interior, more non-manifold)
+    Flags: torch.Tensor          # [V] uint8: ADJ_BOUNDARY | ADJ_NONMANIFOLD, 0 for an unused vertex
+    Stats: torch.Tensor          # [8] int64: bad-index faces, repeated-corner faces, used vertices, edges, boundary edges, non-manifold edges, longest rows
+    NumVerts: int
+    NumFaces: int
+
+    @property
+    def stats(self):
+        """Stats as a dict of Python ints (one host synchronisation)"""
+        names = ("bad_index", "repeated_corner", "used_vertices", "edges", "boundary_edges", "nonmanifold_edges", "longest_face_row", "longest_nbr_row")
+        return dict(zip(names, (int(v) for v in self.Stats.cpu().tolist())))
+
+
+def _faces_of(mesh_or_faces, n_verts, who):
+    """(faces [F, 3] int32 contiguous on the GPU, V) of a Mesh or of faces over n_verts vertices (default: the largest index + 1)"""
+    if isinstance(mesh_or_faces, Mesh):
+        faces, v = mesh_or_faces.Faces, int(mesh_or_faces.Vertices.shape[0]) if n_verts is None else int(n_verts)
+    else:
+        faces = torch.as_tensor(mesh_or_faces)
+        v = (max(int(faces.max()) + 1, 0) if faces.numel() else 0) if n_verts is None else int(n_verts)
+    if faces.numel() % 3 != 0 or v < 0:
+        raise L.NrfError(f"{who}: faces must be [F, 3] and n_verts >= 0, got {tuple(faces.shape)} and {v}")
+    dev = faces.device if faces.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return faces.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous(), v
+
+
+def BuildAdjacency(mesh_or_faces, n_verts=None):
+    """nrf_mesh_adjacency_count / _emit: the MeshAdjacency of a Mesh or of faces [F, 3] over n_verts vertices (default: the largest index + 1).  A face with a
+    corner outside [0, n_verts) or with two equal corners is left out and counted.  Every array but FaceList is the same for any order of the faces; two runs give
+    the same bits."""
+    faces, v = _faces_of(mesh_or_faces, n_verts, "BuildAdjacency")
+    f, dev, lib = int(faces.shape[0]), faces.device, L.lib()
+    ws = torch.empty((max(1, int(lib.nrf_mesh_adjacency_workspace_bytes(v, f))),), device=dev, dtype=torch.uint8)
+    ni, nn = C.c_int64(0), C.c_int64(0)
+    L.check(lib.nrf_mesh_adjacency_count(_ptr(faces), v, f, C.addressof(ni), C.addressof(nn), _ptr(ws), ws.numel(), _stream()))
+    ni, nn = int(ni.value), int(nn.value)
+    adj = MeshAdjacency(torch.empty((v + 1,), device=dev, dtype=torch.int64), torch.empty((ni,), device=dev, dtype=torch.int32),
+                        torch.empty((v + 1,), device=dev, dtype=torch.int64), torch.empty((nn,), device=dev, dtype=torch.int32),
+                        torch.empty((nn,), device=dev, dtype=torch.int32), torch.empty((v,), device=dev, dtype=torch.uint8),
+                        torch.empty((8,), device=dev, dtype=torch.int64), v, f)
+    L.check(lib.nrf_mesh_adjacency_emit(_ptr(faces), v, f, ni, nn, _ptr(adj.FaceStart), _ptr(adj.FaceList), _ptr(adj.NbrStart), _ptr(adj.Nbr), _ptr(adj.NbrFaces),
+                                        _ptr(adj.Flags), _ptr(adj.Stats), _ptr(ws), ws.numel(), _stream()))
+    return adj
+
+
+def MeshTopology(mesh_or_adjacency):
+    """How a mesh hangs together, from the adjacency's statistics (one host synchronisation): vertices_used, edges, faces_valid, boundary_edges,
+    nonmanifold_edges, euler = vertices_used - edges + faces_valid, closed (no boundary edge) and manifold (no edge with more than two faces)."""
+    adj = mesh_or_adjacency if isinstance(mesh_or_adjacency, MeshAdjacency) else BuildAdjacency(mesh_or_adjacency)
+    s = adj.stats
+    faces_valid = adj.NumFaces - s["bad_index"] - s["repeated_corner"]
+    return dict(vertices_used=s["used_vertices"], edges=s["edges"], faces_valid=faces_valid, boundary_edges=s["boundary_edges"],
+                nonmanifold_edges=s["nonmanifold_edges"], euler=s["used_vertices"] - s["edges"] + faces_valid, closed=s["boundary_edges"] == 0,
+                manifold=s["nonmanifold_edges"] == 0)
+
+
+def _adjacency_for(mesh, adjacency, who):
+    adj = BuildAdjacency(mesh) if adjacency is None else adjacency
+    if not isinstance(adj, MeshAdjacency) or adj.NumVerts != int(mesh.Vertices.shape[0]) or adj.NumFaces != int(mesh.Faces.shape[0]):
+        raise L.NrfError(f"{who}: the adjacency is not a MeshAdjacency of this mesh's {int(mesh.Vertices.shape[0])} vertices and {int(mesh.Faces.shape[0])} faces")
+    return adj
+
+
+def VertexNormals(mesh, weighting="area", adjacency=None):
+    """nrf_mesh_vertex_normals: [V, 3] unit normals from the faces -- per vertex the sum of its faces' e1 x e2 ("area": weighted by twice the face area; "unit":
+    every face alike), added in ascending face index and normalised; 0 for a vertex without a face or with a vanishing sum.  Outward for the counter-clockwise
+    faces of this package.  Deterministic, not invariant under a permutation of the faces."""
+    if weighting not in _WEIGHTINGS:
+        raise L.NrfError(f"VertexNormals: weighting must be 'area' or 'unit', got {weighting!r}")
+    adj = _adjacency_for(mesh, adjacency, "VertexNormals")
+    verts = _dev_f32(mesh.Vertices).reshape(-1, 3)
+    faces = mesh.Faces.to(device=verts.device, dtype=torch.int32).reshape(-1, 3).contiguous()
+    out = torch.empty_like(verts)
+    L.check(L.lib().nrf_mesh_vertex_normals(_ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0], _ptr(adj.FaceStart), _ptr(adj.FaceList), adj.FaceList.numel(),
+                                            _WEIGHTINGS[weighting], _ptr(out), _stream()))
+    return out
+
+
+def _smooth_args(who, iterations, lam, mu, boundary):
+    iterations, lam, mu = int(iterations), float(lam), float(mu)
+    if boundary not in _BOUNDARIES:
+        raise L.NrfError(f"{who}: boundary must be 'free', 'fixed' or 'curve', got {boundary!r}")
+    if iterations < 0 or not (math.isfinite(lam) and math.isfinite(mu)):
+        raise L.NrfError(f"{who}: iterations must be >= 0 and lam, mu finite, got {iterations}, {lam}, {mu}")
+    return iterations, lam, mu, _BOUNDARIES[boundary]
+
+
+def _smooth(who, x, adj, iterations, lam, mu, boundary):
+    """nrf_mesh_smooth of x [V] or [V, C], C <= SMOOTH_MAX_CHANNELS -> a new tensor of x's shape"""
+    x = _dev_f32(x)
+    v = adj.NumVerts
+    if x.dim() not in (1, 2) or x.shape[0] != v or not 1 <= (x.shape[1] if x.dim() == 2 else 1) <= SMOOTH_MAX_CHANNELS:
+        raise L.NrfError(f"{who}: a smoothed array must be [{v}] or [{v}, 1 .. {SMOOTH_MAX_CHANNELS}], got {tuple(x.shape)}")
+    x = x.contiguous()
+    out, tmp = torch.empty_like(x), torch.empty_like(x)
+    L.check(L.lib().nrf_mesh_smooth(_ptr(x), _ptr(out), _ptr(tmp), v, x.shape[1] if x.dim() == 2 else 1, iterations, lam, mu, boundary, _ptr(adj.NbrStart), _ptr(adj.Nbr),
+                                    _ptr(adj.NbrFaces), _ptr(adj.Flags), adj.Nbr.numel(), _stream()))
+    return out
+
+
+def _attributes(who, mesh, names):
+    names = (names,) if isinstance(names, str) else tuple(names)
+    for n in names:
+        if n not in _ATTRIBUTES or getattr(mesh, n) is None:
+            raise L.NrfError(f"{who}: {n!r} is not an attribute this mesh carries (of {_ATTRIBUTES})")
+    return names
+
+
+def SmoothMesh(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="curve", attributes=(), recompute_normals=True, adjacency=None):
+    """nrf_mesh_smooth on the vertices: Taubin's lambda|mu filter -- per iteration a step x += lam * (mean of the neighbours - x), then one with mu < -lam that undoes
+    the shrinkage; mu=0 is the plain Laplacian, which shrinks.  boundary: "free" treats every vertex alike, "fixed" leaves the vertices of boundary edges where they
+    are, "curve" smooths them along the boundary only (over their neighbours across boundary edges).  Faces are unchanged.  attributes: names of "Colors" /
+    "Relevancy" to smooth by the same call; the others are carried as they are.  Normals are VertexNormals of the new geometry unless recompute_normals=False.
+    adjacency: BuildAdjacency(mesh) when not given.  Sums run over the neighbours in ascending index, no atomics: two runs give the same bits."""
+    iterations, lam, mu, mode = _smooth_args("SmoothMesh", iterations, lam, mu, boundary)
+    names = _attributes("SmoothMesh", mesh, attributes)
+    adj = _adjacency_for(mesh, adjacency, "SmoothMesh")
+    out = Mesh(_smooth("SmoothMesh", mesh.Vertices.reshape(-1, 3), adj, iterations, lam, mu, mode), mesh.Faces, mesh.Normals, mesh.Colors, mesh.Relevancy)
+    for n in names:
+        setattr(out, n, _smooth("SmoothMesh", getattr(mesh, n), adj, iterations, lam, mu, mode))
+    if recompute_normals:
+        out.Normals = VertexNormals(out, adjacency=adj)
+    return out
+
+
+def SmoothAttributes(mesh, names, iterations, lam=0.5, mu=0.0, boundary="free", adjacency=None):
+    """nrf_mesh_smooth on the named attributes ("Colors", "Relevancy") alone: vertices, faces and normals are the input's own tensors.  Made to denoise
+    query.VertexRelevancy before query.SegmentMesh; the defaults are the plain Laplacian, which only averages."""
+    iterations, lam, mu, mode = _smooth_args("SmoothAttributes", iterations, lam, mu, boundary)
+    names = _attributes("SmoothAttributes", mesh, names)
+    adj = _adjacency_for(mesh, adjacency, "SmoothAttributes")
+    out = Mesh(mesh.Vertices, mesh.Faces, mesh.Normals, mesh.Colors, mesh.Relevancy)
+    for n in names:
+        setattr(out, n, _smooth("SmoothAttributes", getattr(mesh, n), adj, iterations, lam, mu, mode))
+    return out
 
 
 def SavePLY(path, mesh):

@@ -6,7 +6,7 @@
 //   k_cc_union_*   one thread per face: union(v0, v1), union(v1, v2); one thread per set lattice point: union with its set neighbours of the forward
 //                  half-neighbourhood (every undirected edge once)
 //   k_cc_resolve   root[i] = the root of i, by pointer chasing, into the label array; per-block count of the roots (root[i] == i) among the items that take part
-//   k_cc_scan      one workgroup: exclusive scan of the per-block counts; header[0] = K
+//   k_totals_scan  (scan.h) one workgroup: exclusive scan of the per-block counts; header[0] = K
 //   k_cc_rank      rank of every root = its block's offset + the count of roots before it in the block (written over parent, which is dead by then)
 //   k_cc_label     label[i] = rank[root[i]]
 // Invariants of the union launch:
@@ -31,7 +31,6 @@ namespace nrf {
 namespace {
 
 constexpr int CC_BLOCK = 256;
-constexpr int SCAN_BLOCK = 1024;
 
 __device__ __forceinline__ int32_t load_parent(const int32_t *parent, int32_t x) { return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -108,26 +107,6 @@ __global__ void __launch_bounds__(CC_BLOCK) k_cc_union_lattice(Lattice g, const 
     }
 }
 
-// count of set flags in the block before this thread's; `total` = the block's count
-__device__ __forceinline__ int block_rank(bool flag, int *sh, int &total)
-{
-    constexpr int NW = CC_BLOCK / 64;
-    const unsigned long long bal = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sh[wave] = __popcll(bal);
-    __syncthreads();
-    int before = __popcll(bal & ((1ull << lane) - 1ull));
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-        const int c = sh[w];
-        if (w < wave) before += c;
-        total += c;
-    }
-    __syncthreads();
-    return before;
-}
-
 // takes part: mask[i] != 0 (lattice) or label[i] != -1 (mesh: a face marked it).  label[i] = root, -1 for the others; bsum[block] = roots in the block
 __global__ void __launch_bounds__(CC_BLOCK) k_cc_resolve(int64_t n, const int32_t *__restrict__ parent, const uint8_t *__restrict__ mask, int32_t *__restrict__ label,
                                                          int32_t *__restrict__ bsum)
@@ -144,24 +123,8 @@ __global__ void __launch_bounds__(CC_BLOCK) k_cc_resolve(int64_t n, const int32_
         label[i] = r;
         is_root = r == (int32_t)i;
     }
-    int total;
-    (void)block_rank(is_root, sh, total);
+    const int total = block_count<CC_BLOCK>(is_root, sh);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one workgroup: exclusive scan of the per-block counts in place; header[0] = K
-__global__ void __launch_bounds__(SCAN_BLOCK) k_cc_scan(int64_t nb, int32_t *__restrict__ bsum, int64_t *__restrict__ header)
-{
-    __shared__ int sh[SCAN_BLOCK];
-    int carry = 0;                                          // K <= n < 2^31
-    for (int64_t b0 = 0; b0 < nb; b0 += SCAN_BLOCK) {
-        const int64_t b = b0 + threadIdx.x;
-        int total;
-        const int e = block_exclusive_scan<int, SCAN_BLOCK>(b < nb ? bsum[b] : 0, sh, total);
-        if (b < nb) bsum[b] = carry + e;
-        carry += total;
-    }
-    if (threadIdx.x == 0) header[0] = carry;
 }
 
 __global__ void __launch_bounds__(CC_BLOCK) k_cc_rank(int64_t n, const int32_t *__restrict__ label, const int32_t *__restrict__ bsum, int32_t *__restrict__ rank)
@@ -170,7 +133,7 @@ __global__ void __launch_bounds__(CC_BLOCK) k_cc_rank(int64_t n, const int32_t *
     const int64_t i = (int64_t)blockIdx.x * CC_BLOCK + threadIdx.x;
     const bool is_root = i < n && label[i] == (int32_t)i;
     int total;
-    const int before = block_rank(is_root, sh, total);
+    const int before = block_rank<CC_BLOCK>(is_root, sh, total);
     if (is_root) rank[i] = bsum[blockIdx.x] + before;
 }
 
@@ -204,7 +167,7 @@ int cc_finish(const CcWs &w, int64_t n, const uint8_t *mask, int32_t *label, int
     const dim3 grid((unsigned)w.nb), block(CC_BLOCK);
     hipLaunchKernelGGL(k_cc_resolve, grid, block, 0, st, n, w.parent, mask, label, w.bsum);
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, w.nb, w.bsum, w.header);
+    hipLaunchKernelGGL((k_totals_scan<int32_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, w.nb, w.bsum, w.header);          // K <= n < 2^31; header[0] = K
     NRF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_cc_rank, grid, block, 0, st, n, label, w.bsum, w.parent);
     NRF_LAUNCH_CHECK();

@@ -3,12 +3,12 @@
 // stated in include/nerfpp_hip.h and restated in numpy by tests/geometry_ref.py, which the GPU tests compare with bit for bit.
 //
 // Sampling.  k_sample_faces: one lane per face -- indices checked before anything is read, the fp32 area, the face's point count n_f (floor of area * density plus
-//   one Bernoulli draw of the fraction), the block's total of n_f and its ordered fp64 sum of the areas.  k_geo_scan (one workgroup) turns the block totals into block
+//   one Bernoulli draw of the fraction), the block's total of n_f and its ordered fp64 sum of the areas.  k_totals_scan (scan.h, one workgroup) turns the block totals into block
 //   offsets, k_geo_finish adds the area partials in image_metrics.hip's order, k_sample_offsets writes every face's first point.  The emit kernel runs one lane per
 //   POINT and finds its face by a binary search in the offsets: a face clamped to NRF_SAMPLE_MAX_PER_FACE points costs its lanes nothing extra.  Every position comes
 //   from an integer prefix sum and every draw is a pure function of (seed, stream, index): two runs give the same arrays.
-// Nearest points.  A uniform grid over the caller's box: k_nn_bin<0> (one non-returning atomic add per finite target), the scan of the cell counts (k_nn_cell_sums,
-//   k_geo_scan, k_nn_cell_starts), k_nn_bin<1> (16-byte records {x, y, z, index} in cell order; the order INSIDE a cell is whatever the atomics gave).  k_nn_query:
+// Nearest points.  A uniform grid over the caller's box: k_nn_bin<0> (one non-returning atomic add per finite target), the scan of the cell counts (scan.h's k_block_sums
+//   and k_totals_scan, then k_nn_cell_starts), k_nn_bin<1> (16-byte records {x, y, z, index} in cell order; the order INSIDE a cell is whatever the atomics gave).  k_nn_query:
 //   one lane per query scans rings of cells outward, every ring as contiguous runs of records (the x-neighbours of a row are one range of the start array), keeps the
 //   minimum of ((uint64)float_bits(d2) << 32) | index and stops by the rule the header proves.  A query still open after NRF_NN_MAX_RINGS rings is appended to a list
 //   (ballot, popcount, one returning atomic per wave); k_nn_far, a fixed grid of workgroups, brute-forces all records for each listed query with a block-wide minimum.
@@ -30,29 +30,12 @@ namespace nrf {
 namespace {
 
 constexpr int GEO_BLOCK = 256;
-constexpr int SCAN_BLOCK = 1024;
 constexpr int FAR_GRID = 1024;           // workgroups of k_nn_far: 4 per CU
 constexpr int STATS_TILE = 4096;         // entries per block of k_dist_stats
 constexpr int STATS_VALUES = 8;          // count, sum d, sum d2, max d, four tau counts
 constexpr unsigned long long NN_NONE = ((unsigned long long)0x7f800000u << 32) | 0xffffffffu;          // d2 = +inf, index = -1: above every key with a valid index
 
-// ---------------------------------------------------------------------------------------------- shared: scan of block totals, ordered fp64 sums
-// one workgroup: exclusive scan of bsum[0 .. nb) in place; *total = the sum
-__global__ void __launch_bounds__(SCAN_BLOCK) k_geo_scan(int64_t nb, int64_t *__restrict__ bsum, int64_t *__restrict__ total)
-{
-    __shared__ int64_t sh[SCAN_BLOCK];
-    int64_t carry = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += SCAN_BLOCK) {
-        const int64_t b = b0 + threadIdx.x;
-        const int64_t v = b < nb ? bsum[b] : 0;
-        int64_t t;
-        const int64_t e = block_exclusive_scan<int64_t, SCAN_BLOCK>(v, sh, t);
-        if (b < nb) bsum[b] = carry + e;
-        carry += t;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
+// ---------------------------------------------------------------------------------------------- shared: ordered fp64 sums
 // the block's sum of one double per lane: wave shuffle tree, then the four wave sums in wave order (valid in thread 0)
 __device__ __forceinline__ double block_sum_ordered(double v, double *s_wave)
 {
@@ -141,7 +124,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_sample_faces(const float *__restr
                                                             uint64_t seed, int32_t *__restrict__ count, int64_t *__restrict__ bsum, double *__restrict__ area_part,
                                                             uint32_t *__restrict__ stats)
 {
-    __shared__ int sh[GEO_BLOCK];
+    __shared__ int sh[GEO_BLOCK / 64];
     __shared__ double s_wave[GEO_BLOCK / 64];
     const int64_t f = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
     int n = 0, cls = -1;          // class 0 bad index, 1 non-finite, 2 clamped
@@ -174,17 +157,14 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_sample_faces(const float *__restr
         }
         count[f] = n;
     }
-    int total, t0, t1, t2;
-    (void)block_exclusive_scan<int, GEO_BLOCK>(n, sh, total);
+    const int total = block_sum<int, GEO_BLOCK>(n, sh);
     const double part = block_sum_ordered(area64, s_wave);
     if (threadIdx.x == 0) {
         bsum[blockIdx.x] = total;
         area_part[blockIdx.x] = part;
     }
     if (!stats) return;          // uniform
-    (void)block_exclusive_scan<int, GEO_BLOCK>(cls == 0, sh, t0);
-    (void)block_exclusive_scan<int, GEO_BLOCK>(cls == 1, sh, t1);
-    (void)block_exclusive_scan<int, GEO_BLOCK>(cls == 2, sh, t2);
+    const int t0 = block_count<GEO_BLOCK>(cls == 0, sh), t1 = block_count<GEO_BLOCK>(cls == 1, sh), t2 = block_count<GEO_BLOCK>(cls == 2, sh);
     if (threadIdx.x == 0) {          // counts: their values do not depend on the order of the additions
         if (t0) atomicAdd(stats + 0, (uint32_t)t0);
         if (t1) atomicAdd(stats + 1, (uint32_t)t1);
@@ -326,9 +306,9 @@ template <int PASS>
 __global__ void __launch_bounds__(GEO_BLOCK) k_nn_bin(const float *__restrict__ target, int64_t nt, NnGrid g, uint32_t *__restrict__ cell_word, float4 *__restrict__ rec,
                                                       uint32_t *__restrict__ stats)
 {
-    __shared__ int sh[GEO_BLOCK];
+    __shared__ int sh[GEO_BLOCK / 64];
     const int64_t j = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
-    int bad = 0;
+    bool bad = false;
     if (j < nt) {
         const float x = target[j * 3 + 0], y = target[j * 3 + 1], z = target[j * 3 + 2];
         if (isfinite(x) && isfinite(y) && isfinite(z)) {
@@ -340,22 +320,12 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_nn_bin(const float *__restrict__ 
                 rec[at] = make_float4(x, y, z, __uint_as_float((uint32_t)j));
             }
         } else {
-            bad = 1;
+            bad = true;
         }
     }
     if (PASS != 0 || !stats) return;          // uniform
-    int total;
-    (void)block_exclusive_scan<int, GEO_BLOCK>(bad, sh, total);
+    const int total = block_count<GEO_BLOCK>(bad, sh);
     if (threadIdx.x == 0 && total) atomicAdd(stats + 1, (uint32_t)total);
-}
-
-__global__ void __launch_bounds__(GEO_BLOCK) k_nn_cell_sums(int64_t cells, const uint32_t *__restrict__ count, int64_t *__restrict__ bsum)
-{
-    __shared__ int sh[GEO_BLOCK];
-    const int64_t c = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
-    int total;
-    (void)block_exclusive_scan<int, GEO_BLOCK>(c < cells ? (int)count[c] : 0, sh, total);          // a block holds at most nt < 2^31 targets
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
 // counts -> starts in place (start[cells] = the number of records), and the scatter's cursors
@@ -377,7 +347,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_nn_query(const float *__restrict_
                                                         const float4 *__restrict__ rec, float *__restrict__ dist2, int32_t *__restrict__ index, int32_t *__restrict__ far,
                                                         uint32_t *__restrict__ n_far, uint32_t *__restrict__ stats)
 {
-    __shared__ int sh[GEO_BLOCK];
+    __shared__ int sh[GEO_BLOCK / 64];
     const int64_t q = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool live = q < nq;
@@ -433,8 +403,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_nn_query(const float *__restrict_
         index[q] = (int32_t)(uint32_t)best;
     }
     if (!stats) return;          // uniform
-    int total;
-    (void)block_exclusive_scan<int, GEO_BLOCK>(live && !finite, sh, total);
+    const int total = block_count<GEO_BLOCK>(live && !finite, sh);
     if (threadIdx.x == 0 && total) atomicAdd(stats + 0, (uint32_t)total);
 }
 
@@ -551,7 +520,7 @@ int nrf_mesh_sample_count(const float *d_verts, int64_t n_verts, const int32_t *
         hipLaunchKernelGGL(k_sample_faces, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, density, seed, ws.count, ws.bsum, ws.area,
                            d_stats);
         NRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_geo_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, nb, ws.bsum, ws.header);
+        hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, nb, ws.bsum, ws.header);
         NRF_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_geo_finish, dim3(1), dim3(GEO_BLOCK), 0, st, nb, 1, -1, (const double *)ws.area, reinterpret_cast<double *>(ws.header + 1), 1);
         NRF_LAUNCH_CHECK();
@@ -635,9 +604,9 @@ int nrf_nearest_points(const float *d_query, int64_t nq, const float *d_target, 
         const unsigned tb = (unsigned)ceil_div(nt, GEO_BLOCK);
         hipLaunchKernelGGL(k_nn_bin<0>, dim3(tb), dim3(GEO_BLOCK), 0, st, d_target, nt, g, ws.start, ws.rec, d_stats);
         NRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_nn_cell_sums, dim3((unsigned)cb), dim3(GEO_BLOCK), 0, st, g.cells, (const uint32_t *)ws.start, ws.bsum);
+        hipLaunchKernelGGL((k_block_sums<uint32_t, GEO_BLOCK>), dim3((unsigned)cb), dim3(GEO_BLOCK), 0, st, g.cells, (const uint32_t *)ws.start, ws.bsum);
         NRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_geo_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, cb, ws.bsum, ws.total);
+        hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, cb, ws.bsum, ws.total);
         NRF_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_nn_cell_starts, dim3((unsigned)cb), dim3(GEO_BLOCK), 0, st, g.cells, ws.start, (const int64_t *)ws.bsum, ws.cursor);
         NRF_LAUNCH_CHECK();

@@ -4,11 +4,12 @@
 // Density lattice.  Slabs of lattice points in linear order: k_lattice_points writes P(i, j, k) of the slab to the workspace, renderer_density (render.hip) runs the
 // coarse pass's exact-fp32 sigma kernels on them straight into the caller's grid.  A value depends on its point alone, so slabs change nothing.
 //
-// Isosurface: marching tetrahedra on the Kuhn split (6 tetrahedra per cell, all sharing the cell's (0,0,0)-(1,1,1) diagonal).  Four launches, one thread per lattice
-// point in blocks of ISO_BLOCK:
+// Isosurface: marching tetrahedra on the Kuhn split (6 tetrahedra per cell, all sharing the cell's (0,0,0)-(1,1,1) diagonal).  Five launches, four of them one thread per
+// lattice point in blocks of ISO_BLOCK:
 //   k_iso_classify   7-bit crossing mask of the edges starting at the point, triangle count of the cell whose min corner it is (<= 12), non-finite count;
 //                    per-block totals of both counts
-//   k_iso_scan       one workgroup: exclusive int64 scan of the per-block totals (the totals of the whole lattice land in the workspace header)
+//   k_totals_scan    (scan.h; once for the vertices, once for the faces) one workgroup: exclusive int64 scan of the per-block totals (the totals of the whole
+//                    lattice land in the workspace header)
 //   k_iso_vertices   block-local exclusive scan of popcount(mask) + the block's offset = the point's first vertex id (kept: the faces need it); vertex and normal
 //   k_iso_faces      block-local exclusive scan of the triangle counts + the block's offset = the cell's first triangle; a vertex id is its edge origin's first
 //                    id + popcount of the origin's lower mask bits
@@ -25,7 +26,6 @@ namespace nrf {
 namespace {
 
 constexpr int ISO_BLOCK = 256;
-constexpr int SCAN_BLOCK = 1024;
 
 // edge type t starts at corner 0 of a cell and ends at corner EDGE_END[t] (corner bits: 1 = +x, 2 = +y, 4 = +z)
 __constant__ const uint8_t EDGE_END[7] = {1, 2, 4, 3, 5, 6, 7};
@@ -76,7 +76,7 @@ __device__ __forceinline__ unsigned tet_mask(unsigned inside, int perm)
 __global__ void __launch_bounds__(ISO_BLOCK) k_iso_classify(Grid g, const float *__restrict__ f, float iso, uint8_t *__restrict__ vmask, uint8_t *__restrict__ tcount,
                                                             int64_t *__restrict__ bsum_v, int64_t *__restrict__ bsum_f, unsigned long long *__restrict__ nonfinite)
 {
-    __shared__ int sh[ISO_BLOCK];
+    __shared__ int sh[ISO_BLOCK / 64];
     const int64_t i = (int64_t)blockIdx.x * ISO_BLOCK + threadIdx.x;
     int m = 0, tc = 0, bad = 0;
     if (i < g.n) {
@@ -98,32 +98,12 @@ __global__ void __launch_bounds__(ISO_BLOCK) k_iso_classify(Grid g, const float 
         vmask[i] = (uint8_t)m;
         tcount[i] = (uint8_t)tc;
     }
-    int tv, tf, tb;
-    (void)block_exclusive_scan<int, ISO_BLOCK>(__popc(m), sh, tv);
-    (void)block_exclusive_scan<int, ISO_BLOCK>(tc, sh, tf);
-    (void)block_exclusive_scan<int, ISO_BLOCK>(bad, sh, tb);
+    const int tv = block_sum<int, ISO_BLOCK>(__popc(m), sh), tf = block_sum<int, ISO_BLOCK>(tc, sh), tb = block_count<ISO_BLOCK>(bad, sh);
     if (threadIdx.x == 0) {
         bsum_v[blockIdx.x] = tv;
         bsum_f[blockIdx.x] = tf;
         if (tb) atomicAdd(nonfinite, (unsigned long long)tb);        // a count: its value does not depend on the order of the additions
     }
-}
-
-// one workgroup: exclusive scans of the per-block totals in place; header[0] = V, header[1] = F
-__global__ void __launch_bounds__(SCAN_BLOCK) k_iso_scan(int64_t nb, int64_t *__restrict__ bsum_v, int64_t *__restrict__ bsum_f, int64_t *__restrict__ header)
-{
-    __shared__ int64_t sh[SCAN_BLOCK];
-    int64_t carry_v = 0, carry_f = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += SCAN_BLOCK) {
-        const int64_t b = b0 + threadIdx.x;
-        const int64_t v = b < nb ? bsum_v[b] : 0, f = b < nb ? bsum_f[b] : 0;
-        int64_t tv, tf;
-        const int64_t ev = block_exclusive_scan<int64_t, SCAN_BLOCK>(v, sh, tv);
-        const int64_t ef = block_exclusive_scan<int64_t, SCAN_BLOCK>(f, sh, tf);
-        if (b < nb) { bsum_v[b] = carry_v + ev; bsum_f[b] = carry_f + ef; }
-        carry_v += tv; carry_f += tf;
-    }
-    if (threadIdx.x == 0) { header[0] = carry_v; header[1] = carry_f; }
 }
 
 // central difference of the lattice along one axis, one-sided at the border
@@ -374,7 +354,9 @@ int nrf_isosurface_count(const float *d_sigma, int nx, int ny, int nz, const flo
     hipLaunchKernelGGL(k_iso_classify, dim3((unsigned)w.nb), dim3(ISO_BLOCK), 0, st, g, d_sigma, iso, w.vmask, w.tcount, w.bsum_v, w.bsum_f,
                        reinterpret_cast<unsigned long long *>(w.header + 2));
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, w.nb, w.bsum_v, w.bsum_f, w.header);
+    hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, w.nb, w.bsum_v, w.header + 0);          // header[0] = V
+    NRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, w.nb, w.bsum_f, w.header + 1);          // header[1] = F
     NRF_LAUNCH_CHECK();
     int64_t h[4] = {0, 0, 0, 0};
     NRF_HIP(hipMemcpyAsync(h, w.header, sizeof(h), hipMemcpyDeviceToHost, st));

@@ -15,7 +15,7 @@
 //   k_sp_decide    one lane per candidate: reads its slot (complete: the launch before has ended) and keeps the face iff it is the lowest face of the parity net
 //                  names; a face not kept gets first cell -1; a kept face marks its three cells; the block's count of kept faces
 //   k_sp_stats     one workgroup: d_stats += the blocks' class counts
-//   k_sp_scan      one workgroup: exclusive scan of block totals (faces, then cells)
+//   k_totals_scan  (scan.h) one workgroup: exclusive scan of block totals (faces, then cells)
 //   k_sp_cell_sums / k_sp_cell_ids   marked cells -> output vertex ids in ascending cell order, -1 elsewhere
 // Emit call.
 //   k_sp_members<0>  one lane per vertex: d_cluster, and the integer atomics of step 5 (sum of the 2^-20 fixed-point offsets and the member count per output vertex),
@@ -38,8 +38,6 @@ namespace nrf {
 namespace {
 
 constexpr int SP_BLOCK = 256;
-constexpr int SCAN_BLOCK = 1024;
-constexpr int SCAN_ITEMS = 8;            // entries per thread and round of k_sp_scan
 constexpr int32_t SP_EMPTY = -1;
 constexpr float SP_FIXED = 1048576.0f;          // 2^20 steps per cell
 
@@ -101,38 +99,6 @@ bool sp_shape_ok(int64_t n_verts, int64_t n_faces, int nx, int ny, int nz)
            ny <= NRF_SIMPLIFY_MAX_DIM && nz >= 1 && nz <= NRF_SIMPLIFY_MAX_DIM && (int64_t)nx * ny * nz <= NRF_SIMPLIFY_MAX_CELLS;
 }
 
-// the count of set flags over the block, in every thread
-__device__ __forceinline__ int block_count(bool flag, int *sh)
-{
-    const unsigned long long bal = __ballot(flag);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int w = 0; w < SP_BLOCK / 64; w++) total += sh[w];
-    __syncthreads();
-    return total;
-}
-
-// the count of set flags in the block before this thread's; `total` = the block's count
-__device__ __forceinline__ int block_rank(bool flag, int *sh, int &total)
-{
-    const unsigned long long bal = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sh[wave] = __popcll(bal);
-    __syncthreads();
-    int before = __popcll(bal & ((1ull << lane) - 1ull));
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < SP_BLOCK / 64; w++) {
-        const int c = sh[w];
-        if (w < wave) before += c;
-        total += c;
-    }
-    __syncthreads();
-    return before;
-}
-
 // step 1 on one axis: t = (x - bmin) * inv_h and the clamped cell coordinate (clamped as a float, so the conversion is defined for every finite x)
 __device__ __forceinline__ int sp_coord(float x, float bmin, float inv_h, int n, float &t)
 {
@@ -184,7 +150,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_classify(const int32_t *__restr
     }
     if (!bstat) return;          // uniform
     // nearly every block of an extracted mesh has collapsed faces: the counts go to a row per block (k_sp_decide adds the fourth), one atomic per call adds them up
-    const int t0 = block_count(cls == 0, sh), t1 = block_count(cls == 1, sh), t2 = block_count(cls == 2, sh);
+    const int t0 = block_count<SP_BLOCK>(cls == 0, sh), t1 = block_count<SP_BLOCK>(cls == 1, sh), t2 = block_count<SP_BLOCK>(cls == 2, sh);
     if (threadIdx.x == 0) bstat[blockIdx.x] = make_uint4((uint32_t)t0, (uint32_t)t1, (uint32_t)t2, 0u);
 }
 
@@ -267,10 +233,10 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_decide(int64_t n_faces, int32_t
             }
         }
     }
-    const int kept = block_count(keep, sh);
+    const int kept = block_count<SP_BLOCK>(keep, sh);
     if (threadIdx.x == 0) fbsum[blockIdx.x] = kept;
     if (!bstat) return;          // uniform
-    const int gone = block_count(removed, sh);
+    const int gone = block_count<SP_BLOCK>(removed, sh);
     if (threadIdx.x == 0) bstat[blockIdx.x].w = (uint32_t)gone;
 }
 
@@ -296,18 +262,11 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_sp_stats(int64_t nb, const uint4
     if (threadIdx.x < 4 && sh[threadIdx.x]) atomicAdd(stats + threadIdx.x, sh[threadIdx.x]);
 }
 
-// one workgroup: exclusive scan of bsum[0 .. nb) in place; *total = the sum (scan.h)
-__global__ void __launch_bounds__(SCAN_BLOCK) k_sp_scan(int64_t nb, int64_t *__restrict__ bsum, int64_t *__restrict__ total)
-{
-    __shared__ int64_t sh[SCAN_BLOCK];
-    block_totals_scan<int64_t, SCAN_BLOCK, SCAN_ITEMS>(nb, bsum, total, sh);
-}
-
 __global__ void __launch_bounds__(SP_BLOCK) k_sp_cell_sums(int64_t cells, const int32_t *__restrict__ cellid, int64_t *__restrict__ cbsum)
 {
     __shared__ int sh[SP_BLOCK / 64];
     const int64_t c = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
-    const int total = block_count(c < cells && cellid[c] != 0, sh);
+    const int total = block_count<SP_BLOCK>(c < cells && cellid[c] != 0, sh);
     if (threadIdx.x == 0) cbsum[blockIdx.x] = total;
 }
 
@@ -317,7 +276,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_cell_ids(int64_t cells, int32_t
     const int64_t c = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
     const bool marked = c < cells && cellid[c] != 0;
     int total;
-    const int before = block_rank(marked, sh, total);
+    const int before = block_rank<SP_BLOCK>(marked, sh, total);
     if (c < cells) cellid[c] = marked ? (int32_t)(cbsum[blockIdx.x] + before) : -1;
 }
 
@@ -427,7 +386,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_faces(int64_t n_faces, const in
     const int64_t f = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
     const bool keep = f < n_faces && ftri[f * 3 + 0] >= 0;
     int total;
-    const int before = block_rank(keep, sh, total);
+    const int before = block_rank<SP_BLOCK>(keep, sh, total);
     if (!keep) return;
     const int64_t at = fbsum[blockIdx.x] + before;
     if (at < 0 || at >= n_out_faces) return;          // never beyond the caller's buffers
@@ -520,11 +479,11 @@ int nrf_mesh_simplify_count(const float *d_verts, int64_t n_verts, const int32_t
             hipLaunchKernelGGL(k_sp_stats, dim3(1), dim3(SCAN_BLOCK), 0, st, fb, (const uint4 *)w.bstat, d_stats);
             NRF_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, fb, w.fbsum, w.header + 1);
+        hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, fb, w.fbsum, w.header + 1);
         NRF_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_sp_cell_sums, dim3((unsigned)cb), block, 0, st, g.cells, (const int32_t *)w.cellid, w.cbsum);
         NRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, cb, w.cbsum, w.header);
+        hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, cb, w.cbsum, w.header);
         NRF_LAUNCH_CHECK();
     }
     // without a face no cell is marked: every id is -1 (the scanned block sums are not read for an unmarked cell)

@@ -4,7 +4,7 @@
 //
 // Count call.
 //   k_adj_classify   one lane per face: BAD / REPEATED / valid; a valid face adds 1 to the degree of its three corners (integer atomics); the block's two skip counts
-//   k_adj_block_sums / k_adj_scan / k_adj_starts   exclusive scan of the degrees -> the row starts [V+1] (int64); run twice, for the face rows and the neighbour rows
+//   k_block_sums / k_totals_scan (scan.h) / k_adj_starts   exclusive scan of the degrees -> the row starts [V+1] (int64); run twice, for the face rows and the neighbour rows
 //   k_adj_fill       one lane per valid face: each corner takes the next free place of its row (an integer cursor): the row holds the right faces in ARRIVAL order
 //   k_adj_rows<1>    one lane per vertex with a row of at most NRF_ADJ_SHORT_ROW faces; a longer row is appended to a list (its order does not matter) for
 //   k_adj_rows<256>  one workgroup per listed row.  Both run the same four steps over one row:
@@ -31,8 +31,6 @@ namespace {
 
 constexpr int ADJ_BLOCK = 256;
 constexpr int ADJ_LONG_GRID = 1024;          // workgroups that share the long rows
-constexpr int SCAN_BLOCK = 1024;
-constexpr int SCAN_ITEMS = 8;                // entries per thread and round of k_adj_scan
 
 struct AdjWs {
     unsigned long long *header;          // [0] long rows, [1] faces with a bad index, [2] faces with a repeated corner
@@ -121,28 +119,13 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_adj_classify(const int32_t *__res
     block_add(cls == 2 ? 1ull : 0ull, header + 2, &sh);
 }
 
-__global__ void __launch_bounds__(ADJ_BLOCK) k_adj_block_sums(const int32_t *__restrict__ deg, int64_t n_verts, int64_t *__restrict__ bsum)
-{
-    __shared__ unsigned long long sh;
-    const int64_t v = (int64_t)blockIdx.x * ADJ_BLOCK + threadIdx.x;
-    if (threadIdx.x == 0) bsum[blockIdx.x] = 0;          // ordered before the block's atomic by the barriers of block_add
-    block_add(v < n_verts ? (unsigned long long)deg[v] : 0ull, reinterpret_cast<unsigned long long *>(bsum + blockIdx.x), &sh);
-}
-
-// one workgroup: exclusive scan of bsum[0 .. nb) in place; *total = the sum (scan.h)
-__global__ void __launch_bounds__(SCAN_BLOCK) k_adj_scan(int64_t nb, int64_t *__restrict__ bsum, int64_t *__restrict__ total)
-{
-    __shared__ int64_t sh[SCAN_BLOCK];
-    block_totals_scan<int64_t, SCAN_BLOCK, SCAN_ITEMS>(nb, bsum, total, sh);
-}
-
 __global__ void __launch_bounds__(ADJ_BLOCK) k_adj_starts(const int32_t *__restrict__ deg, int64_t n_verts, const int64_t *__restrict__ bsum, int64_t *__restrict__ start)
 {
     __shared__ int64_t sh[ADJ_BLOCK];
     const int64_t v = (int64_t)blockIdx.x * ADJ_BLOCK + threadIdx.x;
     int64_t total;
     const int64_t before = block_exclusive_scan<int64_t, ADJ_BLOCK>(v < n_verts ? (int64_t)deg[v] : 0, sh, total);
-    if (v < n_verts) start[v] = bsum[blockIdx.x] + before;          // start[V] is k_adj_scan's total
+    if (v < n_verts) start[v] = bsum[blockIdx.x] + before;          // start[V] is k_totals_scan's total
 }
 
 __global__ void __launch_bounds__(ADJ_BLOCK) k_adj_fill(const int32_t *__restrict__ faces, int64_t n_faces, int32_t n_verts, const int64_t *__restrict__ fstart,
@@ -292,10 +275,10 @@ int adj_scan(const int32_t *deg, int64_t n_verts, int64_t *bsum, int64_t *start,
 {
     const int64_t vb = ceil_div(n_verts, ADJ_BLOCK);
     if (n_verts > 0) {
-        hipLaunchKernelGGL(k_adj_block_sums, dim3((unsigned)vb), dim3(ADJ_BLOCK), 0, st, deg, n_verts, bsum);
+        hipLaunchKernelGGL((k_block_sums<int32_t, ADJ_BLOCK>), dim3((unsigned)vb), dim3(ADJ_BLOCK), 0, st, n_verts, deg, bsum);
         NRF_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_adj_scan, dim3(1), dim3(SCAN_BLOCK), 0, st, vb, bsum, start + n_verts);
+    hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, vb, bsum, start + n_verts);
     NRF_LAUNCH_CHECK();
     if (n_verts > 0) {
         hipLaunchKernelGGL(k_adj_starts, dim3((unsigned)vb), dim3(ADJ_BLOCK), 0, st, deg, n_verts, (const int64_t *)bsum, start);

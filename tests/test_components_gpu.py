@@ -49,6 +49,23 @@ def test_mesh_components_equal_the_restatement(api, mesh_cases, name):
         assert (got == -1).sum() == 37
 
 
+def test_mesh_components_more_than_one_scan_round(api):
+    """The per-block root counts are scanned 8 192 blocks of 256 at a time: 2 097 153 vertices need a second round and end one past a block boundary.  A few dozen
+    faces; components whose smallest vertex lies in block 0, in block 8 191 and -- the (a, a, a) face on the last vertex -- at index 2 097 152, whose rank is K - 1
+    and comes through the carry of the first round."""
+    mesh = api[1]
+    v = 8192 * 256 + 1
+    rng = np.random.default_rng(12)
+    faces = np.concatenate([rng.integers(0, v, (40, 3)),
+                            [[3, 1000000, v - 2], [200, 7, 90], [8191 * 256 + 4, 8191 * 256 + 100, v - 3], [v - 4, 8191 * 256, 8191 * 256 + 200],
+                             [v - 1, v - 1, v - 1], [90, 200, 1000001]]]).astype(np.int32)
+    faces = faces[rng.permutation(len(faces))]
+    want, kw = R.mesh_components(faces, v)
+    assert kw > 40 and want[v - 1] == kw - 1 and want[3] == 0 and want[8191 * 256] == want[v - 4] == kw - 3 and want[v - 3] == kw - 2 and (want == -1).sum() > v - 140
+    got, kg = _twice(mesh.MeshComponents, torch.from_numpy(faces).cuda(), v)
+    assert kg == kw and np.array_equal(got, want)
+
+
 def test_mesh_components_empty_inputs(api):
     mesh = api[1]
     none = torch.empty((0, 3), dtype=torch.int32, device="cuda")

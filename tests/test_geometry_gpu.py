@@ -118,6 +118,24 @@ def test_adversarial_mesh_every_class_counted(api):
         assert np.isfinite(got["points"]).all()
 
 
+def test_sampling_more_than_one_scan_round_of_faces(api):
+    """The block totals of the point counts are scanned 8 192 blocks of 256 at a time: 2 097 153 faces need a second round and end one past a block boundary.  Small
+    faces over eleven vertices at a density that gives most of them no point and nearly all the others one; the first and the last face are large.  A point's face is
+    found by a search in the offsets, so `face` equal to the restatement's is the offsets equal to its; the total is n_points"""
+    nf = 8192 * 256 + 1
+    rng = np.random.default_rng(21)
+    verts = np.concatenate([rng.uniform(-0.05, 0.05, (8, 3)), [[-1, -1, 0], [1, -1, 0], [0, 1, 0.5]]]).astype(F32)
+    faces = rng.integers(0, 8, (nf, 3)).astype(np.int32)
+    faces[0] = faces[nf - 1] = [8, 9, 10]
+    density = 2.0
+    want = dict(zip(("c", "points", "face", "uv"), G.sample(verts, faces, density, 6)))
+    c = want.pop("c")
+    want.update(n_points=c["n_points"], total_area=c["total_area"], stats=c["stats"])
+    assert 1000 < c["n_points"] < 40000 and (c["count"][1:-1] <= 1).all() and c["count"][0] >= 4 and c["count"][-1] >= 4 and c["offset"][-1] == c["n_points"] - c["count"][-1]
+    assert want["face"][-1] == nf - 1 and ((want["face"] >= 8191 * 256) & (want["face"] < nf - 1)).any()
+    assert_sample_equal(run_sample(api, verts, faces, density, 6, pattern=0x5A), want, "two scan rounds")
+
+
 def test_empty_meshes(api):
     _, faces = sphere()
     got = run_sample(api, np.zeros((0, 3), F32), faces, 10.0, 0)          # no vertices: every face has a bad index
@@ -205,6 +223,26 @@ def test_every_grid_gives_the_same_bits(api, cells):
     assert len(np.unique(want[1])) > 500
     assert_nearest_equal(run_nearest(api, cloud(1000, 1100), cloud(4097, 4297), cells=cells, pattern=0xA5), want, f"grid {cells}")
     assert_nearest_equal(run_nearest(api, cloud(4097, 4197), cloud(1000, 1200), cells=cells, stats=False), cloud_reference(4097, 1000), f"grid {cells}, swapped")
+
+
+def test_more_than_one_scan_round_of_cells(api):
+    """The block totals of the cell counts are scanned 8 192 blocks of 256 at a time: a grid of 129 x 128 x 128 = 2 113 536 cells (the call allows 2^26, each side up to
+    1 024) needs a second round.  A sparse cloud, with targets in the first cell, either side of cell 2 097 152, beyond it and in the last cell; every query lies
+    within a fifth of a cell of a target, so the rings serve it from the start array -- a wrong start would send it to the fallback, which no query here needs"""
+    cells = (129, 128, 128)
+    h = np.array([2.0 / n for n in cells])
+    corner = np.array([[0, 0, 0], [127, 0, 127], [128, 0, 127], [0, 1, 127], [64, 64, 127], [128, 127, 127]], np.float64)
+    own = (corner[:, 2] * cells[1] + corner[:, 1]) * cells[0] + corner[:, 0]
+    assert own.tolist() == [0, 8192 * 256 - 1, 8192 * 256, 8192 * 256 + 1, own[4], cells[0] * cells[1] * cells[2] - 1] and own[4] > 8192 * 256 + 256
+    rng = np.random.default_rng(31)
+    target = np.concatenate([(-1.0 + (corner + 0.5) * h)[np.arange(60) % 6] + rng.uniform(-0.3, 0.3, (60, 3)) * h, cloud(4097, 4297)]).astype(F32)
+    near = np.concatenate([np.arange(60), rng.choice(np.arange(60, len(target)), 900, replace=False)])
+    query = (target[near] + rng.uniform(-0.2, 0.2, (len(near), 3)) * h.min()).astype(F32)
+    want = G.nearest(query, target)
+    assert len(np.unique(want[1])) > 900 and (want[0] < (0.4 * h.min()) ** 2).all()
+    got = run_nearest(api, query, target, cells=cells, pattern=0xA5)
+    assert_nearest_equal(got, want, "two scan rounds")
+    assert got[2][2] == 0, "no query needs the fallback"
 
 
 def face_points(n_cells=8):

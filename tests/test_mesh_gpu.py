@@ -110,6 +110,25 @@ def test_isosurface_equals_restatement(api):
     _assert_same(mesh, g, sc["bbox"], iso)
 
 
+def test_isosurface_more_than_one_scan_round(api):
+    """The block totals are scanned 8 192 blocks of 256 at a time: the 129 x 128 x 128 lattice has 2 113 536 points, 8 256 blocks, so the vertex and the face totals
+    need a second round.  All zero but for a few isolated inside points: in block 0, either side of point 2 097 152 (the first of block 8 192), beyond block 8 192
+    and in the last block.  Point 2 097 152 lies in the lattice's top plane, so the second round holds vertex counts (and the faces below read those vertex ids);
+    a cell's min corner never lies in the top plane, so the face totals of the second round are all zero -- they still pass through the carry."""
+    L, mesh, scene = api
+    nx, ny, nz = 129, 128, 128
+    inside = [(1, 1, 0), (60, 61, 62), (127, 0, 127), (0, 1, 127), (64, 64, 127), (127, 127, 127)]
+    lin = [(z * ny + y) * nx + x for x, y, z in inside]
+    assert lin[0] < 256 and lin[2] == 8192 * 256 - 1 and lin[3] == 8192 * 256 + 1 and lin[4] // 256 > 8192 and lin[5] // 256 == nx * ny * nz // 256 - 1 == 8255
+    f = np.zeros((nz, ny, nx), np.float32)
+    for k, (x, y, z) in enumerate(inside):
+        f[z, y, x] = 1.0 + 0.25 * k
+    box = np.array([-1.0, -0.5, -0.25, 1.0, 0.75, 0.5], np.float32)
+    v, fc = _assert_same(mesh, f, box, 0.5)
+    # vertices come in the order of their edge's origin: the last ones start in the top plane, beyond block 8 192, and faces use them
+    assert len(v) > 40 and len(fc) > 40 and fc.max() == len(v) - 1 and (v[-8:, 2] == box[5]).all()
+
+
 def test_isosurface_deterministic_256(api):
     L, mesh, scene = api
     sc = _scene(scene, "cu")

@@ -175,6 +175,19 @@ def test_fans_on_both_sides_of_the_row_threshold_and_a_hub(api, n):
         same_floats(normals(api, verts, d, weighting), S.vertex_normals(verts, faces, want, weighting), f"fan {n} normals {weighting}")
 
 
+def test_more_than_one_scan_round_of_vertices(api):
+    """The block totals of the degrees are scanned 8 192 blocks of 256 at a time: 2 097 153 vertices need a second round and end one past a block boundary.  A handful
+    of faces on the first vertex, the last one (index 2 097 152, alone in its block) and the last of block 8 191 beside it; both row-start arrays and all rows"""
+    nv = 8192 * 256 + 1
+    faces = np.array([[0, 1, 2], [2, 1, 255], [0, nv - 2, nv - 1], [nv - 1, nv - 2, nv - 3], [256, nv - 1, 8191 * 256], [1000000, 1000001, nv - 2], [nv - 1, 0, 1000000],
+                      [5, 5, 6], [nv, 0, 1]], np.int32)
+    want = S.adjacency(faces, nv)
+    assert want["stats"].tolist()[:3] == [1, 1, 11] and want["face_start"][nv - 1] == 3 * 7 - 4 and want["face_start"][nv] == 3 * 7 and want["nbr_start"][nv] == len(want["nbr"])
+    assert np.diff(want["nbr_start"])[[0, nv - 2, nv - 1]].tolist() == [5, 5, 6]
+    got, _ = adjacency(api, faces, nv)
+    assert_adjacency(got, want, "two scan rounds")
+
+
 def test_the_dirty_mesh(api):
     verts, faces = S.dirty()
     want = S.adjacency(faces, len(verts))

@@ -19,6 +19,32 @@ from .modules import _HashBase, CuHashEmbedder, NeRF, NeRFSmall, _ptr, _stream, 
 from .renderer import NeRFRenderer, NeRFRenderParams, RngFill, StochasticPrecondition, TangentScatter
 
 
+def _rng_u32(seed, stream, idx):
+    """include/nrf_rng.h's nrf_rng_u32 on the host (three draws per level and step do not need a kernel)."""
+    m = (1 << 64) - 1
+    x = (seed + idx * 0x9E3779B97F4A7C15) & m
+    x ^= (stream * 0xD1B54A32D192ED03) & m
+    x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & m
+    x ^= x >> 27; x = (x * 0x94D049BB133111EB) & m
+    x ^= x >> 31
+    return x >> 32
+
+
+def tv_cuboids(base, finest, n_levels, seed, t):
+    """The cuboid TotalVariationLoss (NeRF.h:255-300) looks at on each level of a HashEmbedder ladder at step count t -> [(level, res, cube, min_vertex)]:
+    the level's resolution (:265-266), the cube size clip(res / 10, base - 1, finest - 1) (:269-273) and min_vertex = randint(0, res - cube, {3}) (:276), drawn from
+    the counter RNG (stream 18, index (t * n_levels + level) * 3 + axis).  Pure host arithmetic: Trainer.add_tv_loss launches one nrf_hash_tv_loss per entry."""
+    b = math.exp((math.log(finest) - math.log(base)) / (n_levels - 1))          # NeRF.h:265
+    out = []
+    for level in range(n_levels):
+        res = int(math.floor(b ** level * base))
+        cube = int(math.floor(min(max(float(np.float32(res) / np.float32(10.0)), base - 1), finest - 1)))      # :269-273
+        span = max(res - cube, 1)
+        mv = tuple(int(_rng_u32(seed, 18, (t * n_levels + level) * 3 + a) * span >> 32) for a in range(3))   # randint(0, res - cube), :276
+        out.append((level, res, cube, mv))
+    return out
+
+
 class Trainer:
     def __init__(self, embedder: _HashBase, embeddirs, mlp: NeRFSmall, table, mlp_blob, learning_rate=5e-4, betas=(0.9, 0.99), eps=1e-15,
                  tv_loss_weight=0.0, seed=0, mlp_backward="f32", hash_backward="f32", grad_sync=None, train_dense_budget=256 << 20,
@@ -318,16 +344,7 @@ class Trainer:
     def skipped_steps(self, v):
         self._skipped = int(v)
 
-    @staticmethod
-    def _rng_u32(seed, stream, idx):
-        """include/nrf_rng.h's nrf_rng_u32 on the host (three draws per level and step do not need a kernel)."""
-        m = (1 << 64) - 1
-        x = (seed + idx * 0x9E3779B97F4A7C15) & m
-        x ^= (stream * 0xD1B54A32D192ED03) & m
-        x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & m
-        x ^= x >> 27; x = (x * 0x94D049BB133111EB) & m
-        x ^= x >> 31
-        return x >> 32
+    _rng_u32 = staticmethod(_rng_u32)
 
     def add_tv_loss(self):
         """loss += w * TotalVariationLoss(level) for every level (NeRF.h:255-300): accumulates into self.g_table and self.tv_loss."""
@@ -335,12 +352,8 @@ class Trainer:
         if self.tv_loss_weight <= 0 or not self.has_table or e.mode != L.NRF_HASH_NGP:
             return
         self.tv_loss.zero_()
-        b = math.exp((math.log(e.FinestResolution) - math.log(e.BaseResolution)) / (e.NLevels - 1))          # NeRF.h:265
-        for level in range(e.NLevels):
-            res = int(math.floor(b ** level * e.BaseResolution))
-            cube = int(math.floor(min(max(float(np.float32(res) / np.float32(10.0)), e.BaseResolution - 1), e.FinestResolution - 1)))      # :269-273
-            span = max(res - cube, 1)
-            mv = np.array([self._rng_u32(self.seed, 18, (self.t * e.NLevels + level) * 3 + a) * span >> 32 for a in range(3)], np.int32)   # randint(0, res - cube), :276
+        for level, _, cube, min_vertex in tv_cuboids(e.BaseResolution, e.FinestResolution, e.NLevels, self.seed, self.t):
+            mv = np.array(min_vertex, np.int32)
             L.check(L.lib().nrf_hash_tv_loss(e._h, _ptr(self.table), level, mv.ctypes.data_as(C.c_void_p), cube, self.tv_loss_weight, _ptr(self.tv_loss),
                                              _ptr(self.g_table), _stream()))
 

@@ -1001,6 +1001,78 @@ NRF_API size_t nrf_density_grad_workspace_bytes(const nrf_renderer *r, int64_t p
 NRF_API int nrf_density_grad(const nrf_renderer *r, const float *d_pts, int64_t p, float *d_sigma, float *d_grad, void *d_workspace, size_t workspace_bytes,
                              void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Closest point on a mesh (geometry.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* For every query point the nearest FACE of a triangle list, the point on that face, its barycentrics and the squared distance: the exact point-to-triangle query
+ * under the sampled point-to-point one of nrf_nearest_points.  It shares that entry's grid (bbox, dims, inv_h, h, the cell coordinate, NRF_NN_MAX_DIM / _MAX_CELLS /
+ * _MAX_RINGS), its key, its stop rule and its conventions: fp32 operations rounded once each, / correctly rounded, caller-owned buffers, refusals (NRF_ERR_INVALID_ARG,
+ * or NRF_ERR_WORKSPACE for a short workspace, the message starting with the entry's name) before any launch or write, two runs the same bits.
+ *
+ * Order of calls.  nrf_face_grid_count (workspace of nrf_face_grid_workspace_bytes) returns *n_refs and *n_large to the host: the ONE synchronisation.  The caller
+ * allocates nrf_face_grid_bytes(F, dims, n_refs, n_large) bytes; nrf_face_grid_build fills them from the same mesh, box, dims and workspace (untouched in between).
+ * The workspace may then go; any number of nrf_closest_on_mesh calls read the grid buffer (both directions of a distance, slab after slab of a bake).  Build and
+ * query synchronise nothing.
+ *
+ * CONTRACT.
+ *   Faces.  d_verts [V,3] fp32, d_faces [F,3] int32, 0 <= V, F < 2^31.  A face with a corner outside [0, V) is BAD, a face with a non-finite vertex coordinate is
+ *   NON-FINITE (the classes of nrf_mesh_sample_count, without its area test: a face of finite corners whose area overflows is a face here).  Both are skipped whole,
+ *   nothing of a bad face is dereferenced.  Repeated corners and zero area do not make a face invalid.
+ *   Cell box of a face.  Per axis cell(min of the three coordinates) .. cell(max of the three), cell() the clamped cell coordinate of nrf_nearest_points.
+ *   Binned and large faces.  A face whose cell box holds at most NRF_FG_MAX_FACE_CELLS cells has one reference in every cell of the box (integer atomics count, the
+ *   counts are scanned, a cursor scatters; the order inside a cell may vary, nothing depends on it); n_refs is their number, refused at 2^32 or more (the message says
+ *   so).  A face with a larger box goes to the large list (n_large entries), which every query tests in full.  NRF_FG_MAX_FACE_CELLS is a tuning constant: no result
+ *   depends on it, nor on the grid.
+ *   Closest point of query q on the face (a, b, c), the Voronoi-region form of Ericson, Real-Time Collision Detection, 5.1.5.  Per component ab = b - a, ac = c - a,
+ *   ap = q - a, bp = q - b, cp = q - c.  dot(x, y) = (xx*yx + xy*yy) + xz*yz.  d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp),
+ *   d6 = dot(ac, cp); vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4 (each product rounded, then the difference).  The first region that holds, in
+ *   this order, gives (v, w) and P per component:
+ *     A        d1 <= 0 and d2 <= 0                          (0, 0)    P = a
+ *     B        d3 >= 0 and d4 <= d3                         (1, 0)    P = b
+ *     edge AB  vc <= 0 and d1 >= 0 and d3 <= 0              v = d1 / (d1 - d3), w = 0                                          P = a + v*ab
+ *     C        d6 >= 0 and d5 <= d6                         (0, 1)    P = c
+ *     edge AC  vb <= 0 and d2 >= 0 and d6 <= 0              v = 0, w = d2 / (d2 - d6)                                          P = a + w*ac
+ *     edge BC  va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1.0f - w              P = b + w*(c - b)
+ *     interior otherwise                                    denom = 1.0f / ((va + vb) + vc), v = vb * denom, w = vc * denom    P = (a + ab*v) + ac*w
+ *   Then P is clamped per component to the face's own coordinate box, lo = min(a, b, c), hi = max(a, b, c): P = P < lo ? lo : (P > hi ? hi : P), a form under which a
+ *   NaN stays a NaN.  Then d2 = (dx*dx + dy*dy) + dz*dz with dx = qx - Px (nn_d2, the function nrf_nearest_points uses).  (v, w) is the pair nrf_mesh_sample_emit
+ *   writes: P is about (1 - v - w) a + v b + w c; the clamp moves P by rounding errors only and leaves (v, w) as computed.
+ *   Result.  For a finite query the minimum of the key ((uint64)float_bits(d2) << 32) | f over all valid faces f with d2 <= fl(max_dist * max_dist); max_dist >= 0,
+ *   +inf for no limit.  A NaN d2 (a zero-area face can give 0 / 0) fails that comparison and never wins; on an exact tie, across a shared edge or vertex, the lowest
+ *   face index wins.  d_dist2 [nq], d_face [nq] int32, and, each or NULL, d_uv [nq,2] = (v, w) and d_point [nq,3] = P of the winning face.  No such face: +inf, -1,
+ *   zeros; a non-finite query gets the same.  A d2 that overflows to +inf with a valid face is a valid answer.  d_stats [4] uint32 or NULL (ADDED to; the caller
+ *   zeroes it): nrf_closest_on_mesh adds [0] non-finite queries and [3] queries served by the fallback, nrf_face_grid_count adds [1] bad and [2] non-finite faces.
+ *   F == 0 is valid everywhere; nq == 0 is valid and launches nothing.
+ * SCAN AND STOP.  One lane per query: first the large list, then ring r = 0, 1, ... of cells exactly as nrf_nearest_points walks them, every reference of every cell of
+ *   the ring (a face met twice is harmless: the minimum is idempotent), and after ring r the same stop: every cell scanned, or min(best_d2, fl(max_dist * max_dist)) <
+ *   fl(B * B), strictly, B = fl(fl((float)r * h_min) * 0.999f).
+ * WHY THE STOP STAYS EXACT.  The clamp puts every coordinate of P between the face's smallest and largest coordinate on that axis, and the cell coordinate is monotone
+ *   in x (fl(x - bmin), the product with inv_h > 0, floorf and the clamp all are): P's cell lies inside the face's cell box.  A binned face without a reference in the
+ *   cube of radius r around the query's cell has a cell box that misses the cube on some axis, so P is a "target in a cell at least r + 1 away on that axis" and WHY
+ *   THE STOP IS EXACT of nrf_nearest_points applies to P word for word: d2 >= fl(B * B).  Large faces are never unscanned.  Without the clamp the computed P can leave
+ *   the box by a rounding error and the argument fails: the clamp is part of the definition, not an optimisation.
+ * FALLBACK.  A query with no stop after ring NRF_NN_MAX_RINGS is appended to a list in the workspace; a second kernel, a fixed grid of workgroups striding the list by
+ *   the count read on the device, brute-forces ALL faces for it with a block-wide minimum of the key.  Rings, large list and fallback form the candidate through one
+ *   inline function.  Every loop is bounded by a clamped range or a count; nothing waits on another workgroup.
+ * REFUSED: V, F, nq or the dims out of range; a null bbox, d_faces (F > 0), d_verts (V > 0 and F > 0), n_refs / n_large (count), d_query, d_dist2 or d_face (nq > 0); a
+ *   box nrf_nearest_points refuses; max_dist < 0 or NaN; n_refs outside [0, 2^32) or n_large outside [0, F]; a null or misaligned (8 bytes) workspace or grid buffer, a
+ *   short workspace; a grid buffer whose size is not nrf_face_grid_bytes of these F, dims, n_refs and n_large.  The build also writes what it was built for (F, dims,
+ *   counts, the bits of the box) at the head of the buffer; a query whose arguments pass the host's size check but disagree with that head reads nothing more of the
+ *   buffer and writes nothing. */
+#ifndef NRF_FG_MAX_FACE_CELLS            /* tuning builds set another (make EXTRA=-DNRF_FG_MAX_FACE_CELLS=n); no result depends on it */
+#define NRF_FG_MAX_FACE_CELLS 64         /* the largest cell box of a binned face; a face with more cells goes to the large list */
+#endif
+NRF_API size_t nrf_face_grid_workspace_bytes(int64_t n_faces, int nx, int ny, int nz);
+NRF_API size_t nrf_face_grid_bytes(int64_t n_faces, int nx, int ny, int nz, int64_t n_refs, int64_t n_large);
+NRF_API int nrf_face_grid_count(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz,
+                                int64_t *n_refs, int64_t *n_large, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_face_grid_build(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz,
+                                int64_t n_refs, int64_t n_large, void *d_grid, size_t grid_bytes, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_closest_on_mesh_workspace_bytes(int64_t nq);
+NRF_API int nrf_closest_on_mesh(const float *d_query, int64_t nq, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox,
+                                int nx, int ny, int nz, int64_t n_refs, int64_t n_large, const void *d_grid, size_t grid_bytes, float max_dist, float *d_dist2,
+                                int32_t *d_face, float *d_uv, float *d_point, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */
 NRF_API size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p);

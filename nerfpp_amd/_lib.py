@@ -215,6 +215,12 @@ _ABI = """
     nrf_mesh_vertex_normals(plplpplipp)
     nrf_density_grad_workspace_bytes(pl)->z
     nrf_density_grad(pplpppzp)
+    nrf_face_grid_workspace_bytes(liii)->z
+    nrf_face_grid_bytes(liiill)->z
+    nrf_face_grid_count(plplpiiippppzp)
+    nrf_face_grid_build(plplpiiillpzpzp)
+    nrf_closest_on_mesh_workspace_bytes(l)->z
+    nrf_closest_on_mesh(plplplpiiillpzfppppppzp)
     nrf_render_rays_workspace_bytes(plp)->z
     nrf_render_rays(ppilpppppzp)
     nrf_batchify_rays_workspace_bytes(plip)->z

@@ -16,6 +16,11 @@
 //   the scheduling nor the order of the targets (beyond the tie-break by index the key states).
 // Statistics.  k_dist_stats: 4096 entries per block, lane t takes t, t + 256, ... in ascending order; wave shuffle tree, four wave sums in order, one row of eight fp64
 //   partials per block; k_geo_finish adds the rows in image_metrics.hip's k_finish order.  No atomics.
+// Closest point on a mesh.  The same grid holds FACES: k_fg_bin<0> counts one reference per cell of a face's cell box (a box of more than NRF_FG_MAX_FACE_CELLS cells:
+//   the large list), the scan, k_fg_starts (starts into the caller's grid buffer, with what it was built for at its head), k_fg_bin<1> scatters face indices.
+//   k_cm_query: one lane per query, the large list, then k_nn_query's ring walk over references, the same stop; k_cm_far brute-forces all faces for the listed
+//   queries.  cm_take / cm_closest are the one copy of the candidate: Ericson's regions in a fixed order, P clamped to the face's coordinate box (the stop's proof
+//   needs it), d2 through nn_d2.  tests/closest_ref.py restates it.
 // Every loop is bounded by a clamped range or a count; no kernel waits on another workgroup.
 #include "common.h"
 #include "scan.h"
@@ -487,6 +492,386 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_dist_stats(const float *__restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------- 4. closest point on a mesh
+constexpr long long FG_MAGIC = 0x4e52464647524431ll;          // "NRFFGRD1": the first word of a built grid buffer
+
+// what a grid buffer was built for, as the header states it: the query kernels compare it with their own arguments before they read anything else of the buffer
+struct FgKey {
+    long long w[8];          // magic, F, dims packed, n_refs, n_large, the bits of the box two floats to a word
+};
+
+struct FgWs {                // count and build
+    uint32_t *count;         // [cells] references per cell
+    uint32_t *cursor;        // [cells] where the next reference of a cell goes
+    int64_t *bsum;           // [cell blocks]
+    int64_t *total;          // [1] n_refs
+    uint32_t *counters;      // [0] n_large (count), [1] the large list's cursor (build)
+};
+
+struct FgGrid {              // the caller-owned buffer the queries read
+    long long *key;          // [8]
+    uint32_t *start;         // [cells + 1] the references of cell c are refs[start[c] .. start[c + 1])
+    int32_t *refs;           // [n_refs] face indices in cell order
+    int32_t *large;          // [n_large] the faces every query tests
+};
+
+struct CmWs {
+    int32_t *far;            // [nq] the queries of the brute-force kernel
+    uint32_t *n_far;         // [1]
+};
+
+FgWs fg_ws_layout(Bump &b, int64_t cells)
+{
+    FgWs s;
+    s.count = b.take<uint32_t>((size_t)cells);
+    s.cursor = b.take<uint32_t>((size_t)cells);
+    s.bsum = b.take<int64_t>((size_t)ceil_div(cells, GEO_BLOCK));
+    s.total = b.take<int64_t>(1);
+    s.counters = b.take<uint32_t>(2);
+    return s;
+}
+
+FgGrid fg_grid_layout(Bump &b, int64_t cells, int64_t n_refs, int64_t n_large)
+{
+    FgGrid s;
+    s.key = b.take<long long>(8);
+    s.start = b.take<uint32_t>((size_t)cells + 1);
+    s.refs = b.take<int32_t>((size_t)n_refs);
+    s.large = b.take<int32_t>((size_t)n_large);
+    return s;
+}
+
+CmWs cm_layout(Bump &b, int64_t nq)
+{
+    CmWs s;
+    s.far = b.take<int32_t>((size_t)nq);
+    s.n_far = b.take<uint32_t>(1);
+    return s;
+}
+
+bool fg_shape_ok(int64_t n_verts, int64_t n_faces, int nx, int ny, int nz) { return sample_shape_ok(n_verts, n_faces) && nn_shape_ok(0, 0, nx, ny, nz); }
+
+bool fg_counts_ok(int64_t n_faces, int64_t n_refs, int64_t n_large) { return n_refs >= 0 && n_refs < ((int64_t)1 << 32) && n_large >= 0 && n_large <= n_faces; }
+
+FgKey fg_key(int64_t n_faces, int nx, int ny, int nz, int64_t n_refs, int64_t n_large, const float *bbox)
+{
+    FgKey k;
+    uint32_t bits[6];
+    std::memcpy(bits, bbox, sizeof(bits));
+    k.w[0] = FG_MAGIC;
+    k.w[1] = n_faces;
+    k.w[2] = ((long long)nz << 40) | ((long long)ny << 20) | nx;
+    k.w[3] = n_refs;
+    k.w[4] = n_large;
+    for (int a = 0; a < 3; a++) k.w[5 + a] = (long long)(((unsigned long long)bits[3 + a] << 32) | bits[a]);
+    return k;
+}
+
+// the corners of face f -> 0: a face; 1: a corner outside [0, V) (nothing dereferenced) or f outside [0, F); 2: a non-finite coordinate
+__device__ __forceinline__ int cm_face(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, int64_t f, float a[3], float b[3],
+                                       float c[3])
+{
+    if (f < 0 || f >= n_faces) return 1;
+    const int32_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+    if (i0 < 0 || i0 >= n_verts || i1 < 0 || i1 >= n_verts || i2 < 0 || i2 >= n_verts) return 1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        a[k] = verts[(int64_t)i0 * 3 + k];
+        b[k] = verts[(int64_t)i1 * 3 + k];
+        c[k] = verts[(int64_t)i2 * 3 + k];
+    }
+    return finite3(a) && finite3(b) && finite3(c) ? 0 : 2;
+}
+
+// the cell box of a face: per axis nn_cell(min of the three) .. nn_cell(max of the three); its cell count (<= 2^30)
+__device__ __forceinline__ int64_t fg_box(const NnGrid &g, const float a[3], const float b[3], const float c[3], int lo[3], int hi[3])
+{
+    int64_t n = 1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        lo[k] = nn_cell(fminf(fminf(a[k], b[k]), c[k]), g.bmin[k], g.inv_h[k], g.n[k]);
+        hi[k] = nn_cell(fmaxf(fmaxf(a[k], b[k]), c[k]), g.bmin[k], g.inv_h[k], g.n[k]);
+        n *= hi[k] - lo[k] + 1;
+    }
+    return n;
+}
+
+__device__ __forceinline__ float cm_dot(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+struct CmHit {
+    float d2, v, w, p[3];
+};
+
+// the one place the closest point of a triangle is formed (the header's steps, Ericson 5.1.5): region, (v, w), P, the clamp to the face's own box, d2
+__device__ __forceinline__ void cm_closest(const float q[3], const float a[3], const float b[3], const float c[3], CmHit &h)
+{
+    float ab[3], ac[3], ap[3], bp[3], cp[3], p[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        ab[k] = b[k] - a[k];
+        ac[k] = c[k] - a[k];
+        ap[k] = q[k] - a[k];
+        bp[k] = q[k] - b[k];
+        cp[k] = q[k] - c[k];
+    }
+    const float d1 = cm_dot(ab, ap), d2 = cm_dot(ac, ap), d3 = cm_dot(ab, bp), d4 = cm_dot(ac, bp), d5 = cm_dot(ab, cp), d6 = cm_dot(ac, cp);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    float v, w;
+    if (d1 <= 0.0f && d2 <= 0.0f) {                                                  // A
+        v = 0.0f; w = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = a[k];
+    } else if (d3 >= 0.0f && d4 <= d3) {                                             // B
+        v = 1.0f; w = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = b[k];
+    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {                             // edge AB
+        v = d1 / (d1 - d3); w = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = a[k] + v * ab[k];
+    } else if (d6 >= 0.0f && d5 <= d6) {                                             // C
+        v = 0.0f; w = 1.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = c[k];
+    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {                             // edge AC
+        v = 0.0f; w = d2 / (d2 - d6);
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = a[k] + w * ac[k];
+    } else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {               // edge BC
+        w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); v = 1.0f - w;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = b[k] + w * (c[k] - b[k]);
+    } else {                                                                         // interior
+        const float denom = 1.0f / ((va + vb) + vc);
+        v = vb * denom; w = vc * denom;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = (a[k] + ab[k] * v) + ac[k] * w;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {          // P stays inside the face's coordinate box (the stop rule's proof needs it); the comparisons keep a NaN a NaN
+        const float lo = fminf(fminf(a[k], b[k]), c[k]), hi = fmaxf(fmaxf(a[k], b[k]), c[k]);
+        h.p[k] = p[k] < lo ? lo : (p[k] > hi ? hi : p[k]);
+    }
+    h.v = v;
+    h.w = w;
+    h.d2 = nn_d2(q[0], q[1], q[2], make_float4(h.p[0], h.p[1], h.p[2], 0.0f));
+}
+
+// face f as a candidate of query q: rings, large list and fallback all come through here
+__device__ __forceinline__ void cm_take(const float q[3], const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, int64_t f,
+                                        float md2, unsigned long long &best)
+{
+    float a[3], b[3], c[3];
+    if (cm_face(verts, n_verts, faces, n_faces, f, a, b, c) != 0) return;
+    CmHit h;
+    cm_closest(q, a, b, c, h);
+    const unsigned long long k = ((unsigned long long)__float_as_uint(h.d2) << 32) | (uint32_t)f;
+    if (h.d2 <= md2 && k < best) best = k;          // a NaN d2 fails the comparison
+}
+
+// the outputs of query qi from its key: (v, w) and P are those of the winning face, formed once more by the same function
+__device__ __forceinline__ void cm_write(const float q[3], int64_t qi, unsigned long long best, const float *__restrict__ verts, int32_t n_verts,
+                                         const int32_t *__restrict__ faces, int64_t n_faces, float *__restrict__ dist2, int32_t *__restrict__ face, float *__restrict__ uv,
+                                         float *__restrict__ point)
+{
+    const int32_t f = (int32_t)(uint32_t)best;
+    dist2[qi] = __uint_as_float((uint32_t)(best >> 32));
+    face[qi] = f;
+    if (!uv && !point) return;
+    CmHit h;
+    h.v = h.w = h.p[0] = h.p[1] = h.p[2] = 0.0f;
+    float a[3], b[3], c[3];
+    if (f >= 0 && cm_face(verts, n_verts, faces, n_faces, f, a, b, c) == 0) cm_closest(q, a, b, c, h);
+    if (uv) { uv[qi * 2 + 0] = h.v; uv[qi * 2 + 1] = h.w; }
+    if (point) { point[qi * 3 + 0] = h.p[0]; point[qi * 3 + 1] = h.p[1]; point[qi * 3 + 2] = h.p[2]; }
+}
+
+// pass 0: count[cell]++ for every cell of a binned face's box, n_large++ for a large one; pass 1: the face's index goes to cursor[cell]++ resp. to the large list
+template <int PASS>
+__global__ void __launch_bounds__(GEO_BLOCK) k_fg_bin(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, NnGrid g,
+                                                      uint32_t *__restrict__ cell_word, uint32_t *__restrict__ counters, int32_t *__restrict__ refs, uint32_t n_refs,
+                                                      int32_t *__restrict__ large, uint32_t n_large, uint32_t *__restrict__ stats)
+{
+    __shared__ int sh[GEO_BLOCK / 64];
+    const int64_t f = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    int cls = -1;
+    bool is_large = false;
+    if (f < n_faces) {
+        float a[3], b[3], c[3];
+        cls = cm_face(verts, n_verts, faces, n_faces, f, a, b, c);
+        if (cls == 0) {
+            int lo[3], hi[3];
+            is_large = fg_box(g, a, b, c, lo, hi) > NRF_FG_MAX_FACE_CELLS;
+            if (!is_large) {
+                for (int z = lo[2]; z <= hi[2]; z++)
+                    for (int y = lo[1]; y <= hi[1]; y++)
+                        for (int x = lo[0]; x <= hi[0]; x++) {          // at most NRF_FG_MAX_FACE_CELLS cells
+                            const int64_t cell = ((int64_t)z * g.n[1] + y) * g.n[0] + x;
+                            if (PASS == 0) {
+                                (void)__hip_atomic_fetch_add(cell_word + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            } else {
+                                const uint32_t at = atomicAdd(cell_word + cell, 1u);
+                                if (at < n_refs) refs[at] = (int32_t)f;          // always, for the workspace of the count call over this mesh
+                            }
+                        }
+            } else if (PASS == 1) {
+                const uint32_t at = atomicAdd(counters + 1, 1u);
+                if (at < n_large) large[at] = (int32_t)f;
+            }
+        }
+    }
+    if (PASS != 0) return;          // uniform
+    const int nl = block_count<GEO_BLOCK>(is_large, sh);
+    if (threadIdx.x == 0 && nl) atomicAdd(counters + 0, (uint32_t)nl);
+    if (!stats) return;             // uniform
+    const int t1 = block_count<GEO_BLOCK>(cls == 1, sh), t2 = block_count<GEO_BLOCK>(cls == 2, sh);
+    if (threadIdx.x == 0) {
+        if (t1) atomicAdd(stats + 1, (uint32_t)t1);
+        if (t2) atomicAdd(stats + 2, (uint32_t)t2);
+    }
+}
+
+// counts -> the grid buffer's starts (start[cells] = n_refs) and the scatter's cursors; block 0 writes what the buffer is built for
+__global__ void __launch_bounds__(GEO_BLOCK) k_fg_starts(int64_t cells, const uint32_t *__restrict__ count, const int64_t *__restrict__ bsum, uint32_t *__restrict__ start,
+                                                         uint32_t *__restrict__ cursor, FgKey key, long long *__restrict__ out_key)
+{
+    __shared__ uint32_t sh[GEO_BLOCK];
+    const int64_t c = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    const uint32_t n = c < cells ? count[c] : 0u;
+    uint32_t total;
+    const uint32_t e = block_exclusive_scan<uint32_t, GEO_BLOCK>(n, sh, total);
+    if (blockIdx.x == 0 && threadIdx.x < 8) out_key[threadIdx.x] = key.w[threadIdx.x];
+    if (c >= cells) return;
+    const uint32_t at = (uint32_t)(bsum[blockIdx.x] + e);
+    start[c] = at;
+    cursor[c] = at;
+    if (c == cells - 1) start[cells] = at + n;
+}
+
+__device__ __forceinline__ bool fg_key_matches(const long long *__restrict__ grid_key, const FgKey &key)
+{
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < 8; k++) same = same && grid_key[k] == key.w[k];
+    return same;
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_cm_query(const float *__restrict__ query, int64_t nq, const float *__restrict__ verts, int32_t n_verts,
+                                                        const int32_t *__restrict__ faces, int64_t n_faces, NnGrid g, FgKey key, float md2,
+                                                        const long long *__restrict__ grid_key, const uint32_t *__restrict__ start, const int32_t *__restrict__ refs,
+                                                        const int32_t *__restrict__ large, float *__restrict__ dist2, int32_t *__restrict__ face, float *__restrict__ uv,
+                                                        float *__restrict__ point, int32_t *__restrict__ far, uint32_t *__restrict__ n_far, uint32_t *__restrict__ stats)
+{
+    __shared__ int sh[GEO_BLOCK / 64];
+    if (!fg_key_matches(grid_key, key)) return;          // uniform: not the buffer nrf_face_grid_build made for these arguments; nothing of it is read, nothing written
+    const int64_t qi = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool live = qi < nq;
+    const uint32_t n_refs = (uint32_t)key.w[3], n_large = (uint32_t)key.w[4];
+    float q[3] = {0.0f, 0.0f, 0.0f};
+    if (live) { q[0] = query[qi * 3 + 0]; q[1] = query[qi * 3 + 1]; q[2] = query[qi * 3 + 2]; }
+    const bool finite = live && finite3(q);
+    unsigned long long best = NN_NONE;
+    bool open = false;          // rings exhausted without a stop: the brute-force kernel's
+    if (finite) {
+        for (uint32_t i = 0; i < n_large; i++) cm_take(q, verts, n_verts, faces, n_faces, large[i], md2, best);
+        auto run = [&](uint32_t a, uint32_t b) {          // the references of a run of cells; never beyond the list
+            b = b < n_refs ? b : n_refs;
+            for (uint32_t i = a; i < b; i++) cm_take(q, verts, n_verts, faces, n_faces, refs[i], md2, best);
+        };
+        if (n_refs != 0) {
+            const int cx = nn_cell(q[0], g.bmin[0], g.inv_h[0], g.n[0]), cy = nn_cell(q[1], g.bmin[1], g.inv_h[1], g.n[1]), cz = nn_cell(q[2], g.bmin[2], g.inv_h[2], g.n[2]);
+            const int r_all = max(max(max(cx, g.n[0] - 1 - cx), max(cy, g.n[1] - 1 - cy)), max(cz, g.n[2] - 1 - cz));
+            open = true;
+            for (int r = 0; r <= NRF_NN_MAX_RINGS; r++) {          // k_nn_query's walk, cell for cell
+                const int z0 = max(cz - r, 0), z1 = min(cz + r, g.n[2] - 1), y0 = max(cy - r, 0), y1 = min(cy + r, g.n[1] - 1);
+                const int x0 = max(cx - r, 0), x1 = min(cx + r, g.n[0] - 1);
+                for (int z = z0; z <= z1; z++) {
+                    for (int y = y0; y <= y1; y++) {
+                        const int64_t row = ((int64_t)z * g.n[1] + y) * g.n[0];
+                        const bool shell = z == cz - r || z == cz + r || y == cy - r || y == cy + r;
+                        if (shell) {
+                            run(start[row + x0], start[row + x1 + 1]);
+                        } else {
+                            if (cx - r >= 0) run(start[row + cx - r], start[row + cx - r + 1]);
+                            if (cx + r <= g.n[0] - 1) run(start[row + cx + r], start[row + cx + r + 1]);
+                        }
+                    }
+                }
+                if (r >= r_all) { open = false; break; }
+                const float B = ((float)r * g.h_min) * 0.999f;
+                const float B2 = B * B;
+                // the closest point of every face without a reference in the cube lies in a cell at least r + 1 away on some axis (the clamp): d2 >= B2 (header)
+                if (fminf(__uint_as_float((uint32_t)(best >> 32)), md2) < B2) { open = false; break; }
+            }
+        }
+    }
+    const unsigned long long wm = __ballot(open);          // every lane of the wave arrives here
+    if (wm) {
+        uint32_t at = 0;
+        if (lane == 0) at = atomicAdd(n_far, (uint32_t)__popcll(wm));
+        at = __shfl(at, 0, 64);
+        if (open) far[at + __popcll(wm & ((1ull << lane) - 1))] = (int32_t)qi;          // at + rank < nq: every query is appended at most once
+    }
+    if (live && !open) cm_write(q, qi, best, verts, n_verts, faces, n_faces, dist2, face, uv, point);
+    if (!stats) return;          // uniform
+    const int total = block_count<GEO_BLOCK>(live && !finite, sh);
+    if (threadIdx.x == 0 && total) atomicAdd(stats + 0, (uint32_t)total);
+}
+
+__global__ void __launch_bounds__(GEO_BLOCK) k_cm_far(const float *__restrict__ query, const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces,
+                                                      int64_t n_faces, FgKey key, float md2, const long long *__restrict__ grid_key, float *__restrict__ dist2,
+                                                      int32_t *__restrict__ face, float *__restrict__ uv, float *__restrict__ point, const int32_t *__restrict__ far,
+                                                      const uint32_t *__restrict__ n_far, uint32_t *__restrict__ stats)
+{
+    __shared__ unsigned long long s_best[GEO_BLOCK / 64];
+    if (!fg_key_matches(grid_key, key)) return;          // uniform, as in k_cm_query
+    const uint32_t n = *n_far;
+    if (stats && blockIdx.x == 0 && threadIdx.x == 0 && n) atomicAdd(stats + 3, n);
+    for (uint32_t i = blockIdx.x; i < n; i += FAR_GRID) {          // uniform over the workgroup
+        const int64_t qi = far[i];
+        const float q[3] = {query[qi * 3 + 0], query[qi * 3 + 1], query[qi * 3 + 2]};
+        unsigned long long best = NN_NONE;
+        for (int64_t f = threadIdx.x; f < n_faces; f += GEO_BLOCK) cm_take(q, verts, n_verts, faces, n_faces, f, md2, best);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off, 64), lo = __shfl_xor((uint32_t)best, off, 64);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            best = o < best ? o : best;
+        }
+        if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 1; k < GEO_BLOCK / 64; k++) best = s_best[k] < best ? s_best[k] : best;
+            cm_write(q, qi, best, verts, n_verts, faces, n_faces, dist2, face, uv, point);
+        }
+        __syncthreads();
+    }
+}
+
+// the grid of a box and dims, as nrf_nearest_points states it; false with the offending axis where the box is refused
+bool nn_grid_make(const float *bbox, int nx, int ny, int nz, NnGrid &g, int &axis)
+{
+    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
+    g.cells = (int64_t)nx * ny * nz;
+    g.h_min = INFINITY;
+    for (int a = 0; a < 3; a++) {
+        const float extent = bbox[3 + a] - bbox[a];
+        const float inv_h = (float)g.n[a] / extent;
+        const float h = 1.0f / inv_h;
+        if (!(std::isfinite(bbox[a]) && std::isfinite(bbox[3 + a]) && extent > 0.0f && std::isfinite(extent) && std::isfinite(inv_h) && inv_h > 0.0f && std::isfinite(h) &&
+              h > 0.0f)) {
+            axis = a;
+            return false;
+        }
+        g.bmin[a] = bbox[a];
+        g.inv_h[a] = inv_h;
+        g.h_min = h < g.h_min ? h : g.h_min;
+    }
+    return true;
+}
+
 }  // namespace
 
 }  // namespace nrf
@@ -576,20 +961,9 @@ int nrf_nearest_points(const float *d_query, int64_t nq, const float *d_target, 
     NRF_CHECK_ARG(bbox, "nrf_nearest_points: null bbox");
     NRF_CHECK_ARG(max_dist >= 0.0f, "nrf_nearest_points: max_dist must be >= 0 or +inf (got %g)", (double)max_dist);          // NaN fails
     NnGrid g;
-    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
-    g.cells = (int64_t)nx * ny * nz;
-    g.h_min = INFINITY;
-    for (int a = 0; a < 3; a++) {
-        const float extent = bbox[3 + a] - bbox[a];
-        const float inv_h = (float)g.n[a] / extent;
-        const float h = 1.0f / inv_h;
-        NRF_CHECK_ARG(std::isfinite(bbox[a]) && std::isfinite(bbox[3 + a]) && extent > 0.0f && std::isfinite(extent) && std::isfinite(inv_h) && inv_h > 0.0f &&
-                          std::isfinite(h) && h > 0.0f,
-                      "nrf_nearest_points: empty, inverted or non-finite box on axis %d ([%g, %g])", a, (double)bbox[a], (double)bbox[3 + a]);
-        g.bmin[a] = bbox[a];
-        g.inv_h[a] = inv_h;
-        g.h_min = h < g.h_min ? h : g.h_min;
-    }
+    int axis = 0;
+    NRF_CHECK_ARG(nn_grid_make(bbox, nx, ny, nz, g, axis), "nrf_nearest_points: empty, inverted or non-finite box on axis %d ([%g, %g])", axis, (double)bbox[axis],
+                  (double)bbox[3 + axis]);
     NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 15) == 0, "nrf_nearest_points: the workspace must be non-null and 16-byte aligned");
     Bump bump(d_workspace, workspace_bytes);
     const NnWs ws = nn_layout(bump, nq, nt, g.cells);
@@ -649,6 +1023,133 @@ int nrf_distance_stats(const float *d_dist2, int64_t n, const float *taus, int n
     hipLaunchKernelGGL(k_dist_stats, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, d_dist2, n, t, ws.partials);
     NRF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_geo_finish, dim3(1), dim3(GEO_BLOCK), 0, st, nb, STATS_VALUES, 3, (const double *)ws.partials, d_out, 4 + n_tau);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
+size_t nrf_face_grid_workspace_bytes(int64_t n_faces, int nx, int ny, int nz)
+{
+    if (!fg_shape_ok(0, n_faces, nx, ny, nz)) return 0;
+    return measure([&](Bump &b) { fg_ws_layout(b, (int64_t)nx * ny * nz); });
+}
+
+size_t nrf_face_grid_bytes(int64_t n_faces, int nx, int ny, int nz, int64_t n_refs, int64_t n_large)
+{
+    if (!fg_shape_ok(0, n_faces, nx, ny, nz) || !fg_counts_ok(n_faces, n_refs, n_large)) return 0;
+    return measure([&](Bump &b) { fg_grid_layout(b, (int64_t)nx * ny * nz, n_refs, n_large); });
+}
+
+// the argument checks the three face-grid entries share: shapes, pointers of the mesh, the box
+#define NRF_FG_CHECK_MESH(who)                                                                                                                                            \
+    NRF_CHECK_ARG(fg_shape_ok(n_verts, n_faces, nx, ny, nz), who ": %lld vertices, %lld faces (both 0 .. 2^31 - 1), grid %d x %d x %d (each 1 .. %d, product <= %d)",    \
+                  (long long)n_verts, (long long)n_faces, nx, ny, nz, NRF_NN_MAX_DIM, NRF_NN_MAX_CELLS);                                                                   \
+    NRF_CHECK_ARG(n_faces == 0 || d_faces, who ": null d_faces");                                                                                                         \
+    NRF_CHECK_ARG(d_verts || n_verts == 0 || n_faces == 0, who ": null d_verts");                                                                                         \
+    NRF_CHECK_ARG(bbox, who ": null bbox");                                                                                                                               \
+    NnGrid g;                                                                                                                                                             \
+    int axis = 0;                                                                                                                                                         \
+    NRF_CHECK_ARG(nn_grid_make(bbox, nx, ny, nz, g, axis), who ": empty, inverted or non-finite box on axis %d ([%g, %g])", axis, (double)bbox[axis], (double)bbox[3 + axis])
+
+int nrf_face_grid_count(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz, int64_t *n_refs,
+                        int64_t *n_large, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_FG_CHECK_MESH("nrf_face_grid_count");
+    NRF_CHECK_ARG(n_refs && n_large, "nrf_face_grid_count: null n_refs or n_large");
+    NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_face_grid_count: the workspace must be non-null and 8-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    const FgWs ws = fg_ws_layout(bump, g.cells);
+    NRF_TRY(ws_check(bump, nrf_face_grid_workspace_bytes(n_faces, nx, ny, nz), "nrf_face_grid_count"));
+    hipStream_t st = as_stream(stream);
+    const int64_t cb = ceil_div(g.cells, GEO_BLOCK);
+    NRF_HIP(hipMemsetAsync(ws.count, 0, (size_t)g.cells * sizeof(uint32_t), st));
+    NRF_HIP(hipMemsetAsync(ws.total, 0, sizeof(int64_t), st));
+    NRF_HIP(hipMemsetAsync(ws.counters, 0, 2 * sizeof(uint32_t), st));
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_fg_bin<0>, dim3((unsigned)ceil_div(n_faces, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, g, ws.count,
+                           ws.counters, (int32_t *)nullptr, 0u, (int32_t *)nullptr, 0u, d_stats);
+        NRF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((k_block_sums<uint32_t, GEO_BLOCK>), dim3((unsigned)cb), dim3(GEO_BLOCK), 0, st, g.cells, (const uint32_t *)ws.count, ws.bsum);
+    NRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_totals_scan<int64_t, int64_t>), dim3(1), dim3(SCAN_BLOCK), 0, st, cb, ws.bsum, ws.total);
+    NRF_LAUNCH_CHECK();
+    int64_t total = 0;
+    uint32_t counters[2] = {0, 0};
+    NRF_HIP(hipMemcpyAsync(&total, ws.total, sizeof(total), hipMemcpyDeviceToHost, st));
+    NRF_HIP(hipMemcpyAsync(counters, ws.counters, sizeof(counters), hipMemcpyDeviceToHost, st));
+    NRF_HIP(hipStreamSynchronize(st));
+    *n_refs = total;
+    *n_large = (int64_t)counters[0];
+    NRF_CHECK_ARG(total < ((int64_t)1 << 32), "nrf_face_grid_count: %lld references are 2^32 or more, beyond the uint32 range of the cell starts (use a coarser grid)",
+                  (long long)total);
+    return NRF_OK;
+}
+
+int nrf_face_grid_build(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz, int64_t n_refs,
+                        int64_t n_large, void *d_grid, size_t grid_bytes, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_FG_CHECK_MESH("nrf_face_grid_build");
+    NRF_CHECK_ARG(fg_counts_ok(n_faces, n_refs, n_large), "nrf_face_grid_build: %lld references (0 .. 2^32 - 1), %lld large faces (0 .. %lld): not the count call's",
+                  (long long)n_refs, (long long)n_large, (long long)n_faces);
+    NRF_CHECK_ARG(d_grid && (reinterpret_cast<uintptr_t>(d_grid) & 7) == 0, "nrf_face_grid_build: the grid buffer must be non-null and 8-byte aligned");
+    NRF_CHECK_ARG(grid_bytes == nrf_face_grid_bytes(n_faces, nx, ny, nz, n_refs, n_large), "nrf_face_grid_build: a grid buffer of %zu bytes, nrf_face_grid_bytes gives %zu",
+                  grid_bytes, nrf_face_grid_bytes(n_faces, nx, ny, nz, n_refs, n_large));
+    NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_face_grid_build: the workspace must be non-null and 8-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    const FgWs ws = fg_ws_layout(bump, g.cells);
+    NRF_TRY(ws_check(bump, nrf_face_grid_workspace_bytes(n_faces, nx, ny, nz), "nrf_face_grid_build"));
+    Bump gb(d_grid, grid_bytes);
+    const FgGrid grid = fg_grid_layout(gb, g.cells, n_refs, n_large);
+    hipStream_t st = as_stream(stream);
+    const int64_t cb = ceil_div(g.cells, GEO_BLOCK);
+    hipLaunchKernelGGL(k_fg_starts, dim3((unsigned)cb), dim3(GEO_BLOCK), 0, st, g.cells, (const uint32_t *)ws.count, (const int64_t *)ws.bsum, grid.start, ws.cursor,
+                       fg_key(n_faces, nx, ny, nz, n_refs, n_large, bbox), grid.key);
+    NRF_LAUNCH_CHECK();
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_fg_bin<1>, dim3((unsigned)ceil_div(n_faces, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, g, ws.cursor,
+                           ws.counters, grid.refs, (uint32_t)n_refs, grid.large, (uint32_t)n_large, (uint32_t *)nullptr);
+        NRF_LAUNCH_CHECK();
+    }
+    return NRF_OK;
+}
+
+size_t nrf_closest_on_mesh_workspace_bytes(int64_t nq)
+{
+    if (nq < 0 || nq > INT32_MAX) return 0;
+    return measure([&](Bump &b) { cm_layout(b, nq); });
+}
+
+int nrf_closest_on_mesh(const float *d_query, int64_t nq, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny,
+                        int nz, int64_t n_refs, int64_t n_large, const void *d_grid, size_t grid_bytes, float max_dist, float *d_dist2, int32_t *d_face, float *d_uv,
+                        float *d_point, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(nq >= 0 && nq <= INT32_MAX, "nrf_closest_on_mesh: %lld queries (0 .. 2^31 - 1)", (long long)nq);
+    NRF_FG_CHECK_MESH("nrf_closest_on_mesh");
+    NRF_CHECK_ARG(nq == 0 || (d_query && d_dist2 && d_face), "nrf_closest_on_mesh: null d_query, d_dist2 or d_face");
+    NRF_CHECK_ARG(max_dist >= 0.0f, "nrf_closest_on_mesh: max_dist must be >= 0 or +inf (got %g)", (double)max_dist);          // NaN fails
+    NRF_CHECK_ARG(fg_counts_ok(n_faces, n_refs, n_large), "nrf_closest_on_mesh: %lld references (0 .. 2^32 - 1), %lld large faces (0 .. %lld): not the count call's",
+                  (long long)n_refs, (long long)n_large, (long long)n_faces);
+    NRF_CHECK_ARG(d_grid && (reinterpret_cast<uintptr_t>(d_grid) & 7) == 0, "nrf_closest_on_mesh: the grid buffer must be non-null and 8-byte aligned");
+    NRF_CHECK_ARG(grid_bytes == nrf_face_grid_bytes(n_faces, nx, ny, nz, n_refs, n_large),
+                  "nrf_closest_on_mesh: a grid buffer of %zu bytes was not built for these faces, dims and counts (nrf_face_grid_bytes gives %zu)", grid_bytes,
+                  nrf_face_grid_bytes(n_faces, nx, ny, nz, n_refs, n_large));
+    NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_closest_on_mesh: the workspace must be non-null and 8-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    const CmWs ws = cm_layout(bump, nq);
+    NRF_TRY(ws_check(bump, nrf_closest_on_mesh_workspace_bytes(nq), "nrf_closest_on_mesh"));
+    if (nq == 0) return NRF_OK;
+    Bump gb(const_cast<void *>(d_grid), grid_bytes);
+    const FgGrid grid = fg_grid_layout(gb, g.cells, n_refs, n_large);
+    hipStream_t st = as_stream(stream);
+    const float md2 = max_dist * max_dist;
+    const FgKey key = fg_key(n_faces, nx, ny, nz, n_refs, n_large, bbox);
+    NRF_HIP(hipMemsetAsync(ws.n_far, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_cm_query, dim3((unsigned)ceil_div(nq, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_query, nq, d_verts, (int32_t)n_verts, d_faces, n_faces, g, key, md2,
+                       (const long long *)grid.key, (const uint32_t *)grid.start, (const int32_t *)grid.refs, (const int32_t *)grid.large, d_dist2, d_face, d_uv, d_point, ws.far,
+                       ws.n_far, d_stats);
+    NRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_cm_far, dim3(FAR_GRID), dim3(GEO_BLOCK), 0, st, d_query, d_verts, (const int32_t)n_verts, d_faces, n_faces, key, md2, (const long long *)grid.key,
+                       d_dist2, d_face, d_uv, d_point, (const int32_t *)ws.far, (const uint32_t *)ws.n_far, d_stats);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

@@ -1,11 +1,12 @@
-"""Comparing surfaces in space: SampleSurface, InterpolateAttributes, NearestPoints, TransferAttributes and SurfaceDistance over the C ABI (include/nerfpp_hip.h,
-geometry.hip).
+"""Comparing surfaces in space: SampleSurface, InterpolateAttributes, NearestPoints, FaceGrid, ClosestOnMesh, TransferAttributes and SurfaceDistance over the C ABI
+(include/nerfpp_hip.h, geometry.hip).
 
 The reference has no geometry metrics; the names follow the mirror's style.  A Mesh is sampled in proportion to area (every draw a pure function of seed and index),
 two point sets are compared through a uniform-grid nearest-neighbour search whose result is the minimum of a packed (distance bits, index) key -- so it depends on
 neither the grid nor the order of the points -- and the sums behind Chamfer distance, Hausdorff distance and precision / recall / F-score at a distance are ordered
-fp64 reductions.  tests/geometry_ref.py equals every output bit for bit and two runs agree.  This is the sampled point-to-point distance of the DTU / Tanks and Temples
-benchmarks, not an exact point-to-triangle distance.
+fp64 reductions.  tests/geometry_ref.py equals every output bit for bit and two runs agree.  That is the sampled point-to-point distance of the DTU / Tanks and Temples
+benchmarks; FaceGrid / ClosestOnMesh are the exact point-to-triangle query beside it (the nearest face, the point on it, its barycentrics; tests/closest_ref.py),
+which SurfaceDistance(to="surface"), TransferAttributes(source="surface") and texture.BakeTexture(source=<Mesh>) are thin layers over.
 """
 import ctypes as C
 import math
@@ -21,6 +22,7 @@ from .modules import _ptr, _stream, _dev_f32
 
 # NRF_SAMPLE_* / NRF_NN_* / NRF_STATS_* of the header (tests/test_geometry_host.py holds them to it)
 SAMPLE_MAX_PER_FACE, NN_MAX_DIM, NN_MAX_CELLS, NN_MAX_RINGS, STATS_MAX_TAU = 65536, 1024, 1 << 26, 16, 4
+FG_MAX_FACE_CELLS = 64          # NRF_FG_MAX_FACE_CELLS (tests/test_closest_host.py holds it to the header)
 OCCUPANCY = 128.0        # what GridDims aims at by default: about 20-30 targets per occupied cell as measured; coarse enough that 16 rings reach far
 _ATTRS = ("Colors", "Normals", "Relevancy")
 
@@ -45,6 +47,18 @@ class SurfaceDistanceResult:          # float64 device tensors, as EvaluateViews
     Recall: torch.Tensor              # [n_tau] the share of b's points within tau of a
     FScore: torch.Tensor              # [n_tau] 2 P R / (P + R), 0 where P + R = 0
     Taus: tuple = ()
+
+
+@dataclass
+class ClosestResult:                  # ClosestOnMesh's; InterpolateAttributes takes it as it takes SurfaceSamples
+    Dist2: torch.Tensor               # [n] f32 squared distance to the nearest face; +inf where there is none (within max_dist) or the query is not finite
+    Face: torch.Tensor                # [n] int32 that face; -1 where there is none
+    UV: torch.Tensor                  # [n, 2] f32: the closest point is about (1 - u - v) v0 + u v1 + v v2 of that face; zeros where there is none
+    Points: torch.Tensor              # [n, 3] f32 the closest point itself
+
+    @property
+    def Faces(self):
+        return self.Face
 
 
 def _mesh_arrays(mesh):
@@ -92,9 +106,13 @@ def InterpolateAttributes(mesh, samples, name):
         raise L.NrfError(f"InterpolateAttributes: the mesh has no {name!r}")
     attr = _dev_f32(getattr(mesh, name))
     a = attr.reshape(attr.shape[0], -1)
-    f = mesh.Faces.to(device=a.device, dtype=torch.int64)[samples.Faces.to(torch.int64)]
+    at = samples.Faces.to(torch.int64)
+    miss = at < 0 if isinstance(samples, ClosestResult) else None          # a ClosestResult has -1 where no face was found: zeros there
+    f = mesh.Faces.to(device=a.device, dtype=torch.int64)[at if miss is None else at.clamp(min=0)]
     u, v = samples.UV[:, :1], samples.UV[:, 1:]
     out = (1.0 - u - v) * a[f[:, 0]] + u * a[f[:, 1]] + v * a[f[:, 2]]
+    if miss is not None:
+        out = torch.where(miss[:, None], torch.zeros_like(out), out)
     return out[:, 0] if attr.dim() == 1 else out
 
 
@@ -149,6 +167,59 @@ def NearestPoints(query, target, max_dist=None, bbox=None, cells=None, stats=Non
     return d2, idx
 
 
+def _host_box(bbox):
+    return np.ascontiguousarray(torch.as_tensor(bbox).detach().cpu().numpy() if torch.is_tensor(bbox) else bbox, np.float32).reshape(6)
+
+
+class FaceGrid:
+    """The faces of `mesh` binned into a uniform grid for ClosestOnMesh (nrf_face_grid_count / _build); build it once, query it many times.  bbox [6] is where the
+    grid lies (faces and queries outside it are still found); bbox=None takes the box of the vertices, which costs ONE host synchronisation; the count call costs
+    one more.  cells = (nx, ny, nz) overrides GridDims(box, n_faces).  No result depends on either.  The grid keeps its buffer and the mesh's arrays alive.
+    stats: an int32 [4] device tensor whose entries 1 and 2 the faces with a corner outside the vertices and with a non-finite vertex are added to."""
+
+    def __init__(self, mesh, bbox=None, cells=None, stats=None):
+        self.Mesh = mesh
+        self.Verts, self.Faces = _mesh_arrays(mesh)
+        dev = self.Verts.device
+        nv, nf = int(self.Verts.shape[0]), int(self.Faces.shape[0])
+        self.Box = _bbox_of(self.Verts) if bbox is None else _host_box(bbox)
+        self.Dims = tuple(GridDims(self.Box, nf)) if cells is None else tuple(int(c) for c in cells)
+        nx, ny, nz = self.Dims
+        lib = L.lib()
+        ws = _workspace(lib.nrf_face_grid_workspace_bytes(nf, nx, ny, nz), dev)
+        n_refs, n_large = C.c_int64(0), C.c_int64(0)
+        box = self.Box.ctypes.data_as(C.c_void_p)
+        L.check(lib.nrf_face_grid_count(_ptr(self.Verts), nv, _ptr(self.Faces), nf, box, nx, ny, nz, C.addressof(n_refs), C.addressof(n_large), _ptr(stats), _ptr(ws),
+                                        ws.numel(), _stream()))
+        self.NRefs, self.NLarge = int(n_refs.value), int(n_large.value)
+        self.Buffer = torch.empty((int(lib.nrf_face_grid_bytes(nf, nx, ny, nz, self.NRefs, self.NLarge)),), device=dev, dtype=torch.uint8)
+        L.check(lib.nrf_face_grid_build(_ptr(self.Verts), nv, _ptr(self.Faces), nf, box, nx, ny, nz, self.NRefs, self.NLarge, _ptr(self.Buffer), self.Buffer.numel(),
+                                        _ptr(ws), ws.numel(), _stream()))
+
+
+def ClosestOnMesh(query, mesh_or_grid, max_dist=None, stats=None, bbox=None, cells=None, uv=True, points=True):
+    """For every point of query [nq, 3] the closest point on the surface of a Mesh or its FaceGrid -> ClosestResult (nrf_closest_on_mesh): the nearest face (on an
+    exact tie the lowest index), the point on it, its (u, v) and the squared distance; +inf, -1 and zeros where no face lies within max_dist or the query is not
+    finite.  A Mesh is binned first (FaceGrid(mesh, bbox, cells): two host synchronisations, one with a bbox); pass a FaceGrid to query the same mesh again without
+    either.  uv=False / points=False leave that output out (None).  stats: an int32 [4] device tensor; entry 0 += non-finite queries, entry 3 += queries served by the
+    brute-force fallback."""
+    grid = mesh_or_grid if isinstance(mesh_or_grid, FaceGrid) else FaceGrid(mesh_or_grid, bbox=bbox, cells=cells, stats=stats)
+    q = _dev_f32(query).reshape(-1, 3).to(grid.Verts.device)
+    dev, nq = q.device, int(q.shape[0])
+    d2 = torch.empty((nq,), device=dev, dtype=torch.float32)
+    face = torch.empty((nq,), device=dev, dtype=torch.int32)
+    out_uv = torch.empty((nq, 2), device=dev, dtype=torch.float32) if uv else None
+    out_p = torch.empty((nq, 3), device=dev, dtype=torch.float32) if points else None
+    lib = L.lib()
+    ws = _workspace(lib.nrf_closest_on_mesh_workspace_bytes(nq), dev)
+    nx, ny, nz = grid.Dims
+    L.check(lib.nrf_closest_on_mesh(_ptr(q), nq, _ptr(grid.Verts), int(grid.Verts.shape[0]), _ptr(grid.Faces), int(grid.Faces.shape[0]),
+                                    grid.Box.ctypes.data_as(C.c_void_p), nx, ny, nz, grid.NRefs, grid.NLarge, _ptr(grid.Buffer), grid.Buffer.numel(),
+                                    float("inf") if max_dist is None else float(max_dist), _ptr(d2), _ptr(face), _ptr(out_uv), _ptr(out_p), _ptr(stats), _ptr(ws),
+                                    ws.numel(), _stream()))
+    return ClosestResult(d2, face, out_uv, out_p)
+
+
 def DistanceStats(dist2, taus=()):
     """[4 + len(taus)] float64 on the device: count, sum of d, sum of d^2, max d and count(d <= tau) over the finite entries of dist2 (nrf_distance_stats)."""
     d2 = _dev_f32(dist2).reshape(-1)
@@ -160,10 +231,18 @@ def DistanceStats(dist2, taus=()):
     return out
 
 
-def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_dist=None, bbox=None):
+def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_dist=None, bbox=None, source="vertex"):
     """A copy of dst_mesh whose attributes `names` are those of the nearest vertex of src_mesh (the ones src_mesh carries): TSDF colours onto an isosurface, relevancy
-    onto another mesh.  A vertex without a neighbour (within max_dist) gets zeros."""
+    onto another mesh.  A vertex without a neighbour (within max_dist) gets zeros.  source="surface" takes the attribute at the closest point ON src_mesh instead,
+    interpolated over its face (ClosestOnMesh; src_mesh may be a FaceGrid): what a coarse mesh needs from a dense one."""
     import dataclasses
+    if source not in ("vertex", "surface"):
+        raise L.NrfError(f"TransferAttributes: source must be 'vertex' or 'surface', got {source!r}")
+    if source == "surface":
+        grid = src_mesh if isinstance(src_mesh, FaceGrid) else FaceGrid(src_mesh, bbox=bbox)
+        res = ClosestOnMesh(dst_mesh.Vertices, grid, max_dist=max_dist, points=False)
+        new = {name: InterpolateAttributes(grid.Mesh, res, name) for name in names if getattr(grid.Mesh, name) is not None}
+        return dataclasses.replace(dst_mesh, **new)
     _, idx = NearestPoints(dst_mesh.Vertices, src_mesh.Vertices, max_dist=max_dist, bbox=bbox)
     found = idx >= 0
     at = idx.clamp(min=0).to(torch.int64)
@@ -177,15 +256,24 @@ def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_di
     return dataclasses.replace(dst_mesh, **new)
 
 
-def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_dist=None, bbox=None):
+def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_dist=None, bbox=None, to="points"):
     """How far apart two surfaces are, a the prediction and b the truth, each a Mesh (sampled: SampleSurface(n_points=n_points, seed=seed)) or a [N, 3] tensor of
     points (used as they are).  Returns a SurfaceDistanceResult of float64 device tensors.  With max_dist, points without a neighbour that near are left out of the
-    means and count as misses in Precision / Recall.  bbox as in NearestPoints (None: two synchronisations, one per direction)."""
+    means and count as misses in Precision / Recall.  bbox as in NearestPoints (None: two synchronisations, one per direction).
+    to="surface" measures the samples of each side against the FACES of the other where that side is a Mesh (ClosestOnMesh: the exact point-to-triangle distance,
+    whose floor is zero, not the other side's sampling density); a side given as points is still searched as points."""
     if len(taus) > STATS_MAX_TAU:
         raise L.NrfError(f"SurfaceDistance: {len(taus)} thresholds, at most {STATS_MAX_TAU}")
+    if to not in ("points", "surface"):
+        raise L.NrfError(f"SurfaceDistance: to must be 'points' or 'surface', got {to!r}")
     pa, pb = _as_points(a, n_points, seed), _as_points(b, n_points, seed)
-    sa = DistanceStats(NearestPoints(pa, pb, max_dist=max_dist, bbox=bbox)[0], taus)
-    sb = DistanceStats(NearestPoints(pb, pa, max_dist=max_dist, bbox=bbox)[0], taus)
+
+    def dist2(p, other, other_points):
+        if to == "surface" and isinstance(other, M.Mesh):
+            return ClosestOnMesh(p, other, max_dist=max_dist, bbox=bbox, uv=False, points=False).Dist2
+        return NearestPoints(p, other_points, max_dist=max_dist, bbox=bbox)[0]
+    sa = DistanceStats(dist2(pa, b, pb), taus)
+    sb = DistanceStats(dist2(pb, a, pa), taus)
     acc, comp = sa[1] / sa[0], sb[1] / sb[0]
     # tensor / tensor: a division by a Python scalar is carried out as a multiplication by its reciprocal, which is not the correctly rounded quotient
     na, nb = (torch.full((), float(x.shape[0]), device=sa.device, dtype=torch.float64) for x in (pa, pb))

@@ -86,10 +86,21 @@ def AtlasTexels(mesh, tile, offset=0.0, rows=None):
     return face, bary, pos, rays
 
 
-def _colour_source(source, mode, rparams, offset):
+def _colour_source(source, mode, rparams, offset, attribute="Colors", max_dist=None):
     """-> (colour(pos [n, 3], rays [n, 11]) -> (rgb [n, C], acc [n] or None), the offset of the rays)"""
+    from . import geometry as G
+    from .mesh import Mesh
     from .renderer import LeRFRenderer, NeRFRenderer
     from .tsdf import TSDFVolume
+    if isinstance(source, (Mesh, G.FaceGrid)):
+        grid = source if isinstance(source, G.FaceGrid) else G.FaceGrid(source)          # binned once per bake
+        if attribute not in ("Colors", "Relevancy") or getattr(grid.Mesh, attribute) is None:
+            raise L.NrfError(f"BakeTexture: the source mesh has no {attribute!r} to bake (attribute is 'Colors' or 'Relevancy')")
+
+        def closest(pos, rays):
+            res = G.ClosestOnMesh(pos, grid, max_dist=max_dist, points=False)
+            return G.InterpolateAttributes(grid.Mesh, res, attribute).reshape(pos.shape[0], -1), None
+        return closest, 0.0
     if isinstance(source, LeRFRenderer):
         raise L.NrfError("BakeTexture: a LeRF renderer renders no colour; bake from its NeRFRenderer")
     if isinstance(source, TSDFVolume):
@@ -117,19 +128,22 @@ def _colour_source(source, mode, rparams, offset):
         return render, float(offset)
     if callable(source):
         return (lambda pos, rays: (source(pos, rays[:, 3:6].contiguous()), None)), 0.0
-    raise L.NrfError(f"BakeTexture: no way to take colour from {type(source).__name__} (a NeRFRenderer, a TSDFVolume or a callable (pos, dir) -> [n, C])")
+    raise L.NrfError(f"BakeTexture: no way to take colour from {type(source).__name__} (a NeRFRenderer, a TSDFVolume, a Mesh or a callable (pos, dir) -> [n, C])")
 
 
-def BakeTexture(mesh, source, tile=8, mode="point", rparams=None, offset=None, chunk_rows=None):
+def BakeTexture(mesh, source, tile=8, mode="point", rparams=None, offset=None, chunk_rows=None, attribute="Colors", max_dist=None):
     """Bake the atlas of `mesh` at `tile` texels from `source`, slab by slab of chunk_rows atlas rows (default: about SLAB_TEXELS texels); texels without an owner
     get 0.  No host synchronisation of its own.  source:
       a NeRFRenderer, mode="point"   sigmoid(RunNetwork(P, -N)[..., :3]) at the texel's surface point P seen along -N: what ExtractMesh does per vertex;
       a NeRFRenderer, mode="render"  BatchifyRays over AtlasTexels' short rays (rparams.NSamples / NImportance / WhiteBkgr / Precision / Chunk, no cone): the colour
                                      a camera `offset` (world units, required) above the surface on its normal sees; the AccMap is kept as Acc.  NDC is refused;
       a TSDFVolume                   its colour volume at P (nrf_tsdf_sample_color);
-      a callable                     source(pos [n, 3], dir [n, 3]) -> [n, C], C <= 8, dir = -N.
+      a callable                     source(pos [n, 3], dir [n, 3]) -> [n, C], C <= 8, dir = -N;
+      a Mesh (or its FaceGrid)       its `attribute` ("Colors" or "Relevancy") interpolated at the closest point of ITS surface to P (geometry.ClosestOnMesh): the
+                                     detail of a dense mesh carried onto a simplified one.  The source is binned once per bake (two host synchronisations; none
+                                     with a FaceGrid); texels with no face within max_dist get 0.
     LeRF renderers are refused as FuseViews refuses them."""
-    colour, off = _colour_source(source, mode, rparams, offset)
+    colour, off = _colour_source(source, mode, rparams, offset, attribute, max_dist)
     nf, t = int(mesh.Faces.shape[0]), int(tile)
     w, h, _, _ = AtlasLayout(nf, t)
     step = max(1, SLAB_TEXELS // max(w, 1)) if chunk_rows is None else int(chunk_rows)

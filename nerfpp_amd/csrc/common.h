@@ -65,21 +65,7 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ---- reductions over the 64 lanes of a wave ----
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
+// (the reductions over a wave and a block: reduce.h)
 // inclusive prefix sum in lane order (lane = the caller's lane id)
 __device__ __forceinline__ double wave_incl_scan(double v, int lane)
 {

@@ -8,8 +8,8 @@
 // so the scan reproduces the sequential result.  exp/log/sigmoid come from include/nrf_math.h (the same bits on
 // the CPU oracle and here), which makes the whole stage -- and with it the fine-pass sample set -- reproducible.  The pdf normaliser sum(w) is evaluated in ATen's own lane
 // order (sum_vec) because it feeds searchsorted: the sample INDICES are bit-exact against the oracle.
-#include "common.h"
 #include "live_points.h"
+#include "reduce.h"
 #include "stoch.h"
 
 #include <type_traits>
@@ -27,14 +27,6 @@ __device__ __forceinline__ T wave_incl_scan_t(T v, int lane)
         const T t = __shfl_up(v, off);
         if (lane >= off) v += t;
     }
-    return v;
-}
-
-template <class T>
-__device__ __forceinline__ T wave_sum_t(T v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
 
@@ -154,7 +146,7 @@ k_raw2outputs(int64_t n, int s, int c, int sigma_ch, int white, const float *__r
             sw += (acc_t)w; swz += (acc_t)(w * zj);
         }
     }
-    sr = wave_sum_t<acc_t>(sr); sg = wave_sum_t<acc_t>(sg); sb = wave_sum_t<acc_t>(sb); sw = wave_sum_t<acc_t>(sw); swz = wave_sum_t<acc_t>(swz);
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sw = wave_sum(sw); swz = wave_sum(swz);
     if (flag) { if (__any(bad_acc != bad_acc) && lane == 0) atomicOr(flag, 1u); }
     if (lane == 0) {
         const float a = (float)sw;
@@ -513,12 +505,9 @@ __global__ void __launch_bounds__(256) k_clip_embedding(int s, int stride, int d
         out[ray * dim + k] = v;
         ss += (double)v * (double)v;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (flag && threadIdx.x == 0 && !(red[0] + red[1] + red[2] + red[3] <= 1.7e308)) atomicOr(flag, 1u);
-    const float nrm = fmaxf((float)sqrt(red[0] + red[1] + red[2] + red[3]), 1e-8f);
+    ss = ordered_block_sum<256>(ss, red);
+    if (flag && threadIdx.x == 0 && !(ss <= 1.7e308)) atomicOr(flag, 1u);
+    const float nrm = fmaxf((float)sqrt(ss), 1e-8f);
     for (int k = threadIdx.x; k < dim; k += 256) out[ray * dim + k] = out[ray * dim + k] / nrm;
 }
 

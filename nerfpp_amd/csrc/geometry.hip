@@ -3,8 +3,8 @@
 // stated in include/nerfpp_hip.h and restated in numpy by tests/geometry_ref.py, which the GPU tests compare with bit for bit.
 //
 // Sampling.  k_sample_faces: one lane per face -- indices checked before anything is read, the fp32 area, the face's point count n_f (floor of area * density plus
-//   one Bernoulli draw of the fraction), the block's total of n_f and its ordered fp64 sum of the areas.  k_totals_scan (scan.h, one workgroup) turns the block totals into block
-//   offsets, k_geo_finish adds the area partials in image_metrics.hip's order, k_sample_offsets writes every face's first point.  The emit kernel runs one lane per
+//   one Bernoulli draw of the fraction), the block's total of n_f and its ordered fp64 sum of the areas (reduce.h).  k_totals_scan (scan.h, one workgroup) turns the block totals into block
+//   offsets, k_geo_finish adds the area partials in reduce.h's finish pass, k_sample_offsets writes every face's first point.  The emit kernel runs one lane per
 //   POINT and finds its face by a binary search in the offsets: a face clamped to NRF_SAMPLE_MAX_PER_FACE points costs its lanes nothing extra.  Every position comes
 //   from an integer prefix sum and every draw is a pure function of (seed, stream, index): two runs give the same arrays.
 // Nearest points.  A uniform grid over the caller's box: k_nn_bin<0> (one non-returning atomic add per finite target), the scan of the cell counts (scan.h's k_block_sums
@@ -14,15 +14,15 @@
 //   (ballot, popcount, one returning atomic per wave); k_nn_far, a fixed grid of workgroups, brute-forces all records for each listed query with a block-wide minimum.
 //   Both form d2 in nn_d2: one copy of the arithmetic.  The minimum of a set does not depend on the order it arrives in, so the result depends on neither the grid,
 //   the scheduling nor the order of the targets (beyond the tie-break by index the key states).
-// Statistics.  k_dist_stats: 4096 entries per block, lane t takes t, t + 256, ... in ascending order; wave shuffle tree, four wave sums in order, one row of eight fp64
-//   partials per block; k_geo_finish adds the rows in image_metrics.hip's k_finish order.  No atomics.
+// Statistics.  k_dist_stats: 4096 entries per block, lane t takes t, t + 256, ... in ascending order; reduce.h's ordered block sum (block maximum) per column, one row of
+//   eight fp64 partials per block; k_geo_finish is reduce.h's ordered finish pass per column.  No atomics.
 // Closest point on a mesh.  The same grid holds FACES: k_fg_bin<0> counts one reference per cell of a face's cell box (a box of more than NRF_FG_MAX_FACE_CELLS cells:
 //   the large list), the scan, k_fg_starts (starts into the caller's grid buffer, with what it was built for at its head), k_fg_bin<1> scatters face indices.
 //   k_cm_query: one lane per query, the large list, then k_nn_query's ring walk over references, the same stop; k_cm_far brute-forces all faces for the listed
 //   queries.  cm_take / cm_closest are the one copy of the candidate: Ericson's regions in a fixed order, P clamped to the face's coordinate box (the stop's proof
 //   needs it), d2 through nn_d2.  tests/closest_ref.py restates it.
 // Every loop is bounded by a clamped range or a count; no kernel waits on another workgroup.
-#include "common.h"
+#include "reduce.h"
 #include "scan.h"
 #include "workspace.h"
 #include "nrf_rng.h"
@@ -40,44 +40,13 @@ constexpr int STATS_TILE = 4096;         // entries per block of k_dist_stats
 constexpr int STATS_VALUES = 8;          // count, sum d, sum d2, max d, four tau counts
 constexpr unsigned long long NN_NONE = ((unsigned long long)0x7f800000u << 32) | 0xffffffffu;          // d2 = +inf, index = -1: above every key with a valid index
 
-// ---------------------------------------------------------------------------------------------- shared: ordered fp64 sums
-// the block's sum of one double per lane: wave shuffle tree, then the four wave sums in wave order (valid in thread 0)
-__device__ __forceinline__ double block_sum_ordered(double v, double *s_wave)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double a = s_wave[0];
-#pragma unroll
-    for (int k = 1; k < GEO_BLOCK / 64; k++) a += s_wave[k];
-    __syncthreads();
-    return a;
-}
-
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
-// out[v] = the sum over k of partials[k * nv + v] (v == max_at: the maximum): one block; thread t takes k = t, t + 256, ... in ascending order, then a fixed tree
+// out[v] = the ordered sum over k of partials[k * nv + v] (v == max_at: the maximum), v < n_out: one block, reduce.h's finish pass per column
 __global__ void __launch_bounds__(GEO_BLOCK) k_geo_finish(int64_t count, int nv, int max_at, const double *__restrict__ partials, double *__restrict__ out, int n_out)
 {
     __shared__ double s_a[GEO_BLOCK];
-    const int t = threadIdx.x;
     for (int v = 0; v < n_out; v++) {
-        const bool is_max = v == max_at;
-        double a = 0.0;
-        for (int64_t k = t; k < count; k += GEO_BLOCK) a = is_max ? fmax(a, partials[k * nv + v]) : a + partials[k * nv + v];
-        s_a[t] = a;
-        __syncthreads();
-        for (int off = GEO_BLOCK / 2; off > 0; off >>= 1) {
-            if (t < off) s_a[t] = is_max ? fmax(s_a[t], s_a[t + off]) : s_a[t] + s_a[t + off];
-            __syncthreads();
-        }
-        if (t == 0) out[v] = s_a[0];
-        __syncthreads();
+        const double a = v == max_at ? ordered_finish<GEO_BLOCK, true>(partials, count, nv, v, s_a) : ordered_finish<GEO_BLOCK>(partials, count, nv, v, s_a);
+        if (threadIdx.x == 0) out[v] = a;
     }
 }
 
@@ -163,7 +132,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_sample_faces(const float *__restr
         count[f] = n;
     }
     const int total = block_sum<int, GEO_BLOCK>(n, sh);
-    const double part = block_sum_ordered(area64, s_wave);
+    const double part = ordered_block_sum<GEO_BLOCK>(area64, s_wave);
     if (threadIdx.x == 0) {
         bsum[blockIdx.x] = total;
         area_part[blockIdx.x] = part;
@@ -424,21 +393,12 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_nn_far(const float *__restrict__ 
         const float qx = query[q * 3 + 0], qy = query[q * 3 + 1], qz = query[q * 3 + 2];
         unsigned long long best = NN_NONE;
         for (uint32_t t = threadIdx.x; t < n_rec; t += GEO_BLOCK) nn_take(qx, qy, qz, rec[t], md2, best);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off, 64), lo = __shfl_xor((uint32_t)best, off, 64);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            best = o < best ? o : best;
-        }
-        if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
-        __syncthreads();
+        best = block_key_min<GEO_BLOCK>(best, s_best);
         if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 1; k < GEO_BLOCK / 64; k++) best = s_best[k] < best ? s_best[k] : best;
             dist2[q] = __uint_as_float((uint32_t)(best >> 32));
             index[q] = (int32_t)(uint32_t)best;
         }
-        __syncthreads();
+        __syncthreads();          // the next query goes through the same words
     }
 }
 
@@ -478,17 +438,9 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_dist_stats(const float *__restric
     }
 #pragma unroll
     for (int v = 0; v < STATS_VALUES; v++) {
-        double a;
-        if (v == 3) {
-            a = wave_max(acc[3]);
-            if ((t & 63) == 0) s_wave[t >> 6] = a;
-            __syncthreads();
-            a = fmax(fmax(s_wave[0], s_wave[1]), fmax(s_wave[2], s_wave[3]));
-            __syncthreads();
-        } else {
-            a = block_sum_ordered(acc[v], s_wave);
-        }
+        const double a = v == 3 ? ordered_block_max<GEO_BLOCK>(acc[3], s_wave) : ordered_block_sum<GEO_BLOCK>(acc[v], s_wave);
         if (t == 0) partials[(int64_t)blockIdx.x * STATS_VALUES + v] = a;
+        __syncthreads();          // the next column goes through the same words
     }
 }
 
@@ -833,20 +785,9 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_cm_far(const float *__restrict__ 
         const float q[3] = {query[qi * 3 + 0], query[qi * 3 + 1], query[qi * 3 + 2]};
         unsigned long long best = NN_NONE;
         for (int64_t f = threadIdx.x; f < n_faces; f += GEO_BLOCK) cm_take(q, verts, n_verts, faces, n_faces, f, md2, best);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off, 64), lo = __shfl_xor((uint32_t)best, off, 64);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            best = o < best ? o : best;
-        }
-        if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 1; k < GEO_BLOCK / 64; k++) best = s_best[k] < best ? s_best[k] : best;
-            cm_write(q, qi, best, verts, n_verts, faces, n_faces, dist2, face, uv, point);
-        }
-        __syncthreads();
+        best = block_key_min<GEO_BLOCK>(best, s_best);
+        if (threadIdx.x == 0) cm_write(q, qi, best, verts, n_verts, faces, n_faces, dist2, face, uv, point);
+        __syncthreads();          // the next query goes through the same words
     }
 }
 

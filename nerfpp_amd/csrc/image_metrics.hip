@@ -13,12 +13,12 @@
 //   LDS: 14.1 KB + 53.8 KB = 67.9 KB with fp32 inputs (two workgroups per CU), 82.0 KB with fp64 inputs (the pooled scales of MS-SSIM: small grids).  A lane's 8-byte
 //   accesses in both passes go to consecutive doubles across the 32 lanes of a tile row: 64 distinct banks per 32-lane group, conflict-free; the fp32 tile reads
 //   are consecutive words of a 42-word row.
-//   Sums: lane, wave shuffle tree, the four wave sums in wave order -> one fp64 pair per workgroup in the workspace; k_finish (one block per image channel) adds
-//   the pairs in a fixed strided order and tree and divides by the count.  No atomics: two runs give the same bits, and an image's result does not depend on the batch
-//   it came in.
+//   Sums: the lane's, then reduce.h's ordered block sum -> one fp64 pair per workgroup in the workspace; k_finish (one block per image channel) is reduce.h's ordered
+//   finish pass over the pairs and divides by the count.  No atomics: two runs give the same bits, and an image's result does not depend on the batch it came in.
 // k_pool2<T>: ((a00 + a01) + (a10 + a11)) * 0.25 in double, an odd trailing row / column dropped; the pooled planes are doubles in the workspace.
 // k_mse: 4096 elements per block, lane t takes t, t + 256, ... in ascending order; the same partials and k_finish.
 // k_ssim_loss<CT> / k_ssim_loss_finish: 1 - mean SSIM as a training loss and its gradient d loss / d x (nrf_ssim_loss); described where they stand.
+#include "reduce.h"
 #include "workspace.h"
 
 #include <cmath>
@@ -57,7 +57,7 @@ k_ssim(const T *__restrict__ x, const T *__restrict__ y, int h, int w, int c, in
 {
     __shared__ T s_x[SS_IN * SS_IN], s_y[SS_IN * SS_IN];
     __shared__ double s_m[5][SS_IN][SS_TILE];
-    __shared__ double s_sum[2][IM_THREADS / 64];
+    __shared__ double s_sum[2 * (IM_THREADS / 64)];
     const int t = threadIdx.x;
     const int ty0 = (int)(blockIdx.x / (unsigned)tiles_x) * SS_TILE, tx0 = (int)(blockIdx.x % (unsigned)tiles_x) * SS_TILE;
     const int img = (int)(blockIdx.y / (unsigned)c), ch = (int)(blockIdx.y % (unsigned)c);
@@ -115,35 +115,19 @@ k_ssim(const T *__restrict__ x, const T *__restrict__ y, int h, int w, int c, in
             if (map) map[(((int64_t)img * oh + oy) * ow + ox) * c + ch] = ssim;
         }
     }
-    sum_ssim = wave_sum(sum_ssim); sum_cs = wave_sum(sum_cs);
-    if ((t & 63) == 0) { s_sum[0][t >> 6] = sum_ssim; s_sum[1][t >> 6] = sum_cs; }
-    __syncthreads();
-    if (t < 2) {
-        double a = s_sum[t][0];
-#pragma unroll
-        for (int k = 1; k < IM_THREADS / 64; k++) a += s_sum[t][k];
-        partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + t] = a;
-    }
+    double sums[2] = {sum_ssim, sum_cs};
+    ordered_block_sum<IM_THREADS, 2>(sums, s_sum);
+    if (t < 2) partials[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + t] = t == 0 ? sums[0] : sums[1];
 }
 
-// out[i][v] = (sum over k of partials[i][k][v]) / count, v < nv <= 2: one block per i; thread t adds k = t, t + 256, ... in ascending order, then a fixed tree
-__global__ void __launch_bounds__(IM_THREADS) k_finish(int64_t per_image, int nv, const double *__restrict__ partials, double count, double *__restrict__ out)
+// out[i][v] = (the ordered sum over k of partials[i][k][v]) / count, v < NV: one block per i
+template <int NV>
+__global__ void __launch_bounds__(IM_THREADS) k_finish(int64_t per_image, const double *__restrict__ partials, double count, double *__restrict__ out)
 {
-    __shared__ double s_a[IM_THREADS], s_b[IM_THREADS];
-    const int t = threadIdx.x;
-    const double *p = partials + (int64_t)blockIdx.x * per_image * nv;
-    double a = 0.0, b = 0.0;
-    for (int64_t k = t; k < per_image; k += IM_THREADS) {
-        a += p[k * nv];
-        if (nv == 2) b += p[k * 2 + 1];
-    }
-    s_a[t] = a; s_b[t] = b;
-    __syncthreads();
-    for (int off = IM_THREADS / 2; off > 0; off >>= 1) {
-        if (t < off) { s_a[t] += s_a[t + off]; s_b[t] += s_b[t + off]; }
-        __syncthreads();
-    }
-    if (t < nv) out[(int64_t)blockIdx.x * nv + t] = (t == 0 ? s_a[0] : s_b[0]) / count;
+    __shared__ double s_a[NV * IM_THREADS];
+    double a[NV];
+    ordered_finish<IM_THREADS, NV>(partials + (int64_t)blockIdx.x * per_image * NV, per_image, NV, 0, a, s_a);
+    if (threadIdx.x < NV) out[(int64_t)blockIdx.x * NV + threadIdx.x] = (threadIdx.x == 0 ? a[0] : a[NV - 1]) / count;
 }
 
 // [b, h, w, c] -> [b, h / 2, w / 2, c] doubles, one lane per output element
@@ -177,15 +161,8 @@ __global__ void __launch_bounds__(IM_THREADS) k_mse(const float *__restrict__ x,
         const double d = (double)px[e] - (double)py[e];
         acc += d * d;
     }
-    acc = wave_sum(acc);
-    if ((t & 63) == 0) s_sum[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) {
-        double a = s_sum[0];
-#pragma unroll
-        for (int k = 1; k < IM_THREADS / 64; k++) a += s_sum[k];
-        partials[img * gridDim.x + blockIdx.x] = a;
-    }
+    acc = ordered_block_sum<IM_THREADS>(acc, s_sum);
+    if (t == 0) partials[img * gridDim.x + blockIdx.x] = acc;
 }
 
 inline int64_t ssim_tiles(int h, int w) { return ceil_div(h - SS_APRON, SS_TILE) * ceil_div(w - SS_APRON, SS_TILE); }
@@ -244,7 +221,7 @@ int ssim_launch(const T *x, const T *y, int b, int h, int w, int c, const SsimWi
     const int64_t tiles = ssim_tiles(h, w);
     hipLaunchKernelGGL(k_ssim<T>, dim3((unsigned)tiles, (unsigned)(b * c)), dim3(IM_THREADS), 0, st, x, y, h, w, c, tiles_x, win, c1, c2, map, partials);
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_finish, dim3((unsigned)(b * c)), dim3(IM_THREADS), 0, st, tiles, 2, (const double *)partials,
+    hipLaunchKernelGGL(k_finish<2>, dim3((unsigned)(b * c)), dim3(IM_THREADS), 0, st, tiles, (const double *)partials,
                        (double)(h - SS_APRON) * (double)(w - SS_APRON), means);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
@@ -271,7 +248,7 @@ inline bool range_ok(double data_range) { return std::isfinite(data_range) && da
 //   1. inputs -> LDS;  2. row pass of the five moments (k_ssim's order);  3. column pass, the SSIM formula, A / B / Cc -> LDS, and the sum of ssim over the valid
 //   pixels INSIDE the gradient tile (each valid pixel lies in exactly one);  4. transposed window along the column into the moments' LDS (dead by then);  5. along
 //   the row, the combination with x and y, grad64 and the accumulation into g_x: one lane per element, no atomics.
-//   The sums: lane, wave shuffle tree, four wave sums in order -> one fp64 partial per workgroup; k_ssim_loss_finish adds them in k_finish's fixed order.
+//   The sums: the lane's, reduce.h's ordered block sum -> one fp64 partial per workgroup; k_ssim_loss_finish is the same finish pass as k_finish's.
 constexpr int SL_CT_TILE = SS_TILE + SS_APRON, SL_CT_WHOLE = SS_TILE - SS_APRON;
 
 inline int64_t ssim_loss_tiles(int h, int w) { return ceil_div(h, SS_TILE) * ceil_div(w, SS_TILE); }
@@ -347,15 +324,8 @@ k_ssim_loss(const float *__restrict__ x, const float *__restrict__ y, int h, int
         co[CT * CT] = -(ssim / cd);
         co[2 * CT * CT] = 2.0 * lum / cd;
     }
-    sum_ssim = wave_sum(sum_ssim);
-    if ((t & 63) == 0) s_sum[t >> 6] = sum_ssim;
-    __syncthreads();
-    if (t == 0) {
-        double a = s_sum[0];
-#pragma unroll
-        for (int k = 1; k < IM_THREADS / 64; k++) a += s_sum[k];
-        partials[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = a;
-    }
+    sum_ssim = ordered_block_sum<IM_THREADS>(sum_ssim, s_sum);
+    if (t == 0) partials[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = sum_ssim;
     for (int e = t; e < n_gy * n_cx; e += IM_THREADS) {
         const int gr = e / n_cx, q = e - gr * n_cx;
         const int r0 = gy0 + gr - cy0;          // the coefficient row of tap 0; tap k reads row r0 - k
@@ -397,21 +367,13 @@ k_ssim_loss(const float *__restrict__ x, const float *__restrict__ y, int h, int
     }
 }
 
-// loss[1] = (sum of the partials) / n, loss[0] = 1 - loss[1]: one block; thread t adds k = t, t + 256, ... in ascending order, then k_finish's tree
+// loss[1] = (the ordered sum of the partials) / n, loss[0] = 1 - loss[1]: one block
 __global__ void __launch_bounds__(IM_THREADS) k_ssim_loss_finish(int64_t count, const double *__restrict__ partials, double n_valid, double *__restrict__ loss)
 {
     __shared__ double s_a[IM_THREADS];
-    const int t = threadIdx.x;
-    double a = 0.0;
-    for (int64_t k = t; k < count; k += IM_THREADS) a += partials[k];
-    s_a[t] = a;
-    __syncthreads();
-    for (int off = IM_THREADS / 2; off > 0; off >>= 1) {
-        if (t < off) s_a[t] += s_a[t + off];
-        __syncthreads();
-    }
-    if (t == 0) {
-        const double mean = s_a[0] / n_valid;
+    const double total = ordered_finish<IM_THREADS>(partials, count, 1, 0, s_a);
+    if (threadIdx.x == 0) {
+        const double mean = total / n_valid;
         loss[1] = mean;
         loss[0] = 1.0 - mean;
     }
@@ -516,7 +478,7 @@ int nrf_image_mse(const float *d_x, const float *d_y, int b, int64_t elems_per_i
     const int64_t blocks = ceil_div(elems_per_image, MSE_PER_BLOCK);
     hipLaunchKernelGGL(k_mse, dim3((unsigned)blocks, (unsigned)b), dim3(IM_THREADS), 0, st, d_x, d_y, elems_per_image, ws.partials);
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_finish, dim3((unsigned)b), dim3(IM_THREADS), 0, st, blocks, 1, (const double *)ws.partials, (double)elems_per_image, d_mse);
+    hipLaunchKernelGGL(k_finish<1>, dim3((unsigned)b), dim3(IM_THREADS), 0, st, blocks, (const double *)ws.partials, (double)elems_per_image, d_mse);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

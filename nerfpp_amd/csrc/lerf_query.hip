@@ -13,6 +13,7 @@
 #include "chunk_loop.h"
 #include "mlp.h"
 #include "mlp_lerf_net.h"
+#include "reduce.h"
 #include "stoch.h"
 
 #include <cmath>

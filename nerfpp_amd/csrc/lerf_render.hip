@@ -24,6 +24,7 @@
 // and anchored on the reference's call sites; no reference run or fixture pins them.
 #include "chunk_loop.h"
 #include "mlp.h"
+#include "reduce.h"
 #include "stoch.h"
 
 #include <cstdlib>

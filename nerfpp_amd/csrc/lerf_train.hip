@@ -12,6 +12,7 @@
 // Pinned by LibTorch autograd over the compiled LeRF.cpp / RawToOutputs weights / the reference's inline RenderCLIPEmbedding: goldens train_lerf*.
 #include "encode.h"
 #include "mlp.h"
+#include "reduce.h"
 #include "workspace.h"
 #include "nrf_math.h"
 
@@ -55,16 +56,6 @@ static int64_t lt_rays_per_pass(const nrf_mlp *m, int64_t n, int s)
     return (n + passes - 1) / passes;
 }
 
-// block-wide sum of one double per thread (blockDim.x = 256: four waves); every thread gets the result
-__device__ __forceinline__ double lt_block_sum(double v, double *sh /*[4]*/)
-{
-    v = wave_sum(v);
-    __syncthreads();                                 // sh may still be read from the previous use
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // huber(reduction none, delta) summed over a row; row_loss[i] (NaN for a row that holds a NaN)
 __global__ void k_huber_rows(int64_t n, int e, float delta, const float *__restrict__ pred, const float *__restrict__ target, float *__restrict__ row_loss)
 {
@@ -84,15 +75,15 @@ __global__ void k_huber_rows(int64_t n, int e, float delta, const float *__restr
 // nanmean over the rows: out[0] = loss, out[1] = 1 / (count of non-NaN rows)
 __global__ void k_nanmean(int64_t n, const float *__restrict__ row_loss, float *__restrict__ loss, float *__restrict__ inv_count)
 {
-    __shared__ double sh[4];
+    __shared__ double sh[2 * 4];
     double acc = 0.0, cnt = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
         const float v = row_loss[i];
         if (v == v) { acc += (double)v; cnt += 1.0; }
     }
-    acc = lt_block_sum(acc, sh);
-    cnt = lt_block_sum(cnt, sh);
-    if (threadIdx.x == 0) { *loss = (float)(acc / cnt); *inv_count = 1.0f / (float)cnt; }
+    double sums[2] = {acc, cnt};
+    ordered_block_sum<256, 2>(sums, sh);
+    if (threadIdx.x == 0) { *loss = (float)(sums[0] / sums[1]); *inv_count = 1.0f / (float)sums[1]; }
 }
 
 // d loss / d pred: nansum hands a NaN row (1 / count) * 0 instead of 1 / count; huber's own derivative multiplies it (NaN * 0 = NaN at a NaN element: what LibTorch
@@ -135,7 +126,7 @@ __global__ void __launch_bounds__(256) k_lt_ray(int s, int e, const float *__res
     extern __shared__ float lds[];
     float *alpha = lds, *trans = lds + s, *xx = lds + 2 * s, *lt = lds + 3 * s, *wgt = lds + 4 * s, *gw = lds + 5 * s, *sg = lds + 6 * s;
     float *v = lds + 7 * s, *gv = v + e;
-    __shared__ double sh[4];
+    __shared__ double sh[2 * 4];
     const int64_t ray = blockIdx.x;
     const int64_t p0 = ray * s;
     const float *dv = dirs + ray * d_stride;
@@ -173,8 +164,9 @@ __global__ void __launch_bounds__(256) k_lt_ray(int s, int e, const float *__res
         vss += (double)vk * (double)vk;
         gdot += (double)g_rendered[ray * e + k] * (double)vk;
     }
-    vss = lt_block_sum(vss, sh);
-    gdot = lt_block_sum(gdot, sh);
+    double sums[2] = {vss, gdot};
+    ordered_block_sum<256, 2>(sums, sh);          // (blockDim.x = 256) every thread gets both
+    vss = sums[0]; gdot = sums[1];
     const float vn = (float)sqrt(vss), vc = fmaxf(vn, 1e-8f);
     const bool through_norm = vn >= 1e-8f && vn > 0.0f;                     // clamp_min passes the gradient to ||v|| only where it did not clamp
     for (int k = threadIdx.x; k < e; k += blockDim.x) {
@@ -322,7 +314,7 @@ __global__ void __launch_bounds__(256) k_ltg_ray_u(int s, int hd, const float *_
 // per ray: v = W u (given), rendered = v / max(||v||, eps), g_v = d loss / d v (RenderCLIPEmbedding's normalize backward, as k_lt_ray)
 __global__ void __launch_bounds__(256) k_ltg_ray_v(int e, const float *__restrict__ v, const float *__restrict__ g_rendered, float *__restrict__ gv, float *__restrict__ rendered)
 {
-    __shared__ double sh[4];
+    __shared__ double sh[2 * 4];
     const int64_t ray = blockIdx.x;
     double vss = 0.0, gdot = 0.0;
     for (int k = threadIdx.x; k < e; k += blockDim.x) {
@@ -330,8 +322,9 @@ __global__ void __launch_bounds__(256) k_ltg_ray_v(int e, const float *__restric
         vss += (double)vk * (double)vk;
         gdot += (double)g_rendered[ray * e + k] * (double)vk;
     }
-    vss = lt_block_sum(vss, sh);
-    gdot = lt_block_sum(gdot, sh);
+    double sums[2] = {vss, gdot};
+    ordered_block_sum<256, 2>(sums, sh);          // (blockDim.x = 256) every thread gets both
+    vss = sums[0]; gdot = sums[1];
     const float vn = (float)sqrt(vss), vc = fmaxf(vn, 1e-8f);
     const bool through_norm = vn >= 1e-8f && vn > 0.0f;
     for (int k = threadIdx.x; k < e; k += blockDim.x) {

@@ -10,9 +10,10 @@
 //   A sample with w == 0 contributes exactly 0 to both sums and gets a zero gradient whatever pred and g hold (0 * inf never forms).
 //   Memory: a block's 256 raw rows (7 floats each) and gradient rows (3 floats) are contiguous: they are staged through LDS with 16-byte loads, a lane then reads its
 //   row from LDS (row strides 7 and 3 words are odd: conflict-free).  The gradient columns are three 4-byte stores per lane into 28-byte rows.
-//   Sums: per lane in fp64, wave shuffle tree, the block's four wave sums added in wave order -> one fp64 partial pair per block; k_normal_losses_finish (one block)
-//   adds the partials in a fixed strided order and tree.  No atomics: two runs give the same bits.
+//   Sums: per lane in fp64, reduce.h's ordered block sum -> one fp64 partial pair per block; its k_finish_loss_pair (one block) is the ordered finish pass over the
+//   pairs.  No atomics: two runs give the same bits.
 #include "mlp.h"
+#include "reduce.h"
 
 namespace nrf {
 
@@ -41,7 +42,7 @@ k_normal_losses(int64_t total, int s, const float *__restrict__ w, const float *
 {
     __shared__ __attribute__((aligned(16))) float s_raw[NL_THREADS * NL_C];
     __shared__ __attribute__((aligned(16))) float s_g[NL_THREADS * 3];
-    __shared__ double s_sum[2][NL_THREADS / 64];
+    __shared__ double s_sum[2 * (NL_THREADS / 64)];
     const int t = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * NL_THREADS;
     const int64_t left = total - base;
@@ -78,31 +79,9 @@ k_normal_losses(int64_t total, int s, const float *__restrict__ w, const float *
         float *o = g_raw + i * NL_C + 4;
         o[0] = gx; o[1] = gy; o[2] = gz;
     }
-    l_pn = wave_sum(l_pn); l_or = wave_sum(l_or);
-    if ((t & 63) == 0) { s_sum[0][t >> 6] = l_pn; s_sum[1][t >> 6] = l_or; }
-    __syncthreads();
-    if (t < 2) {
-        double a = s_sum[t][0];
-#pragma unroll
-        for (int k = 1; k < NL_THREADS / 64; k++) a += s_sum[t][k];
-        partials[(int64_t)blockIdx.x * 2 + t] = a;
-    }
-}
-
-// losses[0] = sum_b partials[b][0] / count_pn, losses[1] = sum_b partials[b][1] / count_or: thread t adds blocks t, t + 256, ... in ascending order, then a fixed tree
-__global__ void __launch_bounds__(NL_THREADS) k_normal_losses_finish(int64_t blocks, const double *__restrict__ partials, double count_pn, double count_or, float *__restrict__ losses)
-{
-    __shared__ double s_a[NL_THREADS], s_b[NL_THREADS];
-    const int t = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int64_t k = t; k < blocks; k += NL_THREADS) { a += partials[k * 2]; b += partials[k * 2 + 1]; }
-    s_a[t] = a; s_b[t] = b;
-    __syncthreads();
-    for (int off = NL_THREADS / 2; off > 0; off >>= 1) {
-        if (t < off) { s_a[t] += s_a[t + off]; s_b[t] += s_b[t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) { losses[0] = (float)(s_a[0] / count_pn); losses[1] = (float)(s_b[0] / count_or); }
+    double sums[2] = {l_pn, l_or};
+    ordered_block_sum<NL_THREADS, 2>(sums, s_sum);
+    if (t < 2) partials[(int64_t)blockIdx.x * 2 + t] = t == 0 ? sums[0] : sums[1];
 }
 
 }  // namespace
@@ -141,7 +120,7 @@ int nrf_normal_losses(const float *d_weights, const float *d_density_grad, const
     hipLaunchKernelGGL(k_normal_losses, dim3((unsigned)blocks), dim3(NL_THREADS), 0, st, total, s, d_weights, d_density_grad, d_raw, d_dirs, d_stride, k_pn, k_or, vec, d_g_raw,
                        partials);
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_normal_losses_finish, dim3(1), dim3(NL_THREADS), 0, st, blocks, (const double *)partials, cnt_pn, cnt_or, d_losses);
+    hipLaunchKernelGGL(k_finish_loss_pair<NL_THREADS>, dim3(1), dim3(NL_THREADS), 0, st, blocks, (const double *)partials, cnt_pn, cnt_or, d_losses);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

@@ -16,9 +16,9 @@
 //   fp32's eye, which an fp32 prefix row read back from memory would not.  So the per-ray scratch row holds the exclusive log-transmittance only (4 B per sample).
 //   Chain dL/dw -> raw[..., 3]: k_raw2outputs_bwd's, with gw_i := distortion_weight * dL_dist/dw_i / n -- TruncExp's clamped derivatives, the 1 - alpha >= 1e-10 guard,
 //   the relu mask on sigma + noise, the reverse suffix scan of g_L.  The sparsity term is added to it and the sum is ADDED to g_raw[..., 3]; no other column is read or written.
-//   Sums: per lane fp64, wave shuffle tree, the block's four wave sums in wave order -> one fp64 pair per block; k_ray_reg_finish (one block) adds the pairs in a fixed
-//   strided order and tree.  No atomics: two runs give the same bits.
-#include "common.h"
+//   Sums: per lane fp64, reduce.h's ordered block sum -> one fp64 pair per block; its k_finish_loss_pair (one block) is the ordered finish pass over the pairs.  No
+//   atomics: two runs give the same bits.
+#include "reduce.h"
 
 #include <cmath>
 
@@ -29,22 +29,12 @@ namespace {
 constexpr int RR_RAYS = 4;          // waves (rays) per block
 constexpr int RR_FIN = 256;
 
-__device__ __forceinline__ double rr_incl_scan(double v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
 __global__ void __launch_bounds__(64 * RR_RAYS)
 k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *__restrict__ z, const float *__restrict__ dirs, int d_stride, const float *__restrict__ noise,
           float noise_std, float k_dist /* distortion_weight / n */, float k_sparse /* sparsity_weight / n */, int terms /* bit 0: distortion, bit 1: sparsity */, float *__restrict__ g_raw,
           float *__restrict__ weights_out, float *__restrict__ lt_scratch /* [n, s] exclusive log-transmittance */, double *__restrict__ partials /* [blocks][2] */)
 {
-    __shared__ double s_sum[2][RR_RAYS];
+    __shared__ double s_sum[2 * RR_RAYS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t ray = (int64_t)blockIdx.x * RR_RAYS + wv;
     double l_dist = 0.0, l_sparse = 0.0;
@@ -79,7 +69,7 @@ k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *_
                     lg = nrf_logf(om > 1e-10f ? om : 1e-10f);
                     if (dist_on) mj = 0.5f * ((zj - z0) / span + (zn - z0) / span);          // (the last sample: zn = zj, m = t_{s-1})
                 }
-                const double incl = rr_incl_scan((double)lg, lane);
+                const double incl = wave_incl_scan((double)lg, lane);
                 const float excl = (float)(carry + (incl - (double)lg));
                 carry += __shfl(incl, 63);
                 if (live) {
@@ -123,7 +113,7 @@ k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *_
                 float g_sigma = 0.0f;
                 if (dist_on) {
                     const double wd = (double)w, wm = (double)w * (double)mj;
-                    const double w_incl = rr_incl_scan(wd, lane), m_incl = rr_incl_scan(wm, lane);
+                    const double w_incl = wave_incl_scan(wd, lane), m_incl = wave_incl_scan(wm, lane);
                     const double w_blk = __shfl(w_incl, 63), m_blk = __shfl(m_incl, 63);
                     const double w_after = w_suf + (w_blk - w_incl), m_after = m_suf + (m_blk - m_incl);
                     w_suf += w_blk; m_suf += m_blk;
@@ -135,7 +125,7 @@ k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *_
                     const float gw = live ? k_dist * (float)(2.0 * (before + after) + self * (2.0 / 3.0)) : 0.0f;
                     // k_raw2outputs_bwd's chain from g_w
                     const float gL = gw * alpha * nrf_expf(cl);                   // g_T * dT/dL with TruncExp's clamped derivative
-                    const double g_incl = rr_incl_scan((double)gL, lane);
+                    const double g_incl = wave_incl_scan((double)gL, lane);
                     const double g_blk = __shfl(g_incl, 63);
                     const double later = gl_suf + (g_blk - g_incl);
                     gl_suf += g_blk;
@@ -158,31 +148,9 @@ k_ray_reg(int64_t n, int s, int c, const float *__restrict__ raw, const float *_
             }
         }
     }
-    l_dist = wave_sum(l_dist); l_sparse = wave_sum(l_sparse);
-    if (lane == 0) { s_sum[0][wv] = l_dist; s_sum[1][wv] = l_sparse; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double a = s_sum[threadIdx.x][0];
-#pragma unroll
-        for (int k = 1; k < RR_RAYS; k++) a += s_sum[threadIdx.x][k];
-        partials[(int64_t)blockIdx.x * 2 + threadIdx.x] = a;
-    }
-}
-
-// losses[k] = sum_b partials[b][k] / n: thread t adds blocks t, t + 256, ... in ascending order, then a fixed tree
-__global__ void __launch_bounds__(RR_FIN) k_ray_reg_finish(int64_t blocks, const double *__restrict__ partials, double count, float *__restrict__ losses)
-{
-    __shared__ double s_a[RR_FIN], s_b[RR_FIN];
-    const int t = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int64_t k = t; k < blocks; k += RR_FIN) { a += partials[k * 2]; b += partials[k * 2 + 1]; }
-    s_a[t] = a; s_b[t] = b;
-    __syncthreads();
-    for (int off = RR_FIN / 2; off > 0; off >>= 1) {
-        if (t < off) { s_a[t] += s_a[t + off]; s_b[t] += s_b[t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) { losses[0] = (float)(s_a[0] / count); losses[1] = (float)(s_b[0] / count); }
+    double sums[2] = {l_dist, l_sparse};
+    ordered_block_sum<64 * RR_RAYS, 2>(sums, s_sum);
+    if (threadIdx.x < 2) partials[(int64_t)blockIdx.x * 2 + threadIdx.x] = threadIdx.x == 0 ? sums[0] : sums[1];
 }
 
 inline size_t rr_row_bytes(int64_t n, int s) { return align_up((size_t)n * (size_t)s * sizeof(float), 8); }
@@ -229,7 +197,7 @@ int nrf_ray_regularizers(const float *d_raw, const float *d_z, const float *d_di
     hipLaunchKernelGGL(k_ray_reg, dim3((unsigned)blocks), dim3(64 * RR_RAYS), 0, st, n, s, c, d_raw, d_z, d_dirs, d_stride, d_noise, noise_std, k_dist, k_sparse, terms, d_g_raw,
                        d_weights_out, lt, partials);
     NRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ray_reg_finish, dim3(1), dim3(RR_FIN), 0, st, blocks, (const double *)partials, (double)n, d_losses);
+    hipLaunchKernelGGL(k_finish_loss_pair<RR_FIN>, dim3(1), dim3(RR_FIN), 0, st, blocks, (const double *)partials, (double)n, (double)n, d_losses);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

@@ -6,16 +6,10 @@
 //   Adam(lr, betas (0.9, 0.99), eps 1e-15)      :539               nrf_adam_step
 // Gradients flow only through the fine pass (z_samples are detached, NeRFRenderer.h:429).
 #include "encode.h"
+#include "reduce.h"
 #include "workspace.h"
 
 namespace nrf {
-
-__device__ __forceinline__ double wsum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // out[0] += sum huber, out[1] += sum squared error (both divided by count on the host side of the call)
 __global__ void k_huber(int64_t count, float norm, const float *__restrict__ pred, const float *__restrict__ target, double *__restrict__ out, float *__restrict__ grad)
@@ -28,7 +22,7 @@ __global__ void k_huber(int64_t count, float norm, const float *__restrict__ pre
         q += (double)d * (double)d;
         if (grad) grad[i] = (d < -1.0f) ? -norm : (d > 1.0f ? norm : norm * d);
     }
-    h = wsum(h); q = wsum(q);
+    h = wave_sum(h); q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) { unsafeAtomicAdd(out, h); unsafeAtomicAdd(out + 1, q); }
 }
 
@@ -688,7 +682,7 @@ __global__ void k_tv_loss(int n, int cube, int log2_t, int vx, int vy, int vz, f
             }
         }
     }
-    tv = wsum(tv);
+    tv = wave_sum(tv);
     if ((threadIdx.x & 63) == 0 && tv != 0.0) unsafeAtomicAdd(loss, (float)(tv * (double)weight / (double)cube));
 }
 

@@ -3,6 +3,8 @@ per source operation, the fp64 sums in the header's order, and a nearest-neighbo
 compare with it bit for bit.  Also the inputs the host and GPU tests share.  Imports nothing of the package."""
 import numpy as np
 
+from ordered_sum_ref import block_sums as _block_sums, finish as _finish          # the ordered fp64 sums
+
 F32 = np.float32
 RNG_SURFACE_COUNT, RNG_SURFACE_UV = 10, 11
 SAMPLE_MAX_PER_FACE = 65536
@@ -24,32 +26,6 @@ def rng_u32(seed, stream, idx):
 
 def rng_uniform(seed, stream, idx):
     return (rng_u32(seed, stream, idx) >> np.uint32(8)).astype(F32) * F32(1.0 / 16777216.0)
-
-
-# ---- the ordered fp64 sums ----
-def _block_sums(lanes):
-    """[nb, 256] one double per lane -> [nb]: per wave the butterfly v += v[lane ^ o], o = 32 .. 1, then ((w0 + w1) + w2) + w3"""
-    v = np.asarray(lanes, np.float64).reshape(-1, 4, 64)
-    lane = np.arange(64)
-    for o in (32, 16, 8, 4, 2, 1):
-        v = v + v[..., lane ^ o]
-    w = v[..., 0]
-    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
-
-
-def _finish(partials, is_max=False):
-    """thread t of 256 takes k = t, t + 256, ... in ascending order from 0.0; then s[t] (+|max)= s[t + o], o = 128 .. 1"""
-    p = np.asarray(partials, np.float64)
-    rows = -(-len(p) // 256)
-    p = np.concatenate([p, np.zeros(rows * 256 - len(p))]).reshape(rows, 256)
-    s = np.zeros(256)
-    for r in p:
-        s = np.maximum(s, r) if is_max else s + r
-    o = 128
-    while o:
-        s[:o] = np.maximum(s[:o], s[o:2 * o]) if is_max else s[:o] + s[o:2 * o]
-        o >>= 1
-    return s[0]
 
 
 # ---- 1. surface sampling ----

@@ -102,6 +102,43 @@ def mse(x, y):
     return (d * d).sum(axis=1) / d.shape[1]
 
 
+MSE_PER_BLOCK = 4096
+
+
+def mse_partials(x, y):
+    """[b, blocks]: what nrf_image_mse leaves in its workspace.  Blocks of 4096 elements; lane t of 256 takes t, t + 256, ... in ascending order from 0.0; then the
+    ordered block sum (ordered_sum_ref.block_sums)."""
+    from ordered_sum_ref import block_sums
+    d = np.asarray(x).astype(np.float64) - np.asarray(y).astype(np.float64)
+    d = d.reshape(d.shape[0], -1)
+    b, n = d.shape
+    nb = -(-n // MSE_PER_BLOCK)
+    sq = np.zeros((b, nb * MSE_PER_BLOCK))
+    sq[:, :n] = d * d
+    sq = sq.reshape(b, nb, MSE_PER_BLOCK // 256, 256)
+    lanes = np.zeros((b, nb, 256))
+    for i in range(MSE_PER_BLOCK // 256):
+        lanes = lanes + sq[:, :, i]
+    return block_sums(lanes.reshape(-1, 256)).reshape(b, nb)
+
+
+def mse_ordered(x, y):
+    """[b]: nrf_image_mse bit for bit: the ordered finish pass over mse_partials, divided by the count."""
+    from ordered_sum_ref import finish
+    n = np.asarray(x).reshape(np.asarray(x).shape[0], -1).shape[1]
+    return np.array([finish(p) / np.float64(n) for p in mse_partials(x, y)])
+
+
+ORDERED_MSE_ELEMS = (1, 4097, 256 * 4096 + 1)          # one element; one block and one element; 257 block partials: a second strided trip that ends off a multiple of 256
+ORDERED_MSE_SEED = 89          # at which the 257 partials of both images and the lanes of the first block tell summation orders apart (test_ordered_sum_host.py)
+
+
+def ordered_mse_pair(n):
+    """two images of n elements, [2, n] fp32 each: the inputs of the bit-for-bit MSE test"""
+    x, y = pair("indep", 2, 1, n, 1, seed=ORDERED_MSE_SEED)
+    return x.reshape(2, n), y.reshape(2, n)
+
+
 def pair(kind, b, h, w, c, seed=77):
     """Seeded fp32 image pairs [b, h, w, c] in [0, 1] (synth_u01).  SSIM over the SHAPES above with b = 3, as measured with this file:
        noise  a smooth sinusoid (0.3 .. 0.7) plus 0.2 of noise, against the same image plus 0.1 of fresh noise: channel means 0.897 .. 0.941, pixels 0.76 .. 0.98

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import metrics_ref as MR
+import ordered_sum_ref as OS
 
 pytestmark = pytest.mark.gpu
 
@@ -170,6 +171,54 @@ def test_mse_against_numpy(api, n):
     assert (bits(via) == bits(got[0])).all()
     one = host(api.M.MSE(dev(x[1].reshape(1, n)), dev(y[1].reshape(1, n))))          # [H, W]: a scalar, the bits of the batched entry
     assert one.shape == () and bits(one) == bits(got[0][1])
+
+
+@pytest.mark.parametrize("n", MR.ORDERED_MSE_ELEMS)
+def test_mse_has_the_bits_of_the_ordered_sum_end_to_end(api, n):
+    """nrf_image_mse's workspace ([b][blocks] doubles at offset 0) holds the restated block partials and the result is the ordered finish pass over them, bit for bit:
+    the block epilogue and the finish pass, pinned together."""
+    b = 2
+    x, y = MR.ordered_mse_pair(n)
+    blocks = -(-n // MR.MSE_PER_BLOCK)
+    out = torch.full((b,), PATTERN, device="cuda", dtype=torch.float64)
+    nb = int(api.lib.nrf_image_mse_workspace_bytes(b, n))
+    assert nb >= b * blocks * 8
+    ws = torch.zeros((nb,), dtype=torch.uint8, device="cuda")
+    dx, dy = dev(x), dev(y)
+    api.L.check(api.lib.nrf_image_mse(P(dx), P(dy), b, n, P(out), P(ws), nb, None))
+    torch.cuda.synchronize()
+    got, parts = host(out), host(ws[:b * blocks * 8].view(torch.float64)).reshape(b, blocks)
+    want_parts = MR.mse_partials(x, y)
+    print(f"n = {n}: {int((bits(parts) != bits(want_parts)).sum())} of {parts.size} partials differ in bits; mse {got}, restated {MR.mse_ordered(x, y)}")
+    assert (bits(parts) == bits(want_parts)).all()
+    assert (bits(got) == bits(np.array([OS.finish(p) / np.float64(n) for p in parts]))).all()
+    assert (bits(got) == bits(MR.mse_ordered(x, y))).all()
+
+
+@pytest.fixture(scope="module")
+def ssim_many_tiles(api):
+    """One image, one channel, a valid region of 17 x 16 tiles of 32 x 32 plus one pixel in each axis: 18 * 17 = 306 tile partials, a second strided trip of the
+    finish pass that ends off a multiple of 256.  -> (means [1,1,2], the partials [306, 2] read back from the workspace, the valid count)"""
+    h, w = 17 * 32 + 1 + 10, 16 * 32 + 1 + 10
+    x, y = MR.pair("noise", 1, h, w, 1)
+    tiles = 18 * 17
+    need = int(api.lib.nrf_ssim_workspace_bytes(1, h, w, 1))
+    assert need >= tiles * 2 * 8
+    ws = torch.zeros((need,), dtype=torch.uint8, device="cuda")
+    means = torch.full((1, 1, 2), PATTERN, device="cuda", dtype=torch.float64)
+    dx, dy = dev(x), dev(y)
+    api.L.check(api.lib.nrf_ssim(P(dx), P(dy), 1, h, w, 1, 1.0, P(means), None, P(ws), need, None))
+    torch.cuda.synchronize()
+    return host(means), host(ws[:tiles * 2 * 8].view(torch.float64)).reshape(tiles, 2), (h - 10) * (w - 10)
+
+
+@pytest.mark.parametrize("col", [0, 1], ids=["ssim", "cs"])
+def test_ssim_means_have_the_bits_of_the_ordered_finish_pass(ssim_many_tiles, col):
+    means, parts, n = ssim_many_tiles
+    want = OS.finish(parts[:, col]) / np.float64(n)
+    print(f"column {col}: mean {means[0, 0, col]!r}, finish(partials) / n {want!r}, numpy's sum / n {parts[:, col].sum() / n!r}")
+    assert len(parts) > 256 and len(parts) % 256 and np.isfinite(parts).all() and (parts[:, col] != 0.0).all()
+    assert bits(means[0, 0, col]) == bits(want)
 
 
 def ms_call(api, x, y, scales, data_range=1.0, ws_bytes=None, check=True):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import ordered_sum_ref as OS
 from conftest import load_golden
 from nerfpp_amd import synth
 from normal_loss_ref import SmallPNRef, normal_losses, t64
@@ -119,6 +120,34 @@ def test_normal_losses_vs_restatement(api):
     with pytest.raises(api.L.NrfError):          # a 4-column network has no predicted normals
         api.L.check(lib.nrf_normal_losses(P(d_w), P(d_g), P(d_raw), 4, C.c_void_p(d_rays.data_ptr() + 12), 11, C.c_int64(n), s, C.c_float(wpn), C.c_float(wor), P(d_out),
                                           P(d_l), P(ws), C.c_size_t(nb), None))
+
+
+@pytest.mark.parametrize("n", [1025, 4], ids=["257_blocks", "one_block"])
+def test_normal_losses_have_the_bits_of_the_ordered_finish_pass(api, n):
+    """s = 64: 256 samples per block, so n = 1025 leaves 257 partial pairs (a second strided trip of the finish pass, one entry long) and n = 4 one.  The workspace
+    ([blocks][2] doubles at offset 0) is read back: losses == float32(finish(column) / count), bit for bit."""
+    s = 64
+    blocks = -(-n * s // 256)
+    assert blocks == (257 if n == 1025 else 1)
+    rng = np.random.default_rng(12)
+    w = rng.uniform(0, 1, (n, s)).astype(np.float32)
+    g = rng.standard_normal((n, s, 3)).astype(np.float32)
+    raw = rng.standard_normal((n, s, 7)).astype(np.float32)
+    rays = rng.standard_normal((n, 11)).astype(np.float32)
+    lib = api.L.lib()
+    d_w, d_g, d_raw, d_rays = dev(w), dev(g), dev(raw), dev(rays)
+    nb = int(lib.nrf_normal_losses_workspace_bytes(C.c_int64(n), s))
+    assert nb >= blocks * 2 * 8
+    ws = torch.zeros((nb,), dtype=torch.uint8, device="cuda")
+    g_raw, losses = torch.zeros((n, s, 7), device="cuda"), torch.empty((2,), device="cuda")
+    api.L.check(lib.nrf_normal_losses(P(d_w), P(d_g), P(d_raw), 7, C.c_void_p(d_rays.data_ptr() + 12), 11, C.c_int64(n), s, C.c_float(0.7), C.c_float(0.3), P(g_raw),
+                                      P(losses), P(ws), C.c_size_t(nb), None))
+    torch.cuda.synchronize()
+    losses, parts = host(losses), host(ws[:blocks * 2 * 8].view(torch.float64)).reshape(blocks, 2)
+    want = np.array([np.float32(OS.finish(parts[:, 0]) / (np.float64(n * s) * 3.0)), np.float32(OS.finish(parts[:, 1]) / np.float64(n))])
+    print(f"n = {n}: losses {losses}, float32(finish(partials) / count) {want}, numpy's sums {parts.sum(0)}")
+    assert np.isfinite(parts).all() and (parts > 0.0).all()
+    assert np.array_equal(losses.view(np.uint32), want.view(np.uint32))
 
 
 # ------------------------------------------------------------------ 2. the 7-column network backward

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import ordered_sum_ref as OS
 from conftest import load_golden
 import ray_reg_ref as RR
 
@@ -106,6 +107,30 @@ def test_kernel_vs_restatement_seeded(api, seed, n, s, c, nz):
         assert not ref["losses"].any()
     else:
         assert ref["losses"][0] > 0 and ref["losses"][1] > 0 and np.abs(ref["g_dist"]).max() > 0
+
+
+def test_losses_have_the_bits_of_the_ordered_finish_pass(api):
+    """n = 1025 rays of 64 samples, four rays per block: 257 partial pairs, so the finish pass makes a second strided trip, one entry long.  The partials
+    ([blocks][2] doubles after the align_up(n * s * 4, 8) bytes of the row scratch) are read back: losses == float32(finish(column) / n), bit for bit."""
+    n, s, c = 1025, 64, 4
+    blocks, at = -(-n // 4), -(-n * s * 4 // 8) * 8
+    assert blocks == 257
+    b = RR.seeded_inputs(2000, n, s, c, False)
+    b["z"][-1] = b["z"][-2]          # (every 16th ray has no span and adds nothing; the last block is ray 1024 alone: give it one)
+    lib = api.L.lib()
+    raw, z, d = dev(b["raw"]), dev(b["z"]), dev(b["d"])
+    g, losses = torch.zeros((n, s, c), device="cuda"), torch.full((2,), -5.0, device="cuda")
+    nb = int(lib.nrf_ray_regularizers_workspace_bytes(C.c_int64(n), s))
+    assert nb == at + blocks * 2 * 8
+    ws = torch.zeros((nb,), dtype=torch.uint8, device="cuda")
+    api.L.check(lib.nrf_ray_regularizers(P(raw), P(z), P(d), 3, C.c_int64(n), s, c, None, C.c_float(0.0), C.c_float(W_DIST), C.c_float(W_SPARSE), P(g), P(losses), None,
+                                         P(ws), C.c_size_t(nb), None))
+    torch.cuda.synchronize()
+    losses, parts = host(losses), host(ws[at:].view(torch.float64)).reshape(blocks, 2)
+    want = np.array([np.float32(OS.finish(parts[:, k]) / np.float64(n)) for k in (0, 1)])
+    print(f"losses {losses}, float32(finish(partials) / n) {want}, numpy's sums {parts.sum(0)}")
+    assert np.isfinite(parts).all() and (parts > 0.0).all()
+    assert np.array_equal(bits(losses), bits(want))
 
 
 @pytest.mark.parametrize("tag", ["raw2out_192", "raw2out_64", "train_hash"])

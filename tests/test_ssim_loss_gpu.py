@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import metrics_ref as MR
+import ordered_sum_ref as OS
 import ssim_loss_ref as SR
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +98,27 @@ def test_kernel_vs_restatement(api, shape, kind):
     assert none is None and np.array_equal(bits64(loss_b), bits64(loss)) and np.array_equal(bits32(gx_b), bits32(gx)), "the same with and without d_grad64"
     loss_c, gx_c, g64_c, _ = loss_call(api, x, y, pre=pre)
     assert np.array_equal(bits64(loss_c), bits64(loss)) and np.array_equal(bits32(gx_c), bits32(gx)) and np.array_equal(bits64(g64_c), bits64(g64)), "two runs, same bits"
+
+
+def test_loss_has_the_bits_of_the_ordered_finish_pass(api):
+    """One 545 x 513 channel: 18 * 17 = 306 gradient tiles, so the finish pass makes a second strided trip that ends off a multiple of 256.  The workspace
+    ([b * c][tiles] doubles at offset 0) is read back: loss[1] == finish(partials) / n_valid and loss[0] == 1 - loss[1], bit for bit."""
+    h, w, tiles = 17 * 32 + 1, 16 * 32 + 1, 18 * 17
+    x, y = MR.pair("noise", 1, h, w, 1)
+    need = int(api.lib.nrf_ssim_loss_workspace_bytes(1, h, w, 1))
+    assert need >= tiles * 8
+    ws = torch.zeros((need,), dtype=torch.uint8, device="cuda")
+    loss = torch.full((2,), PATTERN, device="cuda", dtype=torch.float64)
+    gx = torch.zeros((1, h, w, 1), device="cuda")
+    dx, dy = dev(x), dev(y)
+    api.L.check(api.lib.nrf_ssim_loss(P(dx), P(dy), 1, h, w, 1, 1.0, WEIGHT, P(loss), P(gx), None, P(ws), need, None))
+    torch.cuda.synchronize()
+    loss, parts = host(loss), host(ws[:tiles * 8].view(torch.float64))
+    n_valid = np.float64((h - 10) * (w - 10))
+    mean = OS.finish(parts) / n_valid
+    print(f"{tiles} tiles: loss {loss[0]!r}, mean {loss[1]!r}; finish(partials) / n {mean!r}, numpy's sum / n {parts.sum() / n_valid!r}")
+    assert np.isfinite(parts).all() and (parts != 0.0).sum() > 256 and 0.5 < mean < 1.0          # (the last tile row and column lie outside the valid region: zeros)
+    assert bits64(loss[1]) == bits64(mean) and bits64(loss[0]) == bits64(1.0 - mean)
 
 
 def test_closed_forms(api):

@@ -1073,6 +1073,123 @@ NRF_API int nrf_closest_on_mesh(const float *d_query, int64_t nq, const float *d
                                 int nx, int ny, int nz, int64_t n_refs, int64_t n_large, const void *d_grid, size_t grid_bytes, float max_dist, float *d_dist2,
                                 int32_t *d_face, float *d_uv, float *d_point, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ray casting on a mesh (raycast.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* For every ray the first face of a triangle list it hits (closest mode) or whether it hits any (any mode), over the face grid of nrf_face_grid_count / _build, whose
+ * buffer is read unchanged; cosine-weighted directions around normals; and the two fused into ambient occlusion.  Conventions as above: fp32 operations rounded once
+ * each (-ffp-contract=off), / and sqrtf correctly rounded, caller-owned buffers, refusals before any launch or write, two runs the same bits.  No output depends on
+ * the grid, the order of the faces (beyond the tie-break the key states) or the scheduling: tests/raycast_ref.py restates every output by brute force over all
+ * (ray, face) pairs and knows nothing of grids.
+ *
+ * CONTRACT.
+ *   Rays.  d_rays [n, stride] fp32, 8 <= stride <= NRF_RC_MAX_STRIDE: the library's packed ray row o[3], d[3], near, far, ... (nrf_pack_rays, nrf_atlas_texels).  d is
+ *   not normalised; t is in units of d, the renderer's z (the point is o + d*t).  The range is [lo, hi] = [max(near, 0), far] (near > 0 ? near : 0); far = +inf is
+ *   allowed; lo <= hi false: an empty range, a miss.  A ray with a non-finite o or d, d == 0 on all three axes, or a NaN near or far is INVALID: the miss values, and
+ *   counted in d_stats[0].
+ *   Faces.  Valid, bad and non-finite faces exactly as for nrf_face_grid_count: bad and non-finite faces are skipped whole, zero area does not make a face invalid.
+ *   Candidate of face (a, b, c) for a ray, Moeller-Trumbore.  dot(x, y) = (x0*y0 + x1*y1) + x2*y2; x cross y = (x1*y2 - x2*y1, x2*y0 - x0*y2, x0*y1 - x1*y0), every
+ *   product rounded, then the difference.  ab = b - a, ac = c - a, p = d cross ac, det = dot(ab, p), inv = 1.0f / det, tv = o - a, v = dot(tv, p) * inv,
+ *   q = tv cross ab, w = dot(d, q) * inv, t = dot(ac, q) * inv, then t = t + 0.0f (-0.0f becomes +0.0f: as bits, -0.0f lies above every positive t, and a ray that
+ *   starts in a face's plane would lose to everything behind it).
+ *   ACCEPTED iff all hold (a NaN fails every comparison and never wins):
+ *     det != 0, and cull agrees: NRF_RC_CULL_NONE any sign; NRF_RC_CULL_BACK det > 0 (the faces nrf_raster_mesh draws with cull == 1: counter-clockwise seen from
+ *     the ray's origin); NRF_RC_CULL_FRONT det < 0;
+ *     v >= 0, w >= 0, v + w <= 1.0f;
+ *     lo <= t <= hi and t < +inf (with t = +inf the point o + t*d is not a number on an axis where d is 0);
+ *     the surface point P = (a + ab*v) + ac*w per component, clamped to the face's coordinate box in the NaN-keeping form of nrf_closest_on_mesh (one inline function
+ *     serves both), and the ray point Pu = o + t*d per component (product and sum rounded) agree: |Pu - P|_inf <= tau, tau = 2^NRF_RC_TAU_LOG2 * max(|o|_inf, |Pu|_inf).
+ *   The last rule is what makes a walk over a grid provably complete; it is grid-free and removes only hits whose t is numerically meaningless.  Measured in fp32
+ *   numpy (tests/test_raycast_host.py repeats it): the worst |Pu - P|_inf / max(|o|_inf, |Pu|_inf) over the candidates that pass the other rules is 2^-14.9 on the
+ *   tests' ordinary ray sets (three sphere levels, also shifted by 100 units; rays at vertices and edges among them) and 2^-17.4 on 1 000 rays grazing the sphere
+ *   within 0.5 % of its radius, nothing rejected; the only candidates the rule removes there belong to rays that lie IN a face's plane (det a rounding error,
+ *   ratio 2^-0.7 .. 2^-2.5).  2^-12 leaves a factor of seven above the worst ordinary ratio.
+ *   Result, NRF_RC_CLOSEST.  The minimum of ((uint64)float_bits(t) << 32) | f over the accepted candidates of all valid faces: t >= +0 orders as its bits, and on an
+ *   exact tie in t, across a shared edge or vertex, the lowest face index wins.  d_t [n], d_face [n] int32, and, each or NULL, d_uv [n,2] = (v, w), d_point [n,3] =
+ *   P of the winning face and d_hit [n] uint8 = 1 on a hit.  A miss: +inf, -1, zeros, 0.
+ *   Result, NRF_RC_ANY.  d_hit [n] = 1 iff some accepted candidate exists; d_t, d_face, d_uv and d_point must be NULL (which candidate a walk meets first is not
+ *   defined).  d_hit of any mode equals isfinite(d_t) of closest mode.
+ *   d_stats [4] uint32 or NULL, ADDED to, laid out as for nrf_closest_on_mesh: [0] invalid rays, [3] rays served by the fallback ([1], [2] are nrf_face_grid_count's).
+ * WALK.  One lane per ray.  cell() is the clamped cell coordinate of nrf_nearest_points, h_min the grid's smallest cell edge, |box|_inf the largest absolute
+ *   coordinate of bbox.
+ *   1. A pass over the faces sets a flag in the workspace if a valid face has a coordinate outside [bbox min, bbox max] (never a host hint).  With the flag set every
+ *      valid ray with a non-empty range goes to the fallback.
+ *   2. Far origin: 4 * fl(2^-12 * |o|_inf) > h_min sends the ray to the fallback.
+ *   3. Clip.  The box is widened on every side by margin = h_min + 2^-10 * |box|_inf.  Per axis with d != 0: ta = (lo_a - o_a) / d_a, tb = (hi_a - o_a) / d_a,
+ *      swapped so that ta <= tb, ta = ta * (1 - 2^-10) where ta > 0, tb = tb * (1 + 2^-10); t0 = max(lo, all ta), t1 = min(hi, all tb).  An axis with d == 0 whose o
+ *      lies outside the widened box, or t0 <= t1 false: a miss.
+ *   4. The large list is tested in full (any mode stops at the first accepted candidate, here and below).
+ *   5. Steps.  dt = h_min / |d|_inf; t_0 = t0, t_k = fl(t0 + fl((float)k * dt)), replaced by t1 where it passes t1 (and t1 > t_k-1).  t_k <= t_k-1: the fallback.
+ *      Pa = o + t_k-1 * d, Pb = o + t_k * d per component; tau_k = 2^-12 * max(|o|_inf, |Pa|_inf, |Pb|_inf); 4 * tau_k <= h_min false: the fallback.  The step
+ *      looks up every cell of [cell(min(Pa, Pb) - 2 tau_k), cell(max(Pa, Pb) + 2 tau_k)] per axis, except those of the previous lookup's range (their references have
+ *      all been tested: a candidate does not depend on the step).
+ *   6. Stop after step k iff best_t <= t_k (any mode: a candidate was accepted), or t_k >= t1.  Still open after NRF_RC_MAX_STEPS steps: the fallback.
+ * WHY THE WALK CANNOT MISS.
+ *   Monotone.  Per component fl(o + fl(t*d)) is monotone in t (a rounded product with a constant and a rounded sum with a constant are), and cell() is monotone in
+ *   its argument.  So for t in [t_k-1, t_k], Pu(t) lies per axis between Pa and Pb, and tau(t) <= tau_k.
+ *   A step is complete.  An accepted candidate with t in the step has P within tau_k of that span per axis, so cell(P) lies in [cell(min - 2 tau_k),
+ *   cell(max + 2 tau_k)]: the factor 2 absorbs the roundings of the subtraction, of min - 2 tau_k and of the comparison, all far below tau_k.  The clamp puts cell(P)
+ *   inside the face's cell box.  So the face has a reference in a looked-up cell or is on the large list.  Steps are closed intervals that share their end points
+ *   and cover [t0, t1].
+ *   The stop is exact.  After step k every accepted candidate with t <= t_k has been seen (steps 1 .. k cover [t0, t_k], and none lies before t0, below).  An unseen
+ *   candidate has t > t_k >= best_t strictly: it can neither win nor tie.
+ *   The clip loses nothing.  All valid faces lie in the box (step 1), so P does, and Pu is within tau of the box.  After step 2, 2^-12 |o|_inf <= h_min / 4; and
+ *   tau = 2^-12 |Pu|_inf with |Pu|_inf <= |box|_inf + tau gives tau < 2^-11 |box|_inf.  Either way tau <= max(h_min / 4, 2^-11 |box|_inf), less than the margin by
+ *   more than 3/4 h_min + 2^-11 |box|_inf.  Pu_a(t) is monotone, so the t with Pu_a(t) within tau of the box form an interval; the computed ta and tb differ from
+ *   the exact parameters of the WIDENED box by two roundings (2^-22 relative, a displacement below 2^-22 (|box|_inf + margin + |o|_inf) <= 2^-12 h_min + 2^-21
+ *   |box|_inf along the axis), the factors 1 -+ 2^-10 only widen the interval, and an axis with d == 0 has Pu_a = o_a for every finite t.
+ *   The large list is never unscanned.
+ * FALLBACK.  Exact and slow, counted in d_stats[3]: rays are appended to a list in the workspace; a second kernel, a fixed grid of workgroups striding the list by the
+ *   count read on the device, tests ALL faces for each with a block-wide minimum of the key.  The conditions, each with a test: a valid face outside the box; a far
+ *   origin (step 2, or 4 * tau_k > h_min at a step); a step that does not advance; a ray still open after NRF_RC_MAX_STEPS steps.  Walk, large list and fallback
+ *   form the candidate through one inline function.  Every loop is bounded by a clamped range or a count; nothing waits on another workgroup.
+ * HEMISPHERE DIRECTIONS.  nrf_hemisphere_dirs: d_dirs [n, k, 3], direction j around normal i a pure function of (seed, index0 + i, j); no trigonometry.
+ *   n-hat: len2 = dot(n, n); a non-finite n, or len2 == 0 or not finite, is a BAD normal: k zero directions, counted once in d_stats[0].  Else n-hat = n / sqrtf(len2)
+ *   per component.  Marsaglia's disc: for attempt a = 0 .. NRF_HEMI_ATTEMPTS - 1, with u(c) = nrf_rng_uniform(seed, NRF_RNG_HEMI_DIR, ((index0 + i) << 20) | (j << 4)
+ *   | c): x1 = 2 u(2a) - 1, x2 = 2 u(2a + 1) - 1 (both exact), s = x1*x1 + x2*x2; the first attempt with s < 1 gives r = sqrtf(1 - s), q = ((2 x1) r, (2 x2) r,
+ *   1 - 2 s), a uniform point of the unit sphere; no such attempt (probability 0.215^8): q = (0, 0, 1).  v = n-hat + q, l2 = dot(v, v); l2 < NRF_HEMI_MIN_LEN2: the
+ *   direction is n-hat, else v / sqrtf(l2) per component.  A uniform point of the sphere tangent to the surface, seen from the point of contact: the cosine law.
+ * AMBIENT OCCLUSION.  nrf_mesh_ambient_occlusion: ray (i, j) has o = p_i + offset * n-hat_i per component, d = direction j of point index0 + i, the range
+ *   [0, max_dist], no culling, any mode; d_ao [n] = (float)(k - hits) / (float)k, exact as the count is an integer.  A bad normal or a non-finite p makes the k rays
+ *   of the point invalid: they miss, d_ao is 1, d_stats[0] grows by k.  No ray or direction is written.  The call equals nrf_hemisphere_dirs followed by
+ *   nrf_ray_cast_mesh(NRF_RC_ANY) bit for bit, and its d_stats[0] and [3] are those of that nrf_ray_cast_mesh call (nrf_hemisphere_dirs given NULL stats: with stats it
+ *   would add one more per bad normal to [0]): both share one device function for the walk and one for the directions.  One lane
+ *   per ray of the flattened [n, k] rays, a point's hits counted by ballot and popcount into an integer counter of the workspace (integer atomics: no order to
+ *   depend on); a ray the walk gives up is tested against all faces by its wave at once.  Workspace: nrf_ray_cast_workspace_bytes(n).  n * k <= NRF_AO_MAX_RAYS
+ *   per call; index0 lets a caller go slab by slab with the same draws.
+ * REFUSED (NRF_ERR_INVALID_ARG, or NRF_ERR_WORKSPACE for a short workspace): n, V, F or the dims out of range; stride outside [8, NRF_RC_MAX_STRIDE]; a cull or mode
+ *   that is none of the constants; a null bbox, d_faces (F > 0), d_verts (V > 0 and F > 0), d_rays (n > 0); closest mode with a null d_t or d_face, any mode with a null
+ *   d_hit or a non-null d_t, d_face, d_uv or d_point; a box nrf_nearest_points refuses, or whose widening is not finite; n_refs, n_large, grid buffer and workspace as
+ *   for nrf_closest_on_mesh; k outside [1, NRF_HEMI_MAX_K]; index0 < 0 or index0 + n > NRF_HEMI_MAX_INDEX; n * k > 2^31 - 1 (nrf_hemisphere_dirs) or > NRF_AO_MAX_RAYS; a null d_normals,
+ *   d_dirs, d_points or d_ao (n > 0); an offset that is not finite; max_dist < 0 or NaN.  A grid buffer that passes the size check but whose head disagrees with the
+ *   arguments: nothing more of it is read and nothing is written.  n == 0 is valid and launches nothing; F == 0 is valid: every ray misses. */
+#define NRF_RC_CLOSEST 0
+#define NRF_RC_ANY 1
+#define NRF_RC_CULL_NONE 0
+#define NRF_RC_CULL_BACK 1
+#define NRF_RC_CULL_FRONT 2
+#define NRF_RC_TAU_LOG2 (-12)            /* the consistency bound of t and P, relative to max(|o|_inf, |Pu|_inf) */
+#define NRF_RC_MAX_STEPS 1024            /* steps of the walk before a ray goes to the fallback: about the cells of the longest axis a grid can have.  The far-origin
+                                            rules keep every point of a walk within 1024 h_min of the origin of the coordinates, so no walk has more than ~2050 steps
+                                            whatever the cap; 1024 is reached by a ray through all cells of a 1024-cell axis and by little else */
+#define NRF_RC_MAX_STRIDE 64             /* floats per packed ray row */
+#define NRF_RNG_HEMI_DIR 12              /* the stream of nrf_rng.h the disc draws of a direction come from: the next after its own ids (NRF_RNG_SURFACE_UV = 11) */
+#define NRF_HEMI_ATTEMPTS 8              /* disc rejections per direction */
+#define NRF_HEMI_MAX_K 65536             /* directions per normal: j takes 16 bits of the draw's index */
+#define NRF_HEMI_MAX_INDEX ((int64_t)1 << 40)
+#define NRF_AO_MAX_RAYS ((int64_t)1 << 38)          /* n * k of one nrf_mesh_ambient_occlusion call: a lane per ray, 2^30 workgroups */
+#define NRF_HEMI_MIN_LEN2 9.5367431640625e-07f          /* 2^-20: below it n-hat + q has no direction and n-hat itself is used */
+NRF_API size_t nrf_ray_cast_workspace_bytes(int64_t n_rays);
+NRF_API int nrf_ray_cast_mesh(const float *d_rays, int64_t n_rays, int stride, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces,
+                              const float *bbox, int nx, int ny, int nz, int64_t n_refs, int64_t n_large, const void *d_grid, size_t grid_bytes, int cull, int mode,
+                              float *d_t, int32_t *d_face, float *d_uv, float *d_point, uint8_t *d_hit, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes,
+                              void *stream);
+NRF_API int nrf_hemisphere_dirs(const float *d_normals, int64_t n, int k, uint64_t seed, int64_t index0, float *d_dirs, uint32_t *d_stats, void *stream);
+NRF_API int nrf_mesh_ambient_occlusion(const float *d_points, const float *d_normals, int64_t n, int k, float offset, float max_dist, uint64_t seed, int64_t index0,
+                                       const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz,
+                                       int64_t n_refs, int64_t n_large, const void *d_grid, size_t grid_bytes, float *d_ao, uint32_t *d_stats, void *d_workspace,
+                                       size_t workspace_bytes, void *stream);
+
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */
 NRF_API size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p);

@@ -18,6 +18,9 @@ NRF_DIRS_NONE, NRF_DIRS_PE, NRF_DIRS_SH_LIBTORCH, NRF_DIRS_SH_CUDA = 0, 1, 2, 3
 (NRF_RNG_T_RAND, NRF_RNG_R_COARSE, NRF_RNG_THETA_COARSE, NRF_RNG_NOISE_COARSE, NRF_RNG_U_PDF, NRF_RNG_PRECOND, NRF_RNG_R_FINE, NRF_RNG_THETA_FINE,
  NRF_RNG_NOISE_FINE) = range(1, 10)       # include/nrf_rng.h
 NRF_RNG_SURFACE_COUNT, NRF_RNG_SURFACE_UV = 10, 11
+NRF_RNG_HEMI_DIR = 12
+NRF_RC_CLOSEST, NRF_RC_ANY = 0, 1          # nrf_ray_cast_mesh: mode
+NRF_RC_CULL_NONE, NRF_RC_CULL_BACK, NRF_RC_CULL_FRONT = 0, 1, 2
 NRF_PROF_NAMES = ("hash", "mlp", "composite", "sample", "other", "sigma", "mlp_colour")
 NRF_COARSE_AUTO, NRF_COARSE_FULL, NRF_COARSE_SIGMA_F32 = 0, 1, 2
 NRF_OVERFLOW_AUTO, NRF_OVERFLOW_RERENDER, NRF_OVERFLOW_ERROR, NRF_OVERFLOW_DEFERRED, NRF_OVERFLOW_IGNORE = 0, 1, 2, 3, 4
@@ -221,6 +224,10 @@ _ABI = """
     nrf_face_grid_build(plplpiiillpzpzp)
     nrf_closest_on_mesh_workspace_bytes(l)->z
     nrf_closest_on_mesh(plplplpiiillpzfppppppzp)
+    nrf_ray_cast_workspace_bytes(l)->z
+    nrf_ray_cast_mesh(pliplplpiiillpziipppppppzp)
+    nrf_hemisphere_dirs(pliqlppp)
+    nrf_mesh_ambient_occlusion(ppliffqlplplpiiillpzpppzp)
     nrf_render_rays_workspace_bytes(plp)->z
     nrf_render_rays(ppilpppppzp)
     nrf_batchify_rays_workspace_bytes(plip)->z

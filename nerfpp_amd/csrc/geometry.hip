@@ -20,11 +20,13 @@
 //   the large list), the scan, k_fg_starts (starts into the caller's grid buffer, with what it was built for at its head), k_fg_bin<1> scatters face indices.
 //   k_cm_query: one lane per query, the large list, then k_nn_query's ring walk over references, the same stop; k_cm_far brute-forces all faces for the listed
 //   queries.  cm_take / cm_closest are the one copy of the candidate: Ericson's regions in a fixed order, P clamped to the face's coordinate box (the stop's proof
-//   needs it), d2 through nn_d2.  tests/closest_ref.py restates it.
+//   needs it), d2 through nn_d2.  tests/closest_ref.py restates it.  What a reader of the grid buffer needs (the grid, the buffer's layout and head, cm_face, the
+//   clamp) lives in face_grid.h, which raycast.hip shares.
 // Every loop is bounded by a clamped range or a count; no kernel waits on another workgroup.
 #include "reduce.h"
 #include "scan.h"
 #include "workspace.h"
+#include "face_grid.h"
 #include "nrf_rng.h"
 
 #include <climits>
@@ -34,11 +36,9 @@ namespace nrf {
 
 namespace {
 
-constexpr int GEO_BLOCK = 256;
-constexpr int FAR_GRID = 1024;           // workgroups of k_nn_far: 4 per CU
+// GEO_BLOCK, FAR_GRID, NN_NONE, the grid and everything a reader of the face-grid buffer needs: face_grid.h (shared with raycast.hip)
 constexpr int STATS_TILE = 4096;         // entries per block of k_dist_stats
 constexpr int STATS_VALUES = 8;          // count, sum d, sum d2, max d, four tau counts
-constexpr unsigned long long NN_NONE = ((unsigned long long)0x7f800000u << 32) | 0xffffffffu;          // d2 = +inf, index = -1: above every key with a valid index
 
 // out[v] = the ordered sum over k of partials[k * nv + v] (v == max_at: the maximum), v < n_out: one block, reduce.h's finish pass per column
 __global__ void __launch_bounds__(GEO_BLOCK) k_geo_finish(int64_t count, int nv, int max_at, const double *__restrict__ partials, double *__restrict__ out, int n_out)
@@ -70,10 +70,6 @@ SampleWs sample_layout(Bump &b, int64_t n_faces)
     s.area = b.take<double>(nb);
     return s;
 }
-
-bool sample_shape_ok(int64_t n_verts, int64_t n_faces) { return n_verts >= 0 && n_verts <= INT32_MAX && n_faces >= 0 && n_faces <= INT32_MAX; }
-
-__device__ __forceinline__ bool finite3(const float p[3]) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
 // the corners of face f; false (nothing dereferenced) where an index lies outside [0, V)
 __device__ __forceinline__ bool face_corners(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t f, float v0[3], float e1[3], float e2[3],
@@ -212,13 +208,6 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_sample_points_by_face(const float
 #endif
 
 // ---------------------------------------------------------------------------------------------- 2. nearest points
-struct NnGrid {
-    int n[3];
-    int64_t cells;
-    float bmin[3], inv_h[3];
-    float h_min;             // the smallest cell edge, fl(1 / inv_h)
-};
-
 struct NnWs {
     uint32_t *start;         // [cells + 1] counts, then the exclusive scan: the records of cell c are start[c] .. start[c + 1]
     uint32_t *cursor;        // [cells] where the next record of a cell goes
@@ -240,19 +229,6 @@ NnWs nn_layout(Bump &b, int64_t nq, int64_t nt, int64_t cells)
     s.far = b.take<int32_t>((size_t)nq);
     s.n_far = b.take<uint32_t>(1);
     return s;
-}
-
-bool nn_shape_ok(int64_t nq, int64_t nt, int nx, int ny, int nz)
-{
-    return nq >= 0 && nq <= INT32_MAX && nt >= 0 && nt <= INT32_MAX && nx >= 1 && nx <= NRF_NN_MAX_DIM && ny >= 1 && ny <= NRF_NN_MAX_DIM && nz >= 1 &&
-           nz <= NRF_NN_MAX_DIM && (int64_t)nx * ny * nz <= NRF_NN_MAX_CELLS;
-}
-
-// the header's cell coordinate: clamp((int)floorf((x - bmin) * inv_h), 0, n - 1), clamped as a float so that the conversion is defined for every finite x
-__device__ __forceinline__ int nn_cell(float x, float bmin, float inv_h, int n)
-{
-    const float t = floorf((x - bmin) * inv_h);
-    return (int)fminf(fmaxf(t, 0.0f), (float)(n - 1));
 }
 
 __device__ __forceinline__ int64_t nn_cell_of(const NnGrid &g, float x, float y, float z)
@@ -445,26 +421,13 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_dist_stats(const float *__restric
 }
 
 // ---------------------------------------------------------------------------------------------- 4. closest point on a mesh
-constexpr long long FG_MAGIC = 0x4e52464647524431ll;          // "NRFFGRD1": the first word of a built grid buffer
-
-// what a grid buffer was built for, as the header states it: the query kernels compare it with their own arguments before they read anything else of the buffer
-struct FgKey {
-    long long w[8];          // magic, F, dims packed, n_refs, n_large, the bits of the box two floats to a word
-};
-
+// FgKey, FgGrid and their makers, cm_face, cm_dot and the clamp: face_grid.h
 struct FgWs {                // count and build
     uint32_t *count;         // [cells] references per cell
     uint32_t *cursor;        // [cells] where the next reference of a cell goes
     int64_t *bsum;           // [cell blocks]
     int64_t *total;          // [1] n_refs
     uint32_t *counters;      // [0] n_large (count), [1] the large list's cursor (build)
-};
-
-struct FgGrid {              // the caller-owned buffer the queries read
-    long long *key;          // [8]
-    uint32_t *start;         // [cells + 1] the references of cell c are refs[start[c] .. start[c + 1])
-    int32_t *refs;           // [n_refs] face indices in cell order
-    int32_t *large;          // [n_large] the faces every query tests
 };
 
 struct CmWs {
@@ -483,56 +446,12 @@ FgWs fg_ws_layout(Bump &b, int64_t cells)
     return s;
 }
 
-FgGrid fg_grid_layout(Bump &b, int64_t cells, int64_t n_refs, int64_t n_large)
-{
-    FgGrid s;
-    s.key = b.take<long long>(8);
-    s.start = b.take<uint32_t>((size_t)cells + 1);
-    s.refs = b.take<int32_t>((size_t)n_refs);
-    s.large = b.take<int32_t>((size_t)n_large);
-    return s;
-}
-
 CmWs cm_layout(Bump &b, int64_t nq)
 {
     CmWs s;
     s.far = b.take<int32_t>((size_t)nq);
     s.n_far = b.take<uint32_t>(1);
     return s;
-}
-
-bool fg_shape_ok(int64_t n_verts, int64_t n_faces, int nx, int ny, int nz) { return sample_shape_ok(n_verts, n_faces) && nn_shape_ok(0, 0, nx, ny, nz); }
-
-bool fg_counts_ok(int64_t n_faces, int64_t n_refs, int64_t n_large) { return n_refs >= 0 && n_refs < ((int64_t)1 << 32) && n_large >= 0 && n_large <= n_faces; }
-
-FgKey fg_key(int64_t n_faces, int nx, int ny, int nz, int64_t n_refs, int64_t n_large, const float *bbox)
-{
-    FgKey k;
-    uint32_t bits[6];
-    std::memcpy(bits, bbox, sizeof(bits));
-    k.w[0] = FG_MAGIC;
-    k.w[1] = n_faces;
-    k.w[2] = ((long long)nz << 40) | ((long long)ny << 20) | nx;
-    k.w[3] = n_refs;
-    k.w[4] = n_large;
-    for (int a = 0; a < 3; a++) k.w[5 + a] = (long long)(((unsigned long long)bits[3 + a] << 32) | bits[a]);
-    return k;
-}
-
-// the corners of face f -> 0: a face; 1: a corner outside [0, V) (nothing dereferenced) or f outside [0, F); 2: a non-finite coordinate
-__device__ __forceinline__ int cm_face(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, int64_t f, float a[3], float b[3],
-                                       float c[3])
-{
-    if (f < 0 || f >= n_faces) return 1;
-    const int32_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-    if (i0 < 0 || i0 >= n_verts || i1 < 0 || i1 >= n_verts || i2 < 0 || i2 >= n_verts) return 1;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        a[k] = verts[(int64_t)i0 * 3 + k];
-        b[k] = verts[(int64_t)i1 * 3 + k];
-        c[k] = verts[(int64_t)i2 * 3 + k];
-    }
-    return finite3(a) && finite3(b) && finite3(c) ? 0 : 2;
 }
 
 // the cell box of a face: per axis nn_cell(min of the three) .. nn_cell(max of the three); its cell count (<= 2^30)
@@ -547,8 +466,6 @@ __device__ __forceinline__ int64_t fg_box(const NnGrid &g, const float a[3], con
     }
     return n;
 }
-
-__device__ __forceinline__ float cm_dot(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
 struct CmHit {
     float d2, v, w, p[3];
@@ -599,11 +516,7 @@ __device__ __forceinline__ void cm_closest(const float q[3], const float a[3], c
 #pragma unroll
         for (int k = 0; k < 3; k++) p[k] = (a[k] + ab[k] * v) + ac[k] * w;
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {          // P stays inside the face's coordinate box (the stop rule's proof needs it); the comparisons keep a NaN a NaN
-        const float lo = fminf(fminf(a[k], b[k]), c[k]), hi = fmaxf(fmaxf(a[k], b[k]), c[k]);
-        h.p[k] = p[k] < lo ? lo : (p[k] > hi ? hi : p[k]);
-    }
+    cm_clamp_to_face(p, a, b, c, h.p);          // P stays inside the face's coordinate box (the stop rule's proof needs it); the comparisons keep a NaN a NaN
     h.v = v;
     h.w = w;
     h.d2 = nn_d2(q[0], q[1], q[2], make_float4(h.p[0], h.p[1], h.p[2], 0.0f));
@@ -700,14 +613,6 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_fg_starts(int64_t cells, const ui
     if (c == cells - 1) start[cells] = at + n;
 }
 
-__device__ __forceinline__ bool fg_key_matches(const long long *__restrict__ grid_key, const FgKey &key)
-{
-    bool same = true;
-#pragma unroll
-    for (int k = 0; k < 8; k++) same = same && grid_key[k] == key.w[k];
-    return same;
-}
-
 __global__ void __launch_bounds__(GEO_BLOCK) k_cm_query(const float *__restrict__ query, int64_t nq, const float *__restrict__ verts, int32_t n_verts,
                                                         const int32_t *__restrict__ faces, int64_t n_faces, NnGrid g, FgKey key, float md2,
                                                         const long long *__restrict__ grid_key, const uint32_t *__restrict__ start, const int32_t *__restrict__ refs,
@@ -789,28 +694,6 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_cm_far(const float *__restrict__ 
         if (threadIdx.x == 0) cm_write(q, qi, best, verts, n_verts, faces, n_faces, dist2, face, uv, point);
         __syncthreads();          // the next query goes through the same words
     }
-}
-
-// the grid of a box and dims, as nrf_nearest_points states it; false with the offending axis where the box is refused
-bool nn_grid_make(const float *bbox, int nx, int ny, int nz, NnGrid &g, int &axis)
-{
-    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
-    g.cells = (int64_t)nx * ny * nz;
-    g.h_min = INFINITY;
-    for (int a = 0; a < 3; a++) {
-        const float extent = bbox[3 + a] - bbox[a];
-        const float inv_h = (float)g.n[a] / extent;
-        const float h = 1.0f / inv_h;
-        if (!(std::isfinite(bbox[a]) && std::isfinite(bbox[3 + a]) && extent > 0.0f && std::isfinite(extent) && std::isfinite(inv_h) && inv_h > 0.0f && std::isfinite(h) &&
-              h > 0.0f)) {
-            axis = a;
-            return false;
-        }
-        g.bmin[a] = bbox[a];
-        g.inv_h[a] = inv_h;
-        g.h_min = h < g.h_min ? h : g.h_min;
-    }
-    return true;
 }
 
 }  // namespace
@@ -980,16 +863,7 @@ size_t nrf_face_grid_bytes(int64_t n_faces, int nx, int ny, int nz, int64_t n_re
     return measure([&](Bump &b) { fg_grid_layout(b, (int64_t)nx * ny * nz, n_refs, n_large); });
 }
 
-// the argument checks the three face-grid entries share: shapes, pointers of the mesh, the box
-#define NRF_FG_CHECK_MESH(who)                                                                                                                                            \
-    NRF_CHECK_ARG(fg_shape_ok(n_verts, n_faces, nx, ny, nz), who ": %lld vertices, %lld faces (both 0 .. 2^31 - 1), grid %d x %d x %d (each 1 .. %d, product <= %d)",    \
-                  (long long)n_verts, (long long)n_faces, nx, ny, nz, NRF_NN_MAX_DIM, NRF_NN_MAX_CELLS);                                                                   \
-    NRF_CHECK_ARG(n_faces == 0 || d_faces, who ": null d_faces");                                                                                                         \
-    NRF_CHECK_ARG(d_verts || n_verts == 0 || n_faces == 0, who ": null d_verts");                                                                                         \
-    NRF_CHECK_ARG(bbox, who ": null bbox");                                                                                                                               \
-    NnGrid g;                                                                                                                                                             \
-    int axis = 0;                                                                                                                                                         \
-    NRF_CHECK_ARG(nn_grid_make(bbox, nx, ny, nz, g, axis), who ": empty, inverted or non-finite box on axis %d ([%g, %g])", axis, (double)bbox[axis], (double)bbox[3 + axis])
+// NRF_FG_CHECK_MESH, the argument checks the face-grid entries share: face_grid.h
 
 int nrf_face_grid_count(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz, int64_t *n_refs,
                         int64_t *n_large, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream)

@@ -6,7 +6,8 @@ two point sets are compared through a uniform-grid nearest-neighbour search whos
 neither the grid nor the order of the points -- and the sums behind Chamfer distance, Hausdorff distance and precision / recall / F-score at a distance are ordered
 fp64 reductions.  tests/geometry_ref.py equals every output bit for bit and two runs agree.  That is the sampled point-to-point distance of the DTU / Tanks and Temples
 benchmarks; FaceGrid / ClosestOnMesh are the exact point-to-triangle query beside it (the nearest face, the point on it, its barycentrics; tests/closest_ref.py),
-which SurfaceDistance(to="surface"), TransferAttributes(source="surface") and texture.BakeTexture(source=<Mesh>) are thin layers over.
+which SurfaceDistance(to="surface"), TransferAttributes(source="surface") and texture.BakeTexture(source=<Mesh>) are thin layers over.  RayCastMesh / Occluded /
+Visible / HemisphereDirections / AmbientOcclusion / ClipRaysToMesh ask the same FaceGrid what a ray hits (raycast.hip; tests/raycast_ref.py).
 """
 import ctypes as C
 import math
@@ -107,7 +108,7 @@ def InterpolateAttributes(mesh, samples, name):
     attr = _dev_f32(getattr(mesh, name))
     a = attr.reshape(attr.shape[0], -1)
     at = samples.Faces.to(torch.int64)
-    miss = at < 0 if isinstance(samples, ClosestResult) else None          # a ClosestResult has -1 where no face was found: zeros there
+    miss = at < 0 if isinstance(samples, (ClosestResult, RayCastResult)) else None          # a ClosestResult / RayCastResult has -1 where no face was found: zeros there
     f = mesh.Faces.to(device=a.device, dtype=torch.int64)[at if miss is None else at.clamp(min=0)]
     u, v = samples.UV[:, :1], samples.UV[:, 1:]
     out = (1.0 - u - v) * a[f[:, 0]] + u * a[f[:, 1]] + v * a[f[:, 2]]
@@ -280,3 +281,165 @@ def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_
     p, r = sa[4:] / na, sb[4:] / nb
     f = torch.where(p + r > 0, 2.0 * p * r / (p + r), torch.zeros_like(p))
     return SurfaceDistanceResult(acc, comp, 0.5 * (acc + comp), sa[2] / sa[0] + sb[2] / sb[0], torch.maximum(sa[3], sb[3]), p, r, f, tuple(float(t) for t in taus))
+
+
+# ---------------------------------------------------------------------------------------------- ray casting (include/nerfpp_hip.h "Ray casting on a mesh", raycast.hip)
+RC_CLOSEST, RC_ANY = 0, 1
+RC_CULL = {"none": 0, "back": 1, "front": 2}
+RC_TAU_LOG2, RC_MAX_STEPS, RC_MAX_STRIDE = -12, 1024, 64         # NRF_RC_* / NRF_HEMI_* of the header (tests/test_raycast_host.py holds them to it)
+HEMI_ATTEMPTS, HEMI_MAX_K, HEMI_MAX_INDEX, HEMI_MIN_LEN2 = 8, 65536, 1 << 40, 2.0 ** -20
+AO_OFFSET, AO_MAX_DIST = 1e-3, 0.25          # AmbientOcclusion's defaults as shares of the box diagonal
+
+
+@dataclass
+class RayCastResult:                  # RayCastMesh's; InterpolateAttributes takes it as it takes a ClosestResult
+    T: torch.Tensor                   # [n] f32 the ray parameter of the first hit in units of d (the renderer's z); +inf on a miss or an invalid ray
+    Face: torch.Tensor                # [n] int32 the face hit; -1 on a miss
+    UV: Optional[torch.Tensor]        # [n, 2] f32: the hit is about (1 - u - v) v0 + u v1 + v v2 of that face; zeros on a miss
+    Points: Optional[torch.Tensor]    # [n, 3] f32 the surface point itself
+
+    @property
+    def Faces(self):
+        return self.Face
+
+
+def _as_grid(mesh_or_grid, stats=None):
+    return mesh_or_grid if isinstance(mesh_or_grid, FaceGrid) else FaceGrid(mesh_or_grid, stats=stats)
+
+
+def _packed_rays(rays, near, far, dev, who):
+    """rays: packed rows [n, >= 8] (o, d, near, far, ...; their own ranges are kept) or a pair (origins [n, 3], dirs [n, 3]) packed here with near / far"""
+    if isinstance(rays, (tuple, list)):
+        o, d = (_dev_f32(x).reshape(-1, 3).to(dev) for x in rays)
+        if o.shape[0] != d.shape[0]:
+            raise L.NrfError(f"{who}: {int(o.shape[0])} origins and {int(d.shape[0])} directions")
+        r = torch.empty((o.shape[0], 8), device=dev, dtype=torch.float32)
+        r[:, 0:3], r[:, 3:6] = o, d
+        r[:, 6] = torch.as_tensor(near, dtype=torch.float32, device=dev)
+        r[:, 7] = torch.as_tensor(far, dtype=torch.float32, device=dev)
+        return r
+    r = _dev_f32(rays).to(dev)
+    if r.dim() != 2 or not 8 <= r.shape[1] <= RC_MAX_STRIDE:
+        raise L.NrfError(f"{who}: packed rays are [n, 8 .. {RC_MAX_STRIDE}] (o, d, near, far, ...), got {tuple(r.shape)}")
+    return r.contiguous()
+
+
+def _ray_cast(who, rays, grid, cull, mode, uv, points, stats):
+    if cull not in RC_CULL:
+        raise L.NrfError(f"{who}: cull must be one of {sorted(RC_CULL)}, got {cull!r}")
+    dev, n = rays.device, int(rays.shape[0])
+    closest = mode == RC_CLOSEST
+    t = torch.empty((n,), device=dev, dtype=torch.float32) if closest else None
+    face = torch.empty((n,), device=dev, dtype=torch.int32) if closest else None
+    out_uv = torch.empty((n, 2), device=dev, dtype=torch.float32) if closest and uv else None
+    out_p = torch.empty((n, 3), device=dev, dtype=torch.float32) if closest and points else None
+    hit = None if closest else torch.empty((n,), device=dev, dtype=torch.uint8)
+    lib = L.lib()
+    ws = _workspace(lib.nrf_ray_cast_workspace_bytes(n), dev)
+    nx, ny, nz = grid.Dims
+    L.check(lib.nrf_ray_cast_mesh(_ptr(rays), n, int(rays.shape[1]), _ptr(grid.Verts), int(grid.Verts.shape[0]), _ptr(grid.Faces), int(grid.Faces.shape[0]),
+                                  grid.Box.ctypes.data_as(C.c_void_p), nx, ny, nz, grid.NRefs, grid.NLarge, _ptr(grid.Buffer), grid.Buffer.numel(), RC_CULL[cull], mode,
+                                  _ptr(t), _ptr(face), _ptr(out_uv), _ptr(out_p), _ptr(hit), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    return t, face, out_uv, out_p, hit
+
+
+def RayCastMesh(rays, mesh_or_grid, near=0.0, far=float("inf"), cull="none", uv=True, points=True, stats=None):
+    """The first face every ray hits on a Mesh or its FaceGrid -> RayCastResult (nrf_ray_cast_mesh, closest mode).  rays: the library's packed rows [n, >= 8]
+    (o, d, near, far, ...: what BatchifyRays and AtlasTexels use; each row's own range holds and near / far here are ignored) or a pair (origins, dirs) with near / far
+    scalars or [n].  d is not normalised and T is in units of d, the renderer's z.  The range is [max(near, 0), far]; on an exact tie in T the lowest face index;
+    +inf, -1 and zeros on a miss, an empty range or an invalid ray.  cull: "none", "back" (only faces counter-clockwise seen from the origin, RenderMesh's "back") or
+    "front".  A Mesh is binned first (FaceGrid(mesh): two host synchronisations); pass a FaceGrid to cast again without them.  A grid whose box does not hold the
+    mesh is still exact, through the brute-force fallback.  stats: an int32 [4] device tensor; entry 0 += invalid rays, entry 3 += rays served by the fallback."""
+    grid = _as_grid(mesh_or_grid, stats)
+    r = _packed_rays(rays, near, far, grid.Verts.device, "RayCastMesh")
+    t, face, out_uv, out_p, _ = _ray_cast("RayCastMesh", r, grid, cull, RC_CLOSEST, uv, points, stats)
+    return RayCastResult(t, face, out_uv, out_p)
+
+
+def Occluded(rays, mesh_or_grid, near=0.0, far=float("inf"), cull="none", stats=None):
+    """[n] bool: whether a ray hits anything within its range (nrf_ray_cast_mesh, any mode: the walk stops at the first face it meets).  Arguments as RayCastMesh's;
+    the answer equals isfinite(RayCastMesh(...).T)."""
+    grid = _as_grid(mesh_or_grid, stats)
+    r = _packed_rays(rays, near, far, grid.Verts.device, "Occluded")
+    return _ray_cast("Occluded", r, grid, cull, RC_ANY, False, False, stats)[4].to(torch.bool)
+
+
+def Visible(points_a, points_b, mesh_or_grid, eps=1e-4, stats=None):
+    """[n] bool: whether the segment from points_a[i] to points_b[i] is free of the mesh.  The ray is o = a, d = b - a with the range [eps, 1 - eps] in units of the
+    segment's length, so a segment that starts or ends ON the surface is not blocked by that very surface.  A pair that coincides (d = 0) or is not finite is an
+    invalid ray, a miss: reported visible and counted in stats[0]."""
+    grid = _as_grid(mesh_or_grid, stats)
+    dev = grid.Verts.device
+    a, b = _dev_f32(points_a).reshape(-1, 3).to(dev), _dev_f32(points_b).reshape(-1, 3).to(dev)
+    return ~Occluded((a, b - a), grid, near=float(eps), far=1.0 - float(eps), stats=stats)
+
+
+def HemisphereDirections(normals, k, seed=0, index0=0, stats=None):
+    """[n, k, 3] f32 unit directions around each normal, distributed by the cosine law (nrf_hemisphere_dirs): direction j of normal i is a pure function of
+    (seed, index0 + i, j), so a slab of a longer list draws what the whole list would.  A zero or non-finite normal gives zeros and is counted in stats[0]."""
+    nrm = _dev_f32(normals).reshape(-1, 3)
+    n = int(nrm.shape[0])
+    dirs = torch.empty((n, int(k), 3), device=nrm.device, dtype=torch.float32)
+    L.check(L.lib().nrf_hemisphere_dirs(_ptr(nrm), n, int(k), int(seed), int(index0), _ptr(dirs), _ptr(stats), _stream()))
+    return dirs
+
+
+def _box_diagonal(box):
+    b = np.asarray(box, np.float64)
+    return float(np.linalg.norm(b[3:] - b[:3]))
+
+
+def AmbientOcclusion(mesh, k=64, max_dist=None, offset=None, seed=0, grid=None, at=None, index0=0, stats=None):
+    """[n] f32 in [0, 1]: the share of k cosine-weighted rays that leave each point unoccluded (nrf_mesh_ambient_occlusion: directions and walk fused, no ray is
+    written); 1 is open sky.  The points are the vertices of `mesh` with mesh.Normals, or at = (points [n, 3], normals [n, 3]).  Ray j of point i starts
+    `offset` above the point along its unit normal and is `max_dist` long; the defaults are AO_OFFSET = 1e-3 and AO_MAX_DIST = 0.25 of the diagonal of the grid's
+    box: above the rounding of a hit's own surface, and the reach within which a wall darkens a corner.  grid: a FaceGrid of the occluding mesh (default:
+    FaceGrid(mesh), two host synchronisations).  The value is an integer count over k, so it is exact; (seed, index0 + i, j) decide a direction, so slabs agree with
+    the whole.  A point with a zero or non-finite normal gets 1 and its k rays are counted in stats[0]; stats[3] += rays served by the fallback."""
+    grid = FaceGrid(mesh, stats=stats) if grid is None else grid
+    dev = grid.Verts.device
+    if at is None:
+        if mesh.Normals is None:
+            raise L.NrfError("AmbientOcclusion: the mesh has no Normals (mesh.VertexNormals gives them), and no at=(points, normals) was passed")
+        pts, nrm = mesh.Vertices, mesh.Normals
+    else:
+        pts, nrm = at
+    pts, nrm = _dev_f32(pts).reshape(-1, 3).to(dev), _dev_f32(nrm).reshape(-1, 3).to(dev)
+    if pts.shape[0] != nrm.shape[0]:
+        raise L.NrfError(f"AmbientOcclusion: {int(pts.shape[0])} points and {int(nrm.shape[0])} normals")
+    diag = _box_diagonal(grid.Box)
+    off = AO_OFFSET * diag if offset is None else float(offset)
+    md = AO_MAX_DIST * diag if max_dist is None else float(max_dist)
+    n = int(pts.shape[0])
+    ao = torch.empty((n,), device=dev, dtype=torch.float32)
+    lib = L.lib()
+    ws = _workspace(lib.nrf_ray_cast_workspace_bytes(n), dev)
+    nx, ny, nz = grid.Dims
+    L.check(lib.nrf_mesh_ambient_occlusion(_ptr(pts), _ptr(nrm), n, int(k), off, md, int(seed), int(index0), _ptr(grid.Verts), int(grid.Verts.shape[0]), _ptr(grid.Faces),
+                                           int(grid.Faces.shape[0]), grid.Box.ctypes.data_as(C.c_void_p), nx, ny, nz, grid.NRefs, grid.NLarge, _ptr(grid.Buffer),
+                                           grid.Buffer.numel(), _ptr(ao), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    return ao
+
+
+def ClipRaysToMesh(rays, mesh_or_grid, band, miss="keep", cull="none", stats=None):
+    """A copy of the packed rays [n, >= 8] whose ranges are narrowed around the mesh: on a hit at T, near = max(near, T - band) and far = min(far, T + band); on a miss
+    the range is kept (miss="keep") or made empty (miss="empty": near 1, far 0).  band is in units of T, that is of each ray's own d (world units where d is a unit
+    vector; BatchifyRays' z otherwise).  The result feeds BatchifyRays as it is: a mesh extracted at one iteration narrows the sampling of every later render."""
+    if miss not in ("keep", "empty"):
+        raise L.NrfError(f"ClipRaysToMesh: miss must be 'keep' or 'empty', got {miss!r}")
+    if isinstance(rays, (tuple, list)):
+        raise L.NrfError("ClipRaysToMesh: pass packed rays [n, >= 8]; a pair of origins and directions has no range to narrow")
+    grid = _as_grid(mesh_or_grid, stats)
+    r = _packed_rays(rays, 0.0, 0.0, grid.Verts.device, "ClipRaysToMesh")
+    t = _ray_cast("ClipRaysToMesh", r, grid, cull, RC_CLOSEST, False, False, stats)[0]
+    out = r.clone()
+    hit = torch.isfinite(t)
+    b = torch.as_tensor(band, dtype=torch.float32, device=r.device)
+    near, far = torch.maximum(r[:, 6], t - b), torch.minimum(r[:, 7], t + b)
+    if miss == "empty":
+        out[:, 6] = torch.where(hit, near, torch.ones_like(near))
+        out[:, 7] = torch.where(hit, far, torch.zeros_like(far))
+    else:
+        out[:, 6] = torch.where(hit, near, r[:, 6])
+        out[:, 7] = torch.where(hit, far, r[:, 7])
+    return out

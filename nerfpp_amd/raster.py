@@ -77,6 +77,25 @@ def RenderMesh(mesh, pose, W, H, K, near=1e-3, cull="none", attrs=_ATTRS):
     return res
 
 
+def RayCastView(mesh, pose, W, H, K, near=0.0, far=float("inf"), cull="none", stats=None):
+    """The view of RenderMesh by ray casting: GetRays(H, W, K, pose) through geometry.RayCastMesh (mesh: a Mesh or its geometry.FaceGrid) -> MeshRender with DepthMap,
+    AccMap, FaceMap and BaryMap in RenderMesh's units (the depth is the ray parameter of GetRays' directions, 0 where nothing is hit), so the two can be compared
+    pixel for pixel.  They are two definitions that round differently: the rasteriser decides coverage in integer sub-pixels and interpolates 1 / z, the ray cast
+    intersects in space, so faces can differ along silhouettes and shared edges, and BaryMap here holds the SURFACE barycentrics (1 - u - v, u, v) of the hit, not
+    the screen-space ones.  Unlike the rasteriser it has no near plane or guard band and sees faces behind other cameras' clip limits."""
+    from . import geometry as G
+    from .renderer import GetRays
+    grid = mesh if isinstance(mesh, G.FaceGrid) else G.FaceGrid(mesh, stats=stats)
+    h, w = int(H), int(W)
+    o, d, _ = GetRays(h, w, _k9(K), _m12(pose).reshape(3, 4), device=grid.Verts.device)
+    res = G.RayCastMesh((o.reshape(-1, 3), d.reshape(-1, 3)), grid, near=near, far=far, cull=cull, points=False, stats=stats)
+    hit = res.Face >= 0
+    depth = torch.where(hit, res.T, torch.zeros_like(res.T)).reshape(h, w)
+    u, v = res.UV[:, 0], res.UV[:, 1]
+    bary = torch.where(hit[:, None], torch.stack([(1.0 - u) - v, u, v], dim=-1), torch.zeros((1, 3), device=u.device)).reshape(h, w, 3)
+    return MeshRender(depth, hit.to(torch.float32).reshape(h, w), res.Face.reshape(h, w), bary, Stats=stats)
+
+
 def RenderMeshView(mesh, view, rparams=None, **kw):
     """RenderMesh at a dataset.View (H, W, K, Pose are read); with rparams its RenderFactor is honoured through RenderViewDims, so the maps line up with
     RenderView(renderer, view.Pose, view.W, view.H, view.K, rparams)."""

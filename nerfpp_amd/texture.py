@@ -168,6 +168,30 @@ def BakeTexture(mesh, source, tile=8, mode="point", rparams=None, offset=None, c
     return TextureAtlas(image, t, nf, acc)
 
 
+def BakeAmbientOcclusion(mesh, tile=8, k=64, max_dist=None, offset=None, seed=0, grid=None, chunk_rows=None, stats=None):
+    """The ambient-occlusion atlas of `mesh` at `tile` texels -> a one-channel TextureAtlas: geometry.AmbientOcclusion at every owned texel's surface point with its
+    FACE normal (AtlasTexels of the mesh without vertex normals), slab by slab of chunk_rows atlas rows as BakeTexture works; texels without an owner get 0.  The
+    occluder is grid (a geometry.FaceGrid; default FaceGrid(mesh): two host synchronisations).  k, max_dist, offset, seed as AmbientOcclusion's; the direction j of
+    the texel (Y, X) is drawn for the index Y * width + X, so the atlas does not depend on chunk_rows.  SaveOBJ(..., occlusion=atlas) multiplies it into the colours."""
+    import dataclasses
+    from . import geometry as G
+    grid = G.FaceGrid(mesh, stats=stats) if grid is None else grid
+    flat = dataclasses.replace(mesh, Normals=None)
+    nf, t = int(mesh.Faces.shape[0]), int(tile)
+    w, h, _, _ = AtlasLayout(nf, t)
+    step = max(1, SLAB_TEXELS // max(w, 1)) if chunk_rows is None else int(chunk_rows)
+    if step < 1:
+        raise L.NrfError(f"BakeAmbientOcclusion: chunk_rows must be >= 1, got {chunk_rows}")
+    image = torch.zeros((h, w, 1), device=mesh.Vertices.device, dtype=torch.float32)
+    for r0 in range(0, h, step):
+        n = min(step, h - r0)
+        face, _, pos, rays = AtlasTexels(flat, t, 0.0, (r0, n))
+        normals = -rays.reshape(-1, 11)[:, 3:6]          # the ray of a texel looks down its normal
+        ao = G.AmbientOcclusion(mesh, k=k, max_dist=max_dist, offset=offset, seed=seed, grid=grid, at=(pos.reshape(-1, 3), normals), index0=r0 * w, stats=stats)
+        image[r0:r0 + n, :, 0] = torch.where(face >= 0, ao.reshape(n, w), torch.zeros_like(ao.reshape(n, w)))
+    return TextureAtlas(image, t, nf)
+
+
 def _filter(filter, who):
     if filter not in _FILTER:
         raise L.NrfError(f"{who}: filter must be one of {sorted(_FILTER)}, got {filter!r}")
@@ -238,10 +262,15 @@ def QuantizeTexture(image):
     return np.clip(np.rint(np.nan_to_num(c) * 255.0), 0, 255).astype(np.uint8)
 
 
-def SaveOBJ(path, mesh, atlas):
+def SaveOBJ(path, mesh, atlas, occlusion=None):
     """Write `path` (v, vn where the mesh has normals, three vt per face, f a/ta/na ...), path + ".mtl" (map_Kd) and path + ".png" (the atlas as 8-bit RGB).  The vt
-    of a corner is ((X + 0.5) / width, 1 - (Y + 0.5) / height) of the centre of the texel (X, Y) the layout gives that corner."""
+    of a corner is ((X + 0.5) / width, 1 - (Y + 0.5) / height) of the centre of the texel (X, Y) the layout gives that corner.  occlusion: a one-channel atlas of
+    the same mesh and tile (BakeAmbientOcclusion) that is multiplied into the image before it is quantised; without it the files are what they always were."""
     atlas.check(mesh, "SaveOBJ")
+    if occlusion is not None:
+        occlusion.check(mesh, "SaveOBJ")
+        if occlusion.Tile != atlas.Tile or int(occlusion.Image.shape[-1]) != 1:
+            raise L.NrfError(f"SaveOBJ: the occlusion atlas must hold one channel at tile {atlas.Tile}, got {int(occlusion.Image.shape[-1])} at tile {occlusion.Tile}")
     nf, t = atlas.NFaces, atlas.Tile
     w, h, cols, _ = AtlasLayout(nf, t)
     if nf == 0:
@@ -271,4 +300,4 @@ def SaveOBJ(path, mesh, atlas):
     with open(path + ".mtl", "w") as fh:
         fh.write(f"newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {name}.png\n")
     with open(path + ".png", "wb") as fh:
-        fh.write(EncodePNG(QuantizeTexture(atlas.Image)))
+        fh.write(EncodePNG(QuantizeTexture(atlas.Image if occlusion is None else atlas.Image * occlusion.Image.to(atlas.Image.device))))

@@ -1190,6 +1190,83 @@ NRF_API int nrf_mesh_ambient_occlusion(const float *d_points, const float *d_nor
                                        int64_t n_refs, int64_t n_large, const void *d_grid, size_t grid_bytes, float *d_ao, uint32_t *d_stats, void *d_workspace,
                                        size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh voxelisation (voxel.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* Scan conversion of a triangle list onto the lattice of nrf_density_grid / nrf_tsdf_integrate (P = bmin + (float)i * step, step = (bmax - bmin) / (float)(n - 1)
+ * per axis, x fastest, nx, ny, nz >= 2, fewer than 2^31 points; bbox[6] on the HOST): what is INSIDE a mesh.  d_verts [V,3] fp32, d_faces [F,3] int32
+ * (counter-clockwise seen from outside), 0 <= V < 2^31, 0 <= F <= 2^31 - 2 -> each or NULL (not all three): d_winding [nz][ny][nx] int32, the winding number;
+ * d_sdf [nz][ny][nx] fp32, the signed distance truncated at +-trunc, outside positive (the TSDF's convention: -sdf is a lattice for nrf_isosurface_*); d_face
+ * [nz][ny][nx] int32, the nearest face within trunc or -1.  d_stats [4] uint32 or NULL (ADDED to; the caller zeroes it): [0] CLIPPED, [1] BAD, [2] NON-FINITE faces;
+ * [3] is not touched.  The work is a scatter, proportional to the faces and to what they cover, not a gather over the lattice; integer atomics only (an add, a
+ * 64-bit min), so the result depends neither on scheduling nor on the order of the face list (beyond the tie-break by index the key states): two runs give the same
+ * bits, and so does any permutation of the faces (d_face then names the same face by its new index).  The call synchronises nothing and allocates nothing.
+ * Each source-level fp32 operation below is rounded once, / and sqrtf correctly; the edge functions are int64 and exact.
+ *   Faces.  The classes of nrf_face_grid_count (one inline function): a face with a corner outside [0, V) is BAD, a face with a non-finite coordinate is NON-FINITE;
+ *   both are skipped whole, nothing of a bad face is dereferenced.  Repeated corners and zero area do not make a face invalid.
+ * WINDING (an orthographic raster along +z; the twin of nrf_raster_mesh's steps 3-5).
+ *   1. Per vertex: gx = (Px - bminx) / stepx, gy and gz likewise (lattice units); X = (int)rintf(gx * 256.0f), Y = (int)rintf(gy * 256.0f) (NRF_RASTER_SUBPIXEL;
+ *      round half to even).  A valid face with a vertex where fabsf(gx) or fabsf(gy) exceeds NRF_RASTER_GUARD, compared as floats (+-inf clips), is CLIPPED: left
+ *      out of the winding pass only (the distance pass takes it).  A NON-ZERO d_stats[0] VOIDS THE WINDING and the sign of d_sdf: a crossing is missing.
+ *   2. In int64, E_ab(p) = (bx-ax)*(py-ay) - (by-ay)*(px-ax); e0 = E_12(p), e1 = E_20(p), e2 = E_01(p) at the column p = (256 i, 256 j); A = E_01(v2).  A == 0
+ *      contributes nothing: a face parallel to z has no projected area.  s = sign(A); s = +1 is a face whose normal has a +z component (counter-clockwise seen from
+ *      outside, x to the right and y up).
+ *   3. Column (i, j) is covered iff step 5 of nrf_raster_mesh calls it inside: for each edge k, s*e_k > 0, or s*e_k == 0 and the edge is top-left (edge k runs
+ *      v1->v2, v2->v0, v0->v1; with (dx, dy) = s*(b - a) top-left iff dy < 0 || (dy == 0 && dx > 0)).  Columns visited: ceil(minX/256) .. floor(maxX/256) clamped to
+ *      [0, nx-1], rows likewise with Y and ny.
+ *      WHY THE WINDING OF A CLOSED MESH IS EXACT.  Two faces that share an edge take its endpoints from the same two vertex records, so both see the same snapped
+ *      segment, in opposite directions.  A column strictly off the segment is on one definite side.  A column exactly ON it has e == 0 for both, and the top-left
+ *      rule, which looks only at s*(b - a), decides: where the faces continue each other across the edge (equal s) the directions s*(b - a) are opposite and exactly
+ *      one of them is top-left -- the column belongs to exactly one face; where they fold back at a silhouette (opposite s) the directions are equal and the column
+ *      belongs to both or to neither, which adds +1 - 1 or nothing.  So along every column of the snapped mesh each sheet is crossed exactly once, no column is
+ *      counted twice on an edge or lost in a crack, and the sum below is the winding number of the snapped surface -- an integer with no tolerance in it.
+ *   4. Crossing height, in lattice units: b_k = (float)((double)(s*e_k) / (double)(s*A)); zc = (b0*gz0 + b1*gz1) + b2*gz2.
+ *   5. t = ceilf(zc) - 1.0f; skipped unless t >= 0 (a crossing at or below level 0, and a NaN); kc = (int)fminf(t, (float)(nz - 1)), the largest k with (float)k < zc;
+ *      one integer atomic add of s on delta[kc][j][i].
+ *   6. winding(i, j, k) = the sum of delta[k'][j][i] over k' >= k: the +z-facing crossings above the point minus the -z-facing ones.  1 inside an outward-oriented
+ *      closed solid and 0 outside; -1 inside an inverted solid, 2 inside two nested like-oriented shells, 0 in a cavity whose shell faces inward.  A point with
+ *      zc == k exactly counts as not below the face.
+ * DISTANCE (a scatter over each face's dilated lattice box; skipped, with its part of the workspace, when d_sdf and d_face are both NULL).
+ *   7. Per valid face and axis, lo / hi the smallest / largest of the three coordinates: fl = floorf((lo - trunc - bmin) / step) - 1.0f, fh = ceilf((hi + trunc -
+ *      bmin) / step) + 1.0f (the subtractions left to right).  The box is EMPTY unless fh >= 0 and fl <= (float)(n - 1) on every axis; else its indices are
+ *      (int)fmaxf(fl, 0) .. (int)fminf(fh, (float)(n - 1)).
+ *   8. Per lattice point P of the box: d2 between P and the face by the closest-point function of nrf_closest_on_mesh (one inline function: Ericson's regions, the
+ *      clamp to the face's coordinate box, nn_d2).  Where d2 <= T2 = fl(trunc * trunc) (a NaN d2 fails), a 64-bit atomic min of ((uint64)float_bits(d2) << 32) | f
+ *      on the point's key, initially d2 = +inf, f = -1.  The final key is the nearest face, the lowest index on a tie: nrf_closest_on_mesh(max_dist = trunc) there.
+ *   WHY THE BOX IS COMPLETE.  Let Q be the closest point the function returns for lattice point P and face f, and suppose d2 <= T2.  The clamp keeps every
+ *      coordinate of Q inside [lo, hi] of the face on that axis.  d2 = fl(fl(dx*dx + dy*dy) + dz*dz) with dx = fl(Px - Qx) is at least dx*dx less three roundings, and
+ *      T2 is trunc*trunc within one, so |Px - Qx| <= trunc (1 + 3u), u = 2^-24: Px >= lo - trunc (1 + 3u), and likewise Px <= hi + trunc (1 + 3u).  Px itself is
+ *      bmin + i*step within two roundings, and fl((lo - trunc - bmin) / step) is the real quotient within three.  All these errors are a few ulp of the largest
+ *      magnitude among bmin, bmax, lo, hi and trunc; on a lattice whose points fp32 can tell apart (that magnitude below 2^20 steps -- any lattice this call accepts
+ *      around a mesh of its own scale) they sum to less than one step, so i >= floor(quotient) - 1 = fl, and i <= fh the same way: the extra lattice step on each side
+ *      pays for the rounding of the bounds.  Points visited needlessly are filtered by the comparison with T2, so the box is an optimisation of "every face against
+ *      every lattice point", never part of the result.
+ * FINISH (fused into the pass of step 6: the volume is read once).
+ *   9. dist = key found ? sqrtf(d2) : trunc; dist = fminf(dist, trunc).  d_face = the key's face or -1.
+ *  10. inside = winding != 0 (NRF_VOX_NONZERO: nested like-oriented shells merge into one solid), winding > 0 (NRF_VOX_POSITIVE: a reversed inner shell is
+ *      subtracted, an inverted solid is empty) or winding & 1 (NRF_VOX_ODD: parity).  d_sdf = inside ? -dist : dist.
+ * A face whose columns (step 3) or lattice box (step 7) hold more than NRF_VOXEL_WIDE_COLUMNS / NRF_VOXEL_WIDE_POINTS entries is scanned by a whole workgroup (same
+ * device functions, same bits).  Every loop is bounded by a clamped range or a count; nothing waits on another workgroup.
+ * d_workspace: 256-byte aligned, nrf_mesh_voxelize_workspace_bytes (0 for a shape the call refuses; 12 B per lattice point + 16 B per vertex + 8 B per face).  A call
+ * without distance outputs needs only the part before the key lattice (8 B per point less).
+ * NRF_ERR_INVALID_ARG, message starting "nrf_mesh_voxelize", nothing launched or written: a null bbox; a null d_faces, or a null d_verts with V > 0, with F > 0;
+ * all three outputs NULL; n < 2 on an axis or 2^31 lattice points or more; an empty, inverted or non-finite box (or a step that is not finite and > 0); trunc not
+ * finite or <= 0 while d_sdf or d_face is asked for (otherwise trunc is not read); a rule outside the three; V or F out of range; a null, misaligned or short
+ * workspace.  F == 0 is valid: winding 0, sdf +trunc, face -1. */
+#define NRF_VOX_NONZERO 0
+#define NRF_VOX_POSITIVE 1
+#define NRF_VOX_ODD 2
+#ifndef NRF_VOXEL_WIDE_COLUMNS           /* tuning builds set another (make EXTRA=-DNRF_VOXEL_WIDE_COLUMNS=n); no result depends on either */
+#define NRF_VOXEL_WIDE_COLUMNS 256       /* columns of a face's clamped bounding box above which the wide kernel rasterises it */
+#endif
+#ifndef NRF_VOXEL_WIDE_POINTS
+#define NRF_VOXEL_WIDE_POINTS 256        /* lattice points of a face's dilated box above which the wide kernel scans it */
+#endif
+NRF_API size_t nrf_mesh_voxelize_workspace_bytes(int64_t n_verts, int64_t n_faces, int nx, int ny, int nz);
+NRF_API int nrf_mesh_voxelize(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const float *bbox, int nx, int ny, int nz, float trunc,
+                              int rule, int32_t *d_winding, float *d_sdf, int32_t *d_face, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes,
+                              void *stream);
+
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */
 NRF_API size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p);

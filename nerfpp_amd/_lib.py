@@ -21,6 +21,7 @@ NRF_RNG_SURFACE_COUNT, NRF_RNG_SURFACE_UV = 10, 11
 NRF_RNG_HEMI_DIR = 12
 NRF_RC_CLOSEST, NRF_RC_ANY = 0, 1          # nrf_ray_cast_mesh: mode
 NRF_RC_CULL_NONE, NRF_RC_CULL_BACK, NRF_RC_CULL_FRONT = 0, 1, 2
+NRF_VOX_NONZERO, NRF_VOX_POSITIVE, NRF_VOX_ODD = 0, 1, 2          # nrf_mesh_voxelize: rule
 NRF_PROF_NAMES = ("hash", "mlp", "composite", "sample", "other", "sigma", "mlp_colour")
 NRF_COARSE_AUTO, NRF_COARSE_FULL, NRF_COARSE_SIGMA_F32 = 0, 1, 2
 NRF_OVERFLOW_AUTO, NRF_OVERFLOW_RERENDER, NRF_OVERFLOW_ERROR, NRF_OVERFLOW_DEFERRED, NRF_OVERFLOW_IGNORE = 0, 1, 2, 3, 4
@@ -228,6 +229,8 @@ _ABI = """
     nrf_ray_cast_mesh(pliplplpiiillpziipppppppzp)
     nrf_hemisphere_dirs(pliqlppp)
     nrf_mesh_ambient_occlusion(ppliffqlplplpiiillpzpppzp)
+    nrf_mesh_voxelize_workspace_bytes(lliii)->z
+    nrf_mesh_voxelize(plplpiiifipppppzp)
     nrf_render_rays_workspace_bytes(plp)->z
     nrf_render_rays(ppilpppppzp)
     nrf_batchify_rays_workspace_bytes(plip)->z

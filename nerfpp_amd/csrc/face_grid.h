@@ -2,6 +2,8 @@
 // nrf_mesh_ambient_occlusion): the uniform grid of nrf_nearest_points (NnGrid, nn_cell, nn_grid_make), the layout and the head of the caller-owned grid buffer
 // (FgGrid, FgKey, fg_key_matches), the classes of a face (cm_face), the dot product in the header's order and the clamp of a surface point to its face's own
 // coordinate box.  One copy of each: a query of either kind reads exactly the buffer the build wrote, and both proofs of completeness lean on the same clamp.
+// Also the closest point of a triangle itself (nn_d2, CmHit, cm_closest): nrf_closest_on_mesh gathers it per query, voxel.hip (nrf_mesh_voxelize) scatters it per
+// face over the lattice, and the two agree bit for bit because it is one function.
 #pragma once
 
 #include "common.h"
@@ -141,6 +143,68 @@ __device__ __forceinline__ void cm_clamp_to_face(const float p[3], const float a
         const float lo = fminf(fminf(a[k], b[k]), c[k]), hi = fmaxf(fmaxf(a[k], b[k]), c[k]);
         out[k] = p[k] < lo ? lo : (p[k] > hi ? hi : p[k]);
     }
+}
+
+// the one place d2 is formed
+__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, const float4 &t)
+{
+    const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+struct CmHit {
+    float d2, v, w, p[3];
+};
+
+// the one place the closest point of a triangle is formed (the header's steps, Ericson 5.1.5): region, (v, w), P, the clamp to the face's own box, d2
+__device__ __forceinline__ void cm_closest(const float q[3], const float a[3], const float b[3], const float c[3], CmHit &h)
+{
+    float ab[3], ac[3], ap[3], bp[3], cp[3], p[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        ab[k] = b[k] - a[k];
+        ac[k] = c[k] - a[k];
+        ap[k] = q[k] - a[k];
+        bp[k] = q[k] - b[k];
+        cp[k] = q[k] - c[k];
+    }
+    const float d1 = cm_dot(ab, ap), d2 = cm_dot(ac, ap), d3 = cm_dot(ab, bp), d4 = cm_dot(ac, bp), d5 = cm_dot(ab, cp), d6 = cm_dot(ac, cp);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    float v, w;
+    if (d1 <= 0.0f && d2 <= 0.0f) {                                                  // A
+        v = 0.0f; w = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = a[k];
+    } else if (d3 >= 0.0f && d4 <= d3) {                                             // B
+        v = 1.0f; w = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = b[k];
+    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {                             // edge AB
+        v = d1 / (d1 - d3); w = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = a[k] + v * ab[k];
+    } else if (d6 >= 0.0f && d5 <= d6) {                                             // C
+        v = 0.0f; w = 1.0f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = c[k];
+    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {                             // edge AC
+        v = 0.0f; w = d2 / (d2 - d6);
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = a[k] + w * ac[k];
+    } else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {               // edge BC
+        w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); v = 1.0f - w;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = b[k] + w * (c[k] - b[k]);
+    } else {                                                                         // interior
+        const float denom = 1.0f / ((va + vb) + vc);
+        v = vb * denom; w = vc * denom;
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = (a[k] + ab[k] * v) + ac[k] * w;
+    }
+    cm_clamp_to_face(p, a, b, c, h.p);          // P stays inside the face's coordinate box (the stop rule's proof needs it); the comparisons keep a NaN a NaN
+    h.v = v;
+    h.w = w;
+    h.d2 = nn_d2(q[0], q[1], q[2], make_float4(h.p[0], h.p[1], h.p[2], 0.0f));
 }
 
 // the argument checks the entries over a face grid share: shapes, pointers of the mesh, the box

@@ -21,7 +21,7 @@
 //   k_cm_query: one lane per query, the large list, then k_nn_query's ring walk over references, the same stop; k_cm_far brute-forces all faces for the listed
 //   queries.  cm_take / cm_closest are the one copy of the candidate: Ericson's regions in a fixed order, P clamped to the face's coordinate box (the stop's proof
 //   needs it), d2 through nn_d2.  tests/closest_ref.py restates it.  What a reader of the grid buffer needs (the grid, the buffer's layout and head, cm_face, the
-//   clamp) lives in face_grid.h, which raycast.hip shares.
+//   clamp) lives in face_grid.h, which raycast.hip shares; so do cm_closest, CmHit and nn_d2, which voxel.hip scatters over a lattice.
 // Every loop is bounded by a clamped range or a count; no kernel waits on another workgroup.
 #include "reduce.h"
 #include "scan.h"
@@ -235,13 +235,6 @@ __device__ __forceinline__ int64_t nn_cell_of(const NnGrid &g, float x, float y,
 {
     const int cx = nn_cell(x, g.bmin[0], g.inv_h[0], g.n[0]), cy = nn_cell(y, g.bmin[1], g.inv_h[1], g.n[1]), cz = nn_cell(z, g.bmin[2], g.inv_h[2], g.n[2]);
     return ((int64_t)cz * g.n[1] + cy) * g.n[0] + cx;
-}
-
-// the one place d2 is formed
-__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, const float4 &t)
-{
-    const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
-    return (dx * dx + dy * dy) + dz * dz;
 }
 
 __device__ __forceinline__ void nn_take(float qx, float qy, float qz, const float4 &t, float md2, unsigned long long &best)
@@ -465,61 +458,6 @@ __device__ __forceinline__ int64_t fg_box(const NnGrid &g, const float a[3], con
         n *= hi[k] - lo[k] + 1;
     }
     return n;
-}
-
-struct CmHit {
-    float d2, v, w, p[3];
-};
-
-// the one place the closest point of a triangle is formed (the header's steps, Ericson 5.1.5): region, (v, w), P, the clamp to the face's own box, d2
-__device__ __forceinline__ void cm_closest(const float q[3], const float a[3], const float b[3], const float c[3], CmHit &h)
-{
-    float ab[3], ac[3], ap[3], bp[3], cp[3], p[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        ab[k] = b[k] - a[k];
-        ac[k] = c[k] - a[k];
-        ap[k] = q[k] - a[k];
-        bp[k] = q[k] - b[k];
-        cp[k] = q[k] - c[k];
-    }
-    const float d1 = cm_dot(ab, ap), d2 = cm_dot(ac, ap), d3 = cm_dot(ab, bp), d4 = cm_dot(ac, bp), d5 = cm_dot(ab, cp), d6 = cm_dot(ac, cp);
-    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    float v, w;
-    if (d1 <= 0.0f && d2 <= 0.0f) {                                                  // A
-        v = 0.0f; w = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = a[k];
-    } else if (d3 >= 0.0f && d4 <= d3) {                                             // B
-        v = 1.0f; w = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = b[k];
-    } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {                             // edge AB
-        v = d1 / (d1 - d3); w = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = a[k] + v * ab[k];
-    } else if (d6 >= 0.0f && d5 <= d6) {                                             // C
-        v = 0.0f; w = 1.0f;
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = c[k];
-    } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {                             // edge AC
-        v = 0.0f; w = d2 / (d2 - d6);
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = a[k] + w * ac[k];
-    } else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {               // edge BC
-        w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); v = 1.0f - w;
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = b[k] + w * (c[k] - b[k]);
-    } else {                                                                         // interior
-        const float denom = 1.0f / ((va + vb) + vc);
-        v = vb * denom; w = vc * denom;
-#pragma unroll
-        for (int k = 0; k < 3; k++) p[k] = (a[k] + ab[k] * v) + ac[k] * w;
-    }
-    cm_clamp_to_face(p, a, b, c, h.p);          // P stays inside the face's coordinate box (the stop rule's proof needs it); the comparisons keep a NaN a NaN
-    h.v = v;
-    h.w = w;
-    h.d2 = nn_d2(q[0], q[1], q[2], make_float4(h.p[0], h.p[1], h.p[2], 0.0f));
 }
 
 // face f as a candidate of query q: rings, large list and fallback all come through here

@@ -126,14 +126,16 @@ def _safe_normalize(v, eps=1e-8):
 
 
 def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, precision=L.NRF_PREC_F32, normals="lattice", keep_largest=None,
-                min_component_faces=0, simplify_cell=None, smooth_iterations=0):
+                min_component_faces=0, simplify_cell=None, smooth_iterations=0, union_resolution=None):
     """DensityGrid -> Isosurface -> per-vertex colour: sigmoid of RunNetwork's rgb at the vertex seen along -normal (a ray hitting the surface head-on), in chunks.
     normals="lattice": the isosurface's central-difference normals; "field": -safe_normalize(DensityGradient(vertices)), the field's own analytic normal
     (also the colour's view direction).  keep_largest / min_component_faces: FilterComponents on the bare isosurface, before the field normals and the colours,
     so a dropped floater costs no network evaluation.  simplify_cell: SimplifyMesh(cell_size=simplify_cell) after that filter and before the field normals and the
     colours, for the same reason; the lattice normals of the result are those of each cluster's representative.  smooth_iterations > 0: SmoothMesh(iterations=
     smooth_iterations) with its defaults after both and before the colours; the normals are then VertexNormals of the smoothed faces whatever `normals` says (neither
-    the lattice's nor the field's belong to the moved geometry).  0 (the default) issues no call."""
+    the lattice's nor the field's belong to the moved geometry).  0 (the default) issues no call.  union_resolution: voxel.RemeshUnion(resolution=union_resolution)
+    after the component filter and before the simplification, the normals and the colours: the interior shells of the isosurface vanish into the solid around them
+    without any camera, and the normals are those of the remesh's lattice.  None (the default) issues no call."""
     if normals not in ("lattice", "field"):
         raise L.NrfError(f"ExtractMesh: normals must be 'lattice' or 'field', got {normals!r}")
     smooth_iterations = int(smooth_iterations)
@@ -146,6 +148,10 @@ def ExtractMesh(renderer, threshold, resolution=256, bbox=None, colors=True, pre
     if keep_largest is not None or min_component_faces > 0:
         kept = FilterComponents(Mesh(verts, faces, lattice_normals), keep_largest, min_component_faces)
         verts, faces, lattice_normals = kept.Vertices, kept.Faces, kept.Normals
+    if union_resolution is not None:
+        from .voxel import RemeshUnion
+        union = RemeshUnion(Mesh(verts, faces, lattice_normals), resolution=union_resolution)
+        verts, faces, lattice_normals = union.Vertices, union.Faces, union.Normals
     if simplify_cell is not None:
         small = SimplifyMesh(Mesh(verts, faces, lattice_normals), cell_size=simplify_cell)
         verts, faces, lattice_normals = small.Vertices, small.Faces, small.Normals

@@ -3,10 +3,11 @@
 // (FgGrid, FgKey, fg_key_matches), the classes of a face (cm_face), the dot product in the header's order and the clamp of a surface point to its face's own
 // coordinate box.  One copy of each: a query of either kind reads exactly the buffer the build wrote, and both proofs of completeness lean on the same clamp.
 // Also the closest point of a triangle itself (nn_d2, CmHit, cm_closest): nrf_closest_on_mesh gathers it per query, voxel.hip (nrf_mesh_voxelize) scatters it per
-// face over the lattice, and the two agree bit for bit because it is one function.
+// face over the lattice, and the two agree bit for bit because it is one function.  And the list of the queries a walk gives up (FarList, far_layout).
 #pragma once
 
 #include "common.h"
+#include "reduce.h"
 #include "workspace.h"
 
 #include <climits>
@@ -17,7 +18,14 @@ namespace nrf {
 
 constexpr int GEO_BLOCK = 256;
 constexpr int FAR_GRID = 1024;           // workgroups of the brute-force kernels: 4 per CU
-constexpr unsigned long long NN_NONE = ((unsigned long long)0x7f800000u << 32) | 0xffffffffu;          // d2 = +inf, index = -1: above every key with a valid index
+
+// the queries (rays) a walk gives up, for the brute-force kernel of its tool: scan.h's wave_append fills it
+struct FarList {
+    int32_t *list;           // [n] in any order
+    uint32_t *n;             // [words] n[0] the length; the ray caster keeps its flag in a second word of the same 256-byte piece, so one memset clears both
+};
+
+inline FarList far_layout(Bump &b, int64_t n, int words = 1) { return FarList{b.take<int32_t>((size_t)n), b.take<uint32_t>((size_t)words)}; }
 
 struct NnGrid {
     int n[3];

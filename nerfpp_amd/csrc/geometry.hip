@@ -10,10 +10,9 @@
 // Nearest points.  A uniform grid over the caller's box: k_nn_bin<0> (one non-returning atomic add per finite target), the scan of the cell counts (scan.h's k_block_sums
 //   and k_totals_scan, then k_nn_cell_starts), k_nn_bin<1> (16-byte records {x, y, z, index} in cell order; the order INSIDE a cell is whatever the atomics gave).  k_nn_query:
 //   one lane per query scans rings of cells outward, every ring as contiguous runs of records (the x-neighbours of a row are one range of the start array), keeps the
-//   minimum of ((uint64)float_bits(d2) << 32) | index and stops by the rule the header proves.  A query still open after NRF_NN_MAX_RINGS rings is appended to a list
-//   (ballot, popcount, one returning atomic per wave); k_nn_far, a fixed grid of workgroups, brute-forces all records for each listed query with a block-wide minimum.
-//   Both form d2 in nn_d2: one copy of the arithmetic.  The minimum of a set does not depend on the order it arrives in, so the result depends on neither the grid,
-//   the scheduling nor the order of the targets (beyond the tie-break by index the key states).
+//   minimum of reduce.h's packed key (d2, index) and stops by the rule the header proves.  A query still open after NRF_NN_MAX_RINGS
+//   rings is appended to a list (scan.h's wave_append); k_nn_far, a fixed grid of workgroups, brute-forces all records for each listed query with a block-wide minimum.
+//   Both form d2 in nn_d2: one copy of the arithmetic.  The result depends on neither the grid, the scheduling nor the order of the targets (beyond the key's tie-break).
 // Statistics.  k_dist_stats: 4096 entries per block, lane t takes t, t + 256, ... in ascending order; reduce.h's ordered block sum (block maximum) per column, one row of
 //   eight fp64 partials per block; k_geo_finish is reduce.h's ordered finish pass per column.  No atomics.
 // Closest point on a mesh.  The same grid holds FACES: k_fg_bin<0> counts one reference per cell of a face's cell box (a box of more than NRF_FG_MAX_FACE_CELLS cells:
@@ -36,7 +35,7 @@ namespace nrf {
 
 namespace {
 
-// GEO_BLOCK, FAR_GRID, NN_NONE, the grid and everything a reader of the face-grid buffer needs: face_grid.h (shared with raycast.hip)
+// GEO_BLOCK, FAR_GRID, the grid and everything a reader of the face-grid buffer needs: face_grid.h (shared with raycast.hip)
 constexpr int STATS_TILE = 4096;         // entries per block of k_dist_stats
 constexpr int STATS_VALUES = 8;          // count, sum d, sum d2, max d, four tau counts
 
@@ -214,8 +213,7 @@ struct NnWs {
     int64_t *bsum;           // [cell blocks]
     int64_t *total;          // [1]
     float4 *rec;             // [nt] {x, y, z, index bits} in cell order
-    int32_t *far;            // [nq] the queries of the brute-force kernel
-    uint32_t *n_far;         // [1]
+    FarList far;             // [nq] the queries of the brute-force kernel
 };
 
 NnWs nn_layout(Bump &b, int64_t nq, int64_t nt, int64_t cells)
@@ -226,8 +224,7 @@ NnWs nn_layout(Bump &b, int64_t nq, int64_t nt, int64_t cells)
     s.bsum = b.take<int64_t>((size_t)ceil_div(cells, GEO_BLOCK));
     s.total = b.take<int64_t>(1);
     s.rec = b.take<float4>((size_t)nt);
-    s.far = b.take<int32_t>((size_t)nq);
-    s.n_far = b.take<uint32_t>(1);
+    s.far = far_layout(b, nq);
     return s;
 }
 
@@ -240,7 +237,7 @@ __device__ __forceinline__ int64_t nn_cell_of(const NnGrid &g, float x, float y,
 __device__ __forceinline__ void nn_take(float qx, float qy, float qz, const float4 &t, float md2, unsigned long long &best)
 {
     const float d2 = nn_d2(qx, qy, qz, t);
-    const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | __float_as_uint(t.w);
+    const unsigned long long k = key_pack(d2, __float_as_uint(t.w));
     if (d2 <= md2 && k < best) best = k;
 }
 
@@ -292,7 +289,6 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_nn_query(const float *__restrict_
 {
     __shared__ int sh[GEO_BLOCK / 64];
     const int64_t q = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const bool live = q < nq;
     float qx = 0.0f, qy = 0.0f, qz = 0.0f;
     if (live) { qx = query[q * 3 + 0]; qy = query[q * 3 + 1]; qz = query[q * 3 + 2]; }
@@ -330,20 +326,13 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_nn_query(const float *__restrict_
             const float B = ((float)r * g.h_min) * 0.999f;
             const float B2 = B * B;
             // every unscanned target has d2 >= B2 (header): a strictly smaller best cannot be beaten or tied, and beyond max_dist nothing counts
-            if (fminf(__uint_as_float((uint32_t)(best >> 32)), md2) < B2) { open = false; break; }
+            if (fminf(key_value(best), md2) < B2) { open = false; break; }
         }
     }
-    // every lane of the wave arrives here, so the ballot sees the whole wave
-    const unsigned long long wm = __ballot(open);
-    if (wm) {
-        uint32_t at = 0;
-        if (lane == 0) at = atomicAdd(n_far, (uint32_t)__popcll(wm));
-        at = __shfl(at, 0, 64);
-        if (open) far[at + __popcll(wm & ((1ull << lane) - 1))] = (int32_t)q;          // at + rank < nq: every query is appended at most once
-    }
+    wave_append(open, (int32_t)q, far, n_far);          // the walk has rejoined: every lane of the wave arrives here.  Every query is appended at most once
     if (live && !open) {
-        dist2[q] = __uint_as_float((uint32_t)(best >> 32));
-        index[q] = (int32_t)(uint32_t)best;
+        dist2[q] = key_value(best);
+        index[q] = key_index(best);
     }
     if (!stats) return;          // uniform
     const int total = block_count<GEO_BLOCK>(live && !finite, sh);
@@ -364,8 +353,8 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_nn_far(const float *__restrict__ 
         for (uint32_t t = threadIdx.x; t < n_rec; t += GEO_BLOCK) nn_take(qx, qy, qz, rec[t], md2, best);
         best = block_key_min<GEO_BLOCK>(best, s_best);
         if (threadIdx.x == 0) {
-            dist2[q] = __uint_as_float((uint32_t)(best >> 32));
-            index[q] = (int32_t)(uint32_t)best;
+            dist2[q] = key_value(best);
+            index[q] = key_index(best);
         }
         __syncthreads();          // the next query goes through the same words
     }
@@ -424,8 +413,7 @@ struct FgWs {                // count and build
 };
 
 struct CmWs {
-    int32_t *far;            // [nq] the queries of the brute-force kernel
-    uint32_t *n_far;         // [1]
+    FarList far;             // [nq] the queries of the brute-force kernel
 };
 
 FgWs fg_ws_layout(Bump &b, int64_t cells)
@@ -442,8 +430,7 @@ FgWs fg_ws_layout(Bump &b, int64_t cells)
 CmWs cm_layout(Bump &b, int64_t nq)
 {
     CmWs s;
-    s.far = b.take<int32_t>((size_t)nq);
-    s.n_far = b.take<uint32_t>(1);
+    s.far = far_layout(b, nq);
     return s;
 }
 
@@ -468,7 +455,7 @@ __device__ __forceinline__ void cm_take(const float q[3], const float *__restric
     if (cm_face(verts, n_verts, faces, n_faces, f, a, b, c) != 0) return;
     CmHit h;
     cm_closest(q, a, b, c, h);
-    const unsigned long long k = ((unsigned long long)__float_as_uint(h.d2) << 32) | (uint32_t)f;
+    const unsigned long long k = key_pack(h.d2, (uint32_t)f);
     if (h.d2 <= md2 && k < best) best = k;          // a NaN d2 fails the comparison
 }
 
@@ -477,8 +464,8 @@ __device__ __forceinline__ void cm_write(const float q[3], int64_t qi, unsigned 
                                          const int32_t *__restrict__ faces, int64_t n_faces, float *__restrict__ dist2, int32_t *__restrict__ face, float *__restrict__ uv,
                                          float *__restrict__ point)
 {
-    const int32_t f = (int32_t)(uint32_t)best;
-    dist2[qi] = __uint_as_float((uint32_t)(best >> 32));
+    const int32_t f = key_index(best);
+    dist2[qi] = key_value(best);
     face[qi] = f;
     if (!uv && !point) return;
     CmHit h;
@@ -560,7 +547,6 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_cm_query(const float *__restrict_
     __shared__ int sh[GEO_BLOCK / 64];
     if (!fg_key_matches(grid_key, key)) return;          // uniform: not the buffer nrf_face_grid_build made for these arguments; nothing of it is read, nothing written
     const int64_t qi = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const bool live = qi < nq;
     const uint32_t n_refs = (uint32_t)key.w[3], n_large = (uint32_t)key.w[4];
     float q[3] = {0.0f, 0.0f, 0.0f};
@@ -597,17 +583,11 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_cm_query(const float *__restrict_
                 const float B = ((float)r * g.h_min) * 0.999f;
                 const float B2 = B * B;
                 // the closest point of every face without a reference in the cube lies in a cell at least r + 1 away on some axis (the clamp): d2 >= B2 (header)
-                if (fminf(__uint_as_float((uint32_t)(best >> 32)), md2) < B2) { open = false; break; }
+                if (fminf(key_value(best), md2) < B2) { open = false; break; }
             }
         }
     }
-    const unsigned long long wm = __ballot(open);          // every lane of the wave arrives here
-    if (wm) {
-        uint32_t at = 0;
-        if (lane == 0) at = atomicAdd(n_far, (uint32_t)__popcll(wm));
-        at = __shfl(at, 0, 64);
-        if (open) far[at + __popcll(wm & ((1ull << lane) - 1))] = (int32_t)qi;          // at + rank < nq: every query is appended at most once
-    }
+    wave_append(open, (int32_t)qi, far, n_far);          // the walk has rejoined: every lane of the wave arrives here.  Every query is appended at most once
     if (live && !open) cm_write(q, qi, best, verts, n_verts, faces, n_faces, dist2, face, uv, point);
     if (!stats) return;          // uniform
     const int total = block_count<GEO_BLOCK>(live && !finite, sh);
@@ -735,7 +715,7 @@ int nrf_nearest_points(const float *d_query, int64_t nq, const float *d_target, 
     const float md2 = max_dist * max_dist;
     const int64_t cb = ceil_div(g.cells, GEO_BLOCK);
     NRF_HIP(hipMemsetAsync(ws.start, 0, ((size_t)g.cells + 1) * sizeof(uint32_t), st));
-    NRF_HIP(hipMemsetAsync(ws.n_far, 0, sizeof(uint32_t), st));
+    NRF_HIP(hipMemsetAsync(ws.far.n, 0, sizeof(uint32_t), st));
     if (nt > 0) {
         const unsigned tb = (unsigned)ceil_div(nt, GEO_BLOCK);
         hipLaunchKernelGGL(k_nn_bin<0>, dim3(tb), dim3(GEO_BLOCK), 0, st, d_target, nt, g, ws.start, ws.rec, d_stats);
@@ -750,10 +730,10 @@ int nrf_nearest_points(const float *d_query, int64_t nq, const float *d_target, 
         NRF_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_nn_query, dim3((unsigned)ceil_div(nq, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_query, nq, g, md2, (const uint32_t *)ws.start, (const float4 *)ws.rec,
-                       d_dist2, d_index, ws.far, ws.n_far, d_stats);
+                       d_dist2, d_index, ws.far.list, ws.far.n, d_stats);
     NRF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_nn_far, dim3(FAR_GRID), dim3(GEO_BLOCK), 0, st, d_query, md2, (const uint32_t *)ws.start, g.cells, (const float4 *)ws.rec, d_dist2, d_index,
-                       (const int32_t *)ws.far, (const uint32_t *)ws.n_far, d_stats);
+                       (const int32_t *)ws.far.list, (const uint32_t *)ws.far.n, d_stats);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
@@ -896,13 +876,13 @@ int nrf_closest_on_mesh(const float *d_query, int64_t nq, const float *d_verts, 
     hipStream_t st = as_stream(stream);
     const float md2 = max_dist * max_dist;
     const FgKey key = fg_key(n_faces, nx, ny, nz, n_refs, n_large, bbox);
-    NRF_HIP(hipMemsetAsync(ws.n_far, 0, sizeof(uint32_t), st));
+    NRF_HIP(hipMemsetAsync(ws.far.n, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_cm_query, dim3((unsigned)ceil_div(nq, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_query, nq, d_verts, (int32_t)n_verts, d_faces, n_faces, g, key, md2,
-                       (const long long *)grid.key, (const uint32_t *)grid.start, (const int32_t *)grid.refs, (const int32_t *)grid.large, d_dist2, d_face, d_uv, d_point, ws.far,
-                       ws.n_far, d_stats);
+                       (const long long *)grid.key, (const uint32_t *)grid.start, (const int32_t *)grid.refs, (const int32_t *)grid.large, d_dist2, d_face, d_uv, d_point, ws.far.list,
+                       ws.far.n, d_stats);
     NRF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_cm_far, dim3(FAR_GRID), dim3(GEO_BLOCK), 0, st, d_query, d_verts, (const int32_t)n_verts, d_faces, n_faces, key, md2, (const long long *)grid.key,
-                       d_dist2, d_face, d_uv, d_point, (const int32_t *)ws.far, (const uint32_t *)ws.n_far, d_stats);
+                       d_dist2, d_face, d_uv, d_point, (const int32_t *)ws.far.list, (const uint32_t *)ws.far.n, d_stats);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

@@ -6,21 +6,21 @@
 //   k_raster_project   one lane per vertex: steps 1-3 of the header into a 16-byte record {X, Y, zd, ok} in the workspace, so a face gathers 16 B per corner and the
 //                      divisions of a vertex are paid once, not once per face that uses it
 //   k_raster_faces     one lane per face: classify (bad index / clipped / degenerate or culled / drawn), the clamped bounding box, then either scan it (at most
-//                      NRF_RASTER_WIDE_PIXELS pixels) or append the face to the wide list (one atomic add per wave: ballot, popcount, lane rank).  A fixed grid strides
+//                      NRF_RASTER_WIDE_PIXELS pixels) or append the face to the wide list (scan.h's wave_append).  A fixed grid strides
 //                      the face list and every lane counts its faces by class in registers: four atomic adds on d_stats per WORKGROUP.  With one add per wave and class
 //                      -- 7 M waves at 447 M faces, all on one 16-byte line -- those adds were the whole kernel: 87.6 ms a view, and 159 ms with culling, which puts
 //                      two classes into every wave (tools/raster_bench.py)
 //   k_raster_wide      a fixed grid of workgroups strides the wide list (its length is read on the device: the host never sees it); the 256 lanes of a workgroup
 //                      stride the pixels of one face's box, so no lane's time grows with a face's area
 //   k_raster_resolve   one lane per pixel: depth and face from the key; barycentrics and attributes recomputed from the winner by the same device functions
-// The z-buffer holds ((uint64)float_bits(depth) << 32) | face per pixel, lowered by agent-scope atomic min (coherent across the XCDs; executed at the memory side).
-// depth > 0, so its bit pattern orders as the value does; the minimum over a set does not depend on the order the set arrives in, so the result depends neither on
-// scheduling nor on the order of the face list (beyond the tie-break by index the key states).  A plain load of the current key filters the atomics: a stale value
-// can only be larger than the current one, so a skipped atomic would not have lowered the key.  The kernel boundary makes the keys visible to the resolve pass.
-// Coverage is decided in int64 (exact); every edge value is e(0, 0) + i * step_x + j * step_y, which in integers is the header's E_ab(p) whatever the visiting order.
+// The z-buffer holds reduce.h's packed key (depth, face) per pixel, lowered by key_lower; depth > 0, so its bit pattern orders as the value does, and the result depends
+// neither on scheduling nor on the order of the face list (beyond the tie-break by index the key states).  The kernel boundary makes the keys visible to the resolve pass.
+// Coverage is decided in int64 (exact; edge_fn.h's edge_cover, the voxeliser's too); every edge value is e(0, 0) + i * step_x + j * step_y, which in integers is the header's E_ab(p) whatever the visiting order.
 // Both face kernels and the resolve pass call tri_setup / tri_pixel for steps 4-7: one copy of the arithmetic, so the bits cannot differ between them.
 // Every loop is bounded by a clamped bounding box or by a count; no kernel waits on another workgroup.
-#include "common.h"
+#include "edge_fn.h"
+#include "reduce.h"
+#include "scan.h"
 #include "workspace.h"
 
 #include <climits>
@@ -33,7 +33,6 @@ namespace {
 constexpr int RS_BLOCK = 256;
 constexpr int FACE_GRID = 1536;          // workgroups of k_raster_faces, striding the face list: 6 per CU, what its 80 registers admit
 constexpr int WIDE_GRID = 1024;          // workgroups of k_raster_wide: 4 per CU
-constexpr unsigned long long NO_KEY = ~0ull;
 
 struct RCam {
     float fx, fy, cx, cy;
@@ -100,27 +99,17 @@ __device__ __forceinline__ int64_t tri_setup(const int4 &a, const int4 &b, const
 // step 5's pixels: columns i0 .. i1 and rows j0 .. j1 (empty where i1 < i0 or j1 < j0).  >> of a negative int is arithmetic: floor
 __device__ __forceinline__ void tri_box(const Tri &t, int h, int w, int &i0, int &i1, int &j0, int &j1)
 {
-    i0 = max((t.xmin + (NRF_RASTER_SUBPIXEL - 1)) >> 8, 0); i1 = min(t.xmax >> 8, w - 1);
-    j0 = max((t.ymin + (NRF_RASTER_SUBPIXEL - 1)) >> 8, 0); j1 = min(t.ymax >> 8, h - 1);
+    edge_box(t.xmin, t.xmax, t.ymin, t.ymax, w, h, i0, i1, j0, j1);
 }
 
 // steps 5-6 at pixel (column i, row j): inside?  and, where inside, b_k, p_k = b_k / zd_k, S and depth
 __device__ __forceinline__ bool tri_pixel(const Tri &t, int i, int j, float b[3], float p[3], float &S, float &depth)
 {
     int64_t se[3];
-    bool in = true;
+    if (!edge_cover(t.e00, t.sx, t.sy, t.tl, i, j, se)) return false;
+    edge_bary(se, t.sA, b);
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        se[k] = t.e00[k] + (int64_t)i * t.sx[k] + (int64_t)j * t.sy[k];
-        in = in && (se[k] > 0 || (se[k] == 0 && t.tl[k]));
-    }
-    if (!in) return false;
-    const double den = (double)t.sA;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        b[k] = (float)((double)se[k] / den);
-        p[k] = b[k] * t.r[k];
-    }
+    for (int k = 0; k < 3; k++) p[k] = b[k] * t.r[k];
     S = (p[0] + p[1]) + p[2];
     depth = 1.0f / S;
     return true;
@@ -131,9 +120,7 @@ __device__ __forceinline__ void tri_draw(const Tri &t, int i, int j, int w, uint
 {
     float b[3], p[3], S, depth;
     if (!tri_pixel(t, i, j, b, p, S, depth)) return;
-    const unsigned long long k = ((unsigned long long)__float_as_uint(depth) << 32) | face;
-    unsigned long long *at = key + (int64_t)j * w + i;
-    if (k < *at) __hip_atomic_fetch_min(at, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    key_lower(key + (int64_t)j * w + i, key_pack(depth, face));
 }
 
 __global__ void __launch_bounds__(RS_BLOCK) k_raster_project(const float *__restrict__ verts, int64_t n, const RCam c, int4 *__restrict__ rec)
@@ -174,9 +161,8 @@ __global__ void __launch_bounds__(RS_BLOCK) k_raster_faces(const int32_t *__rest
     __shared__ uint32_t s_count[4];
     if (threadIdx.x < 4) s_count[threadIdx.x] = 0;
     __syncthreads();
-    const int lane = threadIdx.x & 63;
     uint32_t count[4] = {0, 0, 0, 0};          // this lane's faces by class
-    // the bound is the workgroup's: every lane of a wave makes every round (a lane past the last face has no class), so the ballot sees the whole wave
+    // the bound is the workgroup's: every lane of a wave makes every round (a lane past the last face has no class), so wave_append's ballot sees the whole wave
     for (int64_t base = (int64_t)blockIdx.x * RS_BLOCK; base < n_faces; base += (int64_t)gridDim.x * RS_BLOCK) {
         const int64_t f = base + threadIdx.x;
         Tri t;
@@ -187,13 +173,7 @@ __global__ void __launch_bounds__(RS_BLOCK) k_raster_faces(const int32_t *__rest
         if (cls == 0) tri_box(t, h, w, i0, i1, j0, j1);
         const bool any = i1 >= i0 && j1 >= j0;
         const bool is_wide = any && (int64_t)(i1 - i0 + 1) * (j1 - j0 + 1) > NRF_RASTER_WIDE_PIXELS;
-        const unsigned long long wm = __ballot(is_wide);
-        if (wm) {
-            uint32_t at = 0;
-            if (lane == 0) at = atomicAdd(n_wide, (uint32_t)__popcll(wm));
-            at = __shfl(at, 0, 64);
-            if (is_wide) wide[at + __popcll(wm & ((1ull << lane) - 1))] = (int32_t)f;          // at + rank < n_faces: every face is appended at most once
-        }
+        wave_append(is_wide, (int32_t)f, wide, n_wide);          // every face is appended at most once
         if (!any || is_wide) continue;
         for (int j = j0; j <= j1; j++)
             for (int i = i0; i <= i1; i++) tri_draw(t, i, j, w, (uint32_t)f, key);
@@ -232,8 +212,8 @@ __global__ void __launch_bounds__(RS_BLOCK) k_raster_resolve(const int32_t *__re
     if (pix >= (int64_t)h * w) return;
     const unsigned long long k = key[pix];
     const bool hit = k != NO_KEY;
-    const int32_t f = hit ? (int32_t)(uint32_t)k : -1;
-    depth[pix] = hit ? __uint_as_float((uint32_t)(k >> 32)) : 0.0f;
+    const int32_t f = hit ? key_index(k) : -1;
+    depth[pix] = hit ? key_value(k) : 0.0f;
     if (face) face[pix] = f;
     if (!bary && n_attr == 0) return;
     float b[3] = {0.0f, 0.0f, 0.0f}, p[3] = {0.0f, 0.0f, 0.0f}, S = 1.0f, d;

@@ -9,8 +9,8 @@
 //   complete when all faces lie inside; with the flag set every valid ray goes to the fallback.
 // Walk.  rc_walk, one lane per ray: the far-origin test, the slab clip against the widened box, the large list, then uniform steps in t; every step looks up the
 //   cells between its two end points widened by 2 tau_k, skipping those the previous step looked up, and stops by the header's rule.  It returns open where it
-//   gives the ray up (far origin, a step that does not advance, NRF_RC_MAX_STEPS); k_rc_query appends such rays to a list (ballot, popcount, one returning atomic
-//   per wave) and k_rc_far, a fixed grid of workgroups, brute-forces all faces for each listed ray with reduce.h's block-wide key minimum.
+//   gives the ray up (far origin, a step that does not advance, NRF_RC_MAX_STEPS); k_rc_query appends such rays to a list (scan.h's wave_append) and k_rc_far,
+//   a fixed grid of workgroups, brute-forces all faces for each listed ray with reduce.h's block-wide minimum of the packed key (t, face).
 // Directions.  rc_hemisphere_dir: Marsaglia's disc rejection, no trigonometry; every draw a pure function of (seed, index, j, attempt).
 // Ambient occlusion.  k_rc_ao: one lane per ray of the flattened [n, k] rays, the same rc_hemisphere_dir and rc_walk in any mode, a point's hits in a wave by
 //   ballot and popcount into its integer counter; a ray the walk gives up is brute-forced by its whole wave on the spot, lanes over faces.  k_rc_ao_finish: d_ao.
@@ -33,17 +33,15 @@ static_assert(NRF_RC_TAU_LOG2 == -12, "RC_TAU is written out for -12");
 constexpr float RC_SLACK = 1.0f / 1024.0f;         // the widening of the clip box and of the slab parameters
 
 struct RcWs {
-    int32_t *far;            // [n] the rays of the brute-force kernel
-    uint32_t *n_far;         // [1]
+    FarList far;             // [n] the rays of the brute-force kernel
     uint32_t *outside;       // [1] != 0: some valid face has a coordinate outside the grid's box
 };
 
 RcWs rc_layout(Bump &b, int64_t n)
 {
     RcWs s;
-    s.far = b.take<int32_t>((size_t)n);
-    s.n_far = b.take<uint32_t>(2);          // one array: a single memset clears both
-    s.outside = s.n_far + 1;
+    s.far = far_layout(b, n, 2);          // two words: a single memset clears the length and the flag
+    s.outside = s.far.n + 1;
     return s;
 }
 
@@ -128,11 +126,9 @@ __device__ __forceinline__ void rc_take(const RcRay &r, const float *__restrict_
     if (cm_face(verts, n_verts, faces, n_faces, f, a, b, c) != 0) return;
     RcHit h;
     if (!rc_candidate(r, a, b, c, cull, h)) return;
-    const unsigned long long k = ((unsigned long long)__float_as_uint(h.t) << 32) | (uint32_t)f;
+    const unsigned long long k = key_pack(h.t, (uint32_t)f);
     if (k < best) best = k;
 }
-
-__device__ __forceinline__ float rc_key_t(unsigned long long key) { return __uint_as_float((uint32_t)(key >> 32)); }
 
 struct RcMesh {
     const float *verts;
@@ -222,7 +218,7 @@ __device__ __forceinline__ bool rc_walk(const RcRay &r, const RcMesh &m, const N
 #pragma unroll
             for (int a = 0; a < 3; a++) { plo[a] = lo[a]; phi[a] = hi[a]; }
         }
-        if (ANY ? best != NN_NONE : rc_key_t(best) <= tn) return false;          // every accepted candidate with t <= tn has been seen
+        if (ANY ? best != NN_NONE : key_value(best) <= tn) return false;          // every accepted candidate with t <= tn has been seen
         if (tn >= t1) return false;                                              // the clipped range is exhausted
         tk = tn;
 #pragma unroll
@@ -236,8 +232,8 @@ __device__ __forceinline__ void rc_write(const RcRay &r, int64_t i, unsigned lon
                                          const int32_t *__restrict__ faces, int64_t n_faces, int cull, float *__restrict__ out_t, int32_t *__restrict__ face,
                                          float *__restrict__ uv, float *__restrict__ point, uint8_t *__restrict__ hit)
 {
-    const int32_t f = (int32_t)(uint32_t)best;
-    if (out_t) out_t[i] = rc_key_t(best);
+    const int32_t f = key_index(best);
+    if (out_t) out_t[i] = key_value(best);
     if (face) face[i] = f;
     if (hit) hit[i] = f >= 0 ? 1 : 0;
     if (!uv && !point) return;
@@ -285,7 +281,6 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_rc_query(const float *__restrict_
     __shared__ int sh[GEO_BLOCK / 64];
     if (!fg_key_matches(grid_key, key)) return;          // uniform: not the buffer nrf_face_grid_build made for these arguments; nothing of it is read, nothing written
     const int64_t i = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const bool live = i < n;
     RcRay r;
     bool valid = false;
@@ -293,13 +288,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_rc_query(const float *__restrict_
     unsigned long long best = NN_NONE;
     bool open = false;
     if (valid) open = *outside != 0u ? r.lo <= r.hi : rc_walk<ANY>(r, m, g, box, cull, best);
-    const unsigned long long wm = __ballot(open);          // every lane of the wave arrives here
-    if (wm) {
-        uint32_t at = 0;
-        if (lane == 0) at = atomicAdd(n_far, (uint32_t)__popcll(wm));
-        at = __shfl(at, 0, 64);
-        if (open) far[at + __popcll(wm & ((1ull << lane) - 1))] = (int32_t)i;          // at + rank < n: every ray is appended at most once
-    }
+    wave_append(open, (int32_t)i, far, n_far);          // the walk has rejoined: every lane of the wave arrives here.  Every ray is appended at most once
     if (live && !open) rc_write(r, i, best, m.verts, m.n_verts, m.faces, m.n_faces, cull, out_t, face, uv, point, hit);
     if (!stats) return;          // uniform
     const int total = block_count<GEO_BLOCK>(live && !valid, sh);
@@ -513,7 +502,7 @@ size_t nrf_ray_cast_workspace_bytes(int64_t n_rays)
     hipStream_t st = as_stream(stream);                                                                                                                                   \
     const FgKey key = fg_key(n_faces, nx, ny, nz, n_refs, n_large, bbox);                                                                                                 \
     const RcMesh m = {d_verts, d_faces, grid.start, grid.refs, grid.large, (int32_t)n_verts, n_faces, (uint32_t)n_refs, (uint32_t)n_large};                               \
-    NRF_HIP(hipMemsetAsync(ws.n_far, 0, 2 * sizeof(uint32_t), st));          /* n_far and outside lie side by side */                                                    \
+    NRF_HIP(hipMemsetAsync(ws.far.n, 0, 2 * sizeof(uint32_t), st));          /* the length and outside lie side by side */                                               \
     if (n_faces > 0) {                                                                                                                                                    \
         hipLaunchKernelGGL(k_rc_premise, dim3((unsigned)ceil_div(n_faces, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, grid_box,     \
                            ws.outside);                                                                                                                                   \
@@ -539,13 +528,13 @@ int nrf_ray_cast_mesh(const float *d_rays, int64_t n_rays, int stride, const flo
     const dim3 blocks((unsigned)ceil_div(n_rays, GEO_BLOCK));
     if (mode == NRF_RC_ANY)
         hipLaunchKernelGGL(k_rc_query<true>, blocks, dim3(GEO_BLOCK), 0, st, d_rays, n_rays, stride, m, g, clip, key, cull, (const long long *)grid.key, d_t, d_face, d_uv,
-                           d_point, d_hit, ws.far, ws.n_far, (const uint32_t *)ws.outside, d_stats);
+                           d_point, d_hit, ws.far.list, ws.far.n, (const uint32_t *)ws.outside, d_stats);
     else
         hipLaunchKernelGGL(k_rc_query<false>, blocks, dim3(GEO_BLOCK), 0, st, d_rays, n_rays, stride, m, g, clip, key, cull, (const long long *)grid.key, d_t, d_face, d_uv,
-                           d_point, d_hit, ws.far, ws.n_far, (const uint32_t *)ws.outside, d_stats);
+                           d_point, d_hit, ws.far.list, ws.far.n, (const uint32_t *)ws.outside, d_stats);
     NRF_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_rc_far, dim3(FAR_GRID), dim3(GEO_BLOCK), 0, st, d_rays, stride, m, key, cull, (const long long *)grid.key, d_t, d_face, d_uv, d_point, d_hit,
-                       (const int32_t *)ws.far, (const uint32_t *)ws.n_far, d_stats);
+                       (const int32_t *)ws.far.list, (const uint32_t *)ws.far.n, d_stats);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }
@@ -580,7 +569,7 @@ int nrf_mesh_ambient_occlusion(const float *d_points, const float *d_normals, in
     NRF_RC_PREPARE("nrf_mesh_ambient_occlusion", n);
     if (n == 0) return NRF_OK;
     NRF_RC_LAUNCH_PREMISE();
-    uint32_t *hits = reinterpret_cast<uint32_t *>(ws.far);          // the list of the ray-cast entry serves as the points' hit counters here
+    uint32_t *hits = reinterpret_cast<uint32_t *>(ws.far.list);          // the list of the ray-cast entry serves as the points' hit counters here
     NRF_HIP(hipMemsetAsync(hits, 0, (size_t)n * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_rc_ao, dim3((unsigned)ceil_div(n * k, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_points, d_normals, n, k, offset, max_dist, seed, index0, m, g, clip,
                        key, (const long long *)grid.key, (const uint32_t *)ws.outside, hits, d_stats);

@@ -6,6 +6,7 @@
 //   4. then s[t] += s[t + o] for t < o, o = B / 2 .. 1                                             the same
 //   k_finish_loss_pair<B>      kernel: the two fp32 training losses of a [blocks][2] partial array, each divided by its own count
 //   block_key_min<B>           the block-wide minimum of a packed 64-bit key (order-free; here because it is the same wave tree + one LDS word per wave)
+//   key_pack / key_value / key_index / key_lower, NN_NONE, NO_KEY   that key itself: (float_bits(value) << 32) | index, and its lowering in memory
 // A kernel keeps its accumulation into one double per lane and what it does with the total; it writes none of the steps above itself.
 #pragma once
 
@@ -118,6 +119,19 @@ __global__ void __launch_bounds__(B) k_finish_loss_pair(int64_t blocks, const do
     ordered_finish<B, 2>(partials, blocks, 2, 0, a, sh);
     if (threadIdx.x == 0) { losses[0] = (float)(a[0] / count0); losses[1] = (float)(a[1] / count1); }
 }
+
+// ---- the packed 64-bit key of the mesh tools: (float_bits(value) << 32) | index.  value >= 0 (a squared distance, a depth, a ray parameter with -0 made +0), so its
+// bit pattern orders as the value does: the minimum is the smallest value, ties to the smallest index, whatever order the keys arrive in ----
+constexpr unsigned long long NN_NONE = ((unsigned long long)0x7f800000u << 32) | 0xffffffffu;          // value = +inf, index = -1: above every key with a valid index
+constexpr unsigned long long NO_KEY = ~0ull;                                                              // the rasteriser's empty pixel: what a 0xFF memset leaves
+
+__device__ __forceinline__ unsigned long long key_pack(float value, uint32_t index) { return ((unsigned long long)__float_as_uint(value) << 32) | index; }
+__device__ __forceinline__ float key_value(unsigned long long k) { return __uint_as_float((uint32_t)(k >> 32)); }
+__device__ __forceinline__ int32_t key_index(unsigned long long k) { return (int32_t)(uint32_t)k; }
+
+// *at = min(*at, k) by agent-scope atomic min (coherent across the XCDs; executed at the memory side).  A plain load of the current key filters the atomics: keys
+// only ever fall, so a stale load can only be larger than the current one and a skipped atomic would not have lowered the key
+__device__ __forceinline__ void key_lower(unsigned long long *at, unsigned long long k) { if (k < *at) __hip_atomic_fetch_min(at, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- the block-wide minimum of a packed 64-bit key, in THREAD 0 (the brute-force fallbacks' one writer): wave tree (two 32-bit shuffles per step), one word per wave.
 // sh: B / 64 words, still being read on return like ordered_block_sum's ----

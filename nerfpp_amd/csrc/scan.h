@@ -6,6 +6,7 @@
 //   block_exclusive_scan<T, B> exclusive prefix sum over the block and its total (also the render path's live_points.hip)
 //   k_block_sums<C, B>         kernel: bsum[block] = the sum of the block's B counts
 //   block_totals_scan / k_totals_scan<T, TOTAL>   one workgroup of SCAN_BLOCK threads, SCAN_ITEMS entries each per round: block totals -> block offsets, *total = the sum
+//   wave_append                a wave's flagged lanes onto an unordered list: one returning atomic per wave (the fallback and wide lists of the mesh tools)
 // The pass that turns block offsets into element positions does site-specific work besides and stays with its tool.
 #pragma once
 
@@ -48,6 +49,18 @@ __device__ __forceinline__ int block_rank(bool flag, int *sh, int &total)
     }
     __syncthreads();
     return before;
+}
+
+// list[...] = value for the lanes with `take`, in any order; one atomic add per wave.  EVERY lane of the wave must call it: the ballot is the whole wave's
+__device__ __forceinline__ void wave_append(bool take, int32_t value, int32_t *__restrict__ list, uint32_t *__restrict__ count)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long m = __ballot(take);
+    if (!m) return;          // uniform
+    uint32_t at = 0;
+    if (lane == 0) at = atomicAdd(count, (uint32_t)__popcll(m));
+    at = __shfl(at, 0, 64);
+    if (take) list[at + __popcll(m & ((1ull << lane) - 1))] = value;
 }
 
 // the sum of v over the block, in every thread (integers: the grouping does not matter).  sh: B / 64 entries

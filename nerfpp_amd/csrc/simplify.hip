@@ -21,12 +21,13 @@
 //   k_sp_members<0>  one lane per vertex: d_cluster, and the integer atomics of step 5 (sum of the 2^-20 fixed-point offsets and the member count per output vertex),
 //                    one per run of lanes that share an output vertex
 //   k_sp_means       one lane per cell: the mean position P of an output vertex, into d_out_verts
-//   k_sp_members<1>  one lane per member: atomic minimum of ((uint64)float_bits(d2) << 32) | v per output vertex
+//   k_sp_members<1>  one lane per member: atomic minimum of reduce.h's packed key (d2, v) per output vertex, one per run of lanes (no load filters it: a run's minimum is sent once)
 //   k_sp_finish      one lane per output vertex: d_rep, and in MEMBER mode the representative's coordinates over P
 //   k_sp_faces       one lane per face: a kept face goes to its block's offset + its rank in the block
 // Sums of integers and minima of keys do not depend on the order they arrive in, every position comes from an integer prefix sum, and nothing that reaches an output
 // depends on the hash function, the table size or which face came to own a slot.  No kernel waits on another workgroup.
 #include "common.h"
+#include "reduce.h"
 #include "scan.h"
 #include "workspace.h"
 
@@ -336,7 +337,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_members(const float *__restrict
         if (o >= 0) {
             const float dx = p[0] - out_verts[(int64_t)o * 3 + 0], dy = p[1] - out_verts[(int64_t)o * 3 + 1], dz = p[2] - out_verts[(int64_t)o * 3 + 2];
             const float d2 = (dx * dx + dy * dy) + dz * dz;
-            k = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)v;
+            k = key_pack(d2, (uint32_t)v);
         }
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
@@ -370,7 +371,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_finish(const float *__restrict_
 {
     const int64_t o = (int64_t)blockIdx.x * SP_BLOCK + threadIdx.x;
     if (o >= n_out) return;
-    const int32_t r = (int32_t)(uint32_t)key[o];
+    const int32_t r = key_index(key[o]);
     if (rep) rep[o] = r;
     if (position == NRF_SIMPLIFY_POS_MEMBER && r >= 0 && r < n_verts) {
 #pragma unroll

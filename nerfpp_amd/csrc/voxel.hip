@@ -8,20 +8,20 @@
 //                   divisions once, not once per face that uses it
 //   k_vox_faces     a fixed grid strides the face list, one lane per face: class (cm_face: bad / non-finite; then clipped), the columns of the winding pass and
 //                   the dilated lattice box of the distance pass.  A face scans what holds at most NRF_VOXEL_WIDE_COLUMNS / _POINTS entries itself and is appended
-//                   to the wide list of the other kind otherwise (one atomic add per wave: ballot, popcount, lane rank).  Every lane counts its faces by class
+//                   to the wide list of the other kind otherwise (scan.h's wave_append).  Every lane counts its faces by class
 //                   in registers: three atomic adds on d_stats per WORKGROUP (DESIGN 8k has what one add per wave cost the rasteriser)
 //   k_vox_wide      a fixed grid of workgroups strides both wide lists (their lengths are read on the device: the host never sees them); the 256 lanes of a workgroup
 //                   stride the columns or the lattice points of one face, so no lane's time grows with a face's size
 //   k_vox_finish    one lane per column, lanes along x so every level is a coalesced row: top-down, the suffix sum of delta is the winding; the key gives distance
 //                   and face, the rule gives the sign.  The volume is read once
-// The winding pass adds s = +-1 to delta[kc][j][i] by an integer atomic add; the distance pass lowers ((uint64)float_bits(d2) << 32) | face by agent-scope atomic min
-// (coherent across the XCDs; executed at the memory side).  Integer sums and minima do not depend on the order their terms arrive in: neither scheduling nor the order
-// of the face list reaches the result.  d2 >= 0, so its bit pattern orders as the value does.  A plain load of the current key filters the atomics: a stale value can
-// only be larger than the current one, so a skipped atomic would not have lowered the key.  Kernel boundaries make delta and the keys visible to the finish pass.
-// Coverage is decided in int64 (exact); every edge value is e(0, 0) + i * step_x + j * step_y, which in integers is the header's E_ab(p) whatever the visiting order.
+// The winding pass adds s = +-1 to delta[kc][j][i] by an integer atomic add; the distance pass lowers reduce.h's packed key (d2, face) by key_lower.
+// Integer sums and minima do not depend on the order their terms arrive in: neither scheduling nor the order of the face list reaches the result.  d2 >= 0, so its
+// bit pattern orders as the value does.  Kernel boundaries make delta and the keys visible to the finish pass.
+// Coverage is decided in int64 (exact; edge_fn.h's edge_cover, the rasteriser's); every edge value is e(0, 0) + i * step_x + j * step_y, which in integers is the header's E_ab(p) whatever the visiting order.
 // vx_column and vx_point are the one copy of steps 2-5 and 8: the face kernel and the wide kernel call them, so the bits cannot differ between the two.
 // Every loop is bounded by a clamped range or by a count; no kernel waits on another workgroup.
-#include "common.h"
+#include "edge_fn.h"
+#include "scan.h"
 #include "workspace.h"
 #include "face_grid.h"
 
@@ -107,9 +107,7 @@ __device__ __forceinline__ int64_t vx_setup(const int4 &a, const int4 &b, const 
     t.gz[2] = __int_as_float(c.z);
     const int xmin = min(a.x, min(b.x, c.x)), xmax = max(a.x, max(b.x, c.x));
     const int ymin = min(a.y, min(b.y, c.y)), ymax = max(a.y, max(b.y, c.y));
-    // >> of a negative int is arithmetic: floor
-    t.i0 = max((xmin + (NRF_RASTER_SUBPIXEL - 1)) >> 8, 0); t.i1 = min(xmax >> 8, g.n[0] - 1);
-    t.j0 = max((ymin + (NRF_RASTER_SUBPIXEL - 1)) >> 8, 0); t.j1 = min(ymax >> 8, g.n[1] - 1);
+    edge_box(xmin, xmax, ymin, ymax, g.n[0], g.n[1], t.i0, t.i1, t.j0, t.j1);
     return A;
 }
 
@@ -117,17 +115,9 @@ __device__ __forceinline__ int64_t vx_setup(const int4 &a, const int4 &b, const 
 __device__ __forceinline__ void vx_column(const VxTri &t, const VxLat &g, int i, int j, int32_t *__restrict__ delta)
 {
     int64_t se[3];
-    bool in = true;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        se[k] = t.e00[k] + (int64_t)i * t.sx[k] + (int64_t)j * t.sy[k];
-        in = in && (se[k] > 0 || (se[k] == 0 && t.tl[k]));
-    }
-    if (!in) return;
-    const double den = (double)t.sA;
+    if (!edge_cover(t.e00, t.sx, t.sy, t.tl, i, j, se)) return;
     float b[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) b[k] = (float)((double)se[k] / den);
+    edge_bary(se, t.sA, b);
     const float zc = (b[0] * t.gz[0] + b[1] * t.gz[1]) + b[2] * t.gz[2];
     const float tt = ceilf(zc) - 1.0f;
     if (!(tt >= 0.0f)) return;          // at or below level 0; NaN
@@ -160,9 +150,7 @@ __device__ __forceinline__ void vx_point(const float a[3], const float b[3], con
     CmHit h;
     cm_closest(q, a, b, c, h);
     if (!(h.d2 <= g.t2)) return;          // a NaN d2 fails the comparison
-    const unsigned long long v = ((unsigned long long)__float_as_uint(h.d2) << 32) | face;
-    unsigned long long *at = key + ((int64_t)k * g.n[1] + j) * g.n[0] + i;
-    if (v < *at) __hip_atomic_fetch_min(at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    key_lower(key + ((int64_t)k * g.n[1] + j) * g.n[0] + i, key_pack(h.d2, face));
 }
 
 __global__ void __launch_bounds__(VX_BLOCK) k_vox_init(int64_t n, int32_t *__restrict__ delta, unsigned long long *__restrict__ key)
@@ -197,18 +185,6 @@ __device__ __forceinline__ int vx_face_tri(const int32_t *__restrict__ faces, in
     return vx_setup(a, b, c, g, t) == 0 ? 2 : 0;
 }
 
-// one atomic add per wave appends the lanes with `take` to list; every lane of the wave calls it
-__device__ __forceinline__ void vx_append(bool take, int32_t f, int32_t *__restrict__ list, uint32_t *__restrict__ count)
-{
-    const int lane = threadIdx.x & 63;
-    const unsigned long long m = __ballot(take);
-    if (!m) return;          // uniform
-    uint32_t at = 0;
-    if (lane == 0) at = atomicAdd(count, (uint32_t)__popcll(m));
-    at = __shfl(at, 0, 64);
-    if (take) list[at + __popcll(m & ((1ull << lane) - 1))] = f;          // at + rank < n_faces: every face is appended at most once to each list
-}
-
 __global__ void __launch_bounds__(VX_BLOCK) k_vox_faces(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces,
                                                         const int4 *__restrict__ rec, const VxLat g, int32_t *__restrict__ delta, unsigned long long *__restrict__ key,
                                                         int32_t *__restrict__ wide_col, int32_t *__restrict__ wide_pts, uint32_t *__restrict__ n_wide,
@@ -218,7 +194,7 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vox_faces(const float *__restrict_
     if (threadIdx.x < 3) s_count[threadIdx.x] = 0;
     __syncthreads();
     uint32_t count[3] = {0, 0, 0};          // this lane's clipped, bad and non-finite faces
-    // the bound is the workgroup's: every lane of a wave makes every round (a lane past the last face has no class), so the ballots see the whole wave
+    // the bound is the workgroup's: every lane of a wave makes every round (a lane past the last face has no class), so wave_append's ballots see the whole wave
     for (int64_t base = (int64_t)blockIdx.x * VX_BLOCK; base < n_faces; base += (int64_t)gridDim.x * VX_BLOCK) {
         const int64_t f = base + threadIdx.x;
         float a[3], b[3], c[3];
@@ -233,8 +209,8 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vox_faces(const float *__restrict_
         int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
         const bool pts = key && cls == 0 && vx_box(a, b, c, g, lo, hi);
         const bool wide_p = pts && (int64_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1) > NRF_VOXEL_WIDE_POINTS;
-        vx_append(wide_c, (int32_t)f, wide_col, n_wide + 0);
-        vx_append(wide_p, (int32_t)f, wide_pts, n_wide + 1);
+        wave_append(wide_c, (int32_t)f, wide_col, n_wide + 0);          // every face is appended at most once to each list
+        wave_append(wide_p, (int32_t)f, wide_pts, n_wide + 1);
         if (cols && !wide_c)
             for (int j = t.j0; j <= t.j1; j++)
                 for (int i = t.i0; i <= t.i1; i++) vx_column(t, g, i, j, delta);
@@ -292,9 +268,9 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vox_finish(const VxLat g, int rule
         if (!key) continue;          // uniform
         const unsigned long long v = key[p];
         const bool found = v != NN_NONE;
-        if (face) face[p] = found ? (int32_t)(uint32_t)v : -1;
+        if (face) face[p] = found ? key_index(v) : -1;
         if (sdf) {
-            const float dist = fminf(found ? sqrtf(__uint_as_float((uint32_t)(v >> 32))) : g.trunc, g.trunc);
+            const float dist = fminf(found ? sqrtf(key_value(v)) : g.trunc, g.trunc);
             const bool inside = rule == NRF_VOX_NONZERO ? w != 0 : (rule == NRF_VOX_POSITIVE ? w > 0 : (w & 1) != 0);
             sdf[p] = inside ? -dist : dist;
         }

@@ -106,6 +106,15 @@ def main():
     put("bench train classic: mlp_backward p4096x192", lib.nrf_mlp_backward_workspace_bytes(cs["mlp"]._m, 4096 * 192))
     put("bench train lerf: lerf_batchify_rays n16384 64+128 chunk32768", lib.nrf_lerf_batchify_rays_workspace_bytes(ls["renderer"]._r, 16384, 32768, C.byref(lrp)))
     put("bench train lerf: lerf_backward_points n16384 s192", lib.nrf_lerf_backward_points_workspace_bytes(ls["renderer"]._r, 16384, 192))
+    # ---- the mesh tools: pure functions of the shapes (a test-sized mesh, odd counts, and the isosurface of the tools' benches)
+    for nv, nf, side in ((0, 0, 2), (37, 61, 9), (5_000_000, 10_000_000, 256)):
+        put(f"raster v{nv} f{nf} {side}x{side + 1}", lib.nrf_raster_workspace_bytes(nv, nf, side, side + 1))
+        put(f"mesh_voxelize v{nv} f{nf} {side}x{side + 1}x{side + 2}", lib.nrf_mesh_voxelize_workspace_bytes(nv, nf, side, side + 1, side + 2))
+        put(f"nearest_points q{nf} t{nv} {side}^3", lib.nrf_nearest_points_workspace_bytes(nf, nv, side, side, side))
+        put(f"face_grid f{nf} {side}^3", lib.nrf_face_grid_workspace_bytes(nf, side, side, side))
+        put(f"face_grid_bytes f{nf} {side}^3 refs{3 * nf} large{nf // 7}", lib.nrf_face_grid_bytes(nf, side, side, side, 3 * nf, nf // 7))
+        put(f"closest_on_mesh q{nf}", lib.nrf_closest_on_mesh_workspace_bytes(nf))
+        put(f"ray_cast n{nf}", lib.nrf_ray_cast_workspace_bytes(nf))
     for name, nbytes in rows:
         print(f"{name}\t{nbytes}")
     return 0

@@ -1267,6 +1267,94 @@ NRF_API int nrf_mesh_voxelize(const float *d_verts, int64_t n_verts, const int32
                               int rule, int32_t *d_winding, float *d_sdf, int32_t *d_face, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes,
                               void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Registration (align.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* Bringing one surface into the frame of another: a pose on the device, points moved through it, the sums of one ICP iteration over given pairs, and the small
+ * solve that updates the pose without a host round trip.  An iteration is nrf_align_apply -> nrf_closest_on_mesh (or nrf_nearest_points and a gather) ->
+ * nrf_align_sums -> nrf_align_solve on one stream; nothing in it synchronises or allocates.  Conventions as above: caller-owned buffers, refusals before any launch
+ * or write, two runs the same bits.  Everything below is fp64 arithmetic on fp32 data: each source-level operation rounded once (-ffp-contract=off), / and sqrt
+ * correctly rounded, nothing but + - * / sqrt and comparisons.  tests/align_ref.py restates every step in numpy float64 and the GPU tests compare bit for bit.
+ *
+ * CONTRACT.
+ *   State.  d_state: 8 doubles, 8-byte aligned: a unit quaternion (w, x, y, z), a scale s > 0, a translation t[3]; the pose is x -> s R x + t.
+ *   nrf_align_state_init: pose == NULL (a HOST pointer) writes (1, 0, 0, 0, 1, 0, 0, 0); else pose[8] with the quaternion divided by
+ *   sqrt(((w*w + x*x) + y*y) + z*z) per component, s and t as given.
+ *   R(w, x, y, z), row-major, wherever a rotation is formed from a quaternion:
+ *     R00 = 1 - 2*(y*y + z*z)   R01 = 2*(x*y - w*z)       R02 = 2*(x*z + w*y)
+ *     R10 = 2*(x*y + w*z)       R11 = 1 - 2*(x*x + z*z)   R12 = 2*(y*z - w*x)
+ *     R20 = 2*(x*z - w*y)       R21 = 2*(y*z + w*x)       R22 = 1 - 2*(x*x + y*y)
+ *   dot(a, b) = (a0*b0 + a1*b1) + a2*b2.
+ *   nrf_align_apply.  One lane per point.  M = s*R per entry; y_a = (float)(((M_a0*x0 + M_a1*x1) + M_a2*x2) + t_a).  rotate_only == 1 (normals):
+ *   y_a = (float)((R_a0*x0 + R_a1*x1) + R_a2*x2), no s, no t, not renormalised.  d_out may be d_points (the three inputs are read before the first write).
+ *   nrf_align_sums.  Pair i is (y_i, p_i) = (d_y[i], d_p[i]), a moved point and its target, with d_face[i] the face of the target mesh p_i lies on: exactly what
+ *   nrf_closest_on_mesh writes, so its max_dist is the trim.  A pair is DROPPED, tested in this order and counted in d_stats [4] uint32 (ADDED to; or NULL):
+ *     [0] d_face[i] < 0 (no pair);  [1] a non-finite coordinate of y_i or p_i;  and, NRF_ALIGN_PLANE only,
+ *     [2] face d_face[i] is bad or non-finite (the classes of nrf_face_grid_count, one inline function; an index >= F is bad);  [3] its normal has zero length.
+ *   The fp32 values are converted to fp64 first; d = p - y per component.
+ *   NRF_ALIGN_POINT, NRF_ALIGN_POINT_COLUMNS = 19 columns: [0] 1; [1..3] y_a; [4..6] p_a; [7 + 3a + b] y_a*p_b; [16] dot(y, y); [17] dot(p, p); [18] dot(d, d).
+ *   The mesh arguments are not read.
+ *   NRF_ALIGN_PLANE, NRF_ALIGN_PLANE_COLUMNS = 37 columns.  With (A, B, C) the face's corners: e1 = B - A, e2 = C - A (fp64 differences of the converted
+ *   corners), c = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), len2 = (cx*cx + cy*cy) + cz*cz (len2 > 0 false: dropped), len = sqrt(len2),
+ *   n = c / len per component (three divisions).  r = dot(n, d).  The row a[7] = (y1*n2 - y2*n1, y2*n0 - y0*n2, y0*n1 - y1*n0, n0, n1, n2, dot(n, y)): the
+ *   coefficients of (alpha, beta, gamma, tx, ty, tz, sigma) in the linearised residual r - a.x of the update y -> (1 + sigma)(y + omega x y) + t.
+ *   Columns: [0..27] a_i*a_j for i <= j, i-major; [28 + i] a_i*r; [35] 1; [36] r*r.
+ *   ORDER OF A SUM.  Block k takes pairs [k*NRF_ALIGN_TILE, (k+1)*NRF_ALIGN_TILE); lane t of 256 adds its entries t, t + 256, ... in ascending order, dropped pairs
+ *   skipped, into one accumulator per column from 0.0; then steps 1 and 2 of the ordered sum (nrf_mesh_sample_count, step 4) give the block's partial.  The
+ *   workspace holds [max(1, ceil(n / NRF_ALIGN_TILE))][columns] partials; n == 0 gives one row of zeros.  So a total is unchanged by any permutation of the pairs
+ *   that keeps every pair in its lane's set of its block in the same relative order -- and by nothing more: swapping two pairs between lanes or tiles may change
+ *   the last bits.
+ *   nrf_align_solve (n and mode as given to nrf_align_sums, the same workspace).  One workgroup: steps 3 and 4 of the ordered sum per column give the totals T;
+ *   one thread computes the update (dq, ds, dt) and a flag, composes it into d_state and writes a row of the history.
+ *   NRF_ALIGN_POINT (Horn's closed form).  cnt = T[0]; cnt >= 3 false: NRF_ALIGN_FLAG_FEW_PAIRS.  Sy = T[1..3], Sp = T[4..6]; ybar = Sy / cnt, pbar = Sp / cnt;
+ *     S_ab = T[7 + 3a + b] - (Sy_a*Sp_b) / cnt;  vy = T[16] - dot(Sy, Sy) / cnt;  vy > 0 false: NRF_ALIGN_FLAG_NO_SPREAD.  The symmetric 4x4
+ *     N00 = (Sxx + Syy) + Szz, N11 = (Sxx - Syy) - Szz, N22 = (Syy - Sxx) - Szz, N33 = (Szz - Sxx) - Syy, N01 = Syz - Szy, N02 = Szx - Sxz, N03 = Sxy - Syx,
+ *     N12 = Sxy + Syx, N13 = Szx + Sxz, N23 = Syz + Szy.  Cyclic Jacobi on A = N with V = I: NRF_ALIGN_JACOBI_SWEEPS sweeps over the pairs (p, q) = (0,1), (0,2),
+ *     (0,3), (1,2), (1,3), (2,3).  A[p][q] == 0: the pair is skipped.  th = (A[q][q] - A[p][p]) / (2*A[p][q]); |th| > NRF_ALIGN_JACOBI_BIG_THETA (th*th would
+ *     overflow): t = 0.5 / th, else t = (th >= 0 ? 1 : -1) / (|th| + sqrt(th*th + 1)); c = 1 / sqrt(t*t + 1), s = t*c.  Then for k = 0..3 the columns
+ *     (A[k][p], A[k][q]) <- (c*A[k][p] - s*A[k][q], s*A[k][p] + c*A[k][q]), then for k = 0..3 the rows (A[p][k], A[q][k]) <- (c*A[p][k] - s*A[q][k],
+ *     s*A[p][k] + c*A[q][k]), then V's columns as A's.  The eigenvector: column k of V with the largest A[k][k] (the lowest k on a tie), negated where its w < 0,
+ *     divided by its norm sqrt(((w*w + x*x) + y*y) + z*z) (not > 0 or not finite: NRF_ALIGN_FLAG_BAD_ROTATION): dq, always a proper rotation.  dR = R(dq).
+ *     ds = 1, or with scale: the sum over (a, b) = (0,0), (0,1), .. (2,2), in that order from the first term, of dR_ab*S_ba, divided by vy; ds > 0 false or not
+ *     finite: NRF_ALIGN_FLAG_BAD_SCALE.  dt_a = pbar_a - ds*((dR_a0*ybar0 + dR_a1*ybar1) + dR_a2*ybar2).
+ *   NRF_ALIGN_PLANE (Gauss-Newton on the point-to-plane residual).  m = 7 with scale, else 6 (the leading block); T[35] >= m false: NRF_ALIGN_FLAG_FEW_PAIRS.
+ *     H = the symmetric matrix of columns 0..27, g = columns 28..34.  Cholesky, for j = 0..m-1: d = H[j][j], then d = d - L[j][k]*L[j][k] for k = 0..j-1; d > 0 false
+ *     or not finite: NRF_ALIGN_FLAG_BAD_PIVOT; L[j][j] = sqrt(d); for i > j: v = H[i][j], v = v - L[i][k]*L[j][k] for k = 0..j-1, L[i][j] = v / L[j][j].  Forward:
+ *     z_i = (g_i - L[i][0]*z_0 - ... - L[i][i-1]*z_i-1) / L[i][i], the subtractions left to right; backward, i = m-1..0: x_i = (z_i - L[i+1][i]*x_i+1 - ... -
+ *     L[m-1][i]*x_m-1) / L[i][i].  A non-finite x_i: NRF_ALIGN_FLAG_BAD_PIVOT.  dq = (1, x0/2, x1/2, x2/2) divided by sqrt(((1 + a*a) + b*b) + c*c) of its vector
+ *     part (not finite: NRF_ALIGN_FLAG_BAD_ROTATION); dt = (x3, x4, x5); ds = 1 + x6 with scale (ds > 0 false: NRF_ALIGN_FLAG_BAD_SCALE), else 1.
+ *   Compose (flag == NRF_ALIGN_FLAG_OK): q' = dq (x) q, the Hamilton product with each component summed left to right in the order
+ *     w' = dw*w - dx*x - dy*y - dz*z,  x' = dw*x + dx*w + dy*z - dz*y,  y' = dw*y - dx*z + dy*w + dz*x,  z' = dw*z + dx*y - dy*x + dz*w,
+ *     divided by its norm; t'_a = ds*((dR_a0*t0 + dR_a1*t1) + dR_a2*t2) + dt_a; s' = ds*s.  With any other flag the update is the identity: d_state keeps its
+ *     bits and the row reports dq = (1, 0, 0, 0), ds = 1, dt = 0.
+ *   History.  d_history [n_history][8] doubles or NULL; row `iteration` = (pairs kept, the sum of dot(d, d) resp. r*r, the flag, 2*sqrt((dx*dx + dy*dy) + dz*dz)
+ *     of dq -- the angle of the update for a small one --, sqrt(dot(dt, dt)), ds, the new s, 0).
+ * d_workspace: 8-byte aligned, nrf_align_workspace_bytes(n, mode) (0 for a shape the calls refuse).
+ * REFUSED (NRF_ERR_INVALID_ARG, or NRF_ERR_WORKSPACE for a short workspace; nothing launched or written): n outside [0, 2^31 - 1]; a mode that is neither
+ *   constant; rotate_only or scale outside {0, 1}; a null d_state; a null d_points, d_out, d_y, d_p or d_face with n > 0; NRF_ALIGN_PLANE with a null d_verts or
+ *   d_faces, or V, F outside [0, 2^31 - 1]; a pointer that is not aligned to its element; d_history given with iteration outside [0, n_history); a pose with a
+ *   non-finite entry, a zero quaternion or s <= 0; a null or misaligned workspace. */
+#define NRF_ALIGN_POINT 0
+#define NRF_ALIGN_PLANE 1
+#define NRF_ALIGN_TILE 1024              /* pairs per block partial */
+#define NRF_ALIGN_POINT_COLUMNS 19
+#define NRF_ALIGN_PLANE_COLUMNS 37
+#define NRF_ALIGN_JACOBI_SWEEPS 8        /* the off-diagonal of the 4x4 reaches 1e-16 of the diagonal after 4 */
+#define NRF_ALIGN_JACOBI_BIG_THETA 1e150 /* above it th*th + 1 is not formed */
+#define NRF_ALIGN_FLAG_OK 0
+#define NRF_ALIGN_FLAG_FEW_PAIRS 1
+#define NRF_ALIGN_FLAG_NO_SPREAD 2
+#define NRF_ALIGN_FLAG_BAD_PIVOT 3
+#define NRF_ALIGN_FLAG_BAD_SCALE 4
+#define NRF_ALIGN_FLAG_BAD_ROTATION 5
+NRF_API int nrf_align_state_init(const double *pose, double *d_state, void *stream);
+NRF_API int nrf_align_apply(const float *d_points, int64_t n, const double *d_state, int rotate_only, float *d_out, void *stream);
+NRF_API size_t nrf_align_workspace_bytes(int64_t n, int mode);
+NRF_API int nrf_align_sums(const float *d_y, const float *d_p, const int32_t *d_face, int64_t n, int mode, const float *d_verts, int64_t n_verts,
+                           const int32_t *d_faces, int64_t n_faces, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_align_solve(int64_t n, int mode, int scale, int iteration, int n_history, double *d_state, double *d_history, void *d_workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */
 NRF_API size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p);

@@ -22,6 +22,7 @@ NRF_RNG_HEMI_DIR = 12
 NRF_RC_CLOSEST, NRF_RC_ANY = 0, 1          # nrf_ray_cast_mesh: mode
 NRF_RC_CULL_NONE, NRF_RC_CULL_BACK, NRF_RC_CULL_FRONT = 0, 1, 2
 NRF_VOX_NONZERO, NRF_VOX_POSITIVE, NRF_VOX_ODD = 0, 1, 2          # nrf_mesh_voxelize: rule
+NRF_ALIGN_POINT, NRF_ALIGN_PLANE = 0, 1          # nrf_align_sums / nrf_align_solve: mode
 NRF_PROF_NAMES = ("hash", "mlp", "composite", "sample", "other", "sigma", "mlp_colour")
 NRF_COARSE_AUTO, NRF_COARSE_FULL, NRF_COARSE_SIGMA_F32 = 0, 1, 2
 NRF_OVERFLOW_AUTO, NRF_OVERFLOW_RERENDER, NRF_OVERFLOW_ERROR, NRF_OVERFLOW_DEFERRED, NRF_OVERFLOW_IGNORE = 0, 1, 2, 3, 4
@@ -231,6 +232,11 @@ _ABI = """
     nrf_mesh_ambient_occlusion(ppliffqlplplpiiillpzpppzp)
     nrf_mesh_voxelize_workspace_bytes(lliii)->z
     nrf_mesh_voxelize(plplpiiifipppppzp)
+    nrf_align_state_init(ppp)
+    nrf_align_apply(plpipp)
+    nrf_align_workspace_bytes(li)->z
+    nrf_align_sums(pppliplplppzp)
+    nrf_align_solve(liiiipppzp)
     nrf_render_rays_workspace_bytes(plp)->z
     nrf_render_rays(ppilpppppzp)
     nrf_batchify_rays_workspace_bytes(plip)->z

@@ -257,16 +257,24 @@ def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_di
     return dataclasses.replace(dst_mesh, **new)
 
 
-def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_dist=None, bbox=None, to="points"):
+def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_dist=None, bbox=None, to="points", align=None):
     """How far apart two surfaces are, a the prediction and b the truth, each a Mesh (sampled: SampleSurface(n_points=n_points, seed=seed)) or a [N, 3] tensor of
     points (used as they are).  Returns a SurfaceDistanceResult of float64 device tensors.  With max_dist, points without a neighbour that near are left out of the
     means and count as misses in Precision / Recall.  bbox as in NearestPoints (None: two synchronisations, one per direction).
     to="surface" measures the samples of each side against the FACES of the other where that side is a Mesh (ClosestOnMesh: the exact point-to-triangle distance,
-    whose floor is zero, not the other side's sampling density); a side given as points is still searched as points."""
+    whose floor is zero, not the other side's sampling density); a side given as points is still searched as points.
+    align: a nerfpp_amd.align.Transform moves side a into b's frame first (a Mesh through TransformMesh, points through Transform.Apply); "icp" finds that pose with
+    align.RegisterICP(a, b) at its defaults (call it yourself for any other setting).  None, the default, measures the two sides as they are."""
     if len(taus) > STATS_MAX_TAU:
         raise L.NrfError(f"SurfaceDistance: {len(taus)} thresholds, at most {STATS_MAX_TAU}")
     if to not in ("points", "surface"):
         raise L.NrfError(f"SurfaceDistance: to must be 'points' or 'surface', got {to!r}")
+    if align is not None:
+        from . import align as A
+        if isinstance(align, str) and align != "icp":
+            raise L.NrfError(f"SurfaceDistance: align must be None, 'icp' or a Transform, got {align!r}")
+        pose = A.RegisterICP(a, b, method="plane" if isinstance(b, (M.Mesh, FaceGrid)) else "point").Transform if isinstance(align, str) else align
+        a = A.TransformMesh(a, pose) if isinstance(a, M.Mesh) else pose.Apply(a)
     pa, pb = _as_points(a, n_points, seed), _as_points(b, n_points, seed)
 
     def dist2(p, other, other_points):

@@ -1355,6 +1355,105 @@ NRF_API int nrf_align_sums(const float *d_y, const float *d_p, const int32_t *d_
 NRF_API int nrf_align_solve(int64_t n, int mode, int scale, int iteration, int n_history, double *d_state, double *d_history, void *d_workspace,
                             size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh BVH (bvh.hip, bvh.h, sort.h; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* A second acceleration structure for the two queries above: a linear bounding-volume hierarchy over the faces (Karras, Maximizing Parallelism in the Construction of
+ * BVHs, Octrees, and k-d Trees, 2012), one face per leaf.  It needs no box, no dims, no large-face list and no fallback, its build makes no host round trip, and its
+ * queries return the bits of nrf_closest_on_mesh / nrf_ray_cast_mesh: both results are defined grid-free as the minimum of a packed key over all valid faces, the
+ * candidates are formed by the same inline functions, and a subtree is skipped only by a proven bound.  Conventions as above: fp32 operations rounded once each,
+ * / correctly rounded, caller-owned buffers, refusals before any launch or write, two runs the same bytes.  The face grid stays what a Mesh gets by default.
+ *
+ * SORT.  nrf_sort_pairs_u32: d_keys [n] uint32 with a payload d_values [n] int32 (NULL: the payload is the index 0 .. n - 1) ordered by bits [begin_bit, end_bit) of
+ *   the key into d_keys_out / d_values_out (whole keys are written, not the masked bits).  A least-significant-digit radix sort in 8-bit digits (the last digit may be
+ *   narrower), STABLE: pairs with equal bits keep their input order, so d_values_out with a NULL d_values is np.argsort(bits, kind="stable").  Per pass: a digit
+ *   histogram per block of 2 048 elements; the exclusive scan of the [256 digits x blocks] counts in digit-major order; a scatter that ranks every element inside its
+ *   block among the equal digits before it.  No atomics on global memory, no synchronisation; the passes ping-pong between the outputs and two arrays of the workspace
+ *   (nrf_sort_workspace_bytes(n)), the inputs are only read.  0 <= n <= 2^31 - 1; n == 0 launches nothing; begin_bit == end_bit copies.  REFUSED: n or the bits out
+ *   of range (0 <= begin_bit <= end_bit <= 32), a null d_keys, d_keys_out or d_values_out (n > 0), an output that is its input, a null, misaligned (8 bytes) or
+ *   short workspace.
+ *
+ * BUILD.  nrf_mesh_bvh_build fills a buffer of nrf_mesh_bvh_bytes(F) bytes with a workspace of nrf_mesh_bvh_workspace_bytes(F) bytes, both pure functions of F; the
+ *   workspace may go (or be overwritten) once the build has run.  The host reads nothing back.
+ *   Classes.  Valid, bad and non-finite faces exactly as for nrf_face_grid_count; d_stats [4] uint32 or NULL, ADDED to: [1] bad, [2] non-finite faces.  n_valid, the
+ *   number of valid faces, is counted on the device.
+ *   Mesh box.  Per axis the smallest and largest corner coordinate of the valid faces, exact: integer atomic min / max on the image of a float, u = bits(x),
+ *   u = (u >> 31) ? ~u : u | 2^31, whose unsigned order is the float's with -0 below +0.  No valid face: lo = +inf, hi = -inf.
+ *   Morton code of a valid face, 30 bits.  Per axis c = lo_f * 0.5f + hi_f * 0.5f, the centre of the face's coordinate box (lo_f / hi_f the smallest / largest of the
+ *   three corners); e = hi - lo of the mesh box; e > 0 and e < +inf false: cell 0, else x = floorf(((c - lo) / e) * 1024.0f), cell = (int)min(max(x, 0), 1023) (a NaN
+ *   x gives 0).  Bit k of the x / y / z cell is bit 3k / 3k + 1 / 3k + 2 of the code.  A face that is not valid gets the code 2^30, above every valid one.
+ *   Leaves.  Four stable 8-bit passes of the sort over the codes, payload the face index: sorted position k holds face leaf_face[k], positions 0 .. n_valid - 1 the
+ *   valid faces, ascending in the unique 64-bit key (code << 32) | f.  Equal codes (copies of a face, coincident centres) need no special case.
+ *   Topology.  One lane per internal node i in [0, n_valid - 1): Karras's direction, range and split on the length of the common prefix of the 64-bit keys.  Node i
+ *   covers a range [l, r] of sorted positions with i == l or i == r and splits it after position s, the last whose key shares the range's longest common prefix with
+ *   the first key's next bit: the node of [l, s] has index s, the node of [s + 1, r] index s + 1, a range of one position is that leaf; node 0 is the root.  The tree,
+ *   numbering included, equals the top-down recursion "split where the highest differing bit of the range's first and last key changes" (tests/bvh_ref.py).
+ *   NRF_BVH_MAX_DEPTH.  A key has at most 62 significant bits (a valid code is below 2^30) and every level of the tree lengthens the common prefix by at least one
+ *   bit, so no leaf lies deeper than 62 edges below the root.  64 bounds the refit's launches and the traversal stack (which holds at most one node per level).
+ *   Boxes.  The box of a leaf is its face's coordinate box, the box of a node the per-axis min / max of its children's.  A node stores its two CHILDREN's boxes.  The
+ *   refit is NRF_BVH_MAX_DEPTH launches with nothing handed over inside a launch (the L2s of the XCDs are not coherent, and a fence per thread costs microseconds):
+ *   launch p finishes the nodes whose two children were finished by an earlier launch and marks them p; a mark equal to p counts as not finished, so no launch reads
+ *   data the same launch wrote.  A device counter of unfinished nodes lets the launches after the tree's height return after one load per block.  min / max are exact
+ *   and order-free: the buffer is the same bytes on every run (the build zeroes it first, padding and unused nodes included).
+ *   Layout of the buffer (every piece starts at a multiple of 256 bytes, as the workspaces do):
+ *     head       8 x int64: "NRFBVH01" (0x4e52464256483031), F, n_valid, then per axis x, y, z the mesh box as bits(lo) | bits(hi) << 32, then 0, 0
+ *     leaf_face  F x int32
+ *     node       max(F - 1, 0) x 64 bytes: lo0[3], hi0[3], lo1[3], hi1[3] fp32 (the boxes of child 0 and child 1), child[2], parent, 0 as int32.  A child >= 0 is an
+ *                internal node, -(k + 1) the leaf at sorted position k; the root's parent is -1; nodes n_valid - 1 .. F - 2 stay zero.
+ *   n_valid == 0: an empty tree, every query misses.  n_valid == 1: no internal node; the tree is leaf 0 alone and a query tests face leaf_face[0] without a box.
+ *   REFUSED: V or F out of range, a null d_faces (F > 0) or d_verts (V > 0 and F > 0), a null or misaligned (64 bytes) BVH buffer, a buffer whose size is not
+ *   nrf_mesh_bvh_bytes(F), a null, misaligned (8 bytes) or short workspace.  A query or nrf_bvh_point_codes whose F passes the size check but disagrees with the head
+ *   (magic, F, 0 <= n_valid <= F) reads nothing more of the buffer and writes nothing.
+ *
+ * CLOSEST POINT.  nrf_bvh_closest_on_mesh: outputs, d_stats[0], max_dist and the result exactly as nrf_closest_on_mesh defines them; d_stats[3] is never touched,
+ *   there is no fallback.  The workspace pair is accepted as it comes: nrf_bvh_query_workspace_bytes(n) is 0 and d_workspace may be NULL.
+ *   Traversal.  One lane per query, a private stack of NRF_BVH_MAX_DEPTH node indices, from the root.  For a node's two child boxes [lo, hi]: per axis
+ *   g = q < lo ? lo - q : (q > hi ? q - hi : 0), b2 = (gx*gx + gy*gy) + gz*gz.  The child with the smaller b2 first; a child is SKIPPED iff
+ *   b2 > min(best_d2, fl(max_dist * max_dist)), strictly (best_d2 = +inf before the first candidate): an equal bound descends, so the lowest face index wins a tie.  A
+ *   leaf is a candidate through the closest-point function above, folded into the same key.
+ *   WHY IT IS EXACT.  The clamp of the closest-point function puts every coordinate of P inside the face's coordinate box, hence inside the box of every ancestor.
+ *   Per axis, with lo <= P <= hi: q < lo gives q - P <= q - lo < 0, so |fl(q - P)| >= fl(lo - q) = g (rounding is monotone and odd); likewise q > hi; else g = 0.  The
+ *   rounded square and the two rounded sums of non-negative terms are monotone in every argument, in the same order for both: b2 <= d2 for every face under the node
+ *   and every finite q, also where either overflows to +inf.  A face that could win or tie has d2 <= min(best_d2, fl(max_dist^2)), so its ancestors are not skipped.
+ *
+ * RAY CAST.  nrf_bvh_ray_cast_mesh: rays, cull, mode, outputs, d_stats[0] and the result exactly as nrf_ray_cast_mesh defines them; no far-origin rule, no premise on
+ *   the faces, no step cap, no fallback, d_stats[3] never touched.
+ *   Node test, for a child box [lo, hi] and a valid ray: M = max(|o|_inf, |lo|_inf, |hi|_inf), m = 2^-10 * M (M < 2^-100: m = +inf, every node is visited: a scene
+ *   at the scale of the denormals is searched exhaustively).  Per axis wlo = lo - m, whi = hi + m.  An axis with d == 0 whose o lies outside [wlo, whi]: a miss.  Else
+ *   ta = (wlo - o) / d, tb = (whi - o) / d, swapped so that ta <= tb.  t_in = max(ray lo, all ta), t_out = min(ray hi, all tb).  The child is VISITED iff
+ *   t_in <= t_out and t_in <= best_t (not strictly: an equal t with a lower face index must still be found; best_t = +inf before the first candidate).  The child
+ *   with the smaller t_in first.  Any mode stops at the first accepted candidate.
+ *   WHY THE TRAVERSAL CANNOT MISS.  Let a candidate of a face under the node be accepted at t, and take an axis with d > 0 (d < 0 mirrors).  P lies in the node's box
+ *   (the clamp), so |P|_inf <= M, and the consistency rule gives |Pu - P| <= tau = 2^-12 max(|o|_inf, |Pu|_inf) <= 2^-12 (M + tau), tau <= 2^-12 (1 + 2^-11) M: on
+ *   this axis Pu >= lo - tau.  Suppose t < ta.  Both are floats and ta = fl(x / d) with x = fl(wlo - o), so t < x / d exactly (a float below the rounded quotient is
+ *   below the quotient), t * d < x, fl(t * d) <= x (x is a float, rounding is monotone) and Pu = fl(o + fl(t * d)) <= fl(o + x).  fl(o + fl(wlo - o)) differs from
+ *   wlo by two roundings of values no larger than 2 (1 + 2^-10) M, and wlo from lo - m by one: Pu <= lo - 2^-10 M + 2^-21 M < lo - tau, a contradiction.  So
+ *   ta <= t, likewise t <= tb; denormal ta or products change nothing (the argument uses monotonicity, and M >= 2^-100 keeps m and the roundings of the sums normal);
+ *   an infinite wlo or whi only widens.  On an axis with d == 0, Pu = o for every finite t, so o lies within tau < m of [lo, hi].  lo_ray <= t <= hi_ray is part of the
+ *   acceptance.  Hence t_in <= t <= t_out for every ancestor of an accepted candidate, and an unseen candidate that could win or tie has t <= best_t, so t_in <= best_t.
+ *   No result depends on the margin.
+ *
+ * SPATIAL ORDER.  nrf_bvh_point_codes writes d_codes [n] uint32, the Morton code above of the point at d_points + i * stride (3 <= stride <= NRF_RC_MAX_STRIDE floats:
+ *   3 for points, the ray stride for ray origins) against the mesh box in the head, the coordinate itself in place of c, clamped the same way.  Both queries take
+ *   d_order, int32 [n] or NULL: lane i serves element d_order[i] and writes that element's outputs.  d_order must be a permutation of 0 .. n - 1 (an entry outside is
+ *   skipped; a repeated one leaves another element unwritten): sorting the codes with nrf_sort_pairs_u32 gives one.  The outputs do not depend on it. */
+#define NRF_BVH_MAX_DEPTH 64
+NRF_API size_t nrf_sort_workspace_bytes(int64_t n);
+NRF_API int nrf_sort_pairs_u32(const uint32_t *d_keys, const int32_t *d_values, int64_t n, int begin_bit, int end_bit, uint32_t *d_keys_out, int32_t *d_values_out,
+                               void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_mesh_bvh_bytes(int64_t n_faces);
+NRF_API size_t nrf_mesh_bvh_workspace_bytes(int64_t n_faces);
+NRF_API int nrf_mesh_bvh_build(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, void *d_bvh, size_t bvh_bytes, uint32_t *d_stats,
+                               void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API size_t nrf_bvh_query_workspace_bytes(int64_t n);
+NRF_API int nrf_bvh_closest_on_mesh(const float *d_query, int64_t nq, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const void *d_bvh,
+                                    size_t bvh_bytes, const int32_t *d_order, float max_dist, float *d_dist2, int32_t *d_face, float *d_uv, float *d_point,
+                                    uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_bvh_ray_cast_mesh(const float *d_rays, int64_t n_rays, int stride, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces,
+                                  const void *d_bvh, size_t bvh_bytes, const int32_t *d_order, int cull, int mode, float *d_t, int32_t *d_face, float *d_uv,
+                                  float *d_point, uint8_t *d_hit, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_bvh_point_codes(const float *d_points, int64_t n, int stride, const void *d_bvh, size_t bvh_bytes, int64_t n_faces, uint32_t *d_codes, void *stream);
+
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */
 NRF_API size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p);

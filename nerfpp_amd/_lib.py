@@ -237,6 +237,15 @@ _ABI = """
     nrf_align_workspace_bytes(li)->z
     nrf_align_sums(pppliplplppzp)
     nrf_align_solve(liiiipppzp)
+    nrf_sort_workspace_bytes(l)->z
+    nrf_sort_pairs_u32(ppliipppzp)
+    nrf_mesh_bvh_bytes(l)->z
+    nrf_mesh_bvh_workspace_bytes(l)->z
+    nrf_mesh_bvh_build(plplpzppzp)
+    nrf_bvh_query_workspace_bytes(l)->z
+    nrf_bvh_closest_on_mesh(plplplpzpfppppppzp)
+    nrf_bvh_ray_cast_mesh(pliplplpzpiipppppppzp)
+    nrf_bvh_point_codes(plipzlpp)
     nrf_render_rays_workspace_bytes(plp)->z
     nrf_render_rays(ppilpppppzp)
     nrf_batchify_rays_workspace_bytes(plip)->z

@@ -134,10 +134,10 @@ def AlignPoints(src, dst, scale=False):
 
 
 def RegisterICP(source, target, init=None, iterations=30, max_dist=None, method="plane", scale=False, n_points=20000, seed=0, tolerance=None, check_every=5,
-                stats=None):
+                stats=None, coherent=False):
     """Iterative closest point: the pose that brings `source` onto `target` -> RegistrationResult.
-    source: a Mesh (sampled once: SampleSurface(n_points=n_points, seed=seed)) or points [n, 3].  target: a Mesh or a FaceGrid (queried through ClosestOnMesh; a Mesh
-    is binned once, over the box of its vertices) or points [m, 3] (NearestPoints over the box of the points, method="point" only).
+    source: a Mesh (sampled once: SampleSurface(n_points=n_points, seed=seed)) or points [n, 3].  target: a Mesh, a FaceGrid or a MeshBVH (queried through ClosestOnMesh, coherent
+    as there; a Mesh is binned once, over the box of its vertices) or points [m, 3] (NearestPoints over the box of the points, method="point" only).
     method "plane" minimises the distance to the tangent plane of the closest face (a few iterations from a start within some tens of degrees), "point" the distance
     to the closest point itself (Horn's closed form per iteration; slower, as a surface slides along itself).  scale=True also fits a uniform scale.
     init: a Transform to start from (default: the identity); it is not modified.  max_dist: pairs farther apart are left out; a scalar or one value per iteration, a
@@ -156,8 +156,8 @@ def RegisterICP(source, target, init=None, iterations=30, max_dist=None, method=
     src = G.SampleSurface(source, n_points=n_points, seed=seed).Points if isinstance(source, M.Mesh) else _dev_f32(source).reshape(-1, 3)
     dev, n = src.device, int(src.shape[0])
     grid = points = box = None
-    if isinstance(target, (M.Mesh, G.FaceGrid)):
-        grid = target if isinstance(target, G.FaceGrid) else G.FaceGrid(target)
+    if isinstance(target, (M.Mesh, G.FaceGrid, G.MeshBVH)):
+        grid = target if isinstance(target, (G.FaceGrid, G.MeshBVH)) else G.FaceGrid(target)
     else:
         if mode != ALIGN_POINT:
             raise L.NrfError("RegisterICP: method='plane' needs the faces of the target; a target given as points takes method='point'")
@@ -172,7 +172,7 @@ def RegisterICP(source, target, init=None, iterations=30, max_dist=None, method=
     for it in range(iterations):
         moved.Apply(src, out=y)
         if grid is not None:
-            res = G.ClosestOnMesh(y, grid, max_dist=dists[it], uv=False)
+            res = G.ClosestOnMesh(y, grid, max_dist=dists[it], uv=False, coherent=coherent)
             p, face = res.Points, res.Face
         else:
             _, face = G.NearestPoints(y, points, max_dist=dists[it], bbox=box)

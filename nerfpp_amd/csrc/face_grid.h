@@ -3,7 +3,8 @@
 // (FgGrid, FgKey, fg_key_matches), the classes of a face (cm_face), the dot product in the header's order and the clamp of a surface point to its face's own
 // coordinate box.  One copy of each: a query of either kind reads exactly the buffer the build wrote, and both proofs of completeness lean on the same clamp.
 // Also the closest point of a triangle itself (nn_d2, CmHit, cm_closest): nrf_closest_on_mesh gathers it per query, voxel.hip (nrf_mesh_voxelize) scatters it per
-// face over the lattice, and the two agree bit for bit because it is one function.  And the list of the queries a walk gives up (FarList, far_layout).
+// face over the lattice, and the two agree bit for bit because it is one function.  And the list of the queries a walk gives up (FarList, far_layout), and a face as a candidate of a query and the outputs of a
+// query from its key (cm_take, cm_write): the grid's rings, its fallback and the BVH of bvh.hip go through them.
 #pragma once
 
 #include "common.h"
@@ -213,6 +214,35 @@ __device__ __forceinline__ void cm_closest(const float q[3], const float a[3], c
     h.v = v;
     h.w = w;
     h.d2 = nn_d2(q[0], q[1], q[2], make_float4(h.p[0], h.p[1], h.p[2], 0.0f));
+}
+
+// face f as a candidate of query q: rings, large list and fallback all come through here
+__device__ __forceinline__ void cm_take(const float q[3], const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, int64_t f,
+                                        float md2, unsigned long long &best)
+{
+    float a[3], b[3], c[3];
+    if (cm_face(verts, n_verts, faces, n_faces, f, a, b, c) != 0) return;
+    CmHit h;
+    cm_closest(q, a, b, c, h);
+    const unsigned long long k = key_pack(h.d2, (uint32_t)f);
+    if (h.d2 <= md2 && k < best) best = k;          // a NaN d2 fails the comparison
+}
+
+// the outputs of query qi from its key: (v, w) and P are those of the winning face, formed once more by the same function
+__device__ __forceinline__ void cm_write(const float q[3], int64_t qi, unsigned long long best, const float *__restrict__ verts, int32_t n_verts,
+                                         const int32_t *__restrict__ faces, int64_t n_faces, float *__restrict__ dist2, int32_t *__restrict__ face, float *__restrict__ uv,
+                                         float *__restrict__ point)
+{
+    const int32_t f = key_index(best);
+    dist2[qi] = key_value(best);
+    face[qi] = f;
+    if (!uv && !point) return;
+    CmHit h;
+    h.v = h.w = h.p[0] = h.p[1] = h.p[2] = 0.0f;
+    float a[3], b[3], c[3];
+    if (f >= 0 && cm_face(verts, n_verts, faces, n_faces, f, a, b, c) == 0) cm_closest(q, a, b, c, h);
+    if (uv) { uv[qi * 2 + 0] = h.v; uv[qi * 2 + 1] = h.w; }
+    if (point) { point[qi * 3 + 0] = h.p[0]; point[qi * 3 + 1] = h.p[1]; point[qi * 3 + 2] = h.p[2]; }
 }
 
 // the argument checks the entries over a face grid share: shapes, pointers of the mesh, the box

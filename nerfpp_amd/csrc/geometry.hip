@@ -447,34 +447,8 @@ __device__ __forceinline__ int64_t fg_box(const NnGrid &g, const float a[3], con
     return n;
 }
 
-// face f as a candidate of query q: rings, large list and fallback all come through here
-__device__ __forceinline__ void cm_take(const float q[3], const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, int64_t f,
-                                        float md2, unsigned long long &best)
-{
-    float a[3], b[3], c[3];
-    if (cm_face(verts, n_verts, faces, n_faces, f, a, b, c) != 0) return;
-    CmHit h;
-    cm_closest(q, a, b, c, h);
-    const unsigned long long k = key_pack(h.d2, (uint32_t)f);
-    if (h.d2 <= md2 && k < best) best = k;          // a NaN d2 fails the comparison
-}
-
-// the outputs of query qi from its key: (v, w) and P are those of the winning face, formed once more by the same function
-__device__ __forceinline__ void cm_write(const float q[3], int64_t qi, unsigned long long best, const float *__restrict__ verts, int32_t n_verts,
-                                         const int32_t *__restrict__ faces, int64_t n_faces, float *__restrict__ dist2, int32_t *__restrict__ face, float *__restrict__ uv,
-                                         float *__restrict__ point)
-{
-    const int32_t f = key_index(best);
-    dist2[qi] = key_value(best);
-    face[qi] = f;
-    if (!uv && !point) return;
-    CmHit h;
-    h.v = h.w = h.p[0] = h.p[1] = h.p[2] = 0.0f;
-    float a[3], b[3], c[3];
-    if (f >= 0 && cm_face(verts, n_verts, faces, n_faces, f, a, b, c) == 0) cm_closest(q, a, b, c, h);
-    if (uv) { uv[qi * 2 + 0] = h.v; uv[qi * 2 + 1] = h.w; }
-    if (point) { point[qi * 3 + 0] = h.p[0]; point[qi * 3 + 1] = h.p[1]; point[qi * 3 + 2] = h.p[2]; }
-}
+// cm_take and cm_write, a face as the candidate of a query (cm_closest(q, a, b, c, h) folded into the key) and the outputs of a query from its key: face_grid.h;
+// bvh.hip forms both through the same two functions
 
 // pass 0: count[cell]++ for every cell of a binned face's box, n_large++ for a large one; pass 1: the face's index goes to cursor[cell]++ resp. to the large list
 template <int PASS>

@@ -7,7 +7,9 @@ neither the grid nor the order of the points -- and the sums behind Chamfer dist
 fp64 reductions.  tests/geometry_ref.py equals every output bit for bit and two runs agree.  That is the sampled point-to-point distance of the DTU / Tanks and Temples
 benchmarks; FaceGrid / ClosestOnMesh are the exact point-to-triangle query beside it (the nearest face, the point on it, its barycentrics; tests/closest_ref.py),
 which SurfaceDistance(to="surface"), TransferAttributes(source="surface") and texture.BakeTexture(source=<Mesh>) are thin layers over.  RayCastMesh / Occluded /
-Visible / HemisphereDirections / AmbientOcclusion / ClipRaysToMesh ask the same FaceGrid what a ray hits (raycast.hip; tests/raycast_ref.py).
+Visible / HemisphereDirections / AmbientOcclusion / ClipRaysToMesh ask the same FaceGrid what a ray hits (raycast.hip; tests/raycast_ref.py).  MeshBVH is a second
+structure for the same two queries (bvh.hip; tests/bvh_ref.py): built without a host synchronisation, no box, dims or fallback, the same bits; every function that
+takes a FaceGrid takes it.
 """
 import ctypes as C
 import math
@@ -24,6 +26,7 @@ from .modules import _ptr, _stream, _dev_f32
 # NRF_SAMPLE_* / NRF_NN_* / NRF_STATS_* of the header (tests/test_geometry_host.py holds them to it)
 SAMPLE_MAX_PER_FACE, NN_MAX_DIM, NN_MAX_CELLS, NN_MAX_RINGS, STATS_MAX_TAU = 65536, 1024, 1 << 26, 16, 4
 FG_MAX_FACE_CELLS = 64          # NRF_FG_MAX_FACE_CELLS (tests/test_closest_host.py holds it to the header)
+BVH_MAX_DEPTH = 64              # NRF_BVH_MAX_DEPTH (tests/test_bvh_host.py holds it to the header)
 OCCUPANCY = 128.0        # what GridDims aims at by default: about 20-30 targets per occupied cell as measured; coarse enough that 16 rings reach far
 _ATTRS = ("Colors", "Normals", "Relevancy")
 
@@ -198,14 +201,69 @@ class FaceGrid:
                                         _ptr(ws), ws.numel(), _stream()))
 
 
-def ClosestOnMesh(query, mesh_or_grid, max_dist=None, stats=None, bbox=None, cells=None, uv=True, points=True):
+class MeshBVH:
+    """A bounding-volume hierarchy over the faces of `mesh` (nrf_mesh_bvh_build), for every function that takes a FaceGrid: build it once, query it many times.  No
+    box, no dims and NO host synchronisation; the results are those of a FaceGrid bit for bit, without a brute-force fallback for far queries, far ray origins or
+    faces outside a box.  It keeps its buffer and the mesh's arrays alive.  stats: an int32 [4] device tensor whose entries 1 and 2 the faces with a corner outside
+    the vertices and with a non-finite vertex are added to."""
+
+    def __init__(self, mesh, stats=None):
+        self.Mesh = mesh
+        self.Verts, self.Faces = _mesh_arrays(mesh)
+        dev = self.Verts.device
+        nv, nf = int(self.Verts.shape[0]), int(self.Faces.shape[0])
+        lib = L.lib()
+        self.Buffer = torch.empty((int(lib.nrf_mesh_bvh_bytes(nf)),), device=dev, dtype=torch.uint8)
+        ws = _workspace(lib.nrf_mesh_bvh_workspace_bytes(nf), dev)
+        L.check(lib.nrf_mesh_bvh_build(_ptr(self.Verts), nv, _ptr(self.Faces), nf, _ptr(self.Buffer), self.Buffer.numel(), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+        self._box = None
+
+    @property
+    def Box(self):
+        """[6] f32 on the host, the box of the valid faces as the build found it (min xyz, max xyz): ONE host synchronisation at the first use, none before"""
+        if self._box is None:
+            w = self.Buffer[24:48].cpu().numpy().view(np.uint32).reshape(3, 2)
+            self._box = np.concatenate([w[:, 0], w[:, 1]]).view(np.float32)
+        return self._box
+
+    def Order(self, points, stride=3):
+        """int32 [n]: the rows of `points` ([n, stride] f32, xyz first) in the order of their Morton codes against the mesh box (nrf_bvh_point_codes and
+        nrf_sort_pairs_u32): neighbours in the list are neighbours in space and walk the same nodes.  What coherent=True passes to the queries as d_order."""
+        n = int(points.shape[0])
+        dev = points.device
+        lib = L.lib()
+        codes = torch.empty((n,), device=dev, dtype=torch.int32)
+        L.check(lib.nrf_bvh_point_codes(_ptr(points), n, int(stride), _ptr(self.Buffer), self.Buffer.numel(), int(self.Faces.shape[0]), _ptr(codes), _stream()))
+        keys, order = torch.empty_like(codes), torch.empty_like(codes)
+        ws = _workspace(lib.nrf_sort_workspace_bytes(n), dev)
+        L.check(lib.nrf_sort_pairs_u32(_ptr(codes), None, n, 0, 30, _ptr(keys), _ptr(order), _ptr(ws), ws.numel(), _stream()))
+        return order
+
+
+def _bvh_closest(q, bvh, max_dist, stats, uv, points, coherent):
+    dev, nq = q.device, int(q.shape[0])
+    d2 = torch.empty((nq,), device=dev, dtype=torch.float32)
+    face = torch.empty((nq,), device=dev, dtype=torch.int32)
+    out_uv = torch.empty((nq, 2), device=dev, dtype=torch.float32) if uv else None
+    out_p = torch.empty((nq, 3), device=dev, dtype=torch.float32) if points else None
+    order = bvh.Order(q) if coherent and nq else None
+    L.check(L.lib().nrf_bvh_closest_on_mesh(_ptr(q), nq, _ptr(bvh.Verts), int(bvh.Verts.shape[0]), _ptr(bvh.Faces), int(bvh.Faces.shape[0]), _ptr(bvh.Buffer),
+                                            bvh.Buffer.numel(), _ptr(order), float("inf") if max_dist is None else float(max_dist), _ptr(d2), _ptr(face), _ptr(out_uv),
+                                            _ptr(out_p), _ptr(stats), None, 0, _stream()))
+    return ClosestResult(d2, face, out_uv, out_p)
+
+
+def ClosestOnMesh(query, mesh_or_grid, max_dist=None, stats=None, bbox=None, cells=None, uv=True, points=True, coherent=False):
     """For every point of query [nq, 3] the closest point on the surface of a Mesh or its FaceGrid -> ClosestResult (nrf_closest_on_mesh): the nearest face (on an
     exact tie the lowest index), the point on it, its (u, v) and the squared distance; +inf, -1 and zeros where no face lies within max_dist or the query is not
     finite.  A Mesh is binned first (FaceGrid(mesh, bbox, cells): two host synchronisations, one with a bbox); pass a FaceGrid to query the same mesh again without
     either.  uv=False / points=False leave that output out (None).  stats: an int32 [4] device tensor; entry 0 += non-finite queries, entry 3 += queries served by the
-    brute-force fallback."""
-    grid = mesh_or_grid if isinstance(mesh_or_grid, FaceGrid) else FaceGrid(mesh_or_grid, bbox=bbox, cells=cells, stats=stats)
+    brute-force fallback.  A MeshBVH in place of the FaceGrid gives the same bits (nrf_bvh_closest_on_mesh; entry 3 stays as it is: there is no fallback);
+    coherent=True then serves the queries in the order of their Morton codes (MeshBVH.Order), which changes no output."""
+    grid = mesh_or_grid if isinstance(mesh_or_grid, (FaceGrid, MeshBVH)) else FaceGrid(mesh_or_grid, bbox=bbox, cells=cells, stats=stats)
     q = _dev_f32(query).reshape(-1, 3).to(grid.Verts.device)
+    if isinstance(grid, MeshBVH):
+        return _bvh_closest(q.contiguous(), grid, max_dist, stats, uv, points, coherent)
     dev, nq = q.device, int(q.shape[0])
     d2 = torch.empty((nq,), device=dev, dtype=torch.float32)
     face = torch.empty((nq,), device=dev, dtype=torch.int32)
@@ -232,16 +290,16 @@ def DistanceStats(dist2, taus=()):
     return out
 
 
-def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_dist=None, bbox=None, source="vertex"):
+def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_dist=None, bbox=None, source="vertex", coherent=False):
     """A copy of dst_mesh whose attributes `names` are those of the nearest vertex of src_mesh (the ones src_mesh carries): TSDF colours onto an isosurface, relevancy
     onto another mesh.  A vertex without a neighbour (within max_dist) gets zeros.  source="surface" takes the attribute at the closest point ON src_mesh instead,
-    interpolated over its face (ClosestOnMesh; src_mesh may be a FaceGrid): what a coarse mesh needs from a dense one."""
+    interpolated over its face (ClosestOnMesh; src_mesh may be a FaceGrid or a MeshBVH, coherent as ClosestOnMesh's): what a coarse mesh needs from a dense one."""
     import dataclasses
     if source not in ("vertex", "surface"):
         raise L.NrfError(f"TransferAttributes: source must be 'vertex' or 'surface', got {source!r}")
     if source == "surface":
-        grid = src_mesh if isinstance(src_mesh, FaceGrid) else FaceGrid(src_mesh, bbox=bbox)
-        res = ClosestOnMesh(dst_mesh.Vertices, grid, max_dist=max_dist, points=False)
+        grid = src_mesh if isinstance(src_mesh, (FaceGrid, MeshBVH)) else FaceGrid(src_mesh, bbox=bbox)
+        res = ClosestOnMesh(dst_mesh.Vertices, grid, max_dist=max_dist, points=False, coherent=coherent)
         new = {name: InterpolateAttributes(grid.Mesh, res, name) for name in names if getattr(grid.Mesh, name) is not None}
         return dataclasses.replace(dst_mesh, **new)
     _, idx = NearestPoints(dst_mesh.Vertices, src_mesh.Vertices, max_dist=max_dist, bbox=bbox)
@@ -257,12 +315,13 @@ def TransferAttributes(src_mesh, dst_mesh, names=("Colors", "Relevancy"), max_di
     return dataclasses.replace(dst_mesh, **new)
 
 
-def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_dist=None, bbox=None, to="points", align=None):
+def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_dist=None, bbox=None, to="points", align=None, coherent=False):
     """How far apart two surfaces are, a the prediction and b the truth, each a Mesh (sampled: SampleSurface(n_points=n_points, seed=seed)) or a [N, 3] tensor of
     points (used as they are).  Returns a SurfaceDistanceResult of float64 device tensors.  With max_dist, points without a neighbour that near are left out of the
     means and count as misses in Precision / Recall.  bbox as in NearestPoints (None: two synchronisations, one per direction).
     to="surface" measures the samples of each side against the FACES of the other where that side is a Mesh (ClosestOnMesh: the exact point-to-triangle distance,
-    whose floor is zero, not the other side's sampling density); a side given as points is still searched as points.
+    whose floor is zero, not the other side's sampling density); a side given as points is still searched as points.  A side may also be a MeshBVH (or a FaceGrid)
+    of its mesh: it is sampled through its mesh and, with to="surface", searched through the structure as it is (coherent as ClosestOnMesh's).
     align: a nerfpp_amd.align.Transform moves side a into b's frame first (a Mesh through TransformMesh, points through Transform.Apply); "icp" finds that pose with
     align.RegisterICP(a, b) at its defaults (call it yourself for any other setting).  None, the default, measures the two sides as they are."""
     if len(taus) > STATS_MAX_TAU:
@@ -273,13 +332,15 @@ def SurfaceDistance(a, b, taus=(0.01, 0.02, 0.05), n_points=100000, seed=0, max_
         from . import align as A
         if isinstance(align, str) and align != "icp":
             raise L.NrfError(f"SurfaceDistance: align must be None, 'icp' or a Transform, got {align!r}")
-        pose = A.RegisterICP(a, b, method="plane" if isinstance(b, (M.Mesh, FaceGrid)) else "point").Transform if isinstance(align, str) else align
+        pose = A.RegisterICP(a, b, method="plane" if isinstance(b, (M.Mesh, FaceGrid, MeshBVH)) else "point").Transform if isinstance(align, str) else align
+        if isinstance(a, (FaceGrid, MeshBVH)):
+            a = a.Mesh          # a moved mesh needs a structure of its own
         a = A.TransformMesh(a, pose) if isinstance(a, M.Mesh) else pose.Apply(a)
-    pa, pb = _as_points(a, n_points, seed), _as_points(b, n_points, seed)
+    pa, pb = (_as_points(x.Mesh if isinstance(x, (FaceGrid, MeshBVH)) else x, n_points, seed) for x in (a, b))
 
     def dist2(p, other, other_points):
-        if to == "surface" and isinstance(other, M.Mesh):
-            return ClosestOnMesh(p, other, max_dist=max_dist, bbox=bbox, uv=False, points=False).Dist2
+        if to == "surface" and isinstance(other, (M.Mesh, FaceGrid, MeshBVH)):
+            return ClosestOnMesh(p, other, max_dist=max_dist, bbox=bbox, uv=False, points=False, coherent=coherent).Dist2
         return NearestPoints(p, other_points, max_dist=max_dist, bbox=bbox)[0]
     sa = DistanceStats(dist2(pa, b, pb), taus)
     sb = DistanceStats(dist2(pb, a, pa), taus)
@@ -312,7 +373,7 @@ class RayCastResult:                  # RayCastMesh's; InterpolateAttributes tak
 
 
 def _as_grid(mesh_or_grid, stats=None):
-    return mesh_or_grid if isinstance(mesh_or_grid, FaceGrid) else FaceGrid(mesh_or_grid, stats=stats)
+    return mesh_or_grid if isinstance(mesh_or_grid, (FaceGrid, MeshBVH)) else FaceGrid(mesh_or_grid, stats=stats)
 
 
 def _packed_rays(rays, near, far, dev, who):
@@ -332,7 +393,7 @@ def _packed_rays(rays, near, far, dev, who):
     return r.contiguous()
 
 
-def _ray_cast(who, rays, grid, cull, mode, uv, points, stats):
+def _ray_cast(who, rays, grid, cull, mode, uv, points, stats, coherent=False):
     if cull not in RC_CULL:
         raise L.NrfError(f"{who}: cull must be one of {sorted(RC_CULL)}, got {cull!r}")
     dev, n = rays.device, int(rays.shape[0])
@@ -343,6 +404,12 @@ def _ray_cast(who, rays, grid, cull, mode, uv, points, stats):
     out_p = torch.empty((n, 3), device=dev, dtype=torch.float32) if closest and points else None
     hit = None if closest else torch.empty((n,), device=dev, dtype=torch.uint8)
     lib = L.lib()
+    if isinstance(grid, MeshBVH):
+        order = grid.Order(rays, int(rays.shape[1])) if coherent and n else None          # by the rays' origins
+        L.check(lib.nrf_bvh_ray_cast_mesh(_ptr(rays), n, int(rays.shape[1]), _ptr(grid.Verts), int(grid.Verts.shape[0]), _ptr(grid.Faces), int(grid.Faces.shape[0]),
+                                          _ptr(grid.Buffer), grid.Buffer.numel(), _ptr(order), RC_CULL[cull], mode, _ptr(t), _ptr(face), _ptr(out_uv), _ptr(out_p),
+                                          _ptr(hit), _ptr(stats), None, 0, _stream()))
+        return t, face, out_uv, out_p, hit
     ws = _workspace(lib.nrf_ray_cast_workspace_bytes(n), dev)
     nx, ny, nz = grid.Dims
     L.check(lib.nrf_ray_cast_mesh(_ptr(rays), n, int(rays.shape[1]), _ptr(grid.Verts), int(grid.Verts.shape[0]), _ptr(grid.Faces), int(grid.Faces.shape[0]),
@@ -351,35 +418,37 @@ def _ray_cast(who, rays, grid, cull, mode, uv, points, stats):
     return t, face, out_uv, out_p, hit
 
 
-def RayCastMesh(rays, mesh_or_grid, near=0.0, far=float("inf"), cull="none", uv=True, points=True, stats=None):
+def RayCastMesh(rays, mesh_or_grid, near=0.0, far=float("inf"), cull="none", uv=True, points=True, stats=None, coherent=False):
     """The first face every ray hits on a Mesh or its FaceGrid -> RayCastResult (nrf_ray_cast_mesh, closest mode).  rays: the library's packed rows [n, >= 8]
     (o, d, near, far, ...: what BatchifyRays and AtlasTexels use; each row's own range holds and near / far here are ignored) or a pair (origins, dirs) with near / far
     scalars or [n].  d is not normalised and T is in units of d, the renderer's z.  The range is [max(near, 0), far]; on an exact tie in T the lowest face index;
     +inf, -1 and zeros on a miss, an empty range or an invalid ray.  cull: "none", "back" (only faces counter-clockwise seen from the origin, RenderMesh's "back") or
     "front".  A Mesh is binned first (FaceGrid(mesh): two host synchronisations); pass a FaceGrid to cast again without them.  A grid whose box does not hold the
-    mesh is still exact, through the brute-force fallback.  stats: an int32 [4] device tensor; entry 0 += invalid rays, entry 3 += rays served by the fallback."""
+    mesh is still exact, through the brute-force fallback.  stats: an int32 [4] device tensor; entry 0 += invalid rays, entry 3 += rays served by the fallback.
+    A MeshBVH in place of the FaceGrid gives the same bits without any fallback (nrf_bvh_ray_cast_mesh); coherent=True then serves the rays in the order of the
+    Morton codes of their origins, which changes no output."""
     grid = _as_grid(mesh_or_grid, stats)
     r = _packed_rays(rays, near, far, grid.Verts.device, "RayCastMesh")
-    t, face, out_uv, out_p, _ = _ray_cast("RayCastMesh", r, grid, cull, RC_CLOSEST, uv, points, stats)
+    t, face, out_uv, out_p, _ = _ray_cast("RayCastMesh", r, grid, cull, RC_CLOSEST, uv, points, stats, coherent)
     return RayCastResult(t, face, out_uv, out_p)
 
 
-def Occluded(rays, mesh_or_grid, near=0.0, far=float("inf"), cull="none", stats=None):
+def Occluded(rays, mesh_or_grid, near=0.0, far=float("inf"), cull="none", stats=None, coherent=False):
     """[n] bool: whether a ray hits anything within its range (nrf_ray_cast_mesh, any mode: the walk stops at the first face it meets).  Arguments as RayCastMesh's;
     the answer equals isfinite(RayCastMesh(...).T)."""
     grid = _as_grid(mesh_or_grid, stats)
     r = _packed_rays(rays, near, far, grid.Verts.device, "Occluded")
-    return _ray_cast("Occluded", r, grid, cull, RC_ANY, False, False, stats)[4].to(torch.bool)
+    return _ray_cast("Occluded", r, grid, cull, RC_ANY, False, False, stats, coherent)[4].to(torch.bool)
 
 
-def Visible(points_a, points_b, mesh_or_grid, eps=1e-4, stats=None):
+def Visible(points_a, points_b, mesh_or_grid, eps=1e-4, stats=None, coherent=False):
     """[n] bool: whether the segment from points_a[i] to points_b[i] is free of the mesh.  The ray is o = a, d = b - a with the range [eps, 1 - eps] in units of the
     segment's length, so a segment that starts or ends ON the surface is not blocked by that very surface.  A pair that coincides (d = 0) or is not finite is an
     invalid ray, a miss: reported visible and counted in stats[0]."""
     grid = _as_grid(mesh_or_grid, stats)
     dev = grid.Verts.device
     a, b = _dev_f32(points_a).reshape(-1, 3).to(dev), _dev_f32(points_b).reshape(-1, 3).to(dev)
-    return ~Occluded((a, b - a), grid, near=float(eps), far=1.0 - float(eps), stats=stats)
+    return ~Occluded((a, b - a), grid, near=float(eps), far=1.0 - float(eps), stats=stats, coherent=coherent)
 
 
 def HemisphereDirections(normals, k, seed=0, index0=0, stats=None):
@@ -403,7 +472,9 @@ def AmbientOcclusion(mesh, k=64, max_dist=None, offset=None, seed=0, grid=None, 
     `offset` above the point along its unit normal and is `max_dist` long; the defaults are AO_OFFSET = 1e-3 and AO_MAX_DIST = 0.25 of the diagonal of the grid's
     box: above the rounding of a hit's own surface, and the reach within which a wall darkens a corner.  grid: a FaceGrid of the occluding mesh (default:
     FaceGrid(mesh), two host synchronisations).  The value is an integer count over k, so it is exact; (seed, index0 + i, j) decide a direction, so slabs agree with
-    the whole.  A point with a zero or non-finite normal gets 1 and its k rays are counted in stats[0]; stats[3] += rays served by the fallback."""
+    the whole.  A point with a zero or non-finite normal gets 1 and its k rays are counted in stats[0]; stats[3] += rays served by the fallback.
+    grid=<MeshBVH>: the composition the header states equal to the fused call, HemisphereDirections and the BVH's any-hit cast slab by slab (the rays of a slab are
+    written); the default offset and max_dist then read the mesh box from the tree's head, one host synchronisation (pass both to avoid it)."""
     grid = FaceGrid(mesh, stats=stats) if grid is None else grid
     dev = grid.Verts.device
     if at is None:
@@ -419,6 +490,8 @@ def AmbientOcclusion(mesh, k=64, max_dist=None, offset=None, seed=0, grid=None, 
     off = AO_OFFSET * diag if offset is None else float(offset)
     md = AO_MAX_DIST * diag if max_dist is None else float(max_dist)
     n = int(pts.shape[0])
+    if isinstance(grid, MeshBVH):
+        return _bvh_ambient_occlusion(pts, nrm, int(k), off, md, int(seed), int(index0), grid, stats)
     ao = torch.empty((n,), device=dev, dtype=torch.float32)
     lib = L.lib()
     ws = _workspace(lib.nrf_ray_cast_workspace_bytes(n), dev)
@@ -429,7 +502,38 @@ def AmbientOcclusion(mesh, k=64, max_dist=None, offset=None, seed=0, grid=None, 
     return ao
 
 
-def ClipRaysToMesh(rays, mesh_or_grid, band, miss="keep", cull="none", stats=None):
+AO_SLAB_RAYS = 1 << 22          # rays of one slab of the composed ambient occlusion: 128 MiB of packed rows
+
+
+def _bvh_ambient_occlusion(pts, nrm, k, offset, max_dist, seed, index0, bvh, stats):
+    """nrf_mesh_ambient_occlusion's rays, formed as its header states them and cast through the BVH in any mode.  n-hat = n / sqrtf((nx*nx + ny*ny) + nz*nz) and
+    o = p + offset * n-hat in single fp32 tensor operations, each rounded once as the kernel's are"""
+    n, dev = int(pts.shape[0]), pts.device
+    if not max_dist >= 0.0:
+        raise L.NrfError(f"AmbientOcclusion: max_dist must be >= 0 or +inf (got {max_dist})")
+    if not math.isfinite(offset):
+        raise L.NrfError(f"AmbientOcclusion: offset must be finite (got {offset})")
+    ao = torch.empty((n,), device=dev, dtype=torch.float32)
+    kf = torch.full((), float(k), device=dev, dtype=torch.float32)
+    off = torch.full((), offset, device=dev, dtype=torch.float32)
+    per = max(1, AO_SLAB_RAYS // k)
+    for i0 in range(0, n, per):
+        p, nr = pts[i0:i0 + per], nrm[i0:i0 + per]
+        m = int(p.shape[0])
+        l2 = (nr[:, 0] * nr[:, 0] + nr[:, 1] * nr[:, 1]) + nr[:, 2] * nr[:, 2]
+        ok = torch.isfinite(nr).all(dim=1) & (l2 > 0) & torch.isfinite(l2)
+        nh = torch.where(ok[:, None], nr / torch.sqrt(torch.where(ok, l2, torch.ones_like(l2)))[:, None], torch.zeros_like(nr))
+        rays = torch.zeros((m, k, 8), device=dev, dtype=torch.float32)
+        rays[:, :, 0:3] = (p + off * nh)[:, None, :]
+        rays[:, :, 3:6] = HemisphereDirections(nr, k, seed=seed, index0=index0 + i0)
+        rays[:, :, 7] = max_dist
+        hit = _ray_cast("AmbientOcclusion", rays.reshape(-1, 8), bvh, "none", RC_ANY, False, False, stats)[4]
+        hits = hit.reshape(m, k).sum(dim=1, dtype=torch.int32)
+        ao[i0:i0 + per] = (k - hits).to(torch.float32) / kf
+    return ao
+
+
+def ClipRaysToMesh(rays, mesh_or_grid, band, miss="keep", cull="none", stats=None, coherent=False):
     """A copy of the packed rays [n, >= 8] whose ranges are narrowed around the mesh: on a hit at T, near = max(near, T - band) and far = min(far, T + band); on a miss
     the range is kept (miss="keep") or made empty (miss="empty": near 1, far 0).  band is in units of T, that is of each ray's own d (world units where d is a unit
     vector; BatchifyRays' z otherwise).  The result feeds BatchifyRays as it is: a mesh extracted at one iteration narrows the sampling of every later render."""
@@ -439,7 +543,7 @@ def ClipRaysToMesh(rays, mesh_or_grid, band, miss="keep", cull="none", stats=Non
         raise L.NrfError("ClipRaysToMesh: pass packed rays [n, >= 8]; a pair of origins and directions has no range to narrow")
     grid = _as_grid(mesh_or_grid, stats)
     r = _packed_rays(rays, 0.0, 0.0, grid.Verts.device, "ClipRaysToMesh")
-    t = _ray_cast("ClipRaysToMesh", r, grid, cull, RC_CLOSEST, False, False, stats)[0]
+    t = _ray_cast("ClipRaysToMesh", r, grid, cull, RC_CLOSEST, False, False, stats, coherent)[0]
     out = r.clone()
     hit = torch.isfinite(t)
     b = torch.as_tensor(band, dtype=torch.float32, device=r.device)

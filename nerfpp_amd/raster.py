@@ -85,7 +85,7 @@ def RayCastView(mesh, pose, W, H, K, near=0.0, far=float("inf"), cull="none", st
     the screen-space ones.  Unlike the rasteriser it has no near plane or guard band and sees faces behind other cameras' clip limits."""
     from . import geometry as G
     from .renderer import GetRays
-    grid = mesh if isinstance(mesh, G.FaceGrid) else G.FaceGrid(mesh, stats=stats)
+    grid = mesh if isinstance(mesh, (G.FaceGrid, G.MeshBVH)) else G.FaceGrid(mesh, stats=stats)
     h, w = int(H), int(W)
     o, d, _ = GetRays(h, w, _k9(K), _m12(pose).reshape(3, 4), device=grid.Verts.device)
     res = G.RayCastMesh((o.reshape(-1, 3), d.reshape(-1, 3)), grid, near=near, far=far, cull=cull, points=False, stats=stats)

@@ -92,8 +92,8 @@ def _colour_source(source, mode, rparams, offset, attribute="Colors", max_dist=N
     from .mesh import Mesh
     from .renderer import LeRFRenderer, NeRFRenderer
     from .tsdf import TSDFVolume
-    if isinstance(source, (Mesh, G.FaceGrid)):
-        grid = source if isinstance(source, G.FaceGrid) else G.FaceGrid(source)          # binned once per bake
+    if isinstance(source, (Mesh, G.FaceGrid, G.MeshBVH)):
+        grid = source if isinstance(source, (G.FaceGrid, G.MeshBVH)) else G.FaceGrid(source)          # binned once per bake
         if attribute not in ("Colors", "Relevancy") or getattr(grid.Mesh, attribute) is None:
             raise L.NrfError(f"BakeTexture: the source mesh has no {attribute!r} to bake (attribute is 'Colors' or 'Relevancy')")
 

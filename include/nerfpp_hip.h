@@ -1454,6 +1454,89 @@ NRF_API int nrf_bvh_ray_cast_mesh(const float *d_rays, int64_t n_rays, int strid
                                   float *d_point, uint8_t *d_hit, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes, void *stream);
 NRF_API int nrf_bvh_point_codes(const float *d_points, int64_t n, int stride, const void *d_bvh, size_t bvh_bytes, int64_t n_faces, uint32_t *d_codes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Point clouds (points.hip, bvh.hip, align.hip; no counterpart in the reference)
+ * ------------------------------------------------------------------------------------------- */
+/* What a scan, a COLMAP cloud or unprojected depth needs and a mesh tool cannot give: a hierarchy over the points themselves, the k nearest neighbours of every
+ * query, normals and local shape from them, outlier scores, and the plane-mode sums of the registration from given normals.  Conventions as above: fp32 operations
+ * rounded once each, caller-owned buffers, refusals before any launch or write, two runs the same bytes; every result is defined without the structure and
+ * tests/points_ref.py restates it bit for bit.
+ *
+ * BUILD.  nrf_point_bvh_build over d_points [n, 3] fills a buffer of nrf_point_bvh_bytes(n) (== nrf_mesh_bvh_bytes(n)) bytes with a workspace of
+ *   nrf_point_bvh_workspace_bytes(n).  DEFINITION: apart from its first word, "NRFPBV01" (0x4e52465042563031), the buffer is byte for byte what nrf_mesh_bvh_build
+ *   writes for verts = d_points and the n faces (i, i, i).  So the leaf box is the point, its code comes from c = p * 0.5f + p * 0.5f, a point with a non-finite
+ *   coordinate is not valid (code 2^30, sorted last, d_stats[2] += 1; d_stats [4] uint32 or NULL, entry 1 is never touched), and everything the Mesh BVH section
+ *   states of classes, box, codes, leaves, topology, depth, boxes and layout holds with "point" for "face"; tests/bvh_ref.py restates the tree as it is.  It is the
+ *   same kernels with another leaf source: no face array exists, no host round trip.  nrf_point_bvh_codes is nrf_bvh_point_codes against the box of a point buffer
+ *   (d_order for nrf_bvh_knn, as SPATIAL ORDER describes).  The two magics keep a mesh buffer out of the point queries and the reverse.
+ *   REFUSED: n outside [0, 2^31 - 1], a null (n > 0) or misaligned d_points, a null or misaligned (64 bytes) buffer, a size that is not nrf_point_bvh_bytes(n), a
+ *   null, misaligned (8 bytes) or short workspace.
+ *
+ * K NEAREST.  nrf_bvh_knn, 1 <= k <= NRF_KNN_MAX_K.  d2(q, j) is the squared distance of nrf_nearest_points: dx = qx - px, .., d2 = (dx*dx + dy*dy) + dz*dz.  For a
+ *   finite query i the candidates are the points j with finite coordinates, d2 <= fl(max_dist * max_dist), and -- exclude_self == 1 -- j != i (the query IS point i
+ *   of the cloud).  Slots 0 .. k - 1 of row i of d_dist2 / d_index [nq, k] hold, ascending, the k smallest keys (bits(d2) << 32) | j over the candidates, as d2 and j;
+ *   slots past the last candidate hold +inf / -1; d_count [nq] (or NULL) the number of filled slots.  A non-finite query: every slot empty, count 0,
+ *   d_stats[0] += 1 (d_stats [4] uint32 or NULL; nothing else is touched).  The same bits whatever the tree, d_order or the scheduling; with k == 1 and
+ *   exclude_self == 0 the outputs are those of nrf_nearest_points bit for bit.  d_order as for the mesh queries.  The workspace pair is accepted as it comes
+ *   (nrf_bvh_query_workspace_bytes is 0).
+ *   Traversal.  As nrf_bvh_closest_on_mesh: one lane per query, a stack of NRF_BVH_MAX_DEPTH node indices, the child with the smaller b2 first.  A child is SKIPPED
+ *   iff b2 > min(d2 of the k-th best key held, fl(max_dist^2)), strictly; the k-th best is +inf until k candidates are held.  An equal bound descends, so a lower
+ *   index still displaces an equal distance.
+ *   WHY IT IS EXACT.  For a point leaf lo == hi == p: q < p gives g = fl(p - q) = -fl(q - p), q > p gives g = fl(q - p), q == p gives g = 0 = |fl(q - p)| (rounding
+ *   is odd), so g*g == dx*dx per axis and the same two sums follow: b2 == d2 bit for bit, and the traversal takes the bound of a leaf child as the candidate's d2.
+ *   For an ancestor the monotonicity argument of the mesh query applies unchanged (p lies inside every ancestor's box): b2 <= d2.  A candidate that belongs to the
+ *   result has a key <= the k-th best key held at any time, so d2 <= its value and d2 <= fl(max_dist^2): no ancestor is skipped.
+ *   The list.  k keys in registers, instantiated for 1, 8, 16 and 32 entries (the smallest that holds k), kept in descending order by an unrolled compare-and-select
+ *   insertion: no indexed private array, no LDS (DESIGN 8u has the compiler's resource figures).
+ *
+ * NORMALS.  nrf_points_normals: d_index [n, k] is what nrf_bvh_knn wrote for the cloud against itself with exclude_self == 1.  For point i the set is i itself, then
+ *   the slots of row i with 0 <= index < n in slot order; m its size.  All values converted to fp64 first.  mean = (the sum in that order from p_i) / m per
+ *   component; with d = x - mean, the six sums cxx, cxy, cxz, cyy, cyz, czz of d_a*d_b in the same order from the first term.  Cyclic Jacobi on the symmetric 3x3 with
+ *   V = I: NRF_POINTS_JACOBI_SWEEPS sweeps over the pairs (0,1), (0,2), (1,2), the rotation of nrf_align_solve verbatim (a zero off-diagonal is skipped, the
+ *   NRF_ALIGN_JACOBI_BIG_THETA branch, columns of A, rows of A, columns of V).  Eigenvalues l0 <= l1 <= l2 = the diagonal ascending, the lowest column first on a
+ *   tie.  The normal is column l0 of V divided by sqrt((x*x + y*y) + z*z) per component, its sign chosen in fp64, then rounded to fp32 once.  SIGN: with d_toward
+ *   (toward_stride 0: one viewpoint [3]; 3: one per point [n, 3]) negated where dot(n, toward - p_i) < 0 (the dot of the registration, the difference in fp64);
+ *   without, negated where the component of largest magnitude (the lowest axis on a tie) is negative.  Orientation by propagation is not offered.
+ *   DEGENERATE: m < 3, a non-finite coordinate in the set, a non-finite eigenvalue or norm, a norm that is not > 0, or l1 > 0 false (coincident or collinear
+ *   points): the normal and the eigenvalues are zeros and d_stats[0] += 1 (d_stats [1] uint32 or NULL).  d_eigen [n, 3] (or NULL) gets (float)l0, l1, l2: sums, not
+ *   divided by m; surface variation is l0 / (l0 + l1 + l2).
+ *   NRF_POINTS_JACOBI_SWEEPS.  Census over every neighbourhood of the test clouds (tests/test_points_host.py: 3 372 sets at k = 8 and 16): the largest
+ *   off-diagonal magnitude relative to the largest diagonal magnitude, worst set after sweeps 1 .. 6: 3.2e-1, 3.4e-2, 9.5e-7, 1.9e-22, 3.2e-38, 1.3e-54.  It stays
+ *   below 1e-16 on every set from sweep 4 on; the constant is that count plus a margin of 2 (a sweep converges quadratically and costs three rotations).
+ *
+ * SCORES.  nrf_knn_mean_distance: s_i = (the fp32 sum from 0 of sqrtf(d2) over the slots of row i with d2 < +inf, in slot order) / (float)count; +inf where none.
+ *   count here is the number of slots with d2 < +inf, read from d_dist2 alone.  It can be BELOW nrf_bvh_knn's d_count: with max_dist = +inf a d2 that overflows to
+ *   +inf (coordinates apart by about 1e19 or more) fills a slot with a valid index, which d_count counts and the score leaves out.
+ *   nrf_value_stats: d_out [4] doubles = count, sum of (double)v, sum of (double)v * (double)v and max(0, largest v) over the finite entries of d_values [n], in the
+ *   order of nrf_distance_stats (4 096 entries per block, the ordered sum); no atomics, no synchronisation.  Workspace: nrf_value_stats_workspace_bytes(n), 8-byte aligned.
+ *
+ * PLANE SUMS FROM GIVEN NORMALS.  nrf_align_sums_normals forms the 37 columns of NRF_ALIGN_PLANE in the same order into the same workspace
+ *   (nrf_align_workspace_bytes(n, NRF_ALIGN_PLANE)); nrf_align_solve follows unchanged.  Pair i is (d_y[i], d_p[i]) with the normal d_n[i] [n, 3], already
+ *   gathered for the pair; d_index[i] < 0: no pair (d_stats[0]); a non-finite y or p: [1]; c = the converted d_n[i], len2 = (cx*cx + cy*cy) + cz*cz; len2 > 0 false
+ *   or len2 not finite: [3]; n = c / sqrt(len2).  [2] is never touched.  The SIGN of a normal changes no column: the row a and the residual r are both odd in n, and
+ *   every column is a product of two of them (or constant); negation is exact.
+ *
+ * REFUSED (nothing launched or written): a count or k out of range, an exclude_self or toward_stride outside its values, a negative or NaN max_dist, a required
+ *   pointer that is null, a pointer not aligned to its element, a buffer of the wrong size; a buffer with the wrong magic or head is read no further and nothing is
+ *   written. */
+#define NRF_KNN_MAX_K 32
+#define NRF_POINTS_JACOBI_SWEEPS 6
+NRF_API size_t nrf_point_bvh_bytes(int64_t n);
+NRF_API size_t nrf_point_bvh_workspace_bytes(int64_t n);
+NRF_API int nrf_point_bvh_build(const float *d_points, int64_t n, void *d_bvh, size_t bvh_bytes, uint32_t *d_stats, void *d_workspace, size_t workspace_bytes,
+                                void *stream);
+NRF_API int nrf_point_bvh_codes(const float *d_query, int64_t nq, int stride, const void *d_bvh, size_t bvh_bytes, int64_t n, uint32_t *d_codes, void *stream);
+NRF_API int nrf_bvh_knn(const float *d_query, int64_t nq, const float *d_points, int64_t n, const void *d_bvh, size_t bvh_bytes, const int32_t *d_order, int k,
+                        float max_dist, int exclude_self, float *d_dist2, int32_t *d_index, int32_t *d_count, uint32_t *d_stats, void *d_workspace,
+                        size_t workspace_bytes, void *stream);
+NRF_API int nrf_points_normals(const float *d_points, int64_t n, const int32_t *d_index, int k, const float *d_toward, int toward_stride, float *d_normals,
+                               float *d_eigen, uint32_t *d_stats, void *stream);
+NRF_API int nrf_knn_mean_distance(const float *d_dist2, int64_t n, int k, float *d_score, void *stream);
+NRF_API size_t nrf_value_stats_workspace_bytes(int64_t n);
+NRF_API int nrf_value_stats(const float *d_values, int64_t n, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+NRF_API int nrf_align_sums_normals(const float *d_y, const float *d_p, const float *d_n, const int32_t *d_index, int64_t n, uint32_t *d_stats, void *d_workspace,
+                                   size_t workspace_bytes, void *stream);
+
 /* RenderRays (NeRFRenderer.h:366-459) over one chunk of n packed rays [n, 8 | 11].
  * d_t: [n_samples] linspace(0,1,n_samples); d_u: [n_importance] linspace(0,1,n_importance). */
 NRF_API size_t nrf_render_rays_workspace_bytes(const nrf_renderer *r, int64_t n, const nrf_render_params *p);

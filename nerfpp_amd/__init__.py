@@ -6,12 +6,12 @@ compute call does, and raises if it has not been built (there is no CPU fallback
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "modules", "renderer", "scene", "mesh", "tsdf", "raster", "texture", "geometry", "voxel", "align", "query", "metrics"]
+__all__ = ["synth", "modules", "renderer", "scene", "mesh", "tsdf", "raster", "texture", "geometry", "voxel", "align", "points", "query", "metrics"]
 
 
 def __getattr__(name):
     import importlib
-    if name in ("modules", "renderer", "scene", "_lib", "dist", "mesh", "tsdf", "raster", "texture", "geometry", "voxel", "align", "query", "metrics"):
+    if name in ("modules", "renderer", "scene", "_lib", "dist", "mesh", "tsdf", "raster", "texture", "geometry", "voxel", "align", "points", "query", "metrics"):
         return importlib.import_module(f"{__name__}.{name}")
     for mod in ("modules", "renderer"):
         m = importlib.import_module(f"{__name__}.{mod}")

@@ -246,6 +246,16 @@ _ABI = """
     nrf_bvh_closest_on_mesh(plplplpzpfppppppzp)
     nrf_bvh_ray_cast_mesh(pliplplpzpiipppppppzp)
     nrf_bvh_point_codes(plipzlpp)
+    nrf_point_bvh_bytes(l)->z
+    nrf_point_bvh_workspace_bytes(l)->z
+    nrf_point_bvh_build(plpzppzp)
+    nrf_point_bvh_codes(plipzlpp)
+    nrf_bvh_knn(plplpzpifipppppzp)
+    nrf_points_normals(plpipipppp)
+    nrf_knn_mean_distance(plipp)
+    nrf_value_stats_workspace_bytes(l)->z
+    nrf_value_stats(plppzp)
+    nrf_align_sums_normals(pppplppzp)
     nrf_render_rays_workspace_bytes(plp)->z
     nrf_render_rays(ppilpppppzp)
     nrf_batchify_rays_workspace_bytes(plip)->z

@@ -15,6 +15,7 @@ import torch
 from . import _lib as L
 from . import geometry as G
 from . import mesh as M
+from . import points as P
 from .modules import _ptr, _stream, _dev_f32
 
 ALIGN_POINT, ALIGN_PLANE = L.NRF_ALIGN_POINT, L.NRF_ALIGN_PLANE
@@ -110,11 +111,16 @@ def _workspace(n, mode, dev):
     return torch.empty((max(1, int(L.lib().nrf_align_workspace_bytes(int(n), mode))),), device=dev, dtype=torch.uint8)
 
 
-def _sums_solve(y, p, face, mode, scale, grid, state, history, iteration, ws, stats=None):
+def _sums_solve(y, p, face, mode, scale, grid, state, history, iteration, ws, stats=None, normals=None):
+    """One update from the pairs (y, p): the sums, then the solve.  normals [n, 3]: plane mode with the normal of each pair given (nrf_align_sums_normals; `face`
+    only says by its sign whether there is a pair), else nrf_align_sums with the faces of `grid`"""
     lib, n = L.lib(), int(y.shape[0])
-    verts, faces = (grid.Verts, grid.Faces) if grid is not None else (None, None)
-    L.check(lib.nrf_align_sums(_ptr(y), _ptr(p), _ptr(face), n, mode, _ptr(verts), 0 if verts is None else int(verts.shape[0]), _ptr(faces),
-                               0 if faces is None else int(faces.shape[0]), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    if normals is not None:
+        L.check(lib.nrf_align_sums_normals(_ptr(y), _ptr(p), _ptr(normals), _ptr(face), n, _ptr(stats), _ptr(ws), ws.numel(), _stream()))
+    else:
+        verts, faces = (grid.Verts, grid.Faces) if grid is not None else (None, None)
+        L.check(lib.nrf_align_sums(_ptr(y), _ptr(p), _ptr(face), n, mode, _ptr(verts), 0 if verts is None else int(verts.shape[0]), _ptr(faces),
+                                   0 if faces is None else int(faces.shape[0]), _ptr(stats), _ptr(ws), ws.numel(), _stream()))
     L.check(lib.nrf_align_solve(n, mode, int(bool(scale)), int(iteration), int(history.shape[0]), _ptr(state), _ptr(history), _ptr(ws), ws.numel(), _stream()))
 
 
@@ -134,7 +140,7 @@ def AlignPoints(src, dst, scale=False):
 
 
 def RegisterICP(source, target, init=None, iterations=30, max_dist=None, method="plane", scale=False, n_points=20000, seed=0, tolerance=None, check_every=5,
-                stats=None, coherent=False):
+                stats=None, coherent=False, target_normals=None):
     """Iterative closest point: the pose that brings `source` onto `target` -> RegistrationResult.
     source: a Mesh (sampled once: SampleSurface(n_points=n_points, seed=seed)) or points [n, 3].  target: a Mesh, a FaceGrid or a MeshBVH (queried through ClosestOnMesh, coherent
     as there; a Mesh is binned once, over the box of its vertices) or points [m, 3] (NearestPoints over the box of the points, method="point" only).
@@ -143,7 +149,10 @@ def RegisterICP(source, target, init=None, iterations=30, max_dist=None, method=
     init: a Transform to start from (default: the identity); it is not modified.  max_dist: pairs farther apart are left out; a scalar or one value per iteration, a
     coarse-to-fine schedule.  Each iteration is apply -> closest -> sums -> solve on the current stream.  tolerance=None synchronises nothing; otherwise the host
     reads the history after every check_every iterations and stops once the last update's angle (radians) and shift are both below the tolerance.
-    stats: an int32 [4] device tensor the dropped pairs are added to (no pair within max_dist, non-finite, bad face, face without a normal)."""
+    stats: an int32 [4] device tensor the dropped pairs are added to (no pair within max_dist, non-finite, bad face, face without a normal).
+    target_normals: with a target given as points, a [m, 3] tensor of its normals or "estimate" (points.EstimateNormals at its defaults) lets it take
+    method="plane": the target is searched through a points.PointBVH built once (no box, no host synchronisation; coherent as KNearest's) and the update comes from
+    nrf_align_sums_normals, the plane sums with the matched point's normal.  The sign of a normal changes nothing.  Without it, a cloud takes method="point" only."""
     if method not in _METHODS:
         raise L.NrfError(f"RegisterICP: method must be 'plane' or 'point', got {method!r}")
     mode = _METHODS[method]
@@ -155,14 +164,27 @@ def RegisterICP(source, target, init=None, iterations=30, max_dist=None, method=
         raise L.NrfError(f"RegisterICP: {len(dists)} values of max_dist for {iterations} iterations")
     src = G.SampleSurface(source, n_points=n_points, seed=seed).Points if isinstance(source, M.Mesh) else _dev_f32(source).reshape(-1, 3)
     dev, n = src.device, int(src.shape[0])
-    grid = points = box = None
+    grid = points = box = pbvh = normals = None
     if isinstance(target, (M.Mesh, G.FaceGrid, G.MeshBVH)):
         grid = target if isinstance(target, (G.FaceGrid, G.MeshBVH)) else G.FaceGrid(target)
     else:
-        if mode != ALIGN_POINT:
+        if mode != ALIGN_POINT and target_normals is None:
             raise L.NrfError("RegisterICP: method='plane' needs the faces of the target; a target given as points takes method='point'")
         points = _dev_f32(target).reshape(-1, 3).to(dev)
-        box = G._bbox_of(points)
+        if target_normals is None:
+            box = G._bbox_of(points)
+        else:
+            if mode != ALIGN_PLANE:
+                raise L.NrfError("RegisterICP: target_normals belongs to method='plane'")
+            pbvh = P.PointBVH(points)
+            if isinstance(target_normals, str):
+                if target_normals != "estimate":
+                    raise L.NrfError(f"RegisterICP: target_normals must be a [m, 3] tensor or 'estimate', got {target_normals!r}")
+                normals = P.EstimateNormals(points, bvh=pbvh).Normals
+            else:
+                normals = _dev_f32(target_normals).reshape(-1, 3).to(dev)
+                if normals.shape[0] != points.shape[0]:
+                    raise L.NrfError(f"RegisterICP: {int(normals.shape[0])} target_normals for {int(points.shape[0])} target points")
     state = Transform(device=dev).State if init is None else init.State.to(dev).clone()
     history = torch.zeros((iterations, 8), device=dev, dtype=torch.float64)
     ws = _workspace(n, mode, dev)
@@ -171,13 +193,18 @@ def RegisterICP(source, target, init=None, iterations=30, max_dist=None, method=
     done = iterations
     for it in range(iterations):
         moved.Apply(src, out=y)
+        nrm = None
         if grid is not None:
             res = G.ClosestOnMesh(y, grid, max_dist=dists[it], uv=False, coherent=coherent)
             p, face = res.Points, res.Face
+        elif pbvh is not None:
+            face = P.KNearest(y, pbvh, 1, max_dist=dists[it], coherent=coherent).Index.reshape(-1)
+            at = face.clamp(min=0).to(torch.int64)
+            p, nrm = (points[at], normals[at]) if points.shape[0] else (torch.zeros_like(y), torch.zeros_like(y))
         else:
             _, face = G.NearestPoints(y, points, max_dist=dists[it], bbox=box)
             p = points[face.clamp(min=0).to(torch.int64)] if points.shape[0] else torch.zeros_like(y)
-        _sums_solve(y, p, face, mode, scale, grid, state, history, it, ws, stats)
+        _sums_solve(y, p, face, mode, scale, grid, state, history, it, ws, stats, normals=nrm)
         if tolerance is not None and (it + 1) % int(check_every) == 0:
             row = history[it].cpu().numpy()
             if row[H_ANGLE] < tolerance and row[H_SHIFT] < tolerance:

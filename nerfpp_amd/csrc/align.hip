@@ -92,7 +92,9 @@ __global__ void __launch_bounds__(ALIGN_BLOCK) k_align_apply(const float *points
     out[i * 3 + 2] = y[2];
 }
 
-template <int MODE>
+// GIVEN (plane mode only): the normal of pair i is verts[i] -- the caller's d_n, one per pair -- not the cross product of face[i]'s corners; face is any index whose
+// sign says whether there is a pair (nrf_align_sums_normals)
+template <int MODE, bool GIVEN = false>
 __global__ void __launch_bounds__(ALIGN_BLOCK) k_align_sums(const float *__restrict__ ym, const float *__restrict__ pm, const int32_t *__restrict__ face, int64_t n,
                                                             const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces,
                                                             double *__restrict__ partials, uint32_t *__restrict__ stats)
@@ -129,13 +131,18 @@ __global__ void __launch_bounds__(ALIGN_BLOCK) k_align_sums(const float *__restr
             acc[17] += dot3(p, p);
             acc[18] += dot3(d, d);
         } else {
-            float fa[3], fb[3], fc[3];
-            if (cm_face(verts, n_verts, faces, n_faces, f, fa, fb, fc) != 0) { drop[2]++; continue; }
-            const double e1[3] = {(double)fb[0] - (double)fa[0], (double)fb[1] - (double)fa[1], (double)fb[2] - (double)fa[2]};
-            const double e2[3] = {(double)fc[0] - (double)fa[0], (double)fc[1] - (double)fa[1], (double)fc[2] - (double)fa[2]};
-            const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+            double cx, cy, cz;
+            if (GIVEN) {
+                cx = (double)verts[i * 3 + 0]; cy = (double)verts[i * 3 + 1]; cz = (double)verts[i * 3 + 2];
+            } else {
+                float fa[3], fb[3], fc[3];
+                if (cm_face(verts, n_verts, faces, n_faces, f, fa, fb, fc) != 0) { drop[2]++; continue; }
+                const double e1[3] = {(double)fb[0] - (double)fa[0], (double)fb[1] - (double)fa[1], (double)fb[2] - (double)fa[2]};
+                const double e2[3] = {(double)fc[0] - (double)fa[0], (double)fc[1] - (double)fa[1], (double)fc[2] - (double)fa[2]};
+                cx = e1[1] * e2[2] - e1[2] * e2[1]; cy = e1[2] * e2[0] - e1[0] * e2[2]; cz = e1[0] * e2[1] - e1[1] * e2[0];
+            }
             const double len2 = (cx * cx + cy * cy) + cz * cz;
-            if (!(len2 > 0.0)) { drop[3]++; continue; }
+            if (!(len2 > 0.0) || (GIVEN && !isfinite(len2))) { drop[3]++; continue; }
             const double len = sqrt(len2);
             const double nn[3] = {cx / len, cy / len, cz / len};
             const double r = dot3(nn, d);
@@ -404,6 +411,23 @@ int nrf_align_sums(const float *d_y, const float *d_p, const int32_t *d_face, in
     else
         hipLaunchKernelGGL(k_align_sums<NRF_ALIGN_PLANE>, grid, dim3(ALIGN_BLOCK), 0, st, d_y, d_p, d_face, n, d_verts, (int32_t)n_verts, d_faces, n_faces, ws.partials,
                            d_stats);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
+
+int nrf_align_sums_normals(const float *d_y, const float *d_p, const float *d_n, const int32_t *d_index, int64_t n, uint32_t *d_stats, void *d_workspace,
+                           size_t workspace_bytes, void *stream)
+{
+    NRF_CHECK_ARG(n >= 0 && n <= INT32_MAX, "nrf_align_sums_normals: %lld pairs (0 .. 2^31 - 1)", (long long)n);
+    NRF_CHECK_ARG(n == 0 || (d_y && d_p && d_n && d_index), "nrf_align_sums_normals: null d_y, d_p, d_n or d_index");
+    NRF_CHECK_ARG(aligned_to(d_y, 4) && aligned_to(d_p, 4) && aligned_to(d_n, 4) && aligned_to(d_index, 4) && aligned_to(d_stats, 4),
+                  "nrf_align_sums_normals: d_y, d_p, d_n, d_index and d_stats must be 4-byte aligned");
+    NRF_CHECK_ARG(d_workspace && aligned_to(d_workspace, 8), "nrf_align_sums_normals: the workspace must be non-null and 8-byte aligned");
+    Bump bump(d_workspace, workspace_bytes);
+    const AlignWs ws = align_layout(bump, n, NRF_ALIGN_PLANE);
+    NRF_TRY(ws_check(bump, nrf_align_workspace_bytes(n, NRF_ALIGN_PLANE), "nrf_align_sums_normals"));
+    hipLaunchKernelGGL((k_align_sums<NRF_ALIGN_PLANE, true>), dim3((unsigned)align_blocks(n)), dim3(ALIGN_BLOCK), 0, as_stream(stream), d_y, d_p, d_index, n, d_n, 0,
+                       (const int32_t *)nullptr, (int64_t)0, ws.partials, d_stats);
     NRF_LAUNCH_CHECK();
     return NRF_OK;
 }

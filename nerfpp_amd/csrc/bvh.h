@@ -11,6 +11,7 @@
 namespace nrf {
 
 constexpr long long BVH_MAGIC = 0x4e52464256483031ll;          // "NRFBVH01": the first word of a built buffer
+constexpr long long PBVH_MAGIC = 0x4e52465042563031ll;         // "NRFPBV01": the first word of a buffer built over points (nrf_point_bvh_build); every other byte is the mesh build's
 constexpr uint32_t BVH_CODE_INVALID = 1u << 30;                // the code of a face that is not valid: above every 30-bit code, so such faces sort last
 
 struct BvhNode {             // 64 bytes: one fetch brings both children's boxes
@@ -42,9 +43,9 @@ struct BvhTree {
     float lo[3], hi[3];
 };
 
-__device__ __forceinline__ bool bvh_head_read(const long long *__restrict__ head, int64_t n_faces, BvhTree &t)
+__device__ __forceinline__ bool bvh_head_read(const long long *__restrict__ head, int64_t n_faces, BvhTree &t, long long magic = BVH_MAGIC)
 {
-    if (head[0] != BVH_MAGIC || head[1] != (long long)n_faces) return false;
+    if (head[0] != magic || head[1] != (long long)n_faces) return false;
     t.n_valid = head[2];
     if (t.n_valid < 0 || t.n_valid > n_faces) return false;
 #pragma unroll
@@ -54,6 +55,15 @@ __device__ __forceinline__ bool bvh_head_read(const long long *__restrict__ head
         t.hi[a] = __uint_as_float((uint32_t)(w >> 32));
     }
     return true;
+}
+
+// a node as four 16-byte reads
+__device__ __forceinline__ void bvh_node_load(const BvhNode *__restrict__ node, int32_t i, BvhNode &n)
+{
+    const float4 *src = reinterpret_cast<const float4 *>(node + i);
+    float4 *dst = reinterpret_cast<float4 *>(&n);
+#pragma unroll
+    for (int k = 0; k < 4; k++) dst[k] = src[k];
 }
 
 // the image of a float whose unsigned order is the float's order (-0 below +0); finite inputs only
@@ -123,5 +133,13 @@ __device__ __forceinline__ bool bvh_box_ray(const RcRay &r, const float lo[3], c
     t_in = t0;
     return t0 <= t1;
 }
+
+// ---- what bvh.hip offers points.hip: the one copy of the build and of the code kernel, over either leaf source (host side; defined in bvh.hip) ----
+// points == false: leaf f is face d_faces[f] of d_verts, the head says BVH_MAGIC.  points == true: leaf f is the point d_verts[f] (d_faces unused, n_verts == n_leaves),
+// the head says PBVH_MAGIC; every other byte is what the face build writes for faces [[i, i, i]].  The caller has checked its arguments; the workspace is checked here
+size_t bvh_build_workspace_bytes(int64_t n_leaves);
+int bvh_build_launch(bool points, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_leaves, void *d_bvh, size_t bvh_bytes, uint32_t *d_stats,
+                     void *d_workspace, size_t workspace_bytes, hipStream_t st, const char *who);
+int bvh_point_codes_launch(const float *d_points, int64_t n, int stride, const void *d_bvh, int64_t n_leaves, long long magic, uint32_t *d_codes, hipStream_t st);
 
 }  // namespace nrf

@@ -8,6 +8,8 @@
 //   lane per internal node) -> NRF_BVH_MAX_DEPTH launches of k_bvh_refit.  A refit launch finishes the nodes whose children were finished by EARLIER launches and marks
 //   them with its pass number; a mark of the current pass counts as not finished, so no launch reads what the same launch wrote and nothing is handed over between
 //   workgroups.  The device's count of unfinished nodes lets the launches after the last level return after one load per block.
+//   The build kernels are templates over the LEAF SOURCE (bvh_leaf<POINTS>): a face of a mesh, or -- nrf_point_bvh_build, points.hip -- the point itself, which is
+//   what the face (i, i, i) gives; bvh_build_launch / bvh_point_codes_launch (bvh.h) are the one copy both entries run.
 // Queries: one lane per query (ray), a private stack of NRF_BVH_MAX_DEPTH node indices, the nearer child first; a child is skipped only by a proven lower bound.
 #include "reduce.h"
 #include "scan.h"
@@ -54,6 +56,19 @@ __device__ __forceinline__ void face_box(const float a[3], const float b[3], con
     }
 }
 
+// the leaf source: the corners of leaf f and its class.  A face (cm_face), or -- POINTS -- the point verts[f] as all three corners: what cm_face gives for the
+// face (f, f, f), without a face array (class 2: a non-finite coordinate; f is always inside)
+template <bool POINTS>
+__device__ __forceinline__ int bvh_leaf(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, int64_t f, float a[3], float b[3],
+                                        float c[3])
+{
+    if (!POINTS) return cm_face(verts, n_verts, faces, n_faces, f, a, b, c);
+    if (f < 0 || f >= n_faces) return 1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) a[k] = b[k] = c[k] = verts[f * 3 + k];
+    return finite3(a) ? 0 : 2;
+}
+
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 {
 #pragma unroll
@@ -68,6 +83,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 }
 
 // classes into stats[1], [2]; n_valid; the mesh box as the integer minimum / maximum of the corner images (exact and order-free)
+template <bool POINTS>
 __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_classify(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces,
                                                             uint32_t *__restrict__ box, uint32_t *__restrict__ stats)
 {
@@ -77,7 +93,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_classify(const float *__restr
     uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
     if (f < n_faces) {
         float a[3], b[3], c[3];
-        cls = cm_face(verts, n_verts, faces, n_faces, f, a, b, c);
+        cls = bvh_leaf<POINTS>(verts, n_verts, faces, n_faces, f, a, b, c);
         if (cls == 0) {
 #pragma unroll
             for (int k = 0; k < 3; k++) {
@@ -119,6 +135,7 @@ __device__ __forceinline__ void bvh_tree_from_ws(const uint32_t *__restrict__ bo
 }
 
 // the head, and the code of every face: the centre of its coordinate box, lo * 0.5f + hi * 0.5f per axis, against the mesh box
+template <bool POINTS>
 __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_codes(const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces,
                                                          const uint32_t *__restrict__ box, long long *__restrict__ head, uint32_t *__restrict__ codes)
 {
@@ -127,7 +144,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_codes(const float *__restrict
     if (blockIdx.x == 0 && threadIdx.x < 8) {
         long long w = 0;
         const int k = threadIdx.x;
-        if (k == 0) w = BVH_MAGIC;
+        if (k == 0) w = POINTS ? PBVH_MAGIC : BVH_MAGIC;
         if (k == 1) w = n_faces;
         if (k == 2) w = t.n_valid;
         if (k >= 3 && k < 6) w = (long long)(((unsigned long long)__float_as_uint(t.hi[k - 3]) << 32) | __float_as_uint(t.lo[k - 3]));
@@ -137,7 +154,7 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_codes(const float *__restrict
     if (f >= n_faces) return;
     float a[3], b[3], c[3];
     uint32_t code = BVH_CODE_INVALID;
-    if (cm_face(verts, n_verts, faces, n_faces, f, a, b, c) == 0) {
+    if (bvh_leaf<POINTS>(verts, n_verts, faces, n_faces, f, a, b, c) == 0) {
         float lo[3], hi[3], ctr[3];
         face_box(a, b, c, lo, hi);
 #pragma unroll
@@ -191,12 +208,13 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_topology(const uint32_t *__re
 }
 
 // the box of child c of a node: a leaf's is its face's coordinate box, an internal node's the union of the two boxes it stores
+template <bool POINTS>
 __device__ __forceinline__ void bvh_child_box(int32_t c, const BvhNode *__restrict__ node, const int32_t *__restrict__ leaf_face, const float *__restrict__ verts,
                                               int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces, float lo[3], float hi[3])
 {
     if (c < 0) {
         float a[3], b[3], cc[3];
-        (void)cm_face(verts, n_verts, faces, n_faces, leaf_face[-(c + 1)], a, b, cc);          // a leaf of the tree is a valid face
+        (void)bvh_leaf<POINTS>(verts, n_verts, faces, n_faces, leaf_face[-(c + 1)], a, b, cc);          // a leaf of the tree is a valid face
         face_box(a, b, cc, lo, hi);
     } else {
         const BvhNode &n = node[c];
@@ -208,6 +226,7 @@ __device__ __forceinline__ void bvh_child_box(int32_t c, const BvhNode *__restri
     }
 }
 
+template <bool POINTS>
 __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_refit(int pass, const float *__restrict__ verts, int32_t n_verts, const int32_t *__restrict__ faces, int64_t n_faces,
                                                          const int32_t *__restrict__ leaf_face, uint32_t *__restrict__ box, int32_t *__restrict__ mark,
                                                          BvhNode *__restrict__ node)
@@ -223,10 +242,10 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_refit(int pass, const float *
         const int m0 = c0 < 0 ? -1 : mark[c0], m1 = c1 < 0 ? -1 : mark[c1];          // a leaf is finished; a mark of this pass is not
         if (m0 != 0 && m0 != pass && m1 != 0 && m1 != pass) {
             float lo[3], hi[3];
-            bvh_child_box(c0, node, leaf_face, verts, n_verts, faces, n_faces, lo, hi);
+            bvh_child_box<POINTS>(c0, node, leaf_face, verts, n_verts, faces, n_faces, lo, hi);
 #pragma unroll
             for (int k = 0; k < 3; k++) { node[i].lo0[k] = lo[k]; node[i].hi0[k] = hi[k]; }
-            bvh_child_box(c1, node, leaf_face, verts, n_verts, faces, n_faces, lo, hi);
+            bvh_child_box<POINTS>(c1, node, leaf_face, verts, n_verts, faces, n_faces, lo, hi);
 #pragma unroll
             for (int k = 0; k < 3; k++) { node[i].lo1[k] = lo[k]; node[i].hi1[k] = hi[k]; }
             mark[i] = pass;
@@ -247,15 +266,6 @@ struct BvhMesh {
     int32_t n_verts;
     int64_t n_faces;
 };
-
-// a node as four 16-byte reads
-__device__ __forceinline__ void bvh_node_load(const BvhNode *__restrict__ node, int32_t i, BvhNode &n)
-{
-    const float4 *src = reinterpret_cast<const float4 *>(node + i);
-    float4 *dst = reinterpret_cast<float4 *>(&n);
-#pragma unroll
-    for (int k = 0; k < 4; k++) dst[k] = src[k];
-}
 
 __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_closest(const float *__restrict__ query, int64_t nq, const int32_t *__restrict__ order, BvhMesh m, float md2,
                                                            float *__restrict__ dist2, int32_t *__restrict__ face, float *__restrict__ uv, float *__restrict__ point,
@@ -365,17 +375,71 @@ __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_ray_cast(const float *__restr
 }
 
 __global__ void __launch_bounds__(GEO_BLOCK) k_bvh_point_codes(const float *__restrict__ points, int64_t n, int stride, const long long *__restrict__ head, int64_t n_faces,
-                                                               uint32_t *__restrict__ codes)
+                                                               long long magic, uint32_t *__restrict__ codes)
 {
     BvhTree t;
-    if (!bvh_head_read(head, n_faces, t)) return;          // uniform
+    if (!bvh_head_read(head, n_faces, t, magic)) return;          // uniform
     const int64_t i = (int64_t)blockIdx.x * GEO_BLOCK + threadIdx.x;
     if (i >= n) return;
     const float c[3] = {points[i * stride + 0], points[i * stride + 1], points[i * stride + 2]};
     codes[i] = bvh_morton(c, t);
 }
 
+template <bool POINTS>
+static int bvh_build_run(const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, void *d_bvh, size_t bvh_bytes, uint32_t *d_stats, void *d_workspace,
+                         size_t workspace_bytes, hipStream_t st, const char *who)
+{
+    Bump bump(d_workspace, workspace_bytes);
+    const BvhWs ws = bvh_ws_layout(bump, n_faces);
+    NRF_TRY(ws_check(bump, bvh_build_workspace_bytes(n_faces), who));
+    Bump bb(d_bvh, bvh_bytes);
+    const BvhBuf buf = bvh_layout(bb, n_faces);
+    const int64_t fb = ceil_div(n_faces, GEO_BLOCK), nb = ceil_div(n_faces - 1, GEO_BLOCK);
+    NRF_HIP(hipMemsetAsync(d_bvh, 0, bvh_bytes, st));          // unused nodes, spare words and the padding: the same bytes on every run
+    NRF_HIP(hipMemsetAsync(ws.box, 0xff, 3 * sizeof(uint32_t), st));
+    NRF_HIP(hipMemsetAsync(ws.box + 3, 0, 5 * sizeof(uint32_t), st));
+    if (n_faces > 1) NRF_HIP(hipMemsetAsync(ws.mark, 0, (size_t)(n_faces - 1) * sizeof(int32_t), st));
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_bvh_classify<POINTS>, dim3((unsigned)fb), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, ws.box, d_stats);
+        NRF_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_bvh_codes<POINTS>, dim3((unsigned)(fb > 0 ? fb : 1)), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, (const uint32_t *)ws.box,
+                       buf.head, ws.codes);
+    NRF_LAUNCH_CHECK();
+    if (n_faces == 0) return NRF_OK;
+    NRF_TRY(sort_pairs_launch(ws.codes, nullptr, n_faces, 0, 32, ws.sorted, buf.leaf_face, ws.sort, st));
+    if (n_faces == 1) return NRF_OK;
+    hipLaunchKernelGGL(k_bvh_topology, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, (const uint32_t *)ws.sorted, (const int32_t *)buf.leaf_face, ws.box, buf.node);
+    NRF_LAUNCH_CHECK();
+    for (int pass = 1; pass <= NRF_BVH_MAX_DEPTH; pass++) {
+        hipLaunchKernelGGL(k_bvh_refit<POINTS>, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, pass, d_verts, (int32_t)n_verts, d_faces, n_faces, (const int32_t *)buf.leaf_face,
+                           ws.box, ws.mark, buf.node);
+        NRF_LAUNCH_CHECK();
+    }
+    return NRF_OK;
+}
+
 }  // namespace
+
+size_t bvh_build_workspace_bytes(int64_t n_leaves)
+{
+    if (n_leaves < 0 || n_leaves > INT32_MAX) return 0;
+    return measure([&](Bump &b) { bvh_ws_layout(b, n_leaves); });
+}
+
+int bvh_build_launch(bool points, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_leaves, void *d_bvh, size_t bvh_bytes, uint32_t *d_stats,
+                     void *d_workspace, size_t workspace_bytes, hipStream_t st, const char *who)
+{
+    return points ? bvh_build_run<true>(d_verts, n_verts, d_faces, n_leaves, d_bvh, bvh_bytes, d_stats, d_workspace, workspace_bytes, st, who)
+                  : bvh_build_run<false>(d_verts, n_verts, d_faces, n_leaves, d_bvh, bvh_bytes, d_stats, d_workspace, workspace_bytes, st, who);
+}
+
+int bvh_point_codes_launch(const float *d_points, int64_t n, int stride, const void *d_bvh, int64_t n_leaves, long long magic, uint32_t *d_codes, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_bvh_point_codes, dim3((unsigned)ceil_div(n, GEO_BLOCK)), dim3(GEO_BLOCK), 0, st, d_points, n, stride, (const long long *)d_bvh, n_leaves, magic, d_codes);
+    NRF_LAUNCH_CHECK();
+    return NRF_OK;
+}
 
 }  // namespace nrf
 
@@ -406,11 +470,7 @@ size_t nrf_mesh_bvh_bytes(int64_t n_faces)
     return measure([&](Bump &b) { bvh_layout(b, n_faces); });
 }
 
-size_t nrf_mesh_bvh_workspace_bytes(int64_t n_faces)
-{
-    if (n_faces < 0 || n_faces > INT32_MAX) return 0;
-    return measure([&](Bump &b) { bvh_ws_layout(b, n_faces); });
-}
+size_t nrf_mesh_bvh_workspace_bytes(int64_t n_faces) { return bvh_build_workspace_bytes(n_faces); }
 
 size_t nrf_bvh_query_workspace_bytes(int64_t n)
 {
@@ -432,35 +492,7 @@ int nrf_mesh_bvh_build(const float *d_verts, int64_t n_verts, const int32_t *d_f
 {
     NRF_BVH_CHECK("nrf_mesh_bvh_build");
     NRF_CHECK_ARG(d_workspace && (reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "nrf_mesh_bvh_build: the workspace must be non-null and 8-byte aligned");
-    Bump bump(d_workspace, workspace_bytes);
-    const BvhWs ws = bvh_ws_layout(bump, n_faces);
-    NRF_TRY(ws_check(bump, nrf_mesh_bvh_workspace_bytes(n_faces), "nrf_mesh_bvh_build"));
-    Bump bb(d_bvh, bvh_bytes);
-    const BvhBuf buf = bvh_layout(bb, n_faces);
-    hipStream_t st = as_stream(stream);
-    const int64_t fb = ceil_div(n_faces, GEO_BLOCK), nb = ceil_div(n_faces - 1, GEO_BLOCK);
-    NRF_HIP(hipMemsetAsync(d_bvh, 0, bvh_bytes, st));          // unused nodes, spare words and the padding: the same bytes on every run
-    NRF_HIP(hipMemsetAsync(ws.box, 0xff, 3 * sizeof(uint32_t), st));
-    NRF_HIP(hipMemsetAsync(ws.box + 3, 0, 5 * sizeof(uint32_t), st));
-    if (n_faces > 1) NRF_HIP(hipMemsetAsync(ws.mark, 0, (size_t)(n_faces - 1) * sizeof(int32_t), st));
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(k_bvh_classify, dim3((unsigned)fb), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, ws.box, d_stats);
-        NRF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_bvh_codes, dim3((unsigned)(fb > 0 ? fb : 1)), dim3(GEO_BLOCK), 0, st, d_verts, (int32_t)n_verts, d_faces, n_faces, (const uint32_t *)ws.box, buf.head,
-                       ws.codes);
-    NRF_LAUNCH_CHECK();
-    if (n_faces == 0) return NRF_OK;
-    NRF_TRY(sort_pairs_launch(ws.codes, nullptr, n_faces, 0, 32, ws.sorted, buf.leaf_face, ws.sort, st));
-    if (n_faces == 1) return NRF_OK;
-    hipLaunchKernelGGL(k_bvh_topology, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, (const uint32_t *)ws.sorted, (const int32_t *)buf.leaf_face, ws.box, buf.node);
-    NRF_LAUNCH_CHECK();
-    for (int pass = 1; pass <= NRF_BVH_MAX_DEPTH; pass++) {
-        hipLaunchKernelGGL(k_bvh_refit, dim3((unsigned)nb), dim3(GEO_BLOCK), 0, st, pass, d_verts, (int32_t)n_verts, d_faces, n_faces, (const int32_t *)buf.leaf_face, ws.box,
-                           ws.mark, buf.node);
-        NRF_LAUNCH_CHECK();
-    }
-    return NRF_OK;
+    return bvh_build_launch(false, d_verts, n_verts, d_faces, n_faces, d_bvh, bvh_bytes, d_stats, d_workspace, workspace_bytes, as_stream(stream), "nrf_mesh_bvh_build");
 }
 
 int nrf_bvh_closest_on_mesh(const float *d_query, int64_t nq, const float *d_verts, int64_t n_verts, const int32_t *d_faces, int64_t n_faces, const void *d_bvh,
@@ -523,10 +555,7 @@ int nrf_bvh_point_codes(const float *d_points, int64_t n, int stride, const void
                   bvh_bytes, (long long)n_faces, nrf_mesh_bvh_bytes(n_faces));
     NRF_CHECK_ARG(n == 0 || (d_points && d_codes), "nrf_bvh_point_codes: null d_points or d_codes");
     if (n == 0) return NRF_OK;
-    hipLaunchKernelGGL(k_bvh_point_codes, dim3((unsigned)ceil_div(n, GEO_BLOCK)), dim3(GEO_BLOCK), 0, as_stream(stream), d_points, n, stride,
-                       (const long long *)d_bvh, n_faces, d_codes);
-    NRF_LAUNCH_CHECK();
-    return NRF_OK;
+    return bvh_point_codes_launch(d_points, n, stride, d_bvh, n_faces, BVH_MAGIC, d_codes, as_stream(stream));
 }
 
 }  // extern "C"

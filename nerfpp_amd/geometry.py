@@ -156,7 +156,13 @@ def NearestPoints(query, target, max_dist=None, bbox=None, cells=None, stats=Non
     On an exact tie the lowest index; +inf and -1 where the target has no finite point (within max_dist, where given) or the query point is not finite.
     bbox [6] (min xyz, max xyz) is where the search grid lies; points outside it are still found.  bbox=None takes the box of the target, which costs ONE host
     synchronisation; pass the renderer's box (or any box around the target) to avoid it.  cells = (nx, ny, nz) overrides GridDims.  The result depends on neither.
-    stats: an int32 [3] device tensor to add {non-finite queries, non-finite targets, queries served by the brute-force fallback} to."""
+    stats: an int32 [3] device tensor to add {non-finite queries, non-finite targets, queries served by the brute-force fallback} to.
+    target may be a points.PointBVH of the cloud: nrf_bvh_knn with k = 1 returns the same bits with no box, no host synchronisation and no fallback (bbox and cells
+    are not used; of stats only entry 0 is added to -- the build counted the non-finite targets)."""
+    from . import points as P
+    if isinstance(target, P.PointBVH):
+        res = P.KNearest(query, target, 1, max_dist=max_dist, stats=stats)
+        return res.Dist2.reshape(-1), res.Index.reshape(-1)
     q, t = _dev_f32(query).reshape(-1, 3), _dev_f32(target).reshape(-1, 3)
     dev = q.device
     nq, nt = int(q.shape[0]), int(t.shape[0])
